@@ -7,7 +7,12 @@ the reference's call, /root/reference/src/my_gsplat/model.py:195-213) -> backwar
 depth-channel gradient to every Gaussian input and to the 4x4 view matrix.  Inputs are resident
 in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload R|S|T|X|D]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload R|S|T|X|D] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the line
+can carry: the per-frame calibration time, per-stage timings and the roofline block, the CPU baseline and parity block,
+the tracker / drop-in API / per-frame side measurements and the workload variants (each leg can still be skipped with
+its --no-* option).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 Workloads (SURVEY.md 8d / BASELINE.json configs): R (default, the metric's configuration) = 1 M random Gaussians,
 1200x680, sigma_px = 1; X = 5 M random Gaussians, 1920x1080; S = a 640x480 depth frame back-projected to 102 400
@@ -85,7 +90,14 @@ def parse():
                          "(exercises the captured-collective path on a one-GPU box)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="dev: run the N-rank path with every rank on cuda:0 and a gloo (host) all-reduce")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline figure: calibration time, per-stage timings and "
+                         "roofline, CPU baseline and parity, tracker / API / per-frame side measurements, workload variants")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; one GPU only)")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1 (a rank of a multi-GPU run holds one strip of the frame)")
     wl = WORKLOADS[args.workload]
     explicit = any(getattr(args, k) is not None for k in ("n", "width", "height", "sigma_px", "order"))
     for key in ("n", "width", "height", "sigma_px", "order"):
@@ -625,6 +637,49 @@ def guarded(fn, *a, **k):
         return {"error": f"{type(exc).__name__}: {exc}"}
 
 
+DUMP_BYTES = 64 << 20       # --dump-outputs: all files together stay below this
+DUMP_GAUSSIANS = 131_072     # per-Gaussian gradients: rows of a fixed sample of this many Gaussians when N is larger
+
+
+def dump_outputs(path, last, ctx, n, scales):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files in `path`: render [H,W,4] and
+    alphas [H,W,1] of the forward; v_viewmat [4,4] and (full gradients) v_means, v_quats, v_scales, v_opacities, v_colors
+    of the backward, rows in the CALLER's Gaussian order.  v_quats is left out when every Gaussian is isotropic (equal
+    scales: every scene this benchmark builds): the covariance then does not depend on the rotation, the exact
+    quaternion gradient is zero, and what the backward returns is float32 cancellation noise whose digits follow the
+    order of the float atomics, different in every run.  The per-Gaussian files hold the rows of a fixed sample of
+    min(N, DUMP_GAUSSIANS) Gaussians (torch.randperm with seed 0, sorted); if the images do not fit in what is left of
+    DUMP_BYTES they are flattened to [pixels, C] and keep a fixed sample of pixels the same way (seed 1).  The inputs are
+    seeded, so two runs with the same arguments -- of one build or of two -- can be compared file by file: the images
+    bit for bit, the gradients to float32 rounding (their sums are float atomics, added in no fixed order)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    grads = last["grads"]
+    arrays = {"v_viewmat": grads["viewmat"]}
+    isotropic = bool((scales == scales[:, :1]).all())
+    per_gaussian = {k: v for k, v in grads.items()
+                    if k != "viewmat" and v is not None and not (k == "quats" and isotropic)}
+    if per_gaussian:
+        idx = torch.arange(n)
+        if n > DUMP_GAUSSIANS:
+            idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_GAUSSIANS].sort().values
+        storage_of = getattr(ctx, "storage_of", None)  # tile-order placement: gradient rows are in storage order
+        rows = storage_of.long().cpu()[idx] if storage_of is not None else idx
+        for k, v in per_gaussian.items():
+            arrays["v_" + k] = v.index_select(0, rows.to(v.device))
+    images = {"render": last["render"], "alphas": last["alphas"]}
+    left = DUMP_BYTES - 4096 * (len(arrays) + len(images)) - sum(a.numel() * 4 for a in arrays.values())
+    n_pix = images["render"].shape[0] * images["render"].shape[1]
+    per_pix = sum(a.shape[-1] * 4 for a in images.values())
+    if n_pix * per_pix > left:
+        pix = torch.randperm(n_pix, generator=torch.Generator().manual_seed(1))[:left // per_pix].sort().values
+        images = {k: v.reshape(n_pix, -1).index_select(0, pix.to(v.device)) for k, v in images.items()}
+    arrays = dict(images, **arrays)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.detach().float().cpu().numpy())
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -694,14 +749,16 @@ def main():
     ctx = C.RenderContext(n_local, W, H, "RGB+ED", sh_degree=1, K_sh=4, device=dev, tile_rows=rows, full_grads=full,
                           staging=args.staging)
     n_isects = ctx.calibrate(sc["means"], sc["quats"], sc["scales"], sc["opacities"], sc["sh"], viewmat, K)
-    # what a frame pays ONCE, outside the timed steps (a tracker runs hundreds of steps per frame): the measuring pass that
-    # sizes lists and bins, the tile-order placement (a stable sort of N tile indices + five gathers) and the allocations;
-    # timed on a second call, when the allocator is warm
-    torch.cuda.synchronize()
-    t_cal = time.perf_counter()
-    n_isects = ctx.calibrate(sc["means"], sc["quats"], sc["scales"], sc["opacities"], sc["sh"], viewmat, K)
-    torch.cuda.synchronize()
-    calibrate_ms = (time.perf_counter() - t_cal) * 1e3
+    calibrate_ms = None
+    if args.full:
+        # what a frame pays ONCE, outside the timed steps (a tracker runs hundreds of steps per frame): the measuring pass
+        # that sizes lists and bins, the tile-order placement (a stable sort of N tile indices + five gathers) and the
+        # allocations; timed on a second call, when the allocator is warm
+        torch.cuda.synchronize()
+        t_cal = time.perf_counter()
+        n_isects = ctx.calibrate(sc["means"], sc["quats"], sc["scales"], sc["opacities"], sc["sh"], viewmat, K)
+        torch.cuda.synchronize()
+        calibrate_ms = (time.perf_counter() - t_cal) * 1e3
     trace(f"calibrated, {n_isects} intersections")
     strip_ok = True
     if world > 1:  # the strip's lists must hold exactly the full frame's entries of its tile rows
@@ -718,10 +775,12 @@ def main():
         host16 = torch.zeros(16).pin_memory()
     args_in = (sc["means"], sc["quats"], sc["scales"], sc["opacities"], sc["sh"], viewmat, K)
 
+    last = {}  # what the step hands its caller: the context's output buffers, rewritten by every step (and replay)
+
     def render_step():
         """The rank's launches of one step: library kernels and memsets only (captured as one HIP graph)."""
-        ctx.forward(*args_in)
-        grads = ctx.backward(v_render, v_alphas, full=full)
+        last["render"], last["alphas"] = ctx.forward(*args_in)
+        grads = last["grads"] = ctx.backward(v_render, v_alphas, full=full)
         if dist is not None:  # pack the 12 pose-gradient entries (+4 spare) into the all-reduce buffer
             C.pack_pose_reduce(grads["viewmat"], pose_grad)
 
@@ -798,10 +857,12 @@ def main():
     ms = dt / args.steps * 1e3
     step_ms = guarded(lambda: event_stats([a.elapsed_time(b) for a, b in events]))
     trace("timed steps done")
+    if args.dump_outputs is not None:  # (before anything below launches the path again)
+        dump_outputs(args.dump_outputs, last, ctx, n_local, sc["scales"])
 
-    # ---- per-kernel durations: HIP events on the launch stream, same steps, second pass -------
+    # ---- per-kernel durations: HIP events on the launch stream, same steps, second pass (--full) --------
     stage_ms = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         stage_ms = guarded(C.time_stages, ctx, args_in, v_render, v_alphas, full, steps=min(args.steps, 20))
         if "error" in stage_ms:
             stage_ms = {}
@@ -849,13 +910,13 @@ def main():
                           if graph is not None else "eager",
                 "backward": backward_name(ctx),
                 "gaussian_placement": placement_name(ctx),
-                "per_frame_calibrate_ms": calibrate_ms,  # (once per frame, NOT in ms_per_step: see the comment at its timing)
+                "per_frame_calibrate_ms": calibrate_ms,  # (--full; once per frame, NOT in ms_per_step: see its timing)
                 "binning": ("keys written into per-tile bins by the projection kernel (sizes from calibrate()), "
                             "register sort per tile" if getattr(ctx, "bins", None) is not None
                             else "count, scan, scatter, register sort per tile"),
                 "staging": args.staging + (" records for compositing (T and accumulators f32)" if args.staging == "fp16" else ""),
             },
-            "roofline": {
+            **({"roofline": {
                 "bound": "hbm", "kernel": dom, "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
                 "frac": (achieved / 8000.0) if achieved else None,
                 "traffic": pmc_traffic(dom) if (world == 1 and headline and N == 1_000_000) else None,
@@ -891,9 +952,9 @@ def main():
                                                              stage_ms.get("raster_fwd" if dom == "raster_bwd" else "raster_bwd"))
                 if (world == 1 and headline and N == 1_000_000) else None,
                 "stage_ms": stage_ms,
-            },
+            }} if args.full else {}),  # (per-stage timings and counters: --full)
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             def gpu_backward(vm):
                 ctx.forward(*args_in)
                 grads = ctx.backward(vm.float().to(dev).contiguous(), v_alphas, full=full)
@@ -932,12 +993,12 @@ def main():
                 out["cpu_baseline"] = res
         else:
             out["cpu_baseline"] = None
-        if world == 1 and not args.no_tracker:
+        if args.full and world == 1 and not args.no_tracker:
             out["pose_opt"] = guarded(pose_opt_rate, dev)
             # the drop-in boundary and the per-frame end-to-end figure
             out["api"] = guarded(api_rate, dev, ms if (headline and N == 1_000_000) else None)
             out["frame"] = guarded(frame_rate, dev)
-        if world == 1 and not args.no_variants:
+        if args.full and world == 1 and not args.no_variants:
             # same N and image, the other synthetic inputs of SURVEY.md 8(d): sigma_px -> 0 is the regime of the
             # reference's as-coded kNN scales; "raster" is the Gaussian order of a back-projected depth frame
             out["variants"] = [guarded(variant_rate, dev, args.n, W, H, s_, o_) for s_, o_ in

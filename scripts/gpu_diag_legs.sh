@@ -1,7 +1,8 @@
 #!/usr/bin/env bash
 # The full default bench line (every leg): do the variants still see host stalls?  (cgroup throttle counters in "host")
 set -o pipefail
-mkdir -p gpurun_out
+export OUT=${OUT:-run_out}  # output folder of this script
+mkdir -p "$OUT"
 cat /sys/fs/cgroup/cpu.max 2>/dev/null; nproc
 show() { python3 - "$1" <<'PY'
 import json, sys
@@ -16,12 +17,12 @@ PY
 }
 for i in 1 2; do
   echo "== bench.py (run $i)"
-  timeout -k 10 400 python3 bench.py > gpurun_out/legs$i.json 2> gpurun_out/legs$i.err; rc=$?
+  timeout -k 10 400 python3 bench.py --full > $OUT/legs$i.json 2> $OUT/legs$i.err; rc=$?
   if [ $rc -ge 124 ]; then exit $rc; fi
-  tail -2 gpurun_out/legs$i.err
-  show gpurun_out/legs$i.json
+  tail -2 $OUT/legs$i.err
+  show $OUT/legs$i.json
 done
 echo "== bench.py --workload D"
-timeout -k 10 400 python3 bench.py --workload D --no-variants > gpurun_out/legsD.json 2> gpurun_out/legsD.err; rc=$?
+timeout -k 10 400 python3 bench.py --workload D --no-variants --full > $OUT/legsD.json 2> $OUT/legsD.err; rc=$?
 if [ $rc -ge 124 ]; then exit $rc; fi
-tail -2 gpurun_out/legsD.err; show gpurun_out/legsD.json
+tail -2 $OUT/legsD.err; show $OUT/legsD.json

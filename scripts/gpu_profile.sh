@@ -1,7 +1,8 @@
 #!/usr/bin/env bash
 # One GPU call that produces everything the round's profiles/ and BASELINE.md table are made of (round 3).
 set -o pipefail
-mkdir -p gpurun_out
+export OUT=${OUT:-run_out}  # output folder of this script
+mkdir -p "$OUT"
 R=$(pwd)
 guard() { if [ "$1" -ge 124 ]; then echo "step ended with rc=$1: stopping"; exit "$1"; fi; }
 line() { python3 - "$1" <<'PY'
@@ -16,19 +17,19 @@ for v in d.get('variants') or []: print('   variant', {k: v.get(k) for k in ('wo
 print('   host', d.get('host'))
 PY
 }
-timeout -k 10 600 python bench.py > gpurun_out/bench_R.json 2> gpurun_out/bench_R.err; rc=$?; guard $rc; [ $rc -eq 0 ] && line gpurun_out/bench_R.json || tail -5 gpurun_out/bench_R.err
+timeout -k 10 600 python bench.py --full > $OUT/bench_R.json 2> $OUT/bench_R.err; rc=$?; guard $rc; [ $rc -eq 0 ] && line $OUT/bench_R.json || tail -5 $OUT/bench_R.err
 for wl in D S T X; do
-  timeout -k 10 600 python bench.py --workload $wl --no-tracker --no-variants > gpurun_out/bench_$wl.json 2> gpurun_out/bench_$wl.err; rc=$?; guard $rc
-  [ $rc -eq 0 ] && line gpurun_out/bench_$wl.json || tail -5 gpurun_out/bench_$wl.err
+  timeout -k 10 600 python bench.py --workload $wl --no-tracker --no-variants --full > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err; rc=$?; guard $rc
+  [ $rc -eq 0 ] && line $OUT/bench_$wl.json || tail -5 $OUT/bench_$wl.err
 done
-timeout -k 10 600 python bench.py --workload X --staging fp32 --no-tracker --no-variants --no-cpu-baseline > gpurun_out/bench_X32.json 2> gpurun_out/bench_X32.err; rc=$?; guard $rc
-[ $rc -eq 0 ] && line gpurun_out/bench_X32.json || tail -5 gpurun_out/bench_X32.err
+timeout -k 10 600 python bench.py --workload X --staging fp32 --no-tracker --no-variants --no-cpu-baseline --full > $OUT/bench_X32.json 2> $OUT/bench_X32.err; rc=$?; guard $rc
+[ $rc -eq 0 ] && line $OUT/bench_X32.json || tail -5 $OUT/bench_X32.err
 cd /tmp && export TMPDIR=/tmp && cd "$R"
 B="--no-cpu-baseline --no-tracker --no-variants"
 for wl in R D X; do
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$wl -o st --output-format csv -- python3 bench.py $B --workload $wl --steps 10 --warmup 3 > gpurun_out/prof_$wl.log 2>&1; guard $?
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$wl -o st --output-format csv -- python3 bench.py $B --workload $wl --steps 10 --warmup 3 > $OUT/prof_$wl.log 2>&1; guard $?
 done
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d gpurun_out/pmc_fetch -o f --output-format csv -- python3 bench.py $B --no-graph --steps 3 --warmup 1 > gpurun_out/pmc_fetch.log 2>&1; guard $?
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d gpurun_out/pmc_write -o w --output-format csv -- python3 bench.py $B --no-graph --steps 3 --warmup 1 > gpurun_out/pmc_write.log 2>&1; guard $?
-python3 scripts/pmc_summary.py $(find gpurun_out/pmc_fetch -name "*counter_collection.csv" | head -1) $(find gpurun_out/pmc_write -name "*counter_collection.csv" | head -1) gpurun_out/pmc_traffic.json
-find gpurun_out/prof_R gpurun_out/prof_D gpurun_out/prof_X -name "*kernel_stats.csv" | head
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -o f --output-format csv -- python3 bench.py $B --no-graph --steps 3 --warmup 1 > $OUT/pmc_fetch.log 2>&1; guard $?
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write -o w --output-format csv -- python3 bench.py $B --no-graph --steps 3 --warmup 1 > $OUT/pmc_write.log 2>&1; guard $?
+python3 scripts/pmc_summary.py $(find $OUT/pmc_fetch -name "*counter_collection.csv" | head -1) $(find $OUT/pmc_write -name "*counter_collection.csv" | head -1) $OUT/pmc_traffic.json
+find $OUT/prof_R $OUT/prof_D $OUT/prof_X -name "*kernel_stats.csv" | head

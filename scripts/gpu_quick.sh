@@ -12,7 +12,7 @@ for l in sys.stdin:
         d = json.loads(l); print('R', d['order'], 'graph median', round(d['graph']['median'], 4), 'stages', {k: round(v, 4) for k, v in d['stages'].items()})
 "
 for m in auto general; do
-GSLOC_BWD=$m timeout -k 10 300 python3 bench.py --workload D --no-cpu-baseline --no-tracker --no-variants --steps 50 2>/dev/null | python3 -c "
+GSLOC_BWD=$m timeout -k 10 300 python3 bench.py --workload D --no-cpu-baseline --no-tracker --no-variants --steps 50 --full 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print('D $m', round(d['ms_per_step'], 4), {k: round(v, 4) for k, v in d['roofline']['stage_ms'].items()})"
 done

@@ -10,7 +10,7 @@ import json,sys
 d=json.loads([l for l in open('$1') if l.startswith('{')][-1])
 print('$2', round(d['ms_per_step'],4), {k: round(v,4) for k,v in d['roofline']['stage_ms'].items()}, d.get('step_ms_hip_events'))
 "; }
-B="--no-cpu-baseline --no-tracker --no-variants"
+B="--no-cpu-baseline --no-tracker --no-variants --full"
 timeout -k 10 300 python bench.py $B > gpurun_out/q_R.json 2> gpurun_out/q_R.err || { tail -5 gpurun_out/q_R.err; exit 1; }
 pl gpurun_out/q_R.json R
 timeout -k 10 300 python bench.py $B --workload D > gpurun_out/q_D.json 2> gpurun_out/q_D.err || { tail -5 gpurun_out/q_D.err; exit 1; }

@@ -3,7 +3,7 @@
 set -o pipefail
 for rows in 36 40 41 42 43 44 48; do
   H=$((rows * 16)); N=$((1000000 * H / 680))
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-tracker --no-variants --gaussians $N --height $H 2>/dev/null | python3 -c "
+  timeout -k 10 300 python bench.py --no-cpu-baseline --no-tracker --no-variants --full --gaussians $N --height $H 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 s=d['roofline']['stage_ms']; t=75*$rows

@@ -3,7 +3,7 @@
 for m in auto general; do
   echo "== GSLOC_BWD=$m"
   for wl in S T D; do
-    GSLOC_BWD=$m timeout -k 10 300 python3 bench.py --workload $wl --no-cpu-baseline --no-tracker --no-variants --steps 50 2>/dev/null | python3 -c "
+    GSLOC_BWD=$m timeout -k 10 300 python3 bench.py --workload $wl --no-cpu-baseline --no-tracker --no-variants --steps 50 --full 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print('$wl', round(d['ms_per_step'], 4), d['step_ms_hip_events']['median'], {k: round(v, 4) for k, v in d['roofline']['stage_ms'].items()})"
   done

@@ -5,6 +5,7 @@ collective, barrier/timing, max over ranks, the JSON line -- can be exercised on
 numbers it prints mean nothing.
 """
 import contextlib
+import json
 import os
 import sys
 
@@ -55,17 +56,28 @@ class FakeContext:
         per_tile = 7  # (a constant: the strip contexts of the N > 1 path must count what the calibration context counted)
         self.offs = torch.arange(self.n_tiles + 1, dtype=torch.int32) * per_tile
         self.v_viewmat = torch.zeros(4, 4)
+        # (not `render` / `alphas`: bench.py's parity leg compares attributes of those names with the C oracle)
+        self._render, self._alphas = torch.zeros(height, width, 4), torch.zeros(height, width, 1)
         self.calls = 0
+        FakeContext.instances.append(self)
 
     def calibrate(self, *a, **k):
         return int(self.offs[self.rows[1] * self.tw] - self.offs[self.rows[0] * self.tw])
 
     def forward(self, *a):
         self.calls += 1
+        self._render.fill_(float(self.calls))
+        self._alphas.fill_(0.5)
+        return self._render, self._alphas
 
     def backward(self, v_render, v_alphas, full=True):
         self.v_viewmat = torch.full((4, 4), float(self.N))
-        return {"viewmat": self.v_viewmat}
+        out = {"viewmat": self.v_viewmat}
+        if full:  # (row i of every per-Gaussian gradient holds i: a dump can be checked against the sample it names)
+            i = torch.arange(self.N, dtype=torch.float32)
+            out.update(means=i[:, None].repeat(1, 3), quats=i[:, None].repeat(1, 4), scales=i[:, None].repeat(1, 3),
+                       opacities=i.clone(), colors=i[:, None, None].repeat(1, 4, 3))
+        return out
 
     def check_capacity(self):
         return self.calibrate()
@@ -74,6 +86,7 @@ class FakeContext:
         pass
 
     order_ids = storage_of = None
+    instances = []
 
     def _place(self, *a):
         return a
@@ -102,6 +115,8 @@ def main():
     import bench
     sys.argv = ["bench.py"] + sys.argv[1:]
     bench.main()
+    # forward passes per context (the tests count the steps a run really made)
+    print("[fake] forward calls " + json.dumps([c.calls for c in FakeContext.instances]), file=sys.stderr)
 
 
 if __name__ == "__main__":
