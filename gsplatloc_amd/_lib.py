@@ -83,6 +83,10 @@ _SIGNATURES = {
     "gsl_rasterize_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P,
                                   c_int64, P, P, P, P, P, P]),
     "gsl_vacc_unpack": (c_int, [P, c_int, c_int, P, P, P, P, P]),
+    "gsl_fused_absgrad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int64, P, P, P, P, P, P,
+                                  P, P, P]),
+    "gsl_rasterize_absgrad": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int64, P, P,
+                                      P, P, P, P]),
 }
 
 

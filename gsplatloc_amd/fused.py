@@ -146,6 +146,198 @@ class _FusedRasterization(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# absgrad=True on the fused path: the same five launches as _FusedRasterization, split into two autograd nodes so that
+# the screen-space means sit in the graph between them (gsplat's means2d: retain_grad() gives .grad, and the compositing
+# backward sets .absgrad).  The projection node runs gsl_fused_project + gsl_fused_bin and outputs means2d [1,N,2]; the
+# compositing node consumes it, and its backward runs gsl_fused_raster_bwd, then gsl_fused_absgrad, and hands the
+# v_xy columns of vacc back as v_means2d.  The rest of vacc travels in the shared `state`; the projection node's
+# backward writes the incoming v_means2d (which includes anything else added into means2d) back into those columns
+# and runs gsl_fused_project_bwd.
+class _FusedProjectNode(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means, quats, scales, opacities, colors, viewmat, K, cfg, state):
+        lib = load_library()
+        (W, H, sh_degree, mode, eps2d, near, far, radius_clip, antialiased, want_isect_ids) = cfg
+        D, _ = _MODES[mode]
+        rgb = D >= 3
+        N = means.shape[0]
+        dev = means.device
+        tw, th = (W + 15) // 16, (H + 15) // 16
+        n_tiles = tw * th
+        f32, i32 = torch.float32, torch.int32
+        radii = torch.empty(N, dtype=i32, device=dev)
+        Q0, Q1, Q2 = alloc_records(lib, N, rgb, dev)
+        comps = torch.empty(N, dtype=f32, device=dev) if antialiased else None
+        tpg = torch.empty(N, dtype=i32, device=dev)
+        offs = torch.empty(n_tiles + 1, dtype=i32, device=dev)
+        n_is = torch.empty(1, dtype=i32, device=dev)
+        ws_bytes = lib.gsl_fused_ws_bytes(N, n_tiles)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        st = current_stream()
+        K_sh = colors.shape[1] if (rgb and sh_degree >= 0) else 0
+        check(lib.gsl_fused_project(
+            ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(colors) if rgb else None, sh_degree, K_sh,
+            ptr(viewmat), ptr(K), N, W, H, eps2d, near, far, radius_clip, int(antialiased), tw, th, 0, th,
+            ptr(radii), ptr(Q0), ptr(Q1), ptr(Q2), ptr(comps), ptr(tpg), ptr(offs), ptr(n_is), ptr(ws), ws_bytes,
+            None, None, 0, None, None, st), "gsl_fused_project")
+        n_isects = int(n_is.item())
+        cap = max(n_isects, 1)
+        keys = torch.empty(cap, dtype=torch.int64, device=dev)
+        flatten_ids = torch.empty(n_isects, dtype=i32, device=dev)
+        isect_ids = torch.empty(n_isects, dtype=torch.int64, device=dev) if want_isect_ids else None
+        check(lib.gsl_fused_bin(ptr(Q0), ptr(radii), N, tw, th, 0, th, tile_n_bits(n_tiles), ptr(offs), n_isects,
+                                ptr(keys), ptr(flatten_ids) if n_isects else None,
+                                ptr(isect_ids) if (want_isect_ids and n_isects) else None, ptr(ws), ws_bytes, 0, None, 0,
+                                None, None, 0, None, None, st), "gsl_fused_bin")
+        state.update(cfg=cfg, N=N, D=D, tw=tw, th=th, n_isects=n_isects, K_sh=K_sh, radii=radii, Q0=Q0, Q1=Q1, Q2=Q2,
+                     comps=comps, tiles_per_gauss=tpg, tile_offsets=offs, flatten_ids=flatten_ids, isect_ids=isect_ids,
+                     ws=ws, vacc=None)
+        ctx.save_for_backward(means, quats, scales, opacities, colors if rgb else torch.empty(0, device=dev), viewmat, K)
+        ctx.state = state
+        return Q0[None, :, 0:2].clone()
+
+    @staticmethod
+    def backward(ctx, v_means2d):
+        lib = load_library()
+        s = ctx.state
+        means, quats, scales, opacities, colors, viewmat, K = ctx.saved_tensors
+        (W, H, sh_degree, mode, eps2d, _, _, _, antialiased, _) = s["cfg"]
+        D, N = s["D"], s["N"]
+        rgb = D >= 3
+        dev = means.device
+        f32 = torch.float32
+        vacc = s["vacc"]
+        s["vacc"] = None
+        if vacc is None:  # (nothing was composited into the loss: means2d is all the gradient there is)
+            vacc = torch.zeros(N, 16, dtype=f32, device=dev)
+        vacc[:, 0:2].copy_(v_means2d[0])
+        ni = ctx.needs_input_grad
+        full = any(ni[:5])
+        v_means = v_quats = v_scales = v_opac = v_colors = None
+        if full:
+            v_means = torch.empty(N, 3, dtype=f32, device=dev)
+            v_quats = torch.empty(N, 4, dtype=f32, device=dev)
+            v_scales = torch.empty(N, 3, dtype=f32, device=dev)
+            v_opac = torch.empty(N, dtype=f32, device=dev)
+            if rgb:
+                v_colors = torch.empty_like(colors)
+        v_viewmat = torch.empty(4, 4, dtype=f32, device=dev) if ni[5] else None
+        ws = s["ws"]
+        comps = s["comps"]
+        check(lib.gsl_fused_project_bwd(
+            ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(colors) if rgb else None, sh_degree, s["K_sh"],
+            ptr(viewmat), ptr(K), N, W, H, eps2d, int(antialiased), D, ptr(s["radii"]), ptr(s["Q1"]),
+            ptr(comps) if antialiased else None, ptr(vacc), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_opac),
+            ptr(v_colors), ptr(v_viewmat), ptr(ws), ws.numel(), s["tw"] * s["th"], None, None, None, None, 0, 0, 0, 0, 0,
+            None, None, 1, None, current_stream()),
+            "gsl_fused_project_bwd")
+        return (v_means if ni[0] else None, v_quats if ni[1] else None, v_scales if ni[2] else None,
+                v_opac if ni[3] else None, v_colors if (ni[4] and rgb) else None, v_viewmat, None, None, None)
+
+
+class _FusedCompositeNode(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means2d, state):
+        lib = load_library()
+        s = state
+        (W, H, _, mode, _, _, _, _, _, _) = s["cfg"]
+        D, ed = _MODES[mode]
+        tw, th = s["tw"], s["th"]
+        n_isects = s["n_isects"]
+        dev = means2d.device
+        f32, i32 = torch.float32, torch.int32
+        cap = max(n_isects, 1)
+        render = torch.empty(H, W, D, dtype=f32, device=dev)
+        alphas = torch.empty(H, W, 1, dtype=f32, device=dev)
+        last_ids = torch.zeros(H, W, dtype=i32, device=dev)
+        hits = torch.empty(4 * cap, dtype=torch.int32, device=dev) if cap < (1 << 28) else None
+        hit_counts = torch.empty(4 * tw * th + 1, dtype=i32, device=dev) if hits is not None else None
+        flatten_ids = s["flatten_ids"]
+        check(lib.gsl_fused_raster_fwd(ptr(s["Q0"]), ptr(s["Q1"]), ptr(s["Q2"]), D, int(ed), W, H, tw, th, 0, th,
+                                       ptr(s["tile_offsets"]), ptr(flatten_ids) if n_isects else None, n_isects,
+                                       ptr(render), ptr(alphas), ptr(last_ids), 0, H, None, None, ptr(hits),
+                                       ptr(hit_counts), 0, None, 0, None, None, None, current_stream()),
+              "gsl_fused_raster_fwd")
+        s["last_ids"] = last_ids
+        ctx.save_for_backward(means2d, render, alphas, last_ids, hits, hit_counts)
+        ctx.state = state
+        ctx.mark_non_differentiable(last_ids)
+        return render, alphas, last_ids
+
+    @staticmethod
+    def backward(ctx, v_render, v_alphas, _v_last):
+        lib = load_library()
+        s = ctx.state
+        means2d, render, alphas, last_ids, hits, hit_counts = ctx.saved_tensors
+        (W, H, _, mode, _, _, _, _, _, _) = s["cfg"]
+        D, ed = _MODES[mode]
+        rgb = D >= 3
+        N, tw, th, n_isects = s["N"], s["tw"], s["th"], s["n_isects"]
+        dev = means2d.device
+        st = current_stream()
+        v_render = v_render.contiguous()
+        v_alphas = v_alphas.contiguous()
+        Q0, Q1, Q2 = s["Q0"], s["Q1"], s["Q2"] if rgb else None
+        offs, flatten_ids = s["tile_offsets"], s["flatten_ids"]
+        vacc = torch.zeros(N, 16, dtype=torch.float32, device=dev)
+        check(lib.gsl_fused_raster_bwd(ptr(Q0), ptr(Q1), ptr(Q2), D, int(ed), W, H, tw, th, 0, th, ptr(offs),
+                                       ptr(flatten_ids) if n_isects else None, n_isects, ptr(render), ptr(alphas),
+                                       ptr(last_ids), ptr(v_render), ptr(v_alphas), ptr(vacc), 0, H, None, None,
+                                       ptr(hits), ptr(hit_counts), 0, None, st),
+              "gsl_fused_raster_bwd")
+        absgrad = torch.zeros(N, 2, dtype=torch.float32, device=dev)
+        check(lib.gsl_fused_absgrad(ptr(Q0), ptr(Q1), ptr(Q2), D, int(ed), W, H, tw, th, ptr(offs),
+                                    ptr(flatten_ids) if n_isects else None, n_isects, ptr(render), ptr(alphas),
+                                    ptr(last_ids), ptr(v_render), ptr(v_alphas), ptr(hits), ptr(hit_counts),
+                                    ptr(absgrad), st),
+              "gsl_fused_absgrad")
+        means2d.absgrad = absgrad[None]  # assigned by every backward, as gsplat does
+        s["vacc"] = vacc  # the projection node's backward consumes it
+        return vacc[None, :, 0:2].clone(), None
+
+
+def fused_absgrad_rasterization(
+    means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor, colors: Tensor, viewmat: Tensor, K: Tensor,
+    width: int, height: int, sh_degree: Optional[int] = None, render_mode: str = "RGB", eps2d: float = 0.3,
+    near_plane: float = 0.01, far_plane: float = 1e10, radius_clip: float = 0.0, antialiased: bool = False,
+    want_isect_ids: bool = True,
+) -> Tuple[Tensor, Tensor, Dict]:
+    """fused_rasterization (whole frame) with meta["means2d"] [1,N,2] in the autograd graph between projection and
+    compositing: after a backward it carries ``.absgrad`` (and ``.grad`` when retained), as gsplat's absgrad=True."""
+    def prep(t, name):
+        assert t.is_cuda, f"{name} must live on the GPU (got {t.device}); there is no CPU path"
+        assert t.dtype == torch.float32, f"{name} must be float32 (got {t.dtype})"
+        return t.contiguous()
+
+    cfg = (int(width), int(height), -1 if sh_degree is None else int(sh_degree), render_mode, float(eps2d),
+           float(near_plane), float(far_plane), float(radius_clip), bool(antialiased), bool(want_isect_ids))
+    render, alphas, means2d, s = fused_absgrad_apply(
+        prep(means, "means"), prep(quats, "quats"), prep(scales, "scales"), prep(opacities, "opacities"),
+        prep(colors, "colors"), prep(viewmat, "viewmats"), prep(K, "Ks"), cfg)
+    tw, th = s["tw"], s["th"]
+    Q0, Q1 = s["Q0"], s["Q1"]
+    meta = {
+        "camera_ids": None, "gaussian_ids": None,
+        "radii": s["radii"][None], "means2d": means2d, "depths": Q0[None, :, 2],
+        "conics": Q1[None, :, 0:3], "opacities": Q0[None, :, 3],
+        "tile_width": tw, "tile_height": th, "tiles_per_gauss": s["tiles_per_gauss"][None],
+        "isect_ids": s["isect_ids"], "flatten_ids": s["flatten_ids"],
+        "isect_offsets": s["tile_offsets"][:-1].reshape(1, th, tw), "width": width, "height": height,
+        "tile_size": 16, "n_cameras": 1,
+    }
+    return render, alphas, meta
+
+
+def fused_absgrad_apply(means, quats, scales, opacities, colors, viewmat, K, cfg):
+    """The two autograd nodes of the absgrad path on prepared tensors: (render [H,W,X], alphas [H,W,1], means2d [1,N,2],
+    the shared state)."""
+    state: Dict = {}
+    means2d = _FusedProjectNode.apply(means, quats, scales, opacities, colors, viewmat, K, cfg, state)
+    render, alphas, _ = _FusedCompositeNode.apply(means2d, state)
+    return render, alphas, means2d, state
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Drop-in call with a cached RenderContext.  `from gsplat import rasterization` under the reference's loop
 # (/root/reference/src/my_gsplat/gs_trainer_total.py:79-267) renders the same N Gaussians at the same size a few hundred
 # times per frame: allocating ~15 tensors per call, binning in two passes and reading the intersection count back to

@@ -290,7 +290,7 @@ class _RasterizeToPixels(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, width, height, tile_size, isect_offsets,
-                flatten_ids):
+                flatten_ids, absgrad=False):
         lib = load_library()
         C, N, D = colors.shape
         th, tw = isect_offsets.shape[1:]
@@ -313,6 +313,7 @@ class _RasterizeToPixels(torch.autograd.Function):
                               backgrounds if backgrounds is not None else torch.empty(0, device=dev), offs_ext,
                               flatten_ids, render_alphas, last_ids)
         ctx.dims = (width, height, tile_size, tw, th, backgrounds is not None)
+        ctx.absgrad = absgrad
         return render_colors, render_alphas
 
     @staticmethod
@@ -341,10 +342,21 @@ class _RasterizeToPixels(torch.autograd.Function):
                     ptr(v_render_alphas[c]), ptr(vacc), st), "gsl_rasterize_bwd")
         check(lib.gsl_vacc_unpack(ptr(vacc), C * N, D, ptr(v_means2d), ptr(v_conics), ptr(v_colors),
                                   ptr(v_opacities), st), "gsl_vacc_unpack")
+        if ctx.absgrad:
+            # sum over pixels of |per-pixel v_means2d| (gsplat's means2d.absgrad), set on the caller's means2d: the
+            # compositing backward's sums cannot give it (|.| of a sum), csrc/absgrad.hip walks the pixels once more
+            absgrad = torch.zeros(C, N, 2, dtype=torch.float32, device=means2d.device)
+            for c in range(C):
+                check(lib.gsl_rasterize_absgrad(
+                    ptr(means2d), ptr(conics), ptr(colors), ptr(opacities), ptr(backgrounds[c]) if has_bg else None,
+                    D, width, height, tile_size, tw, th, ptr(offs_ext[c * n_tiles:]),
+                    ptr(flatten_ids) if n_isects else None, n_isects, ptr(render_alphas[c]), ptr(last_ids[c]),
+                    ptr(v_render_colors[c]), ptr(v_render_alphas[c]), ptr(absgrad), st), "gsl_rasterize_absgrad")
+            means2d.absgrad = absgrad  # assigned by every backward, as gsplat does
         v_backgrounds = None
         if has_bg and ctx.needs_input_grad[4]:
             v_backgrounds = (v_render_colors * (1.0 - render_alphas)).sum(dim=(1, 2))
-        return v_means2d, v_conics, v_colors, v_opacities, v_backgrounds, None, None, None, None, None
+        return v_means2d, v_conics, v_colors, v_opacities, v_backgrounds, None, None, None, None, None, None
 
 
 def rasterize_to_pixels(
@@ -362,11 +374,12 @@ def rasterize_to_pixels(
     packed: bool = False,
     absgrad: bool = False,
 ) -> Tuple[Tensor, Tensor]:
-    """Rasterize to pixels: render_colors [C,H,W,channels], render_alphas [C,H,W,1]."""
+    """Rasterize to pixels: render_colors [C,H,W,channels], render_alphas [C,H,W,1].
+
+    ``absgrad``: the backward also sets ``means2d.absgrad`` [C,N,2], the per-component sum over pixels of
+    |d L_p / d means2d| (gsplat's densification statistic)."""
     if packed:
         raise NotImplementedError("packed=True is not supported")
-    if absgrad:
-        raise NotImplementedError("absgrad is a densification aid GsplatLoc does not use (model.py:124)")
     if masks is not None:
         raise NotImplementedError("tile masks are not supported")
     C, N = means2d.shape[:2]
@@ -392,7 +405,7 @@ def rasterize_to_pixels(
     render_colors, render_alphas = _RasterizeToPixels.apply(
         _dev_f32(means2d, "means2d"), _dev_f32(conics, "conics"), _dev_f32(colors, "colors"),
         _dev_f32(opacities, "opacities"), backgrounds, int(image_width), int(image_height), int(tile_size),
-        isect_offsets.contiguous(), flatten_ids.to(torch.int32).contiguous())
+        isect_offsets.contiguous(), flatten_ids.to(torch.int32).contiguous(), bool(absgrad))
     if padded != channels:
         render_colors = render_colors[..., :channels]
     return render_colors, render_alphas

@@ -17,7 +17,7 @@ from typing_extensions import Literal
 
 import os
 
-from .fused import cached_rasterization, fused_rasterization, fused_supported
+from .fused import cached_rasterization, fused_absgrad_rasterization, fused_rasterization, fused_supported
 from .ops import (
     fully_fused_projection,
     isect_offset_encode,
@@ -63,6 +63,17 @@ def rasterization(
     ``packed`` only changes gsplat's internal memory layout, never the rendered
     result; this implementation always computes densely and returns the dense
     ([C,N,...]) meta tensors.
+
+    ``meta["means2d"]`` [C,N,2]: with ``absgrad=False`` on the fused one-camera
+    path it is a detached view of the projection records (no ``.grad``); on the
+    staged path (several cameras, backgrounds, GSLOC_DISABLE_FUSED=1) it sits in
+    the autograd graph.  With ``absgrad=True`` it sits in the graph on every path
+    (``retain_grad()`` gives ``.grad``), and each backward that reaches the render
+    assigns ``meta["means2d"].absgrad`` [C,N,2]: per Gaussian and component, the
+    sum over pixels of |d L_p / d means2d| (gsplat 1.3.0 semantics, a HIP walk of
+    its own: csrc/absgrad.hip).  The render and every other gradient are those of
+    ``absgrad=False``; the fused path then allocates per call (no cached context).
+    Features composited in channel chunks (more than 32) raise NotImplementedError.
     """
     meta: Dict = {}
     N = means.shape[0]
@@ -81,8 +92,6 @@ def rasterization(
                                   "use gsplatloc_amd.parallel for screen-tile parallelism")
     if ortho:
         raise NotImplementedError("orthographic cameras are not supported")
-    if absgrad:
-        raise NotImplementedError("absgrad is not supported (GsplatLoc: absgrad=False, model.py:124)")
     if sparse_grad:
         raise NotImplementedError("sparse_grad is not supported (GsplatLoc: sparse_grad=False, model.py:122)")
 
@@ -94,9 +103,25 @@ def rasterization(
             colors.dim() == 4 and colors.shape[:2] == (C, N) and colors.shape[3] == 3), colors.shape
         assert (sh_degree + 1) ** 2 <= colors.shape[-2], colors.shape
 
+    fused = os.environ.get("GSLOC_DISABLE_FUSED", "0") != "1" and fused_supported(
+        N, C, colors, sh_degree, width, height, tile_size, backgrounds, render_mode)
+    if absgrad and not fused:
+        n_feat = (colors.shape[-1] if sh_degree is None else 3) if render_mode.startswith("RGB") else 0
+        n_feat += 1 if render_mode != "RGB" else 0
+        if n_feat > min(int(channel_chunk), 32):
+            raise NotImplementedError(
+                f"absgrad with {n_feat} feature channels: they are composited in chunks of {min(int(channel_chunk), 32)} "
+                "and the sum over pixels of |v_means2d| over all channels is not the sum of the per-chunk ones")
+
     # Hot path: one camera, no background -> the fused five-launch pipeline (csrc/fused.hip).
-    if os.environ.get("GSLOC_DISABLE_FUSED", "0") != "1" and fused_supported(
-            N, C, colors, sh_degree, width, height, tile_size, backgrounds, render_mode):
+    if fused and absgrad:
+        # the same kernels with means2d in the graph between projection and compositing (fused.py): it gets .absgrad
+        render, alphas, meta = fused_absgrad_rasterization(
+            means, quats, scales, opacities, colors, viewmats[0], Ks[0], width, height, sh_degree=sh_degree,
+            render_mode=render_mode, eps2d=eps2d, near_plane=near_plane, far_plane=far_plane,
+            radius_clip=radius_clip, antialiased=(rasterize_mode == "antialiased"))
+        return render[None], alphas[None], meta
+    if fused:
         # the same call signature again and again (a tracker's loop): keep the context, see fused.py
         call = cached_rasterization if (N > 0 and os.environ.get("GSLOC_DROPIN_CACHE", "1") != "0") else fused_rasterization
         render, alphas, meta = call(
@@ -155,7 +180,7 @@ def rasterization(
         render_colors = torch.cat(parts, dim=-1)
     else:
         render_colors, render_alphas = rasterize_to_pixels(means2d, conics, feats, opac, width, height, tile_size,
-                                                           isect_offsets, flatten_ids, backgrounds=bg)
+                                                           isect_offsets, flatten_ids, backgrounds=bg, absgrad=absgrad)
     if render_mode in ("ED", "RGB+ED"):  # expected depth: accumulated depth over accumulated alpha
         expected = render_colors[..., -1:] / render_alphas.clamp(min=1e-10)
         render_colors = torch.cat([render_colors[..., :-1], expected], dim=-1)

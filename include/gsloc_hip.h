@@ -395,6 +395,26 @@ int gsl_knn_count(const float* points, int N, const float* bbox, void* ws, size_
 int gsl_knn_query(const float* points, int N, const float* bbox, const int32_t* incl_offsets, int k,
                   float* dists, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- absolute screen-space gradient: gsplat's means2d.absgrad (rasterization(absgrad=True)) (csrc/absgrad.hip) ----
+ * For every Gaussian, sum over pixels p of |dL_p / d means2d| per component (x, y), L_p = <v_render_p, render_p> +
+ * v_alpha_p alpha_p: the per-pixel terms whose plain sum is the v_means2d of the compositing backward.  Both entries
+ * ACCUMULATE into absgrad[n][2], zeroed by the caller, rows indexed like flatten_ids.  Whole frame only, 16x16 tiles.
+ * gsl_fused_absgrad: the records, lists and outputs of gsl_fused_project / _bin / _raster_fwd (no long-list segments,
+ *   float32 records), channels 1 / 3 / 4, ed as there; render is read for ed only.  isect_hits / isect_hit_counts
+ *   (may be NULL together): the forward's hit lists -- each quadrant then walks only the entries it composited.
+ * gsl_rasterize_absgrad: the arrays of gsl_rasterize_fwd / _bwd for one camera (same channel counts, backgrounds may
+ *   be NULL); call once per camera with its tile_offsets, as gsl_rasterize_bwd. */
+int gsl_fused_absgrad(const float* Q0, const float* Q1, const float* Q2, int channels, int ed, int width, int height,
+                      int tile_w, int tile_h, const int32_t* tile_offsets, const int32_t* flatten_ids, int64_t capacity,
+                      const float* render, const float* alphas, const int32_t* last_ids, const float* v_render,
+                      const float* v_alphas, const uint32_t* isect_hits, const int32_t* isect_hit_counts,
+                      float* absgrad, void* stream);
+int gsl_rasterize_absgrad(const float* means2d, const float* conics, const float* colors, const float* opacities,
+                          const float* backgrounds, int channels, int width, int height, int tile_size, int tile_w,
+                          int tile_h, const int32_t* tile_offsets, const int32_t* flatten_ids, int64_t capacity,
+                          const float* render_alphas, const int32_t* last_ids, const float* v_render_colors,
+                          const float* v_render_alphas, float* absgrad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
