@@ -49,6 +49,7 @@ class RenderContext:
         self.order_ids = self.storage_of = None  # int32[N]: original index of a storage slot / slot of an original index
         self._placed = None       # context-owned copies of the per-Gaussian inputs in storage order
         self._placed_key = None   # (data_ptr, version) of the caller's tensors they were made from
+        self._placed_src = None   # ... and those tensors themselves: while the key lives their memory cannot be reused
         # sort_in_forward (callers whose every forward is followed by a backward: the tracker): the compositing forward
         # sorts its own tile's bin -- no gsl_fused_bin launch -- whenever the frame allows it (sorts_in_forward())
         self.sort_in_forward = bool(sort_in_forward)
@@ -152,7 +153,7 @@ class RenderContext:
         """One synchronising projection pass to size the intersection buffers and the per-tile bins -- and, for Gaussians
         in no screen-coherent order, to choose their tile-order placement (_choose_placement)."""
         self.bins, self.bin_cap = None, 0  # two-pass binning for this measuring pass
-        self.order_ids = self.storage_of = self._placed = self._placed_key = None
+        self.order_ids = self.storage_of = self._placed = self._placed_key = self._placed_src = None
         self._project(means, quats, scales, opacities, colors, viewmat, K)
         if self._choose_placement():
             # records in storage order (what _choose_backward looks at); same lists, same sizes
@@ -204,7 +205,11 @@ class RenderContext:
 
     def _place(self, means, quats, scales, opacities, colors):
         """The caller's per-Gaussian inputs -> the context's copies in storage order (re-gathered only when the caller
-        passes other tensors, or has written to them in place, since the last call)."""
+        passes other tensors, or has written to them in place, since the last call).  The key alone cannot tell a new
+        tensor from a freed one whose memory the allocator handed out again (a caller that rebuilds torch.sigmoid(raw)
+        every step gets a version-0 tensor at last step's address): the source tensors are kept alive with the key, so
+        an equal key means the same memory, unwritten since.  (A .detach() view of a static tensor shares pointer and
+        version with it: such callers keep the no-gather path.)"""
         if self.order_ids is None:
             return means, quats, scales, opacities, colors
         srcs = (means, quats, scales, opacities) + ((colors,) if (self.rgb and colors is not None) else ())
@@ -214,7 +219,7 @@ class RenderContext:
                 self._placed = tuple(torch.empty_like(t) for t in srcs)
             for p, t in zip(self._placed, srcs):
                 torch.index_select(t.detach(), 0, self._perm64, out=p)
-            self._placed_key = key
+            self._placed_key, self._placed_src = key, srcs
         pl = self._placed
         return pl[0], pl[1], pl[2], pl[3], (pl[4] if len(pl) > 4 else colors)
 

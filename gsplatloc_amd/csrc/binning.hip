@@ -9,7 +9,9 @@
 // composite key makes the result independent of scatter order and identical to a stable
 // global sort of the gsplat key.  Wave64 lanes that hit the same tile are merged with a
 // ballot so hot tiles see one atomic per wave instead of 64.
+#include <atomic>
 #include <cstdlib>
+#include <cstring>
 #include "gsloc_common.h"
 #include "sort_dev.h"
 
@@ -795,6 +797,17 @@ extern "C" int gsl_tile_sort_keys(int32_t* tile_offsets, int tile_begin, int n_s
                                   int32_t* n_isects, int32_t* flags, int long_min, int occupied_tiles,
                                   const int32_t* storage_of, void* stream);
 
+namespace gsl {
+// launches of k_tile_sort<4>, k_tile_sort<5>, k_tile_sort_wg issued by this process (host-side diagnostics for the
+// tests: which tile-sort kernel a call ran; gsl_dev_tile_sort_launches)
+static std::atomic<int64_t> g_tile_sort_launches[3];
+}  // namespace gsl
+
+extern "C" int64_t gsl_dev_tile_sort_launches(int variant) {
+  if (variant < 0 || variant > 2) return -1;
+  return gsl::g_tile_sort_launches[variant].load(std::memory_order_relaxed);
+}
+
 extern "C" int gsl_tile_sort(const int32_t* tile_offsets, int tile_begin, int n_strip_tiles, int64_t capacity,
                              uint64_t* sort_keys, int32_t* flatten_ids, int64_t* isect_ids, int64_t cam_enc,
                              void* stream) {
@@ -820,18 +833,26 @@ extern "C" int gsl_tile_sort_keys(int32_t* tile_offsets, int tile_begin, int n_s
   // (occupied_tiles: the tiles that can hold entries -- a strip's, when the launch runs over all tiles of the image)
   const int occ = occupied_tiles > 0 ? occupied_tiles : n_strip_tiles;
   const long long mean_list = capacity / (long long)occ;
-  static const char* const force = getenv("GSL_DEV_TILE_SORT");  // dev / test switch: "wave" / "wg" (read once)
+  // dev / test switch, read on every call (tests set it per case): "wg" = k_tile_sort_wg, "wave16" / "wave32" =
+  // k_tile_sort<4> / <5>, "wave" = the wave kernel with MAXLK by the mean list length; unset or anything else = the
+  // library's choice below
+  const char* force = getenv("GSL_DEV_TILE_SORT");
+  int variant;  // 0 = k_tile_sort<4>, 1 = k_tile_sort<5>, 2 = k_tile_sort_wg
+  if (force && !strcmp(force, "wg")) variant = 2;
+  else if (force && !strcmp(force, "wave16")) variant = 0;
+  else if (force && !strcmp(force, "wave32")) variant = 1;
   // (a latency matter: with more tiles than the chip has room for wave sorts at once, one tile per wave keeps more
   // lists in flight and is as fast or faster -- X: 159 against 169 us; with a strip's few hundred tiles the workgroup
   // kernel's shorter critical path decides)
-  const bool wg = force ? force[1] == 'g' : (mean_list > 320 && occ <= 2048);
-  if (wg)
+  else if (!(force && !strcmp(force, "wave")) && mean_list > 320 && occ <= 2048) variant = 2;
+  // (capacity carries ~1.3 x head-room: a mean list of <= ~880 keys, whose longest lists stay below 1024 in a frame of
+  // evenly spread splats; a tile that does exceed 1024 takes the workgroup's LDS sort -- slower, never wrong)
+  else variant = mean_list <= 1150 ? 0 : 1;
+  if (variant == 2)
     hipLaunchKernelGGL(gsl::k_tile_sort_wg, dim3(n_strip_tiles), dim3(256), 0, (hipStream_t)stream, tile_offsets,
                        tile_begin, n_strip_tiles, (long long)capacity, sort_keys, flatten_ids, isect_ids, cam_enc,
                        write_sorted_keys, bins, bin_cap, counts, n_isects, flags, long_min, storage_of);
-  else if (mean_list <= 1150 && !(force && force[0] == 'W'))
-    // (capacity carries ~1.3 x head-room: a mean list of <= ~880 keys, whose longest lists stay below 1024 in a frame of
-    // evenly spread splats; a tile that does exceed 1024 takes the workgroup's LDS sort -- slower, never wrong)
+  else if (variant == 0)
     hipLaunchKernelGGL((gsl::k_tile_sort<4>), dim3((n_strip_tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, tile_offsets,
                        tile_begin, n_strip_tiles, (long long)capacity, sort_keys, flatten_ids, isect_ids, cam_enc,
                        write_sorted_keys, bins, bin_cap, counts, n_isects, flags, long_min, storage_of);
@@ -839,6 +860,7 @@ extern "C" int gsl_tile_sort_keys(int32_t* tile_offsets, int tile_begin, int n_s
     hipLaunchKernelGGL((gsl::k_tile_sort<5>), dim3((n_strip_tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, tile_offsets,
                        tile_begin, n_strip_tiles, (long long)capacity, sort_keys, flatten_ids, isect_ids, cam_enc,
                        write_sorted_keys, bins, bin_cap, counts, n_isects, flags, long_min, storage_of);
+  gsl::g_tile_sort_launches[variant].fetch_add(1, std::memory_order_relaxed);
   GSL_CHECK_LAUNCH();
   return GSL_OK;
 }

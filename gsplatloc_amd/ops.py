@@ -209,7 +209,12 @@ def isect_tiles(
 
     Returns tiles_per_gauss [C,N] int32, isect_ids [I] int64 (camera | tile | depth bits),
     flatten_ids [I] int32 (index into the flattened [C*N] arrays); sorted by isect_ids when
-    ``sort`` (ties in Gaussian-index order, as a stable sort of the emit order gives)."""
+    ``sort`` (ties in Gaussian-index order, as a stable sort of the emit order gives).
+
+    With ``sort``, every Gaussian with radii > 0 must have a depth from +0.0 to +inf (sign bit clear, not NaN):
+    the per-tile sorts compare (depth bits, id) keys partly as doubles and partly as unsigned integers, which agree
+    only there (include/gsloc_hip.h, gsl_tile_sort).  Anything else raises ValueError.  The projection culls z <= near,
+    so its outputs always qualify."""
     if packed:
         raise NotImplementedError("packed=True is not supported")
     C, N, _ = means2d.shape
@@ -232,7 +237,16 @@ def isect_tiles(
         check(lib.gsl_isect_count(ptr(means2d[c]), ptr(radii[c]), N, tile_size, tile_width, tile_height, 0,
                                   tile_height, ptr(tiles_per_gauss[c]), ptr(offs[c]), ptr(counts[c:c + 1]),
                                   ptr(wss[c]), ws_bytes, st), "gsl_isect_count")
-    per_cam = counts.tolist()  # host sync: output sizes depend on it (as in gsplat)
+    if sort:
+        # visible Gaussians whose depth the sort cannot order: sign bit set (negative, -0.0) or NaN (> +inf's bits)
+        bits = depths.view(torch.int32)
+        bad = ((radii > 0) & ((bits < 0) | (bits > 0x7F800000))).sum(dtype=torch.int32).view(1)
+        per_cam = torch.cat([counts, bad]).tolist()  # host sync: output sizes depend on it (as in gsplat)
+        if per_cam.pop():
+            raise ValueError("isect_tiles: a Gaussian with radii > 0 has a negative, -0.0 or NaN depth; the tile sort "
+                             "orders depths from +0.0 to +inf only")
+    else:
+        per_cam = counts.tolist()  # host sync: output sizes depend on it (as in gsplat)
     total = int(sum(per_cam))
     isect_ids = torch.empty(total, dtype=torch.int64, device=dev)
     flatten_ids = torch.empty(total, dtype=torch.int32, device=dev)

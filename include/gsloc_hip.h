@@ -16,7 +16,8 @@
  *     intersection keys int64;
  *   - `stream` is a hipStream_t passed as void* (0 = default stream);
  *   - no allocation, no host synchronisation, no global state inside any call
- *     (safe to capture in a hipGraph); scratch comes from the caller through the
+ *     (safe to capture in a hipGraph; the one exception is the host-side launch
+ *     counter behind gsl_dev_tile_sort_launches); scratch comes from the caller through the
  *     `*_ws` arguments, sized by the matching `*_ws_bytes` query;
  *   - return value: GSL_OK (0) or a negative gsl_status; the launch error of the
  *     last kernel (hipGetLastError) is reported as GSL_ERR_HIP.
@@ -45,6 +46,10 @@ const char* gsl_status_string(int status);
 /* Diagnostics (tests): fill the LDS of every CU with `pattern` (e.g. 0xFFFFFFFF, a NaN), to show that no kernel of the
  * library reads LDS it has not written. */
 int gsl_dev_poison_lds(uint32_t pattern, void* stream);
+/* Diagnostics (tests): how many launches of one tile-sort kernel this process has issued (host-side counters, no
+ * device work; a launch recorded into a captured graph counts once, at capture).  variant 0 = k_tile_sort<4> (16 keys
+ * per lane), 1 = k_tile_sort<5> (32 keys per lane), 2 = k_tile_sort_wg; -1 for any other variant. */
+int64_t gsl_dev_tile_sort_launches(int variant);
 /* ---- projection: gsplat.fully_fused_projection fwd/bwd (IDX:14351, IDX:14270) ----
  * One camera.  viewmat[16] world->camera row-major, K[9] intrinsics, both on device.
  * Outputs for culled Gaussians: radii = 0, other outputs 0.
@@ -100,7 +105,15 @@ int gsl_isect_fill(const float* means2d, const int32_t* radii, const float* dept
                    size_t ws_bytes, void* stream);
 
 /* Sort every tile bucket of tiles [tile_begin, tile_begin+n_strip_tiles) on (depth bits, id) and
- * write flatten_ids / isect_ids (second half of gsl_isect_fill; cam_enc is OR-ed into isect_ids). */
+ * write flatten_ids / isect_ids (second half of gsl_isect_fill; cam_enc is OR-ed into isect_ids).
+ * Keys are (float32 depth bits << 32) | id with 0 <= id < 2^31 and a depth from +0.0 to +inf (sign bit clear, not
+ * NaN; see "Sort keys" below): a negative, -0.0 or NaN depth gets an order that depends on the list length.
+ * gsl_isect_fill takes the same depths.  Positions >= capacity are dropped: a tile's span is cut at capacity, later
+ * entries are left untouched.
+ * The environment variable GSL_DEV_TILE_SORT (read on every call; development and tests) picks the kernel:
+ * "wg" = one tile per workgroup (k_tile_sort_wg), "wave16" / "wave32" = one tile per wave with up to 16 / 32 keys
+ * per lane (k_tile_sort<4> / <5>), "wave" = one tile per wave, keys per lane by the mean list length; unset or any
+ * other value = the library's choice.  Every kernel gives the same result. */
 int gsl_tile_sort(const int32_t* tile_offsets, int tile_begin, int n_strip_tiles, int64_t capacity,
                   uint64_t* sort_keys, int32_t* flatten_ids, int64_t* isect_ids, int64_t cam_enc,
                   void* stream);
@@ -212,8 +225,10 @@ int gsl_vacc_unpack(const float* vacc, int n_gaussians, int channels, float* v_m
  * Sort keys: (depth bits << 32) | Gaussian index, the depth a positive finite normal float -- gsl_fused_project and
  *                     gsl_project_fwd clamp their depth window to [FLT_MIN, FLT_MAX], so every key this library makes is
  *                     one; the per-tile sorts (gsl_fused_bin, gsl_tile_sort_keys, gsl_long_sort, the sorting forward)
- *                     compare keys as doubles on that ground and order other bit patterns differently from an unsigned
- *                     compare (depths handed to the stage-wise isect entry points must be positive and finite).
+ *                     compare keys partly as doubles and partly as unsigned integers.  The two orders agree for every
+ *                     depth from +0.0 to +inf (the high word stays below 0x7FF00000, a double's inf / NaN) and for no
+ *                     other: depths handed to the stage-wise isect entry points must be such (gsplat.isect_tiles raises
+ *                     ValueError for a visible Gaussian with a negative, -0.0 or NaN depth).
  * Limits: N <= 2^26 Gaussians per call (gsl_fused_project returns GSL_ERR_BAD_ARG beyond: the compositing backward
  *                     addresses the 64-byte gradient rows of vacc by 32-bit byte offsets).
  * gsl_fused_project_bwd : consumes AND CLEARS vacc; v_means/v_quats/v_scales/v_opacities (and

@@ -58,6 +58,9 @@ def test_bad_arguments_are_rejected_without_a_gpu():
                                  0.0, 0, 4, 3, 0, 3, None, None, None, None, None, None, None, None, None, 0, None, None,
                                  0, None, None, None) == -1
     assert lib.gsl_project_bwd_ws_bytes(1000) == 4 * 12 * 4
+    # tile-sort launch counters (host-side): one per kernel, -1 for anything else
+    assert [lib.gsl_dev_tile_sort_launches(v) >= 0 for v in range(3)] == [True] * 3
+    assert lib.gsl_dev_tile_sort_launches(3) == -1 and lib.gsl_dev_tile_sort_launches(-1) == -1
     assert lib.gsl_isect_ws_bytes(100) == 800
 
 

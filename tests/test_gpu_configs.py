@@ -94,6 +94,8 @@ def _context_vs_c_oracle(tag, sc, V, W, H, v, max_flipped, grad_names=("means", 
     assert floor32 < FLOOR32_MAX, f"{tag}: the float32 floor itself is {floor32:.2e}"
     kind = "X" if N > 1_100_000 else ("sigma1" if tag.startswith("R") and "sigma=1.0" in tag else "subpixel")
     assert pose_err < pose_grad_bound(floor32, kind), f"{tag}: pose gradient {pose_err:.2e} (float32 floor {floor32:.2e})"
+    if "v_viewmat_deterministic" in errs:  # the float-atomic-free backward, same bound
+        assert det_err < pose_grad_bound(floor32, kind), f"{tag}: deterministic pose gradient {det_err:.2e}"
     for name in grad_names:  # relative L2 over all Gaussians; a splat whose own alpha sits on 1/255 at a nearly opaque
         assert errs["v_" + name] < 5e-3, (tag, name, errs["v_" + name])  # pixel switches without moving the pixel
     return errs

@@ -15,6 +15,7 @@ import torch
 from oracle import gsplat_oracle as G
 from tests.parity import POSE_GRAD_TOL, agreeing_pixels, report
 from tests.scenes import random_scene, sh_from_rgb, small_pose
+from tests.sort_variants import assert_tile_sort_ran, force_tile_sort, forced_tile_sort
 
 pytestmark = pytest.mark.gpu
 
@@ -141,22 +142,23 @@ def test_binning_multi_camera_and_empty():
     assert off.shape == (2, th, tw) and int(off.abs().sum()) == 0
 
 
-@pytest.mark.parametrize("kernel", ["wave", "wg"])
+@pytest.mark.parametrize("kernel", ["wave", "wave16", "wave32", "wg"])
 @pytest.mark.parametrize("N", [5, 63, 200, 256, 257, 700, 1024, 1025, 2048, 2049, 3000, 4097, 8192, 12289, 20000, 70001])
 def test_binning_long_tile_list_uses_global_sort(N, kernel, monkeypatch):
     """One tile list of every size class of the sort: a wave's registers (4, 8, 16, 32 keys per lane, at and around the
     class boundaries), and beyond 2048 entries the block-wise long-list sort with whole and partial last blocks -- by
-    the one-tile-per-wave kernel and by the one-tile-per-workgroup kernel (quarters sorted by the waves, merged in LDS;
-    GSL_DEV_TILE_SORT forces either, the library picks by the mean list length)."""
+    the one-tile-per-wave kernels (16 / 32 keys per lane at most, or as the mean list length picks) and by the
+    one-tile-per-workgroup kernel (quarters sorted by the waves, merged in LDS).  GSL_DEV_TILE_SORT forces each; the
+    launch counters show that it ran (tests/sort_variants.py)."""
     A = _gpu()
-    monkeypatch.setenv("GSL_DEV_TILE_SORT", kernel)
     g = torch.Generator().manual_seed(3)
     m2 = (torch.rand(1, N, 2, generator=g) * 14 + 1).float()
     r = torch.full((1, N), 1, dtype=torch.int32)
     d = (torch.rand(1, N, generator=g) * 5 + 0.5).float()
     d[0, ::7] = d[0, 3]  # depth ties: order falls back to the Gaussian index
     tpg_o, ids_o, fl_o = G.isect_tiles(m2, r, d, 16, 2, 2)
-    tpg_g, ids_g, fl_g = A.isect_tiles(m2.to(DEV), r.to(DEV), d.to(DEV), 16, 2, 2)
+    with forced_tile_sort(monkeypatch, kernel):
+        tpg_g, ids_g, fl_g = A.isect_tiles(m2.to(DEV), r.to(DEV), d.to(DEV), 16, 2, 2)
     assert ids_o.numel() == N
     assert torch.equal(ids_g.cpu(), ids_o) and torch.equal(fl_g.cpu(), fl_o)
 
@@ -408,15 +410,16 @@ def test_tiny_splat_backward_matches_general_backward(mode, full, monkeypatch):
             mostly_close(out["tiny"][k], out["general"][k], rtol=1e-3, atol=1e-5 * scale, max_bad_frac=1e-3, what=k)
 
 
-@pytest.mark.parametrize("kernel", ["wave", "wg"])
+@pytest.mark.parametrize("kernel", ["wave", "wave16", "wave32", "wg"])
 def test_binned_projection_gives_the_lists_of_two_pass_binning(kernel, monkeypatch):
-    """(Both tile-sort kernels.)  RenderContext bins directly from the projection kernel once calibrate() knows the tile sizes (no scatter pass);
+    """(Every tile-sort kernel, forced: the launch counters show that it ran.)  RenderContext bins directly from the
+    projection kernel once calibrate() knows the tile sizes (no scatter pass);
     the sorted lists, offsets, render and gradients are those of the count -> scan -> scatter path, bit for bit
     (integer work) -- also for a strip, for the deterministic mode's sorted keys, and when a pose change makes the
     lists longer than at calibration.  A tile that outgrows its bin is flagged, never silently truncated."""
     _gpu()
     from gsplatloc_amd.context import RenderContext
-    monkeypatch.setenv("GSL_DEV_TILE_SORT", kernel)
+    before = force_tile_sort(monkeypatch, kernel)
     W, H, N = 260, 200, 40000
     sc = _scene32(N, W, H, sigma_px=1.3, opacity=(0.3, 1.0))
     sh = sh_from_rgb(sc["rgbs"]).to(DEV)
@@ -465,6 +468,7 @@ def test_binned_projection_gives_the_lists_of_two_pass_binning(kernel, monkeypat
         rc.forward(*ins, V1, K)
         assert rc.bins_overflowed() == 0 and rc.check_capacity() == got[False]["n"]
         assert torch.equal(rc.flatten_ids[:got[False]["n"]], got[False]["ids"])
+    assert_tile_sort_ran(kernel, before)
 
 
 @pytest.mark.parametrize("case", ["all_culled", "single_gaussian", "odd_image", "huge_splats", "mostly_offscreen"])
@@ -701,16 +705,14 @@ def test_legacy_pair_on_the_gpu():
     assert em < 1e-3, em  # per-Gaussian gradients: largest entry of a single splat, float32 against float64
 
 
-@pytest.mark.parametrize("kernel", ["wave", "wg"])
+@pytest.mark.parametrize("kernel", ["wave", "wave16", "wave32", "wg"])
 @pytest.mark.parametrize("seed", range(4))
 def test_hip_binning_on_adversarial_inputs(seed, kernel, monkeypatch):
     """The HIP tile binning (stage operators) on the inputs of tests/test_c_oracle.py's adversarial case: centres
     outside the image, radii larger than the image, exact tile boundaries, equal depths.  Bit-exact against the
-    oracle, with either tile-sort kernel."""
+    oracle, with every tile-sort kernel (forced; the launch counters show that it ran)."""
     import gsplatloc_amd as A
     from oracle import gsplat_oracle as G
-
-    monkeypatch.setenv("GSL_DEV_TILE_SORT", kernel)
 
     g = torch.Generator().manual_seed(100 + seed)
     N, W, H, ts = 400, 150 + 7 * seed, 90 + 5 * seed, 16
@@ -724,7 +726,8 @@ def test_hip_binning_on_adversarial_inputs(seed, kernel, monkeypatch):
     dep[70:90] = dep[70]
     tpg, ids, fids = G.isect_tiles(m2[None], radii[None], dep[None], ts, tw, th)
     offs = G.isect_offset_encode(ids, 1, tw, th)
-    t2, i2, f2 = A.isect_tiles(m2[None].cuda(), radii[None].cuda(), dep[None].cuda(), ts, tw, th)
+    with forced_tile_sort(monkeypatch, kernel):
+        t2, i2, f2 = A.isect_tiles(m2[None].cuda(), radii[None].cuda(), dep[None].cuda(), ts, tw, th)
     o2 = A.isect_offset_encode(i2, 1, tw, th)
     assert torch.equal(t2.cpu(), tpg) and torch.equal(i2.cpu(), ids) and torch.equal(f2.cpu(), fids)
     assert torch.equal(o2.cpu(), offs)

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests.scenes import sh_from_rgb, small_pose
+from tests.sort_variants import assert_tile_sort_ran, force_tile_sort
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -73,14 +74,16 @@ def _same(a, b):
         assert float((a[k] - b[k]).abs().max()) <= tol * float(a[k].abs().max()), k
 
 
-@pytest.mark.parametrize("variant", ["wave_sort", "wg_sort", "sort_in_forward", "two_pass"])
+_FORCED_SORT = {"wave_sort": "wave16", "wave32_sort": "wave32", "wg_sort": "wg"}
+
+
+@pytest.mark.parametrize("variant", ["wave_sort", "wave32_sort", "wg_sort", "sort_in_forward", "two_pass"])
 def test_depth_ties_on_a_wall_keep_their_order_under_tile_order_placement(variant, monkeypatch):
     W, H, N, sigma = 320, 240, 40000, 1.2
     kw = {}
-    if variant == "wave_sort":
-        monkeypatch.setenv("GSL_DEV_TILE_SORT", "wave")
-    elif variant == "wg_sort":
-        monkeypatch.setenv("GSL_DEV_TILE_SORT", "wg")
+    before = None
+    if variant in _FORCED_SORT:  # (the launch counters show that the forced kernel ran: tests/sort_variants.py)
+        before = force_tile_sort(monkeypatch, _FORCED_SORT[variant])
     elif variant == "sort_in_forward":
         monkeypatch.setenv("GSLOC_SORT_IN_FORWARD", "force")
         kw["sort_in_forward"] = True
@@ -112,6 +115,8 @@ def test_depth_ties_on_a_wall_keep_their_order_under_tile_order_placement(varian
         rc.forward(*ins, V2, K)
     torch.cuda.synchronize()
     assert torch.equal(rc0.render, rc1.render) and torch.equal(rc0.last_ids, rc1.last_ids)
+    if before is not None:
+        assert_tile_sort_ran(_FORCED_SORT[variant], before)
 
 
 def test_long_list_sorted_by_several_workgroups_under_tile_order_placement():
@@ -158,6 +163,90 @@ def test_placement_follows_new_or_modified_input_tensors():
     torch.cuda.synchronize()
     assert torch.equal(rcs[0].render, rcs[1].render)
     assert not torch.equal(rcs[1]._placed[0], ins[0][rcs[1]._perm64])
+
+
+def _reborn(addr, make, holders):
+    """A derived input rebuilt for the next step after the caller dropped last step's, which lived at `addr`.  Unless
+    the placed context still holds that memory (`holders`: what it keeps alive with its placement key), the block is
+    free and the allocator hands it out again: make() until the new tensor sits at `addr` (the misses stay alive
+    meanwhile, so the allocator moves on to its next candidate) -- the address recycling that (data_ptr, _version, shape)
+    cannot see."""
+    if any(h.data_ptr() == addr for h in holders):
+        return make()
+    misses = []
+    for _ in range(16):
+        t = make()
+        if t.data_ptr() == addr:
+            return t
+        misses.append(t)
+    raise AssertionError("precondition: the freed input's block was never handed out again")
+
+
+@pytest.mark.parametrize("path", ["forward_backward", "render_autograd"])
+def test_placement_serves_the_new_values_of_inputs_rebuilt_at_a_freed_address(path):
+    """A caller that rebuilds derived inputs every step (torch.exp(log_scales), torch.sigmoid(logits),
+    torch.cat([sh0, shN], 1)) passes new version-0 tensors, often at the addresses of last step's freed ones: by
+    (data_ptr, _version, shape) alone they look like last step's tensors.  The placed context must render and
+    differentiate the NEW values: images bit-identical to an unplaced context's, gradients equal up to the float atomics'
+    summation order (the tolerances of _same)."""
+    from gsplatloc_amd.context import RenderContext
+    W, H, N = 200, 160, 20000
+    means, quats, scales, opac, sh, K = _wall(N, W, H, 1.1, seed=19)
+    means, quats, K = means.to(DEV), quats.to(DEV), K.to(DEV).contiguous()
+    V = torch.linalg.inv(small_pose(0.4, 0.01, dtype=torch.float32)).to(DEV).contiguous()
+    gen = torch.Generator().manual_seed(4)
+    v = torch.randn(H, W, 4, generator=gen).to(DEV)
+    va = torch.randn(H, W, 1, generator=gen).to(DEV)
+    raws = []  # the caller's raw parameters of two steps (every value moves between them)
+    for step in range(2):
+        d = 0.3 * step
+        raws.append([(scales.log() + d * torch.rand(N, 3, generator=gen)).to(DEV),
+                     (torch.logit(opac) + d * torch.randn(N, generator=gen)).to(DEV),
+                     (sh[:, :1] + d * torch.randn(N, 1, 3, generator=gen)).to(DEV),
+                     (sh[:, 1:] + d * torch.randn(N, 3, 3, generator=gen)).to(DEV)])
+    autograd = path == "render_autograd"
+    leaves = {reorder: [[r.clone().requires_grad_(autograd) for r in raw] for raw in raws] for reorder in (False, True)}
+    makers = (lambda r: torch.exp(r[0]), lambda r: torch.sigmoid(r[1]), lambda r: torch.cat([r[2], r[3]], 1))
+    rcs = {reorder: RenderContext(N, W, H, "RGB+ED", sh_degree=1, K_sh=4, device=DEV, reorder=reorder)
+           for reorder in (False, True)}
+
+    def run(reorder, derived):
+        rc = rcs[reorder]
+        if autograd:
+            render, alphas = rc.render_autograd(means, quats, *derived, V, K)
+            ((render * v).sum() + (alphas * va).sum()).backward()
+            torch.cuda.synchronize()
+            g = [r.grad.clone() for r in leaves[reorder][step]]
+        else:
+            rc.forward(means, quats, *derived, V, K)
+            g = rc.grads_in_input_order(rc.backward(v, va))
+            torch.cuda.synchronize()
+            g = [g[k].clone() for k in ("viewmat", "means", "scales", "opacities", "colors")]
+        return dict(render=rc.render.clone(), alphas=rc.alphas.clone(), last=rc.last_ids.clone(), grads=g)
+
+    step = 0
+    plain0 = [mk(leaves[False][0]) for mk in makers]
+    placed0 = [mk(leaves[True][0]) for mk in makers]
+    rcs[False].calibrate(means, quats, *[t.detach() for t in plain0], V, K)
+    rcs[True].calibrate(means, quats, *[t.detach() for t in placed0], V, K)
+    assert rcs[True].order_ids is not None and rcs[False].order_ids is None
+    first = run(False, plain0), run(True, placed0)
+    addrs = [t.data_ptr() for t in placed0]
+    del plain0, placed0  # the caller drops last step's derived inputs ...
+    step = 1
+    holders = getattr(rcs[True], "_placed_src", None) or ()
+    placed1 = []
+    for addr, mk in zip(addrs, makers):  # ... and builds this step's, with other values
+        placed1.append(_reborn(addr, lambda: mk(leaves[True][1]), holders))
+    del holders
+    plain1 = [mk(leaves[False][1]) for mk in makers]
+    a, b = run(False, plain1), run(True, placed1)
+    assert not torch.equal(a["render"], first[0]["render"]), "the second step's inputs must change the image"
+    assert torch.equal(a["render"], b["render"]) and torch.equal(a["alphas"], b["alphas"]), "stale placed inputs"
+    assert torch.equal(a["last"], b["last"])
+    for i, (x, y) in enumerate(zip(a["grads"], b["grads"])):  # (_same's tolerances; +1e-7 for cancellation noise)
+        tol = 2e-5 if (not autograd and i == 0) else 2e-4
+        assert float((x - y).abs().max()) <= tol * float(x.abs().max()) + 1e-7, i
 
 
 def test_autograd_through_a_placed_context_returns_gradients_in_the_callers_order():
