@@ -33,6 +33,9 @@ TINY_RCULL_MAX = 1.999  # r_cull below this: the alpha >= 1/255 disc spans at mo
 # Render modes with colour only: with one composited channel ("ED", what gsplatloc_amd.eval renders) the slabs still win
 # at 816 k (3 990 against 3 710 it/s).
 TINY_MAX_N = 400_000
+# fp16-staged records hold the conic as halves: its entries reach 1/eps2d for a degenerate splat, and halves end at 65504
+# (1/65504 = 1.53e-5; the bound keeps a margin for the float32 rounding of the inverse)
+FP16_EPS2D_MIN = 2e-5
 
 
 class RenderContext:
@@ -42,6 +45,9 @@ class RenderContext:
                  capacity: Optional[int] = None, full_grads: bool = True,
                  pixel_rows: Optional[Tuple[int, int]] = None, staging: str = "fp32", deterministic: bool = False,
                  sort_in_forward: bool = False, reorder: Optional[bool] = None):
+        if staging == "fp16" and not float(eps2d) >= FP16_EPS2D_MIN:
+            raise ValueError(f"staging='fp16' needs eps2d >= {FP16_EPS2D_MIN} (got {eps2d}): the conic of a degenerate "
+                             f"splat reaches 1/eps2d, and the half records end at 65504")
         self.lib = load_library()
         # reorder (tile-order placement, see calibrate()): True / False, or None = decide at calibration -- on when the
         # Gaussians are numerous and NOT already in a screen-coherent order (a back-projected depth frame is)

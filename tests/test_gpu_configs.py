@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 THREADS = min(os.cpu_count() or 1, 16)
 
 
-def _context_vs_c_oracle(tag, sc, V, W, H, v, max_flipped, grad_names=("means", "scales", "opacities"),
+def _context_vs_c_oracle(tag, sc, V, W, H, v, max_flipped, grad_names=("means", "scales", "opacities", "colors"),
                          with_deterministic=True):
     """RenderContext forward + backward against the C oracle on the same inputs; returns the error report."""
     from gsplatloc_amd.context import RenderContext
@@ -204,7 +204,7 @@ def test_config_S_tracker_200_iterations():
 
 def test_config_X_fp16_staged_compositing():
     """BASELINE.json configs[4]: 5 M random Gaussians, 1920x1080, "fp16 compositing" -- the compositing kernels gather
-    32-byte half-precision records (centre float32; conic, depth, opacity, colour half), transmittance and every
+    32-byte half-precision records (centre and depth float32; conic, opacity, colour half), transmittance and every
     accumulator float32.  Checked against the float64 oracle at the precision half records allow
     (11 significant bits: 3e-3 relative, stated here), and against the float32-staged HIP path."""
     from gsplatloc_amd.context import RenderContext

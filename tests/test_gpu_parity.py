@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from oracle import gsplat_oracle as G
+from tests.grad_paths import compare_grads, failing_subsets, oracle_render
 from tests.parity import POSE_GRAD_TOL, agreeing_pixels, report
 from tests.scenes import random_scene, sh_from_rgb, small_pose
 from tests.sort_variants import assert_tile_sort_ran, force_tile_sort, forced_tile_sort
@@ -531,7 +532,9 @@ def test_render_context_edge_cases(case):
 def test_fuzz_render_context_against_the_oracle(seed):
     """Randomised configurations of the fused path (render mode, SH degree, anti-aliasing, anisotropy, splat size,
     opacity range, image size, tile-row strip, record staging, deterministic mode, near plane) against float64 autograd
-    of the oracle: render, alpha, pose gradient (1e-4, flip-aware) and the summed Gaussian gradients."""
+    of the oracle -- for fp16 records the oracle that rounds what a half record holds (tests/grad_paths.py): render,
+    alpha, pose gradient (1e-4, flip-aware), every per-Gaussian gradient element by element (colours included, quats on
+    anisotropic draws; tests/grad_paths.py's bound) and the summed Gaussian gradients."""
     _gpu()
     from gsplatloc_amd.context import RenderContext
     rng = np.random.default_rng(1000 + seed)
@@ -550,27 +553,31 @@ def test_fuzz_render_context_against_the_oracle(seed):
         rows = (r0, int(rng.integers(r0 + 1, th + 1)))
     det = bool(rng.integers(0, 3) == 0)
     near = float(rng.choice([0.01, 1.5]))
-    sc = _scene32(N, W, H, sigma_px=sigma, opacity=op, aniso=bool(rng.integers(0, 2)), seed=100 + seed)
+    aniso = bool(rng.integers(0, 2))
+    staging = ["fp32", "fp16"][int(rng.integers(0, 2))]
+    sc = _scene32(N, W, H, sigma_px=sigma, opacity=op, aniso=aniso, seed=100 + seed)
     gen = torch.Generator().manual_seed(seed)
     K_sh = (sh_deg + 1) ** 2
     colors = torch.randn(N, K_sh, 3, generator=gen) * 0.4 if rgb else None
     V = torch.linalg.inv(small_pose(float(rng.uniform(0.0, 2.0)), float(rng.uniform(0.0, 0.05)), dtype=torch.float32))
-    kw = dict(sh_degree=sh_deg if rgb else None, width=W, height=H, packed=False, render_mode=mode, near_plane=near,
-              rasterize_mode="antialiased" if aa else "classic")
     names = ("means", "quats", "scales", "opacities")
     ins_o = [sc[k].double().clone().requires_grad_() for k in names]
     col_o = colors.double().clone().requires_grad_() if rgb else sc["rgbs"].double()
-    Vo = V.double()[None].clone().requires_grad_()
-    r_o, a_o, _ = G.rasterization(*ins_o, col_o, Vo, sc["K"].double()[None], **kw)
+    Vo = V.double().clone().requires_grad_()
+    r_o, a_o = oracle_render(*ins_o, col_o, Vo, sc["K"].double(), W, H, mode, sh_degree=sh_deg if rgb else None,
+                             antialiased=aa, near_plane=near, half=staging == "fp16")
+    r_o, a_o = r_o[None], a_o[None]
     rc = RenderContext(N, W, H, mode, sh_degree=sh_deg if rgb else None, K_sh=K_sh if rgb else 0, device=DEV,
-                       near_plane=near, antialiased=aa, tile_rows=rows, deterministic=det, full_grads=True)
+                       near_plane=near, antialiased=aa, tile_rows=rows, deterministic=det, full_grads=True,
+                       staging=staging)
     dev_in = [sc[k].to(DEV).contiguous() for k in names] + [colors.to(DEV).contiguous() if rgb else None,
                                                              V.to(DEV).contiguous(), sc["K"].to(DEV).contiguous()]
     rc.calibrate(*dev_in)
     render, alphas = rc.forward(*dev_in)
     rc.check_capacity()
     y0, y1 = (0, H) if rows is None else (rows[0] * 16, min(rows[1] * 16, H))
-    tag = f"fuzz {seed}: {mode} sh={sh_deg} aa={aa} sigma={sigma} {W}x{H} N={N} rows={rows} det={det} near={near}"
+    tag = (f"fuzz {seed}: {mode} sh={sh_deg} aa={aa} sigma={sigma} {W}x{H} N={N} rows={rows} det={det} near={near} "
+           f"aniso={aniso} {staging}")
     mostly_close(render[None, y0:y1], r_o[:, y0:y1], rtol=1e-4, atol=2e-5, max_bad_frac=5e-3, what=tag + " render")
     mostly_close(alphas[None, y0:y1], a_o[:, y0:y1], rtol=1e-4, atol=2e-5, max_bad_frac=5e-3, what=tag + " alpha")
     ok = agreeing_pixels(render[None], alphas[None], r_o, a_o)
@@ -583,7 +590,7 @@ def test_fuzz_render_context_against_the_oracle(seed):
         return
     loss_o.backward()
     g = rc.backward(v_c[0].float().to(DEV).contiguous(), v_a[0].float().to(DEV).contiguous())
-    want = Vo.grad[0, :3]
+    want = Vo.grad[:3]
     if float(want.abs().max()) > 0:
         err = rel_inf(g["viewmat"][:3], want)
         report(tag, 1.0 - ok[:, y0:y1].double().mean().item(), v_viewmat=err)
@@ -591,6 +598,16 @@ def test_fuzz_render_context_against_the_oracle(seed):
     for nm, o_t in zip(names, ins_o):
         if o_t.grad is not None and float(o_t.grad.abs().max()) > 0 and nm != "quats":
             assert rel_inf(g[nm].sum(0), o_t.grad.sum(0)) < 2e-3, (tag, nm)
+    # element by element, per Gaussian (isotropic draws: v_quats is rounding noise of a cancelling sum)
+    per = {nm: o_t.grad for nm, o_t in zip(names, ins_o)
+           if o_t.grad is not None and float(o_t.grad.abs().max()) > 0 and (nm != "quats" or aniso)}
+    if rgb and col_o.grad is not None and float(col_o.grad.abs().max()) > 0:
+        per["colors"] = col_o.grad
+    if per:
+        worst, counts, _ = compare_grads({nm: g[nm] for nm in per}, per, {"all": torch.arange(N)})
+        report(tag + " per Gaussian", 1.0 - ok[:, y0:y1].double().mean().item(),
+               outliers=float(counts["all"][0]), **{"v_" + k: x for k, x in worst.items()})
+        assert not failing_subsets(counts), (tag, "outlier Gaussians (count, size, allowed)", counts, worst)
 
 
 @pytest.mark.parametrize("mode,full", [("RGB+ED", True), ("ED", False), ("RGB", True)])

@@ -348,3 +348,14 @@ def test_graph_tracker_guard_band_violation_on_one_rank_rebuckets_all(tmp_path):
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
     assert "rank 0 ok" in res.stdout and "rank 1 ok" in res.stdout
+
+
+def test_fp16_staging_refuses_an_eps2d_whose_conic_leaves_the_half_range():
+    """A degenerate splat's conic reaches 1/eps2d, and a half record ends at 65504: refused before any allocation."""
+    import gsplatloc_amd.context as CX
+
+    assert 1.0 / CX.FP16_EPS2D_MIN < 65504.0
+    for eps2d in (1e-5, 1.5e-5, 0.0, float("nan")):
+        with pytest.raises(ValueError, match="eps2d"):
+            CX.RenderContext(16, 32, 32, "RGB+ED", device="cpu", staging="fp16", eps2d=eps2d)
+

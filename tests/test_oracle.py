@@ -175,3 +175,31 @@ def test_zero_pose_gradient_at_gt_and_convergence():
     res = T.track_frame(sc["means"], sc["scales"], sc["rgbs"], gt[..., 3:4], sc["K"], 64, 48,
                         init_c2w=small_pose(0.3, 0.01), gt_c2w=I4, max_steps=60, min_step=5)
     assert min(res.losses) < 0.9 * res.losses[0]
+
+
+@pytest.mark.parametrize("mode,sh_degree,aa", [("RGB+ED", 1, False), ("RGB", None, True), ("D", None, False),
+                                               ("RGB+D", 3, True), ("ED", None, False)])
+def test_half_record_oracle_without_rounding_is_the_oracle(mode, sh_degree, aa):
+    """tests/grad_paths.oracle_render (the oracle's stages, with the fp16 record's rounding when asked) gives
+    G.rasterization's render, alpha and gradients bit for bit when it does not round, and rounding moves them."""
+    from tests.grad_paths import oracle_render
+
+    sc = random_scene(300, 40, 28, seed=3, sigma_px=1.5, aniso=True, opacity=(0.2, 0.9))
+    g = torch.Generator().manual_seed(5)
+    colors = torch.randn(300, (sh_degree + 1) ** 2, 3, generator=g, dtype=torch.float64) if sh_degree else sc["rgbs"]
+    V = torch.linalg.inv(small_pose(1.0, 0.02))
+    outs = []
+    for which in ("oracle", "plain", "half"):
+        ins = [t.clone().requires_grad_() for t in (sc["means"], sc["quats"], sc["scales"], sc["opacities"], colors, V)]
+        if which == "oracle":
+            r, a, _ = G.rasterization(*ins[:5], ins[5][None], sc["K"][None], 40, 28, sh_degree=sh_degree,
+                                      render_mode=mode, rasterize_mode="antialiased" if aa else "classic")
+            r, a = r[0], a[0]
+        else:
+            r, a = oracle_render(*ins, sc["K"], 40, 28, mode, sh_degree=sh_degree, antialiased=aa, half=which == "half")
+        (r.sum() + a.sum()).backward()
+        outs.append([r.detach(), a.detach()] + [t.grad for t in ins])
+    for x, y in zip(outs[0], outs[1]):
+        assert (x is None and y is None) or torch.equal(x, y)
+    assert not torch.equal(outs[0][0], outs[2][0])
+
