@@ -29,6 +29,16 @@ _SIGNATURES = {
     "gsl_project_bwd_ws_bytes": (c_size_t, [c_int]),
     "gsl_project_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P, P, P, P, P, P, P,
                                 P, c_size_t, P]),
+    "gsl_project_packed_ws_bytes": (c_size_t, [c_int, c_int]),
+    "gsl_project_packed_count": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
+                                         P, P, c_size_t, P]),
+    "gsl_project_packed_fill": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
+                                        c_int64, P, P, P, P, P, P, P, P, c_size_t, P]),
+    "gsl_project_packed_bwd_ws_bytes": (c_size_t, [c_int64, c_int]),
+    "gsl_project_packed_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_int64, P, P, P, P, P, P, P,
+                                       P, c_int, P, P, P, P, P, c_size_t, P]),
+    "gsl_gather_rows": (c_int, [P, c_int64, c_int, P, c_int64, P, P]),
+    "gsl_scatter_add_rows": (c_int, [P, P, c_int64, c_int, c_int64, c_int, P, P]),
     "gsl_sh_fwd": (c_int, [c_int, P, P, P, c_int, c_int, P, P]),
     "gsl_sh_bwd": (c_int, [c_int, P, P, P, c_int, c_int, P, P, P, P]),
     "gsl_isect_ws_bytes": (c_size_t, [c_int]),

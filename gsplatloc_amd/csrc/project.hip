@@ -17,38 +17,7 @@ __global__ __launch_bounds__(256) void k_project_fwd(
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   Cam cam = load_cam(V, K);
-  ProjMid p;
-  float q[4], s[3];
-  load_gaussian(means, quats, scales, i, cam, p, q, s);
-  ProjOut o;
-  o.radius = 0; o.mx = o.my = o.depth = o.ca = o.cb = o.cc = o.comp = 0.f;
-  if (p.mc[2] >= near_plane && p.mc[2] <= far_plane) {
-    p.covar = quat_scale_to_covar(q, s);
-    p.covar_c = mul_bt(mul(cam.R, p.covar), cam.R);
-    persp_mid(cam, W, H, p);
-    float a, b, c;
-    cov2d_from(p.J, p.covar_c, a, b, c);
-    float det_orig = a * c - b * b;
-    a += eps2d;
-    c += eps2d;
-    float det = a * c - b * b;
-    if (det > 0.f) {
-      float bb = 0.5f * (a + c);
-      float v1 = bb + sqrtf(fmaxf(0.01f, bb * bb - det));
-      float radius = ceilf(3.f * sqrtf(v1));
-      float mx = cam.fx * p.mc[0] * p.rz + cam.cx;
-      float my = cam.fy * p.mc[1] * p.rz + cam.cy;
-      bool ok = radius > radius_clip;
-      ok = ok && !(mx + radius <= 0.f || mx - radius >= (float)W || my + radius <= 0.f || my - radius >= (float)H);
-      if (ok) {
-        float inv = 1.f / det;
-        o.radius = (int)radius;
-        o.mx = mx; o.my = my; o.depth = p.mc[2];
-        o.ca = c * inv; o.cb = -b * inv; o.cc = a * inv;
-        o.comp = sqrtf(fmaxf(0.f, det_orig / det));
-      }
-    }
-  }
+  ProjOut o = project_pair(means, quats, scales, i, cam, W, H, eps2d, near_plane, far_plane, radius_clip);
   radii[i] = o.radius;
   means2d[2 * (size_t)i] = o.mx;
   means2d[2 * (size_t)i + 1] = o.my;

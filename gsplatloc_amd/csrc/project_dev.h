@@ -66,6 +66,47 @@ __device__ __forceinline__ void load_gaussian(const float* __restrict__ means, c
   for (int k = 0; k < 3; ++k) s[k] = scales[3 * (size_t)i + k];
 }
 
+// Forward of one (camera, Gaussian) pair: cull and the projected quantities.  radius == 0 <=> culled, and then every
+// other field is 0.  The dense kernel (project.hip) and the packed one (project_packed.hip) both call this, so a kept
+// pair has the same bits on either path.
+__device__ __forceinline__ ProjOut project_pair(const float* __restrict__ means, const float* __restrict__ quats,
+                                                const float* __restrict__ scales, int i, const Cam& cam, int W, int H,
+                                                float eps2d, float near_plane, float far_plane, float radius_clip) {
+  ProjMid p;
+  float q[4], s[3];
+  load_gaussian(means, quats, scales, i, cam, p, q, s);
+  ProjOut o;
+  o.radius = 0; o.mx = o.my = o.depth = o.ca = o.cb = o.cc = o.comp = 0.f;
+  if (p.mc[2] >= near_plane && p.mc[2] <= far_plane) {
+    p.covar = quat_scale_to_covar(q, s);
+    p.covar_c = mul_bt(mul(cam.R, p.covar), cam.R);
+    persp_mid(cam, W, H, p);
+    float a, b, c;
+    cov2d_from(p.J, p.covar_c, a, b, c);
+    float det_orig = a * c - b * b;
+    a += eps2d;
+    c += eps2d;
+    float det = a * c - b * b;
+    if (det > 0.f) {
+      float bb = 0.5f * (a + c);
+      float v1 = bb + sqrtf(fmaxf(0.01f, bb * bb - det));
+      float radius = ceilf(3.f * sqrtf(v1));
+      float mx = cam.fx * p.mc[0] * p.rz + cam.cx;
+      float my = cam.fy * p.mc[1] * p.rz + cam.cy;
+      bool ok = radius > radius_clip;
+      ok = ok && !(mx + radius <= 0.f || mx - radius >= (float)W || my + radius <= 0.f || my - radius >= (float)H);
+      if (ok) {
+        float inv = 1.f / det;
+        o.radius = (int)radius;
+        o.mx = mx; o.my = my; o.depth = p.mc[2];
+        o.ca = c * inv; o.cb = -b * inv; o.cc = a * inv;
+        o.comp = sqrtf(fmaxf(0.f, det_orig / det));
+      }
+    }
+  }
+  return o;
+}
+
 // vjp wrt the unit quaternion components of a rotation matrix gradient vR (row-major).
 __device__ __forceinline__ void quat_vjp(const float qin[4], const M3& vR, float vq[4]) {
   float inv = rsqrtf(qin[0] * qin[0] + qin[1] * qin[1] + qin[2] * qin[2] + qin[3] * qin[3]);

@@ -101,6 +101,118 @@ class _FullyFusedProjection(torch.autograd.Function):
                 v_viewmats, None, None, None, None, None, None, None, None)
 
 
+class _PackedProjection(torch.autograd.Function):
+    """Packed projection: one row per (camera, Gaussian) pair with radii > 0, in camera-major order
+    (csrc/project_packed.hip).  With ``sparse_grad`` the gradients of means / quats / scales are sparse COO tensors
+    over the visible rows."""
+
+    @staticmethod
+    def forward(ctx, means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip,
+                calc_compensations, sparse_grad):
+        lib = load_library()
+        C, N = viewmats.shape[0], means.shape[0]
+        dev = means.device
+        st = current_stream()
+        ws_bytes = lib.gsl_project_packed_ws_bytes(C, N)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        nnz_dev = torch.empty(1, dtype=torch.int32, device=dev)
+        args = (ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), C, N, width, height, eps2d, near_plane,
+                far_plane, radius_clip)
+        check(lib.gsl_project_packed_count(*args, ptr(nnz_dev), ptr(ws), ws_bytes, st), "gsl_project_packed_count")
+        nnz = int(nnz_dev.item())  # host sync: output sizes depend on it (as in gsplat)
+        camera_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
+        gaussian_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
+        radii = torch.empty(nnz, dtype=torch.int32, device=dev)
+        means2d = torch.empty(nnz, 2, dtype=torch.float32, device=dev)
+        depths = torch.empty(nnz, dtype=torch.float32, device=dev)
+        conics = torch.empty(nnz, 3, dtype=torch.float32, device=dev)
+        comps = torch.empty(nnz, dtype=torch.float32, device=dev) if calc_compensations else None
+        check(lib.gsl_project_packed_fill(*args, nnz, ptr(camera_ids), ptr(gaussian_ids), ptr(radii), ptr(means2d),
+                                          ptr(depths), ptr(conics), ptr(comps), ptr(ws), ws_bytes, st),
+              "gsl_project_packed_fill")
+        ctx.save_for_backward(means, quats, scales, viewmats, Ks, camera_ids, gaussian_ids, conics,
+                              comps if comps is not None else torch.empty(0, device=dev))
+        ctx.dims = (width, height, eps2d, calc_compensations, sparse_grad)
+        ctx.mark_non_differentiable(camera_ids, gaussian_ids, radii)
+        return camera_ids, gaussian_ids, radii, means2d, depths, conics, comps
+
+    @staticmethod
+    def backward(ctx, v_camera_ids, v_gaussian_ids, v_radii, v_means2d, v_depths, v_conics, v_comps):
+        lib = load_library()
+        means, quats, scales, viewmats, Ks, camera_ids, gaussian_ids, conics, comps = ctx.saved_tensors
+        width, height, eps2d, calc_comp, sparse_grad = ctx.dims
+        C, N = viewmats.shape[0], means.shape[0]
+        nnz = camera_ids.numel()
+        dev = means.device
+        ni = ctx.needs_input_grad
+        need_full = any(ni[:3])
+        v_means2d, v_depths, v_conics = v_means2d.contiguous(), v_depths.contiguous(), v_conics.contiguous()
+        v_comps = v_comps.contiguous() if (calc_comp and v_comps is not None) else None
+        v_means = v_quats = v_scales = None
+        if need_full:
+            rows = nnz if sparse_grad else N
+            v_means = torch.empty(rows, 3, dtype=torch.float32, device=dev)
+            v_quats = torch.empty(rows, 4, dtype=torch.float32, device=dev)
+            v_scales = torch.empty(rows, 3, dtype=torch.float32, device=dev)
+        v_viewmats = torch.empty(C, 4, 4, dtype=torch.float32, device=dev) if ni[3] else None
+        ws_bytes = lib.gsl_project_packed_bwd_ws_bytes(nnz, C)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(lib.gsl_project_packed_bwd(
+            ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), C, N, width, height, eps2d, nnz,
+            ptr(camera_ids), ptr(gaussian_ids), ptr(conics), ptr(comps) if calc_comp else None, ptr(v_means2d),
+            ptr(v_depths), ptr(v_conics), ptr(v_comps), int(sparse_grad), ptr(v_means), ptr(v_quats), ptr(v_scales),
+            ptr(v_viewmats), ptr(ws), ws_bytes, current_stream()), "gsl_project_packed_bwd")
+        if need_full and sparse_grad:
+            # a Gaussian has one row per camera that sees it: the indices are unique (coalesced) for one camera only
+            idx = gaussian_ids[None]
+            v_means = torch.sparse_coo_tensor(idx, v_means, size=means.shape, is_coalesced=(C == 1))
+            v_quats = torch.sparse_coo_tensor(idx, v_quats, size=quats.shape, is_coalesced=(C == 1))
+            v_scales = torch.sparse_coo_tensor(idx, v_scales, size=scales.shape, is_coalesced=(C == 1))
+            if C == 1:
+                # autograd takes a sparse gradient nobody else holds by a shallow copy that forgets the coalesced
+                # flag; a second reference makes it clone the tensor, and the clone keeps the flag
+                ctx.coalesced_grads = (v_means, v_quats, v_scales)
+        return (v_means if ni[0] else None, v_quats if ni[1] else None, v_scales if ni[2] else None, v_viewmats,
+                None, None, None, None, None, None, None, None, None)
+
+
+class _GatherRows(torch.autograd.Function):
+    """src[ids] for the packed rows and its vjp on the HIP kernels (torch's indexing backward serialises on repeated
+    indices: a third of a second for a million rows of one camera's position)."""
+
+    @staticmethod
+    def forward(ctx, src, ids, unique):
+        lib = load_library()
+        n_src, nnz = src.shape[0], ids.numel()
+        D = int(math.prod(src.shape[1:]))  # floats per row
+        dst = torch.empty((nnz,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
+        if D:
+            check(lib.gsl_gather_rows(ptr(src), n_src, D, ptr(ids), nnz, ptr(dst), current_stream()), "gsl_gather_rows")
+        ctx.save_for_backward(ids)
+        ctx.meta = (tuple(src.shape), D, unique)
+        return dst
+
+    @staticmethod
+    def backward(ctx, v_rows):
+        lib = load_library()
+        (ids,) = ctx.saved_tensors
+        shape, D, unique = ctx.meta
+        v_src = torch.empty(shape, dtype=torch.float32, device=v_rows.device)
+        if D:
+            check(lib.gsl_scatter_add_rows(ptr(v_rows.contiguous()), ptr(ids), ids.numel(), D, shape[0], int(unique),
+                                           ptr(v_src), current_stream()), "gsl_scatter_add_rows")
+        return v_src, None, None
+
+
+def gather_rows(src: Tensor, ids: Tensor, unique: bool = False) -> Tensor:
+    """``src[ids]`` for int64 ``ids`` [nnz] and float32 ``src`` [n, ...] on the device: the rows a packed pipeline
+    needs of a per-Gaussian (``gaussian_ids``) or per-camera (``camera_ids``) tensor.  ``unique``: no id occurs twice
+    (one camera's ``gaussian_ids``), the backward then stores instead of adding atomically."""
+    assert ids.dim() == 1 and ids.dtype == torch.int64, (ids.shape, ids.dtype)
+    assert src.dim() >= 1 and src.shape[0] < 2 ** 31, src.shape
+    return _GatherRows.apply(_dev_f32(src, "src"), ids.contiguous(), bool(unique))
+
+
 def fully_fused_projection(
     means: Tensor,  # [N, 3]
     covars: Optional[Tensor],  # [N, 6] or None
@@ -119,7 +231,13 @@ def fully_fused_projection(
     calc_compensations: bool = False,
 ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Optional[Tensor]]:
     """Project Gaussians to the image plane: radii [C,N] int32, means2d [C,N,2],
-    depths [C,N], conics [C,N,3], compensations [C,N] | None."""
+    depths [C,N], conics [C,N,3], compensations [C,N] | None.
+
+    ``packed=True`` returns (camera_ids [nnz] int64, gaussian_ids [nnz] int64, radii [nnz], means2d [nnz,2],
+    depths [nnz], conics [nnz,3], compensations [nnz] | None): one row per (camera, Gaussian) pair with radii > 0, in
+    ascending order of camera * N + gaussian, each row holding the bits of the dense call's.  With ``sparse_grad`` (packed
+    only) the gradients of means / quats / scales are sparse COO tensors indexed by ``gaussian_ids`` (coalesced for one
+    camera); the gradient of viewmats stays dense."""
     C = viewmats.size(0)
     N = means.size(0)
     assert means.size() == (N, 3), means.size()
@@ -131,12 +249,14 @@ def fully_fused_projection(
     assert scales is not None, "covars or scales is required"
     assert quats.size() == (N, 4), quats.size()
     assert scales.size() == (N, 3), scales.size()
-    if packed:
-        raise NotImplementedError("packed=True is not supported (GsplatLoc runs packed=False, model.py:123)")
-    if sparse_grad:
+    if sparse_grad and not packed:
         raise NotImplementedError("sparse_grad requires packed=True")
     means, quats, scales = _dev_f32(means, "means"), _dev_f32(quats, "quats"), _dev_f32(scales, "scales")
     viewmats, Ks = _dev_f32(viewmats, "viewmats"), _dev_f32(Ks, "Ks")
+    if packed:
+        return _PackedProjection.apply(means, quats, scales, viewmats, Ks, int(width), int(height), float(eps2d),
+                                       float(near_plane), float(far_plane), float(radius_clip),
+                                       bool(calc_compensations), bool(sparse_grad))
     return _FullyFusedProjection.apply(means, quats, scales, viewmats, Ks, int(width), int(height), float(eps2d),
                                        float(near_plane), float(far_plane), float(radius_clip),
                                        bool(calc_compensations))
@@ -211,32 +331,60 @@ def isect_tiles(
     flatten_ids [I] int32 (index into the flattened [C*N] arrays); sorted by isect_ids when
     ``sort`` (ties in Gaussian-index order, as a stable sort of the emit order gives).
 
+    ``packed=True``: means2d [nnz,2], radii [nnz], depths [nnz] are the rows of the packed projection (sorted by
+    camera; ``n_cameras``, ``camera_ids``, ``gaussian_ids`` are required), tiles_per_gauss is [nnz] and flatten_ids
+    index the packed rows.
+
     With ``sort``, every Gaussian with radii > 0 must have a depth from +0.0 to +inf (sign bit clear, not NaN):
     the per-tile sorts compare (depth bits, id) keys partly as doubles and partly as unsigned integers, which agree
     only there (include/gsloc_hip.h, gsl_tile_sort).  Anything else raises ValueError.  The projection culls z <= near,
     so its outputs always qualify."""
     if packed:
-        raise NotImplementedError("packed=True is not supported")
-    C, N, _ = means2d.shape
-    assert means2d.shape == (C, N, 2), means2d.size()
-    assert radii.shape == (C, N), radii.size()
-    assert depths.shape == (C, N), depths.size()
+        nnz = means2d.shape[0]
+        assert means2d.shape == (nnz, 2), means2d.size()
+        assert radii.shape == (nnz,), radii.size()
+        assert depths.shape == (nnz,), depths.size()
+        assert n_cameras is not None, "n_cameras is required if packed is True"
+        assert camera_ids is not None and camera_ids.shape == (nnz,), "camera_ids [nnz] is required if packed is True"
+        assert gaussian_ids is not None and gaussian_ids.shape == (nnz,), "gaussian_ids [nnz] is required if packed is True"
+        C = int(n_cameras)
+    else:
+        C, N, _ = means2d.shape
+        assert means2d.shape == (C, N, 2), means2d.size()
+        assert radii.shape == (C, N), radii.size()
+        assert depths.shape == (C, N), depths.size()
     lib = load_library()
     dev = means2d.device
     means2d, depths = _dev_f32(means2d, "means2d"), _dev_f32(depths, "depths")
     radii = radii.to(torch.int32).contiguous()
+    if packed:
+        # camera c's rows are one contiguous slice (the rows are sorted by camera): the per-camera kernels run on the
+        # slices, the slice start is the id offset
+        bounds = torch.searchsorted(camera_ids.contiguous(), torch.arange(C + 1, device=dev)).tolist()  # host sync
+        spans = [(bounds[c], bounds[c + 1] - bounds[c]) for c in range(C)]
+        out_shape = (nnz,)
+    else:
+        spans = [(c * N, N) for c in range(C)]
+        out_shape = (C, N)
+        means2d, depths, radii = means2d.view(C * N, 2), depths.view(C * N), radii.view(C * N)
     n_tiles = tile_width * tile_height
     nbits = tile_n_bits(n_tiles)
     st = current_stream()
-    tiles_per_gauss = torch.empty(C, N, dtype=torch.int32, device=dev)
+    tiles_per_gauss = torch.empty(radii.shape[0], dtype=torch.int32, device=dev)
     ws_bytes = lib.gsl_isect_ws_bytes(n_tiles)
     wss = [torch.empty(ws_bytes, dtype=torch.uint8, device=dev) for _ in range(C)]
     offs = torch.empty(C, n_tiles + 1, dtype=torch.int32, device=dev)
     counts = torch.empty(C, dtype=torch.int32, device=dev)
+
+    def rows(t, c):  # pointer to camera c's first row (NULL for a camera without rows)
+        lo, n = spans[c]
+        return ptr(t[lo:]) if n else None
+
     for c in range(C):
-        check(lib.gsl_isect_count(ptr(means2d[c]), ptr(radii[c]), N, tile_size, tile_width, tile_height, 0,
-                                  tile_height, ptr(tiles_per_gauss[c]), ptr(offs[c]), ptr(counts[c:c + 1]),
+        check(lib.gsl_isect_count(rows(means2d, c), rows(radii, c), spans[c][1], tile_size, tile_width, tile_height, 0,
+                                  tile_height, rows(tiles_per_gauss, c), ptr(offs[c]), ptr(counts[c:c + 1]),
                                   ptr(wss[c]), ws_bytes, st), "gsl_isect_count")
+    tiles_per_gauss = tiles_per_gauss.view(out_shape)
     if sort:
         # visible Gaussians whose depth the sort cannot order: sign bit set (negative, -0.0) or NaN (> +inf's bits)
         bits = depths.view(torch.int32)
@@ -258,20 +406,21 @@ def isect_tiles(
         for c in range(C):
             n = per_cam[c]
             if n:
-                check(lib.gsl_isect_fill(ptr(means2d[c]), ptr(radii[c]), ptr(depths[c]), N, tile_size, tile_width,
-                                         tile_height, 0, tile_height, c, nbits, ptr(offs[c]), n, ptr(keys),
+                check(lib.gsl_isect_fill(rows(means2d, c), rows(radii, c), rows(depths, c), spans[c][1], tile_size,
+                                         tile_width, tile_height, 0, tile_height, c, nbits, ptr(offs[c]), n, ptr(keys),
                                          ptr(flatten_ids[base:]), ptr(isect_ids[base:]), ptr(wss[c]), ws_bytes, st),
                       "gsl_isect_fill")
-                if c:
-                    flatten_ids[base:base + n] += c * N
+                if spans[c][0]:
+                    flatten_ids[base:base + n] += spans[c][0]
             base += n
     else:
-        cum = torch.cumsum(tiles_per_gauss.to(torch.int64), dim=1).contiguous()
         for c in range(C):
             n = per_cam[c]
             if n:
-                check(lib.gsl_isect_emit(ptr(means2d[c]), ptr(radii[c]), ptr(depths[c]), ptr(cum[c]), N, tile_size,
-                                         tile_width, tile_height, c, nbits, c * N, ptr(isect_ids[base:]),
+                lo, m = spans[c]
+                cum = torch.cumsum(tiles_per_gauss.view(-1)[lo:lo + m].to(torch.int64), dim=0)
+                check(lib.gsl_isect_emit(rows(means2d, c), rows(radii, c), rows(depths, c), ptr(cum), m, tile_size,
+                                         tile_width, tile_height, c, nbits, lo, ptr(isect_ids[base:]),
                                          ptr(flatten_ids[base:]), st), "gsl_isect_emit")
             base += n
     return tiles_per_gauss, isect_ids, flatten_ids
@@ -306,8 +455,8 @@ class _RasterizeToPixels(torch.autograd.Function):
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, width, height, tile_size, isect_offsets,
                 flatten_ids, absgrad=False):
         lib = load_library()
-        C, N, D = colors.shape
-        th, tw = isect_offsets.shape[1:]
+        D = colors.shape[-1]  # per-Gaussian arrays: [C,N,.] or, packed, [nnz,.]; flatten_ids index their rows
+        C, th, tw = isect_offsets.shape
         dev = means2d.device
         n_tiles = th * tw
         n_isects = flatten_ids.numel()
@@ -326,7 +475,7 @@ class _RasterizeToPixels(torch.autograd.Function):
         ctx.save_for_backward(means2d, conics, colors, opacities,
                               backgrounds if backgrounds is not None else torch.empty(0, device=dev), offs_ext,
                               flatten_ids, render_alphas, last_ids)
-        ctx.dims = (width, height, tile_size, tw, th, backgrounds is not None)
+        ctx.dims = (width, height, tile_size, tw, th, C, backgrounds is not None)
         ctx.absgrad = absgrad
         return render_colors, render_alphas
 
@@ -335,8 +484,9 @@ class _RasterizeToPixels(torch.autograd.Function):
         lib = load_library()
         (means2d, conics, colors, opacities, backgrounds, offs_ext, flatten_ids, render_alphas,
          last_ids) = ctx.saved_tensors
-        width, height, tile_size, tw, th, has_bg = ctx.dims
-        C, N, D = colors.shape
+        width, height, tile_size, tw, th, C, has_bg = ctx.dims
+        D = colors.shape[-1]
+        n_rows = opacities.numel()
         n_tiles = th * tw
         n_isects = flatten_ids.numel()
         v_render_colors = v_render_colors.contiguous()
@@ -346,7 +496,7 @@ class _RasterizeToPixels(torch.autograd.Function):
         v_colors = torch.empty_like(colors)
         v_opacities = torch.empty_like(opacities)
         st = current_stream()
-        vacc = torch.zeros(lib.gsl_vacc_bytes(C * N, D) // 4, dtype=torch.float32, device=means2d.device)
+        vacc = torch.zeros(lib.gsl_vacc_bytes(n_rows, D) // 4, dtype=torch.float32, device=means2d.device)
         if n_isects:
             for c in range(C):
                 check(lib.gsl_rasterize_bwd(
@@ -354,12 +504,12 @@ class _RasterizeToPixels(torch.autograd.Function):
                     D, width, height, tile_size, tw, th, 0, th, ptr(offs_ext[c * n_tiles:]), ptr(flatten_ids),
                     n_isects, ptr(render_alphas[c]), ptr(last_ids[c]), ptr(v_render_colors[c]),
                     ptr(v_render_alphas[c]), ptr(vacc), st), "gsl_rasterize_bwd")
-        check(lib.gsl_vacc_unpack(ptr(vacc), C * N, D, ptr(v_means2d), ptr(v_conics), ptr(v_colors),
+        check(lib.gsl_vacc_unpack(ptr(vacc), n_rows, D, ptr(v_means2d), ptr(v_conics), ptr(v_colors),
                                   ptr(v_opacities), st), "gsl_vacc_unpack")
         if ctx.absgrad:
             # sum over pixels of |per-pixel v_means2d| (gsplat's means2d.absgrad), set on the caller's means2d: the
             # compositing backward's sums cannot give it (|.| of a sum), csrc/absgrad.hip walks the pixels once more
-            absgrad = torch.zeros(C, N, 2, dtype=torch.float32, device=means2d.device)
+            absgrad = torch.zeros_like(means2d)
             for c in range(C):
                 check(lib.gsl_rasterize_absgrad(
                     ptr(means2d), ptr(conics), ptr(colors), ptr(opacities), ptr(backgrounds[c]) if has_bg else None,
@@ -391,16 +541,25 @@ def rasterize_to_pixels(
     """Rasterize to pixels: render_colors [C,H,W,channels], render_alphas [C,H,W,1].
 
     ``absgrad``: the backward also sets ``means2d.absgrad`` [C,N,2], the per-component sum over pixels of
-    |d L_p / d means2d| (gsplat's densification statistic)."""
-    if packed:
-        raise NotImplementedError("packed=True is not supported")
+    |d L_p / d means2d| (gsplat's densification statistic).
+
+    ``packed=True``: means2d [nnz,2], conics [nnz,3], colors [nnz,channels], opacities [nnz] are packed rows and
+    flatten_ids index them; ``means2d.absgrad`` is then [nnz,2]."""
     if masks is not None:
         raise NotImplementedError("tile masks are not supported")
-    C, N = means2d.shape[:2]
-    assert means2d.shape == (C, N, 2), means2d.shape
-    assert conics.shape == (C, N, 3), conics.shape
-    assert colors.shape[:2] == (C, N), colors.shape
-    assert opacities.shape == (C, N), opacities.shape
+    C = isect_offsets.size(0)
+    if packed:
+        nnz = means2d.size(0)
+        assert means2d.shape == (nnz, 2), means2d.shape
+        assert conics.shape == (nnz, 3), conics.shape
+        assert colors.shape[0] == nnz and colors.dim() == 2, colors.shape
+        assert opacities.shape == (nnz,), opacities.shape
+    else:
+        N = means2d.size(1)
+        assert means2d.shape == (C, N, 2), means2d.shape
+        assert conics.shape == (C, N, 3), conics.shape
+        assert colors.shape[:2] == (C, N), colors.shape
+        assert opacities.shape == (C, N), opacities.shape
     if backgrounds is not None:
         assert backgrounds.shape == (C, colors.shape[-1]), backgrounds.shape
         backgrounds = _dev_f32(backgrounds, "backgrounds")

@@ -20,6 +20,7 @@ import os
 from .fused import cached_rasterization, fused_absgrad_rasterization, fused_rasterization, fused_supported
 from .ops import (
     fully_fused_projection,
+    gather_rows,
     isect_offset_encode,
     isect_tiles,
     rasterize_to_pixels,
@@ -61,8 +62,24 @@ def rasterization(
     depth by alpha ("expected depth").
 
     ``packed`` only changes gsplat's internal memory layout, never the rendered
-    result; this implementation always computes densely and returns the dense
-    ([C,N,...]) meta tensors.
+    result.  By default this implementation computes densely and returns the dense
+    ([C,N,...]) meta tensors whatever ``packed`` says.  The packed pipeline -- packed
+    projection (csrc/project_packed.hip), features and opacities gathered by
+    ``gaussian_ids``, packed binning, compositing over the nnz visible (camera,
+    Gaussian) rows -- runs when ``sparse_grad=True`` (which requires ``packed=True``,
+    as in gsplat), or when ``packed=True`` and the environment has ``GSLOC_PACKED=1``
+    (dense gradients).  It is the staged path (any C, backgrounds, channel chunks,
+    every render mode, antialiased, absgrad), never the fused one, and returns
+    gsplat's packed meta: ``camera_ids`` / ``gaussian_ids`` [nnz] int64 and ``radii``,
+    ``means2d``, ``depths``, ``conics``, ``opacities``, ``tiles_per_gauss`` of length nnz,
+    rows in ascending order of camera * N + gaussian.  With ``sparse_grad`` the
+    gradients that the projection gives means / quats / scales are sparse COO tensors
+    over the visible rows (``torch.optim.SparseAdam``); a gradient that reaches the
+    same tensor through a gather (``means`` through the SH view directions) is dense,
+    and autograd's sum of the two is dense, as with gsplat.
+    Environment switches: ``GSLOC_DISABLE_FUSED=1`` (staged path even where the fused
+    one applies), ``GSLOC_DROPIN_CACHE=0`` (no cached context on the fused path),
+    ``GSLOC_PACKED=1`` (above).
 
     ``meta["means2d"]`` [C,N,2]: with ``absgrad=False`` on the fused one-camera
     path it is a detached view of the projection records (no ``.grad``); on the
@@ -93,7 +110,8 @@ def rasterization(
     if ortho:
         raise NotImplementedError("orthographic cameras are not supported")
     if sparse_grad:
-        raise NotImplementedError("sparse_grad is not supported (GsplatLoc: sparse_grad=False, model.py:122)")
+        assert packed, "sparse_grad requires packed=True"
+    use_packed = sparse_grad or (packed and os.environ.get("GSLOC_PACKED", "0") == "1")
 
     if sh_degree is None:  # colours are final values: [N, D] shared by the cameras, or [C, N, D]
         assert (colors.dim() == 2 and colors.shape[0] == N) or (
@@ -103,7 +121,7 @@ def rasterization(
             colors.dim() == 4 and colors.shape[:2] == (C, N) and colors.shape[3] == 3), colors.shape
         assert (sh_degree + 1) ** 2 <= colors.shape[-2], colors.shape
 
-    fused = os.environ.get("GSLOC_DISABLE_FUSED", "0") != "1" and fused_supported(
+    fused = not use_packed and os.environ.get("GSLOC_DISABLE_FUSED", "0") != "1" and fused_supported(
         N, C, colors, sh_degree, width, height, tile_size, backgrounds, render_mode)
     if absgrad and not fused:
         n_feat = (colors.shape[-1] if sh_degree is None else 3) if render_mode.startswith("RGB") else 0
@@ -135,19 +153,39 @@ def rasterization(
     # chunks of that many channels, as gsplat does; every chunk yields the same alphas, the first one's are returned.
     want_depth = render_mode in ("D", "ED", "RGB+D", "RGB+ED")
     want_rgb = render_mode.startswith("RGB")
-    radii, means2d, depths, conics, compensations = fully_fused_projection(
-        means, None, quats, scales, viewmats, Ks, width, height, eps2d=eps2d, packed=False, near_plane=near_plane,
-        far_plane=far_plane, radius_clip=radius_clip, sparse_grad=False,
-        calc_compensations=(rasterize_mode == "antialiased"))
-    opac = opacities[None].expand(C, N)
+    camera_ids = gaussian_ids = None
+    if use_packed:
+        # one row per visible (camera, Gaussian) pair; everything below is [nnz, ...]
+        camera_ids, gaussian_ids, radii, means2d, depths, conics, compensations = fully_fused_projection(
+            means, None, quats, scales, viewmats, Ks, width, height, eps2d=eps2d, packed=True, near_plane=near_plane,
+            far_plane=far_plane, radius_clip=radius_clip, sparse_grad=sparse_grad,
+            calc_compensations=(rasterize_mode == "antialiased"))
+        one = C == 1  # then no Gaussian has two rows
+        opac = gather_rows(opacities, gaussian_ids, unique=one)
+    else:
+        radii, means2d, depths, conics, compensations = fully_fused_projection(
+            means, None, quats, scales, viewmats, Ks, width, height, eps2d=eps2d, packed=False, near_plane=near_plane,
+            far_plane=far_plane, radius_clip=radius_clip, sparse_grad=False,
+            calc_compensations=(rasterize_mode == "antialiased"))
+        opac = opacities[None].expand(C, N)
     if compensations is not None:  # "antialiased": opacity scaled by sqrt(det Sigma / det(Sigma + eps2d I))
         opac = opac * compensations
     opac = opac.contiguous()
 
-    # per-camera features [C, N, D]: RGB (direct, or SH evaluated along the view direction, shifted by 0.5 and
-    # clamped at 0 as the CUDA backends do), then the camera-space depth as the last channel
+    # per-camera features [C, N, D] ([nnz, D] packed): RGB (direct, or SH evaluated along the view direction, shifted
+    # by 0.5 and clamped at 0 as the CUDA backends do), then the camera-space depth as the last channel
     feats = []
-    if want_rgb:
+    if want_rgb and use_packed:
+        if colors.dim() == (3 if sh_degree is None else 4):  # per camera: row camera * N + gaussian of [C*N, ...]
+            rgb = gather_rows(colors.reshape(C * N, *colors.shape[2:]), camera_ids * N + gaussian_ids, unique=True)
+        else:
+            rgb = gather_rows(colors, gaussian_ids, unique=one)
+        if sh_degree is not None:
+            cam_pos = torch.linalg.inv(viewmats)[:, :3, 3]                      # [C, 3]
+            view_dirs = gather_rows(means, gaussian_ids, unique=one) - gather_rows(cam_pos, camera_ids)  # [nnz, 3]
+            rgb = (spherical_harmonics(sh_degree, view_dirs, rgb) + 0.5).clamp_min(0.0)
+        feats.append(rgb)
+    elif want_rgb:
         if sh_degree is None:
             rgb = colors if colors.dim() == 3 else colors[None].expand(C, N, colors.shape[-1])
         else:
@@ -165,7 +203,8 @@ def rasterization(
 
     tile_width, tile_height = -(-width // tile_size), -(-height // tile_size)
     tiles_per_gauss, isect_ids, flatten_ids = isect_tiles(means2d, radii, depths, tile_size, tile_width, tile_height,
-                                                          packed=False, n_cameras=C)
+                                                          packed=use_packed, n_cameras=C, camera_ids=camera_ids,
+                                                          gaussian_ids=gaussian_ids)
     isect_offsets = isect_offset_encode(isect_ids, C, tile_width, tile_height)
     chunk = min(int(channel_chunk), 32)
     assert chunk >= 1, channel_chunk
@@ -174,19 +213,21 @@ def rasterization(
         for lo in range(0, feats.shape[-1], chunk):
             part, part_alphas = rasterize_to_pixels(means2d, conics, feats[..., lo:lo + chunk].contiguous(), opac, width,
                                                     height, tile_size, isect_offsets, flatten_ids,
-                                                    backgrounds=None if bg is None else bg[..., lo:lo + chunk].contiguous())
+                                                    backgrounds=None if bg is None else bg[..., lo:lo + chunk].contiguous(),
+                                                    packed=use_packed)
             parts.append(part)
             render_alphas = part_alphas if render_alphas is None else render_alphas
         render_colors = torch.cat(parts, dim=-1)
     else:
         render_colors, render_alphas = rasterize_to_pixels(means2d, conics, feats, opac, width, height, tile_size,
-                                                           isect_offsets, flatten_ids, backgrounds=bg, absgrad=absgrad)
+                                                           isect_offsets, flatten_ids, backgrounds=bg, packed=use_packed,
+                                                           absgrad=absgrad)
     if render_mode in ("ED", "RGB+ED"):  # expected depth: accumulated depth over accumulated alpha
         expected = render_colors[..., -1:] / render_alphas.clamp(min=1e-10)
         render_colors = torch.cat([render_colors[..., :-1], expected], dim=-1)
 
     meta.update({
-        "camera_ids": None, "gaussian_ids": None, "radii": radii, "means2d": means2d, "depths": depths,
+        "camera_ids": camera_ids, "gaussian_ids": gaussian_ids, "radii": radii, "means2d": means2d, "depths": depths,
         "conics": conics, "opacities": opac, "tile_width": tile_width, "tile_height": tile_height,
         "tiles_per_gauss": tiles_per_gauss, "isect_ids": isect_ids, "flatten_ids": flatten_ids,
         "isect_offsets": isect_offsets, "width": width, "height": height, "tile_size": tile_size, "n_cameras": C,

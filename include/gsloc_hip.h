@@ -73,6 +73,60 @@ int gsl_project_bwd(const float* means, const float* quats, const float* scales,
                     float* v_quats, float* v_scales, float* v_viewmat, void* ws, size_t ws_bytes,
                     void* stream);
 
+/* ---- packed projection: gsplat.fully_fused_projection(packed=True) fwd/bwd ----
+ * All C cameras in one call: viewmats[C,16], Ks[C,9].  Of the C*N (camera, Gaussian) pairs, those gsl_project_fwd
+ * gives radii > 0 get one output row each, in ascending order of camera * N + gaussian (camera c's rows are one
+ * contiguous slice); a row holds the bits gsl_project_fwd writes for that pair.  C * N must be below 2^31.
+ *
+ * gsl_project_packed_count: evaluates the cull, leaves one ballot per wave and the row offset of every workgroup in
+ *   ws (gsl_project_packed_ws_bytes(C, N)) and writes the number of rows to nnz[1].  The caller reads nnz back to
+ *   size the outputs (the one host round trip of packed mode, as in gsplat).
+ * gsl_project_packed_fill: after gsl_project_packed_count with the same arguments and the same, untouched ws.
+ *   Writes camera_ids[nnz], gaussian_ids[nnz] (int64, as gsplat), radii[nnz], means2d[nnz,2], depths[nnz],
+ *   conics[nnz,3] and, if not NULL, compensations[nnz].  Rows at positions >= capacity are dropped. */
+size_t gsl_project_packed_ws_bytes(int C, int N);
+int gsl_project_packed_count(const float* means, const float* quats, const float* scales,
+                             const float* viewmats, const float* Ks, int C, int N, int width,
+                             int height, float eps2d, float near_plane, float far_plane,
+                             float radius_clip, int32_t* nnz, void* ws, size_t ws_bytes, void* stream);
+int gsl_project_packed_fill(const float* means, const float* quats, const float* scales,
+                            const float* viewmats, const float* Ks, int C, int N, int width,
+                            int height, float eps2d, float near_plane, float far_plane,
+                            float radius_clip, int64_t capacity, int64_t* camera_ids,
+                            int64_t* gaussian_ids, int32_t* radii, float* means2d, float* depths,
+                            float* conics, float* compensations, void* ws, size_t ws_bytes,
+                            void* stream);
+
+/* vjp of the above, one thread per packed row; camera_ids must be ascending (as the fill pass writes them), rows
+ * whose ids lie outside [0,C) x [0,N) are skipped.  v_means/v_quats/v_scales may be NULL together, v_viewmats may be
+ * NULL, v_compensations may be NULL.
+ *   sparse == 0: v_means[N,3], v_quats[N,4], v_scales[N,3] are OVERWRITTEN with the sum over the cameras (zero for a
+ *     Gaussian without a row; plain stores for C == 1, float atomics -- summation order not fixed -- for C > 1);
+ *   sparse != 0: they are the value rows [nnz,3], [nnz,4], [nnz,3] of a sparse gradient indexed by gaussian_ids.
+ * v_viewmats[C,16] is OVERWRITTEN (rows 0..2 used, row 3 zero; fixed summation order).
+ * ws: gsl_project_packed_bwd_ws_bytes(nnz, C), needed when v_viewmats is given. */
+size_t gsl_project_packed_bwd_ws_bytes(int64_t nnz, int C);
+int gsl_project_packed_bwd(const float* means, const float* quats, const float* scales,
+                           const float* viewmats, const float* Ks, int C, int N, int width, int height,
+                           float eps2d, int64_t nnz, const int64_t* camera_ids,
+                           const int64_t* gaussian_ids, const float* conics,
+                           const float* compensations, const float* v_means2d, const float* v_depths,
+                           const float* v_conics, const float* v_compensations, int sparse,
+                           float* v_means, float* v_quats, float* v_scales, float* v_viewmats, void* ws,
+                           size_t ws_bytes, void* stream);
+
+/* Rows of a per-Gaussian (or per-camera) array for the packed rows, and the vjp: what x[gaussian_ids] and its
+ * backward are in gsplat's packed rasterization.  D floats per row, ids int64.
+ * gsl_gather_rows: dst[nnz,D], dst[r] = src[ids[r]] (a zero row for an id outside [0, n_src)).
+ * gsl_scatter_add_rows: v_dst[n_dst,D] is OVERWRITTEN with the sum of the v_rows[nnz,D] that name each row (rows
+ *   nobody names are zero).  unique != 0: the caller guarantees that no id occurs twice (plain stores); otherwise
+ *   float atomics (summation order not fixed), one per wave where all its lanes hold the same id.
+ *   nnz, n_dst < 2^31. */
+int gsl_gather_rows(const float* src, int64_t n_src, int D, const int64_t* ids, int64_t nnz,
+                    float* dst, void* stream);
+int gsl_scatter_add_rows(const float* v_rows, const int64_t* ids, int64_t nnz, int D, int64_t n_dst,
+                         int unique, float* v_dst, void* stream);
+
 /* ---- spherical harmonics: gsplat.spherical_harmonics fwd/bwd (IDX:14306, IDX:14297) ----
  * dirs[M,3], coeffs[M,K,3] with K >= (degree+1)^2, masks[M] (uint8, may be NULL).
  * degree 0..3.  v_dirs may be NULL. */
