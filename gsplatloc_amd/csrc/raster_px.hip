@@ -32,43 +32,69 @@ struct PStage {
   float4 s0[256];
   float4 s1[256];
   float4 s2[(D >= 3) ? 256 : 1];
-  uint16_t qlist[4][256];  // per-quadrant candidate slots, in list order
-  int qcnt[4][4];          // [staging wave][quadrant]
+  // praster_walk zeroes qguard and qlist once per kernel: a lane without a candidate reads the list entry IN FRONT of
+  // its half chunk (v_ffbl of an empty mask is -1), for quadrant 0's first chunk qguard[7] -- every entry a lane can
+  // read is then 0 or something an earlier batch wrote, a record's byte offset, and needs no masking in the trip
+  uint16_t qguard[8];
+  uint16_t qlist[4][256];         // per-quadrant candidate slots, in list order
+  __attribute__((aligned(16))) int qcnt[4][4];  // [staging wave][quadrant]
 };
 
 // Order-preserving compaction of the staged batch into per-quadrant candidate lists.
-// Call with the record of slot `tid` (valid_rec = slot < bsize).  Two barriers inside.
+// Call with the record of slot `tid`; slots >= bsize (wave-uniform) hold no record.  Two barriers inside.
 // Returns the number of candidates of quadrant `wv`.
 // SHIFT = 4: the lists hold the records' BYTE offsets (slot x 16) -- what a trip of praster_walk adds to the array base,
 // sparing it a 4-cycle shift per candidate; 0: slot numbers (k_tiny_bwd compares them with list positions).
+// Everything but the compares and the list write is wave-uniform and is kept on the scalar unit: the wave number comes
+// through readfirstlane (tid >> 6 is uniform, but only that tells the compiler), "slot < bsize" is a scalar lane mask,
+// the counts are s_bcnt1 results that lane 0 stores as one 16-byte row, and the count table comes back with four
+// broadcast 16-byte reads whose rows are added up under scalar branches on the wave number.  Per quadrant that leaves
+// v_mbcnt_lo / v_mbcnt_hi (rank + base) and the address shift in front of a 2-byte write under exec = the ballot.
+// (Written with per-lane bools and a loop over the earlier waves, the compiler took the loop for divergent: an 8-way
+// unrolled body plus a remainder of dependent LDS reads per quadrant, and a 64-bit shift-and-test of the lane's own
+// ballot bit.)
 template <int SHIFT = 0, typename Stage>
-__device__ __forceinline__ int compact_quadrants(Stage& sb, int tid, bool valid_rec, float x, float y, float r,
+__device__ __forceinline__ int compact_quadrants(Stage& sb, int tid, int bsize, float x, float y, float r,
                                                  float tile_x0, float tile_y0) {
-  int lane = tid & 63, wv = tid >> 6;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nv = __builtin_amdgcn_readfirstlane(bsize) - 64 * wv;  // records among this wave's 64 slots
+  const unsigned long long VALID = nv >= 64 ? ~0ull : (nv <= 0 ? 0ull : (1ull << nv) - 1ull);
   unsigned long long B[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     float cx = tile_x0 + 4.f + 8.f * (float)(q & 1), cy = tile_y0 + 4.f + 8.f * (float)(q >> 1);
     // (one ballot per compare, combined as scalar masks: a ballot of a compound predicate is compiled as
     // v_cndmask 0/1 + v_cmp_ne on top of the compares -- two more four-cycle VALU each)
-    B[q] = __ballot(valid_rec) & __ballot(fabsf(x - cx) <= r + 3.5f) & __ballot(fabsf(y - cy) <= r + 3.5f);
+    B[q] = VALID & __ballot(fabsf(x - cx) <= r + 3.5f) & __ballot(fabsf(y - cy) <= r + 3.5f);
   }
-  if (lane < 4) {
-    unsigned long long b = lane == 0 ? B[0] : (lane == 1 ? B[1] : (lane == 2 ? B[2] : B[3]));
-    sb.qcnt[wv][lane] = __popcll(b);
-  }
+  if ((tid & 63) == 0)
+    *reinterpret_cast<int4*>(&sb.qcnt[wv][0]) = make_int4(__popcll(B[0]), __popcll(B[1]), __popcll(B[2]), __popcll(B[3]));
   __syncthreads();
-  unsigned long long lt = (1ull << lane) - 1ull;
+  const int4 c0 = *reinterpret_cast<const int4*>(&sb.qcnt[0][0]), c1 = *reinterpret_cast<const int4*>(&sb.qcnt[1][0]),
+             c2 = *reinterpret_cast<const int4*>(&sb.qcnt[2][0]), c3 = *reinterpret_cast<const int4*>(&sb.qcnt[3][0]);
+  int base[4] = {0, 0, 0, 0}, n;  // candidates of the earlier waves, per quadrant; the quadrant's own total
+  if (wv == 0) {
+    n = c0.x + c1.x + c2.x + c3.x;
+  } else if (wv == 1) {
+    base[0] = c0.x; base[1] = c0.y; base[2] = c0.z; base[3] = c0.w;
+    n = c0.y + c1.y + c2.y + c3.y;
+  } else if (wv == 2) {
+    base[0] = c0.x + c1.x; base[1] = c0.y + c1.y; base[2] = c0.z + c1.z; base[3] = c0.w + c1.w;
+    n = c0.z + c1.z + c2.z + c3.z;
+  } else {
+    base[0] = c0.x + c1.x + c2.x; base[1] = c0.y + c1.y + c2.y; base[2] = c0.z + c1.z + c2.z;
+    base[3] = c0.w + c1.w + c2.w;
+    n = c0.w + c1.w + c2.w + c3.w;
+  }
+  const uint16_t entry = (uint16_t)(tid << SHIFT);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    if ((B[q] >> lane) & 1ull) {
-      int base = 0;
-      for (int w = 0; w < wv; ++w) base += sb.qcnt[w][q];
-      sb.qlist[q][base + __popcll(B[q] & lt)] = (uint16_t)(tid << SHIFT);
-    }
+    const unsigned pos = __builtin_amdgcn_mbcnt_hi(
+        (unsigned)(B[q] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)B[q], (unsigned)base[q]));
+    if (__builtin_amdgcn_inverse_ballot_w64(B[q])) sb.qlist[q][pos] = entry;  // (exec = the ballot: no per-lane test)
   }
   __syncthreads();
-  return sb.qcnt[0][wv] + sb.qcnt[1][wv] + sb.qcnt[2][wv] + sb.qcnt[3][wv];
+  return n;
 }
 
 // Per-lane 64-bit candidate mask of one chunk: bit k set <=> candidate k's box covers this lane's pixel.
@@ -179,6 +205,11 @@ __device__ __forceinline__ void praster_walk(
   // value under a mask with one v_cndmask_b32_e64.  Left to the compiler, per-lane bools cost a second compare for
   // every negation (v_cmp_nge next to v_cmp_ge) and a v_cndmask 0/1 + v_cmp_ne for every bool that crosses a loop.
   unsigned long long DONE = __ballot(done);
+  // the list entries start as zeros (see PStage; ordered before the first batch's list writes by the barriers between)
+  static_assert(offsetof(PStage<D>, qlist) == offsetof(PStage<D>, qguard) + sizeof(sb.qguard) &&
+                offsetof(PStage<D>, qguard) % sizeof(uint4) == 0, "qguard sits right in front of qlist");
+  if (tid < (int)((sizeof(sb.qguard) + sizeof(sb.qlist)) / sizeof(uint4)))
+    reinterpret_cast<uint4*>(sb.qguard)[tid] = make_uint4(0u, 0u, 0u, 0u);
   for (int b = 0; b < nb; ++b) {
     if (__syncthreads_and(DONE == ~0ull)) break;
     long long bstart = rs + (long long)b * 256;
@@ -217,7 +248,7 @@ __device__ __forceinline__ void praster_walk(
     // (read back from LDS: wave-uniform, but only readfirstlane tells the compiler so -- the chunk loop's control then
     // stays on the scalar unit)
     const int n = __builtin_amdgcn_readfirstlane(
-        compact_quadrants<4>(sb, tid, tid < bsize, r0.x, r0.y, r1.w, (float)(txi * 16), (float)(tyi * 16)));
+        compact_quadrants<4>(sb, tid, bsize, r0.x, r0.y, r1.w, (float)(txi * 16), (float)(tyi * 16)));
     for (int c = 0; c < n; c += 64) {
       if (DONE == ~0ull) break;
       int e = c + lane;
@@ -258,8 +289,8 @@ __device__ __forceinline__ void praster_walk(
           const unsigned b1 = m & (0u - m);
           m ^= b1;
           const unsigned long long TWO = __ballot(b1 != 0u);
-          const unsigned t0 = ql[ffbl_raw(b0)] & 0xFF0u;  // byte offsets (masked: a lane without a candidate reads
-          const unsigned t1 = ql[ffbl_raw(b1)] & 0xFF0u;  // whatever sits in front of the chunk's list)
+          const unsigned t0 = ql[ffbl_raw(b0)];  // byte offsets (a lane without a candidate reads the entry in front of
+          const unsigned t1 = ql[ffbl_raw(b1)];  // the half chunk's: zero or an earlier batch's entry, see PStage)
           float4 p0 = rec_at(sb.s0, t0), p1 = rec_at(sb.s1, t0);  // (x, y, a', b'), (c', opacity, r | depth, g | r_cull)
           float4 u0 = rec_at(sb.s0, t1), u1 = rec_at(sb.s1, t1);
           float dx0 = p0.x - px, dy0 = p0.y - py, dx1 = u0.x - px, dy1 = u0.y - py;
@@ -655,7 +686,7 @@ struct TStage {
   float4 s1[256];
   float4 s2[(D >= 3) ? 256 : 1];
   uint16_t qlist[4][256];
-  int qcnt[4][4];
+  __attribute__((aligned(16))) int qcnt[4][4];
   int32_t id[256];
 };
 
@@ -776,7 +807,7 @@ __global__ __launch_bounds__(256) void k_tiny_bwd(
       sb.s1[tid] = r1;
       if (RGB) sb.s2[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    int n = compact_quadrants(sb, tid, tid < bsize, r0.x, r0.y, r1.w, (float)(txi * 16), (float)(tyi * 16));
+    int n = compact_quadrants(sb, tid, bsize, r0.x, r0.y, r1.w, (float)(txi * 16), (float)(tyi * 16));
     int t_first = (int)max((long long)0, bend - (long long)wave_final);
     int t_lane = inside ? (int)max((long long)0, bend - (long long)bin_final) : 1 << 30;
     for (int c = 0; c < n; c += 64) {
