@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 import subprocess
-from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -74,8 +74,8 @@ _SIGNATURES = {
     "gsl_normal_loss": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
                                 P, P, P, c_size_t, P]),
     "gsl_fused_viewmat_rows": (P, [P, c_int]),
-    "gsl_pose_step": (c_int, [P, P, P, P, c_int, P, P, c_int, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
-                              c_float, c_float, c_float, c_float, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "gsl_pose_step": (c_int, [P, P, P, P, c_int, P, P, c_int, P, P, P, c_int, c_int, c_float, c_float, c_float, c_double, c_double,
+                              c_float, c_float, c_float, c_double, c_int, c_int, c_int, c_int, P, P, P, P]),
     "gsl_pack_pose_reduce": (c_int, [P, P, c_int, P, P, P, c_int, P, P, P]),
     "gsl_knn_ws_bytes": (c_size_t, [c_int]),
     "gsl_knn_cells": (c_int, []),

@@ -218,34 +218,53 @@ __global__ __launch_bounds__(256) void k_normal_gather(const float* __restrict__
 //   f[0..3] quat (wxyz)  f[4..6] t      f[7..13] Adam exp_avg   f[14..20] Adam exp_avg_sq
 //   f[21] lr_quat f[22] lr_trans        f[23] best_loss f[24] best_depth f[25] best_edge
 //   f[26] best_eT f[27] best_eR         f[28] last_loss f[29] last_eT f[30] last_eR
+//   f[32] lr_quat f[33] lr_trans at step 0 (f[21], f[22] = these times gamma^step)
 //   i[0] step  i[1] counter  i[2] stopped  i[3] best_step
+// c2w / viewmat: the pose to render next; once stopped, the last pose that was rendered (the reference's final pose).
 // ------------------------------------------------------------------------------------------------
+// The state is float32.  The lone thread that advances it works in double and rounds once where a value is stored:
+// quaternion -> R, the view matrix, the pose errors, the chain back to the quaternion, both Adam updates.  beta1, beta2
+// and gamma arrive as doubles, and 1 - beta, the bias corrections 1 - beta^step and the rates lr0 gamma^step are taken
+// in double, as torch.optim.Adam and ExponentialLR take them (Python floats); eps and the weight decays are float32,
+// which is what a float32 torch.optim.Adam hands to its tensor operations.
 struct PoseHyper {
-  float beta1, beta2, eps, wd_quat, wd_trans, gamma, depth_w, edge_w, inv_P, normal_w, inv_3H;
-  int min_step, patience, early_stop, max_steps;
+  double beta1, beta2, gamma;
+  float eps, wd_quat, wd_trans, depth_w, edge_w, normal_w;
+  int width, height, min_step, patience, early_stop, max_steps;
 };
 
-__device__ __forceinline__ void quat_to_R(const float q[4], float R[9], float qh[4], float& qn) {
-  qn = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  float inv = 1.f / fmaxf(qn, 1e-12f);
-  float w = q[0] * inv, x = q[1] * inv, y = q[2] * inv, z = q[3] * inv;
+// b^n, n >= 0, by squaring: a few double roundings
+__device__ __forceinline__ double ipow(double b, int n) {
+  double r = 1.0;
+  for (; n > 0; n >>= 1) {
+    if (n & 1) r *= b;
+    b *= b;
+  }
+  return r;
+}
+
+__device__ __forceinline__ void quat_to_R(const double q[4], double R[9], double qh[4], double& qn) {
+  qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  double inv = 1.0 / fmax(qn, 1e-12);
+  double w = q[0] * inv, x = q[1] * inv, y = q[2] * inv, z = q[3] * inv;
   qh[0] = w; qh[1] = x; qh[2] = y; qh[3] = z;
-  R[0] = 1.f - 2.f * (y * y + z * z); R[1] = 2.f * (x * y - w * z); R[2] = 2.f * (x * z + w * y);
-  R[3] = 2.f * (x * y + w * z); R[4] = 1.f - 2.f * (x * x + z * z); R[5] = 2.f * (y * z - w * x);
-  R[6] = 2.f * (x * z - w * y); R[7] = 2.f * (y * z + w * x); R[8] = 1.f - 2.f * (x * x + y * y);
+  R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z); R[2] = 2.0 * (x * z + w * y);
+  R[3] = 2.0 * (x * y + w * z); R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
+  R[6] = 2.0 * (x * z - w * y); R[7] = 2.0 * (y * z + w * x); R[8] = 1.0 - 2.0 * (x * x + y * y);
 }
 
 // c2w = [R(q^)|t]; viewmat = c2w^-1 = [R^T | -R^T t] (rows 0..2; row 3 = 0 0 0 1)
-__device__ __forceinline__ void write_pose(const float q[4], const float t[3], float* c2w, float* viewmat) {
-  float R[9], qh[4], qn;
+__device__ __forceinline__ void write_pose(const float qf[4], const float tf[3], float* c2w, float* viewmat) {
+  double q[4] = {qf[0], qf[1], qf[2], qf[3]}, t[3] = {tf[0], tf[1], tf[2]};
+  double R[9], qh[4], qn;
   quat_to_R(q, R, qh, qn);
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) {
-      c2w[r * 4 + c] = R[r * 3 + c];
-      viewmat[r * 4 + c] = R[c * 3 + r];
+      c2w[r * 4 + c] = (float)R[r * 3 + c];
+      viewmat[r * 4 + c] = (float)R[c * 3 + r];
     }
-    c2w[r * 4 + 3] = t[r];
-    viewmat[r * 4 + 3] = -(R[0 * 3 + r] * t[0] + R[1 * 3 + r] * t[1] + R[2 * 3 + r] * t[2]);
+    c2w[r * 4 + 3] = tf[r];
+    viewmat[r * 4 + 3] = (float)-(R[0 * 3 + r] * t[0] + R[1 * 3 + r] * t[1] + R[2 * 3 + r] * t[2]);
   }
   for (int c = 0; c < 4; ++c) { c2w[12 + c] = (c == 3) ? 1.f : 0.f; viewmat[12 + c] = (c == 3) ? 1.f : 0.f; }
 }
@@ -276,6 +295,7 @@ __global__ void k_pose_init(float* __restrict__ f, int* __restrict__ istate, con
   for (int k = 0; k < 3; ++k) f[4 + k] = t[k];
   for (int k = 7; k < 21; ++k) f[k] = 0.f;
   f[21] = lr_quat; f[22] = lr_trans;
+  f[32] = lr_quat; f[33] = lr_trans;
   const float inf = __builtin_huge_valf();
   for (int k = 23; k < 31; ++k) f[k] = inf;
   istate[0] = 0; istate[1] = 0; istate[2] = 0; istate[3] = -1;
@@ -304,11 +324,12 @@ __global__ __launch_bounds__(256) void k_pose_step(float* __restrict__ f, int* _
   // the state thread 0 works on (pose, Adam moments, learning rates, best-so-far, ground truth, counters) is fetched by
   // three groups of lanes while the rows are being summed: read one after the other by the lone thread these were
   // a dozen dependent global loads of the 9 us this kernel takes
-  __shared__ float sF[32], sG[16];
+  __shared__ float sF[32], sG[16], sL[2];
   __shared__ int sI[4];
   if (threadIdx.x >= 64 && threadIdx.x < 96) sF[threadIdx.x - 64] = f[threadIdx.x - 64];
   else if (threadIdx.x >= 96 && threadIdx.x < 112) sG[threadIdx.x - 96] = gt_c2w[threadIdx.x - 96];
   else if (threadIdx.x >= 112 && threadIdx.x < 116) sI[threadIdx.x - 112] = istate[threadIdx.x - 112];
+  else if (threadIdx.x >= 116 && threadIdx.x < 118) sL[threadIdx.x - 116] = f[32 + threadIdx.x - 116];
   if (vm_rows) {  // `viewmat` still holds the pose this iteration rendered with (thread 0 overwrites it at the very end)
     float v = reduce_viewmat_rows(vm_rows, n_vm, viewmat, Kmat, vred, vtot);
     if (threadIdx.x < 16) svm[threadIdx.x] = v;
@@ -331,28 +352,31 @@ __global__ __launch_bounds__(256) void k_pose_step(float* __restrict__ f, int* _
   if (threadIdx.x != 0) return;
   if (sI[2]) return;  // stopped: keep the state frozen (graph replays may still arrive)
   int step = sI[0];
-  float depth_loss = sums[0] * hp.inv_P, edge_loss = sums[1] * hp.inv_P;
-  float total = hp.depth_w * depth_loss + hp.edge_w * edge_loss;
+  const double inv_P = 1.0 / ((double)hp.width * (double)hp.height);
+  double depth_d = sums[0] * inv_P, edge_d = sums[1] * inv_P;
+  double total_d = hp.depth_w * depth_d + hp.edge_w * edge_d;
   if (hp.normal_w != 0.f) {  // sum of the row cosines: this rank's (normal_sum) or all ranks' (loss_sums_in[2])
     float cs = loss_sums_in ? loss_sums_in[2] : (normal_sum ? normal_sum[0] : 0.f);
-    total += hp.normal_w * (1.f - cs * hp.inv_3H);
+    total_d += hp.normal_w * (1.0 - cs / (3.0 * (double)hp.height));
   }
+  float depth_loss = (float)depth_d, edge_loss = (float)edge_d, total = (float)total_d;
   float q[4] = {sF[0], sF[1], sF[2], sF[3]}, t[3] = {sF[4], sF[5], sF[6]};
-  float R[9], qh[4], qn;
-  quat_to_R(q, R, qh, qn);
+  double qd[4] = {q[0], q[1], q[2], q[3]}, td[3] = {t[0], t[1], t[2]};
+  double R[9], qh[4], qn;
+  quat_to_R(qd, R, qh, qn);
   // pose errors of the CURRENT pose vs ground truth (eval/utils.py:122-168)
-  float dt0 = t[0] - sG[3], dt1 = t[1] - sG[7], dt2 = t[2] - sG[11];
-  float eT = sqrtf(dt0 * dt0 + dt1 * dt1 + dt2 * dt2);
+  double dt0 = td[0] - sG[3], dt1 = td[1] - sG[7], dt2 = td[2] - sG[11];
+  float eT = (float)sqrt(dt0 * dt0 + dt1 * dt1 + dt2 * dt2);
   // rotation angle of R_est R_gt^T (eval/utils.py:144-168 takes acos((trace - 1) / 2)).  In float32 that form
   // resolves angles only down to sqrt(2 * 6e-8) rad = 0.02 degrees -- the level of the reference's own AAE table --
   // so the same angle is computed from the difference of the matrices:  |R_est - R_gt|_F^2 = 8 sin^2(theta / 2).
-  float fro = 0.f;
+  double fro = 0.0;
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) {
-      float d = R[i * 3 + j] - sG[i * 4 + j];
+      double d = R[i * 3 + j] - sG[i * 4 + j];
       fro += d * d;
     }
-  float eR = 2.f * asinf(fminf(1.f, sqrtf(fro * 0.125f))) * 57.29577951308232f;
+  float eR = (float)(2.0 * asin(fmin(1.0, sqrt(fro * 0.125))) * 57.29577951308232);
   f[28] = total; f[29] = eT; f[30] = eR;
   if (loss_hist && step < hp.max_steps) loss_hist[step] = total;
   if (hp.early_stop && step > hp.min_step) {
@@ -366,64 +390,67 @@ __global__ __launch_bounds__(256) void k_pose_step(float* __restrict__ f, int* _
   }
   istate[0] = step + 1;
   if (hp.early_stop && sI[1] >= hp.patience) { istate[2] = 1; return; }  // stop BEFORE the optimiser step
-  if (step + 1 >= hp.max_steps) istate[2] = 1;  // last iteration still takes its optimiser step
+  const bool last = step + 1 >= hp.max_steps;
+  if (last) istate[2] = 1;  // last iteration still takes its optimiser step
   // ---- pose chain: viewmat = inv(c2w) => v_c2w = -V^T v_V V^T
-  float V[16], vV[16];
+  double V[16], vV[16];
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) V[r * 4 + c] = R[c * 3 + r];
-    V[r * 4 + 3] = -(R[0 * 3 + r] * t[0] + R[1 * 3 + r] * t[1] + R[2 * 3 + r] * t[2]);
+    V[r * 4 + 3] = -(R[0 * 3 + r] * td[0] + R[1 * 3 + r] * td[1] + R[2 * 3 + r] * td[2]);
   }
-  V[12] = V[13] = V[14] = 0.f; V[15] = 1.f;
+  V[12] = V[13] = V[14] = 0.0; V[15] = 1.0;
   for (int k = 0; k < 12; ++k) vV[k] = svm[k];
-  vV[12] = vV[13] = vV[14] = vV[15] = 0.f;
-  float M1[16];  // V^T vV
+  vV[12] = vV[13] = vV[14] = vV[15] = 0.0;
+  double M1[16];  // V^T vV
   for (int a = 0; a < 4; ++a)
     for (int b = 0; b < 4; ++b) {
-      float s = 0.f;
+      double s = 0.0;
       for (int i = 0; i < 4; ++i) s += V[i * 4 + a] * vV[i * 4 + b];
       M1[a * 4 + b] = s;
     }
-  float vC[16];  // -(M1 V^T)
+  double vC[16];  // -(M1 V^T)
   for (int a = 0; a < 4; ++a)
     for (int c = 0; c < 4; ++c) {
-      float s = 0.f;
+      double s = 0.0;
       for (int b = 0; b < 4; ++b) s += M1[a * 4 + b] * V[c * 4 + b];
       vC[a * 4 + c] = -s;
     }
-  float vR[9], vt[3];
+  double vR[9], vt[3];
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) vR[r * 3 + c] = vC[r * 4 + c];
     vt[r] = vC[r * 4 + 3];
   }
-  float w = qh[0], x = qh[1], y = qh[2], z = qh[3];
-  float gq[4];
-  gq[0] = 2.f * (-z * vR[1] + y * vR[2] + z * vR[3] - x * vR[5] - y * vR[6] + x * vR[7]);
-  gq[1] = 2.f * (y * vR[1] + z * vR[2] + y * vR[3] - 2.f * x * vR[4] - w * vR[5] + z * vR[6] + w * vR[7] - 2.f * x * vR[8]);
-  gq[2] = 2.f * (-2.f * y * vR[0] + x * vR[1] + w * vR[2] + x * vR[3] + z * vR[5] - w * vR[6] + z * vR[7] - 2.f * y * vR[8]);
-  gq[3] = 2.f * (-2.f * z * vR[0] - w * vR[1] + x * vR[2] + w * vR[3] - 2.f * z * vR[4] + y * vR[5] + x * vR[6] + y * vR[7]);
-  float dq = gq[0] * w + gq[1] * x + gq[2] * y + gq[3] * z;
-  float grad[7];
-  for (int k = 0; k < 4; ++k) grad[k] = (gq[k] - dq * qh[k]) / fmaxf(qn, 1e-12f);
+  double w = qh[0], x = qh[1], y = qh[2], z = qh[3];
+  double gq[4];
+  gq[0] = 2.0 * (-z * vR[1] + y * vR[2] + z * vR[3] - x * vR[5] - y * vR[6] + x * vR[7]);
+  gq[1] = 2.0 * (y * vR[1] + z * vR[2] + y * vR[3] - 2.0 * x * vR[4] - w * vR[5] + z * vR[6] + w * vR[7] - 2.0 * x * vR[8]);
+  gq[2] = 2.0 * (-2.0 * y * vR[0] + x * vR[1] + w * vR[2] + x * vR[3] + z * vR[5] - w * vR[6] + z * vR[7] - 2.0 * y * vR[8]);
+  gq[3] = 2.0 * (-2.0 * z * vR[0] - w * vR[1] + x * vR[2] + w * vR[3] - 2.0 * z * vR[4] + y * vR[5] + x * vR[6] + y * vR[7]);
+  double dq = gq[0] * w + gq[1] * x + gq[2] * y + gq[3] * z;
+  double grad[7];
+  for (int k = 0; k < 4; ++k) grad[k] = (gq[k] - dq * qh[k]) / fmax(qn, 1e-12);
   for (int k = 0; k < 3; ++k) grad[4 + k] = vt[k];
   // ---- Adam (torch.optim.Adam semantics, weight decay added to the gradient), per-group lr
-  float b1p = powf(hp.beta1, (float)(step + 1)), b2p = powf(hp.beta2, (float)(step + 1));
-  float bc1 = 1.f - b1p, bc2s = sqrtf(1.f - b2p);
+  double decay = ipow(hp.gamma, step);  // ExponentialLR: lr = lr0 gamma^step
+  double bc1 = 1.0 - ipow(hp.beta1, step + 1), bc2s = sqrt(1.0 - ipow(hp.beta2, step + 1));
+  double step_q = sL[0] * decay / bc1, step_t = sL[1] * decay / bc1;
   for (int k = 0; k < 7; ++k) {
-    float p = (k < 4) ? q[k] : t[k - 4];
-    float wd = (k < 4) ? hp.wd_quat : hp.wd_trans;
-    float lr = (k < 4) ? sF[21] : sF[22];
-    float g = grad[k] + wd * p;
-    float m = sF[7 + k] * hp.beta1 + (1.f - hp.beta1) * g;
-    float v = sF[14 + k] * hp.beta2 + (1.f - hp.beta2) * g * g;
-    f[7 + k] = m; f[14 + k] = v;
-    float denom = sqrtf(v) / bc2s + hp.eps;
-    p -= (lr / bc1) * (m / denom);
-    if (k < 4) q[k] = p; else t[k - 4] = p;
+    double p = (k < 4) ? qd[k] : td[k - 4];
+    double wd = (k < 4) ? hp.wd_quat : hp.wd_trans;
+    double g = grad[k] + wd * p;
+    double m = sF[7 + k] * hp.beta1 + (1.0 - hp.beta1) * g;
+    double v = sF[14 + k] * hp.beta2 + (1.0 - hp.beta2) * g * g;
+    f[7 + k] = (float)m; f[14 + k] = (float)v;
+    double denom = sqrt(v) / bc2s + hp.eps;
+    p -= ((k < 4) ? step_q : step_t) * (m / denom);
+    if (k < 4) q[k] = (float)p; else t[k - 4] = (float)p;
   }
   for (int k = 0; k < 4; ++k) f[k] = q[k];
   for (int k = 0; k < 3; ++k) f[4 + k] = t[k];
-  f[21] = sF[21] * hp.gamma; f[22] = sF[22] * hp.gamma;  // ExponentialLR
-  write_pose(q, t, c2w, viewmat);
+  decay *= hp.gamma;
+  f[21] = (float)(sL[0] * decay); f[22] = (float)(sL[1] * decay);
+  // the pose this step leads to is never rendered after the last iteration: c2w / viewmat keep the last rendered one
+  if (!last) write_pose(q, t, c2w, viewmat);
 }
 
 // The 16 floats one rank contributes to the per-iteration all-reduce: 12 pose-gradient entries (rows 0..2 of
@@ -550,8 +577,8 @@ extern "C" int gsl_pose_init(float* pose_f, int* pose_i, const float* init_c2w, 
 extern "C" int gsl_pose_step(float* pose_f, int* pose_i, const float* v_viewmat, const float* vm_rows, int n_vm_rows,
                              const float* K, const float* loss_partials, int n_partials, const float* loss_sums, const float* normal_sum, const float* gt_c2w,
                              int width, int height, float depth_lambda, float edge_lambda, float normal_lambda,
-                             float beta1, float beta2, float eps,
-                             float wd_quat, float wd_trans, float gamma, int min_step, int patience, int early_stop,
+                             double beta1, double beta2, float eps,
+                             float wd_quat, float wd_trans, double gamma, int min_step, int patience, int early_stop,
                              int max_steps, float* c2w, float* viewmat, float* loss_hist, void* stream) {
   if (!pose_f || !pose_i || !gt_c2w || !c2w || !viewmat) return GSL_ERR_BAD_ARG;
   if (!v_viewmat && !vm_rows) return GSL_ERR_BAD_ARG;
@@ -559,9 +586,10 @@ extern "C" int gsl_pose_step(float* pose_f, int* pose_i, const float* v_viewmat,
   if (!loss_partials && !loss_sums) return GSL_ERR_BAD_ARG;
   if (width <= 0 || height <= 0 || n_partials < 0) return GSL_ERR_BAD_ARG;
   gsl::PoseHyper hp;
-  hp.beta1 = beta1; hp.beta2 = beta2; hp.eps = eps; hp.wd_quat = wd_quat; hp.wd_trans = wd_trans; hp.gamma = gamma;
-  hp.depth_w = depth_lambda; hp.edge_w = edge_lambda; hp.inv_P = 1.0f / ((float)width * (float)height);
-  hp.normal_w = normal_lambda; hp.inv_3H = 1.0f / (3.0f * (float)height);
+  hp.beta1 = beta1; hp.beta2 = beta2; hp.gamma = gamma;
+  hp.eps = eps; hp.wd_quat = wd_quat; hp.wd_trans = wd_trans;
+  hp.depth_w = depth_lambda; hp.edge_w = edge_lambda; hp.normal_w = normal_lambda;
+  hp.width = width; hp.height = height;
   hp.min_step = min_step; hp.patience = patience; hp.early_stop = early_stop; hp.max_steps = max_steps;
   hipLaunchKernelGGL(gsl::k_pose_step, dim3(1), dim3(256), 0, (hipStream_t)stream, pose_f, pose_i, v_viewmat,
                      vm_rows, n_vm_rows, K, loss_partials, n_partials, loss_sums, normal_sum, gt_c2w, hp, c2w, viewmat, loss_hist);

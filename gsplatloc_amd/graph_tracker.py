@@ -82,7 +82,7 @@ class GraphTracker:
         self.gt_depth = torch.zeros(self.H, self.W, dtype=f32, device=d)
         self.init_c2w = torch.eye(4, dtype=f32, device=d)
         self.gt_c2w = torch.eye(4, dtype=f32, device=d)
-        self.pose_f = torch.zeros(32, dtype=f32, device=d)
+        self.pose_f = torch.zeros(40, dtype=f32, device=d)
         self.pose_i = torch.zeros(4, dtype=torch.int32, device=d)
         self.c2w = torch.eye(4, dtype=f32, device=d)
         self.viewmat = torch.eye(4, dtype=f32, device=d)

@@ -411,14 +411,16 @@ int gsl_tiny_raster_bwd(const float* Q0, const float* Q1, const float* Q2, int c
  *   loss_partials[gsl_loss_n_partials(width,height,row0,row1)][2] (inside ws when NULL; ws may be NULL otherwise).
  *   One launch: 16x16 pixel blocks with a two-pixel apron through LDS.  ws: gsl_loss_ws_bytes.
  * gsl_pose_init : pose state <- init_c2w (wxyz quaternion + translation), zero Adam moments, step 0; writes
- *   c2w[16] and viewmat[16] = c2w^-1.  pose_f[32] floats, pose_i[4] ints (layout: csrc/tracker.hip).
+ *   c2w[16] and viewmat[16] = c2w^-1.  pose_f[40] floats, pose_i[4] ints (layout: csrc/tracker.hip).
  * gsl_pose_step : finish the loss, pose errors vs gt_c2w, early-stop bookkeeping (best loss after min_step,
- *   patience), pose chain viewmat->(quat,t), two Adam updates (weight decay in the gradient), lr *= gamma,
+ *   patience), pose chain viewmat->(quat,t), two Adam updates (weight decay in the gradient), lr = lr0 gamma^step,
  *   new c2w / viewmat; appends the loss to loss_hist[max_steps] (may be NULL).  Does nothing once stopped
- *   (pose_i[2]).  The pose gradient is v_viewmat[16], or -- vm_rows not NULL -- the n_vm_rows partial rows a
+ *   (pose_i[2]); c2w / viewmat then hold the last pose that was rendered (the iteration that reaches max_steps takes
+ *   its Adam step but leaves them).  beta1, beta2 and gamma are doubles, as torch.optim keeps them: 1 - beta, the
+ *   bias corrections and gamma^step are taken in double and rounded once.  The pose gradient is v_viewmat[16], or -- vm_rows not NULL -- the n_vm_rows partial rows a
  *   gsl_fused_project_bwd(reduce_viewmat = 0) left (K and the viewmat buffer, which still holds the rendered pose, are
- *   read for the camera-position chain).  loss_sums[3] (already summed over ranks: the two sums and the row-cosine sum) overrides
- *   loss_partials / normal_sum when not NULL.  normal_lambda != 0 adds normal_lambda * (1 - normal_sum / (3 height)).
+ *   read for the camera-position chain).  loss_sums[3] (already summed over ranks: the two sums and the row-cosine
+ *   sum) overrides loss_partials / normal_sum when not NULL.  normal_lambda != 0 adds normal_lambda * (1 - normal_sum / (3 height)).
  * gsl_normal_loss: the normal-consistency term the reference defines and keeps switched off (loss.py:62-101 "cosine",
  *   geometry.py:164-197; call commented out at gs_trainer_total.py:138-143, normal_lambda = 0 at data/base.py:28):
  *   unit normals of the back-projected masked depth images (central differences, replicated borders), cosine
@@ -440,8 +442,8 @@ int gsl_pose_init(float* pose_f, int* pose_i, const float* init_c2w, float lr_qu
 int gsl_pose_step(float* pose_f, int* pose_i, const float* v_viewmat, const float* vm_rows, int n_vm_rows,
                   const float* K, const float* loss_partials, int n_partials, const float* loss_sums, const float* normal_sum, const float* gt_c2w,
                   int width, int height, float depth_lambda, float edge_lambda, float normal_lambda,
-                  float beta1, float beta2, float eps,
-                  float wd_quat, float wd_trans, float gamma, int min_step, int patience, int early_stop,
+                  double beta1, double beta2, float eps,
+                  float wd_quat, float wd_trans, double gamma, int min_step, int patience, int early_stop,
                   int max_steps, float* c2w, float* viewmat, float* loss_hist, void* stream);
 /* Several GPUs: what one rank contributes to the ONE all-reduce of an iteration.  out16[0..11] =
  * v_viewmat[0..11] of its strip (given reduced, or as vm_rows with the viewmat and K they were computed at), out16[12..13] = its (sum |d - g|, sum |S(d) - S(g)|) over loss_partials[n][2]

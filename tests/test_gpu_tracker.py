@@ -410,3 +410,84 @@ def test_pile_that_comes_into_view_during_the_optimisation_switches_the_split_on
     assert res.steps == 150 and torch.isfinite(torch.tensor(res.losses)).all()
     assert gt.rc.long_min > 0 and gt.rc.bin_cap > 20_000, (gt.rc.long_min, gt.rc.bin_cap)
     assert res.losses[-1] < 0.5 * res.losses[0]
+
+
+@pytest.fixture(scope="module")
+def far_tracking():
+    """The frame pair of _setup() moved rigidly by a dataset-scale pose G (tests/pose_ref.py, the m11 branch): the
+    target cloud and both cameras move, the source cloud and the target depth stay.  Holds the oracle's twelve steps
+    in float64 (the reference) and in float32 (how far float32 alone takes the losses from it)."""
+    from tests.pose_ref import far_poses
+    M, fp, K, pts0, pts1, scales0, scales1 = _setup()
+    W, H = fp["W"], fp["H"]
+    G = far_poses()["m11"]
+    pts0m = pts0.double() @ G[:3, :3].T + G[:3, 3]
+    init, gt = G @ fp["c2w0"].double(), G @ fp["c2w1"].double()
+    N = pts1.shape[0]
+    quats = torch.tensor([1.0, 0, 0, 0]).repeat(N, 1)
+    sh = torch.zeros(N, 4, 3)
+    sh[:, 0] = T.rgb_to_sh(fp["rgb"])
+    with torch.no_grad():
+        gt_o, _, _ = T.gs_forward(pts1.double(), quats.double(), scales1.double(), torch.ones(N).double(), sh.double(),
+                                  torch.eye(4).double(), K.double(), W, H, render_mode="ED")
+    steps = 12
+    res = {}
+    for dt in (torch.float64, torch.float32):
+        res[dt] = T.track_frame(pts0m.to(dt), scales0.to(dt), fp["rgb"].to(dt), gt_o.to(dt), K.to(dt), W, H,
+                                init_c2w=init.to(dt), gt_c2w=gt.to(dt), max_steps=steps, min_step=2)
+    lo, l32 = (torch.tensor(res[dt].losses, dtype=torch.float64) for dt in (torch.float64, torch.float32))
+    dev32 = float(((l32 - lo).abs() / lo).max())
+    rtol = 2e-3 if dev32 <= 1e-3 else 2.0 * dev32
+    print(f"[parity] far-pose tracking: float32 oracle losses within {dev32:.2e} of float64, loss rtol {rtol:.2e}")
+    frame = dict(pts=pts0m.float().to(DEV), rgb=fp["rgb"].to(DEV), scales=scales0.to(DEV), depth=gt_o.float().to(DEV),
+                 init=init.float().to(DEV), gt=gt.float().to(DEV), K=K.to(DEV))
+    return dict(M=M, W=W, H=H, steps=steps, frame=frame, oracle=res[torch.float64], losses=lo, rtol=rtol, context={})
+
+
+def _check_far_tracking(ft, name, r):
+    lg = torch.tensor(r.losses, dtype=torch.float64)
+    rel = float(((lg - ft["losses"]).abs() / ft["losses"]).max())
+    print(f"[parity] far-pose tracking {name}: losses within {rel:.2e} of the oracle (rtol {ft['rtol']:.2e}), "
+          f"best_eT {r.best_eT:.3e} vs {ft['oracle'].best_eT:.3e}, best_eR {r.best_eR:.3e} vs {ft['oracle'].best_eR:.3e}")
+    assert r.steps == ft["steps"]
+    assert torch.allclose(lg, ft["losses"], rtol=ft["rtol"], atol=1e-7), (name, lg, ft["losses"])
+    assert abs(r.best_eT - ft["oracle"].best_eT) < 2e-4 and abs(r.best_eR - ft["oracle"].best_eR) < 5e-3
+
+
+def _context_far_tracking(ft):
+    if "res" not in ft["context"]:
+        f, M = ft["frame"], ft["M"]
+        cfg = M.TrackerConfig(max_steps=ft["steps"], min_step=2)
+        ft["context"]["res"] = M.PoseTracker(cfg, engine="context").track_frame(
+            f["pts"], f["rgb"], f["depth"], f["init"], f["gt"], f["K"], ft["W"], ft["H"], scales=f["scales"])
+    return ft["context"]["res"]
+
+
+@pytest.mark.parametrize("engine", ["autograd", "context"])
+def test_pose_tracker_at_a_far_pose_follows_the_oracle(far_tracking, engine):
+    ft = far_tracking
+    f, M = ft["frame"], ft["M"]
+    if engine == "context":
+        r = _context_far_tracking(ft)
+    else:
+        cfg = M.TrackerConfig(max_steps=ft["steps"], min_step=2)
+        r = M.PoseTracker(cfg, engine=engine).track_frame(f["pts"], f["rgb"], f["depth"], f["init"], f["gt"], f["K"],
+                                                          ft["W"], ft["H"], scales=f["scales"])
+    _check_far_tracking(ft, engine, r)
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_graph_tracker_at_a_far_pose_follows_the_oracle(far_tracking, use_graph):
+    from gsplatloc_amd.graph_tracker import GraphTracker
+    ft = far_tracking
+    f, M = ft["frame"], ft["M"]
+    cfg = M.TrackerConfig(max_steps=ft["steps"], min_step=2)
+    gt = GraphTracker(f["pts"].shape[0], ft["W"], ft["H"], cfg, device=DEV, use_graph=use_graph, poll=6)
+    gt.load_frame(f["pts"], f["rgb"], f["scales"], f["depth"], f["init"], f["gt"], f["K"])
+    r = gt.run()
+    _check_far_tracking(ft, f"graph tracker (graph {use_graph})", r)
+    # the final pose is the last one rendered, as the reference loop and the PyTorch tracker have it
+    want = _context_far_tracking(ft).final_c2w
+    err = float((r.final_c2w - want).abs().max())
+    print(f"[parity] far-pose tracking graph tracker (graph {use_graph}): final c2w within {err:.2e} of the context engine's")
+    assert err < 1e-5, err

@@ -55,7 +55,7 @@ def test_tracker_kernel_calls_marshal():
     n_part = lib.gsl_loss_n_partials(W, H, 0, H)
     assert n_part == 4 * 3 and lib.gsl_loss_n_partials(W, H, 16, 32) == 4 * 2 and lib.gsl_loss_n_partials(W, H, 5, 5) == 0
     partials = torch.zeros(n_part * 2)
-    pose_f, pose_i = torch.zeros(32), torch.zeros(4, dtype=torch.int32)
+    pose_f, pose_i = torch.zeros(40), torch.zeros(4, dtype=torch.int32)
     c2w, viewmat, eye = torch.eye(4), torch.eye(4), torch.eye(4)
     hist, v_viewmat = torch.zeros(10), torch.zeros(16)
     _expect_hip_refusal(lambda: check(lib.gsl_tracking_loss(ptr(render), D, ptr(gt), W, H, 0, H, 0.8, 0.2, ptr(v_render),
