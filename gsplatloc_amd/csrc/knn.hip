@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void k_knn_query(const float* __restrict__ pts
   int cx = cell_coord(px, g.ox, g.inv_h), cy = cell_coord(py, g.oy, g.inv_h), cz = cell_coord(pz, g.oz, g.inv_h);
   float best[K];
 #pragma unroll
-  for (int k = 0; k < K; ++k) best[k] = 3.0e38f;
+  for (int k = 0; k < K; ++k) best[k] = __builtin_huge_valf();  // a slot no neighbour fills stays +inf (N < k)
   // position inside the own cell: distance to the searched block's faces after radius R is
   // R*h + min(offset to the cell's faces)
   float fx = (px - g.ox) - cx * g.h, fy = (py - g.oy) - cy * g.h, fz = (pz - g.oz) - cz * g.h;
@@ -143,7 +143,8 @@ extern "C" int gsl_knn_count(const float* points, int N, const float* bbox, void
 }
 
 // Phase 2: incl_offsets[cells] = inclusive cumulative sum of the counts (caller computes it on the device);
-// squared distances to the k nearest points (self included), ascending, into dists[N,k].  k <= 8.
+// squared distances to the k nearest points (self included), ascending, into dists[N,k].  k <= 8.  N < k: the
+// missing neighbours' slots hold +inf.
 extern "C" int gsl_knn_query(const float* points, int N, const float* bbox, const int32_t* incl_offsets, int k,
                              float* dists, void* ws, size_t ws_bytes, void* stream) {
   if (N < 0 || k < 1 || k > GSL_KNN_MAXK || !bbox || !ws || !incl_offsets) return GSL_ERR_BAD_ARG;

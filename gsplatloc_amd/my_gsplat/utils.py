@@ -9,7 +9,8 @@ from torch import Tensor
 
 def knn_device(x: Tensor, K: int) -> Tensor:
     """Exact K nearest neighbours (self included) of a device point cloud: SQUARED distances [N,K],
-    ascending -- csrc/knn.hip (uniform grid, shell search), no host round trip."""
+    ascending -- csrc/knn.hip (uniform grid, shell search), no host round trip.  A cloud of N < K points has
+    only N neighbours per query: the remaining columns hold +inf, as on the host path of ``knn``."""
     from .._lib import check, current_stream, load_library, ptr
 
     lib = load_library()

@@ -459,7 +459,8 @@ int gsl_pack_pose_reduce(const float* v_viewmat, const float* vm_rows, int n_vm_
  * points[N,3]; bbox[6] = (min x,y,z, max x,y,z) on the device; uniform grid of gsl_knn_cells() cells.
  * gsl_knn_count fills the per-cell counts at the start of ws (int32[cells]); the caller turns them into an
  * inclusive cumulative sum incl_offsets[cells] (any device scan); gsl_knn_query then writes the SQUARED
- * distances to the k <= 8 nearest points (the point itself included), ascending, into dists[N,k]. */
+ * distances to the k <= 8 nearest points (the point itself included), ascending, into dists[N,k].  A cloud of
+ * N < k points has only N neighbours per query: the remaining slots hold +inf (as a KD-tree query reports them). */
 size_t gsl_knn_ws_bytes(int N);
 int gsl_knn_cells(void);
 int gsl_knn_count(const float* points, int N, const float* bbox, void* ws, size_t ws_bytes, void* stream);
