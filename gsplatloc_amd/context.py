@@ -20,8 +20,9 @@ from typing import Dict, Optional, Tuple
 import torch
 from torch import Tensor
 
+from . import stages
 from ._lib import check, current_stream, load_library, ptr
-from .fused import _MODES, MAX_STRIP_TILES, alloc_records, tile_n_bits
+from .stages import _MODES, MAX_STRIP_TILES, alloc_records, tile_n_bits
 
 
 LONG_MIN = 2048   # a tile list longer than this is split over workgroups (segments of gsl_long_segment() entries)
@@ -82,7 +83,7 @@ class RenderContext:
         f32, i32 = torch.float32, torch.int32
         N = self.N
         self.radii = torch.zeros(N, dtype=i32, device=dev)
-        self.Q0, self.Q1, self.Q2 = alloc_records(self.lib, N, self.rgb, dev, zero=True)
+        self.Q0, self.Q1, self.Q2 = alloc_records(N, self.rgb, dev, zero=True)
         # "fp16": the compositing kernels gather one 32-byte half-precision record per splat (BASELINE.json configs[4]);
         # transmittance and all accumulators stay float32
         assert staging in ("fp32", "fp16"), staging
@@ -400,108 +401,87 @@ class RenderContext:
                                "projections); call calibrate() again")
         return n
 
-    # ------------------------------------------------------------------ stages (one C-ABI call each)
+    # ------------------------------------------------------------------ stages (one call into stages.py per launch)
     def _project(self, means, quats, scales, opacities, colors, viewmat, K) -> None:
         if self.bins is not None:
             if self._counters_dirty:  # the previous projection was never followed by a compositing forward
                 self.ws.zero_()
             self._counters_dirty = True
-        check(self.lib.gsl_fused_project(
-            ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(colors) if self.rgb else None, self.sh_degree,
-            self.K_sh, ptr(viewmat), ptr(K), self.N, self.W, self.H, self.eps2d, self.near, self.far,
-            self.radius_clip, int(self.antialiased), self.tw, self.th, self.ty0, self.ty1, ptr(self.radii),
-            ptr(self.Q0), ptr(self.Q1), ptr(self.Q2), ptr(self.comps), ptr(self.tiles_per_gauss), ptr(self.offs),
-            ptr(self.n_is),
-            ptr(self.ws), self.ws_bytes, ptr(self.Qh), ptr(self.bins), self.bin_cap, ptr(self.flags),
-            ptr(self.order_ids), current_stream()), "gsl_fused_project")
+        stages.fused_project(means, quats, scales, opacities, colors if self.rgb else None, self.sh_degree, self.K_sh,
+                             viewmat, K, self.N, self.W, self.H, self.eps2d, self.near, self.far, self.radius_clip,
+                             int(self.antialiased), self.tw, self.th, self.ty0, self.ty1, self.radii, self.Q0, self.Q1,
+                             self.Q2, self.comps, self.tiles_per_gauss, self.offs, self.n_is, self.ws, Qh=self.Qh,
+                             bins=self.bins, bin_cap=self.bin_cap, flags=self.flags, order_ids=self.order_ids)
 
     def _bin(self) -> None:
         if self.sorts_in_forward():
             return  # (the compositing forward sorts its own tile's bin)
-        check(self.lib.gsl_fused_bin(ptr(self.Q0), ptr(self.radii), self.N, self.tw, self.th, self.ty0, self.ty1,
-                                     tile_n_bits(self.n_tiles), ptr(self.offs), self.capacity, ptr(self.keys),
-                                     ptr(self.flatten_ids), None, ptr(self.ws), self.ws_bytes, int(self.deterministic),
-                                     ptr(self.bins), self.bin_cap, ptr(self.n_is), ptr(self.flags),
-                                     self.long_min if self.bins is not None else 0, ptr(self.order_ids),
-                                     ptr(self.storage_of), current_stream()),
-              "gsl_fused_bin")
+        stages.fused_bin(self.Q0, self.radii, self.N, self.tw, self.th, self.ty0, self.ty1, tile_n_bits(self.n_tiles),
+                         self.offs, self.capacity, self.keys, self.flatten_ids, self.ws,
+                         write_sorted_keys=int(self.deterministic), bins=self.bins, bin_cap=self.bin_cap,
+                         n_isects=self.n_is, flags=self.flags, long_min=self.long_min if self.bins is not None else 0,
+                         order_ids=self.order_ids, storage_of=self.storage_of)
         if self.long_min and self.bins is not None:  # the long lists: sorted by several workgroups
-            check(self.lib.gsl_long_sort(ptr(self.offs), self.tw, self.th, self.ty0, self.ty1, self.capacity,
-                                         ptr(self.bins), self.bin_cap, ptr(self.keys), ptr(self.flatten_ids),
-                                         self.long_min, ptr(self.long_ws), self.long_ws_bytes, self.max_seg,
-                                         self.long_passes, ptr(self.storage_of), current_stream()), "gsl_long_sort")
+            stages.long_sort(self.offs, self.tw, self.th, self.ty0, self.ty1, self.capacity, self.bins, self.bin_cap,
+                             self.keys, self.flatten_ids, self.long_min, self.long_ws, self.max_seg, self.long_passes,
+                             storage_of=self.storage_of)
+
+    def _frame(self) -> tuple:
+        """The leading arguments every compositing call shares: records, geometry, lists, outputs."""
+        return (self.Q0, self.Q1, self.Q2, self.D, int(self.ed), self.W, self.H, self.tw, self.th, self.ty0, self.ty1,
+                self.offs, self.flatten_ids, self.capacity, self.render, self.alphas, self.last_ids)
 
     def _raster_fwd(self) -> None:
         sif = self.sorts_in_forward()
-        check(self.lib.gsl_fused_raster_fwd(ptr(self.Q0), ptr(self.Q1), ptr(self.Q2), self.D, int(self.ed), self.W,
-                                            self.H, self.tw, self.th, self.ty0, self.ty1, ptr(self.offs),
-                                            ptr(self.flatten_ids), self.capacity, ptr(self.render), ptr(self.alphas),
-                                            ptr(self.last_ids), self.row0, self.row1, ptr(self.Qh),
-                                            ptr(self.ws) if self.bins is not None else None,
-                                            ptr(self.hits) if (self.record_hits and self.hits is not None) else None,
-                                            ptr(self.hit_counts) if (self.record_hits and self.hits is not None) else None,
-                                            self.long_min, ptr(self.bins) if sif else None, self.bin_cap if sif else 0,
-                                            ptr(self.n_is) if sif else None, ptr(self.flags) if sif else None,
-                                            ptr(self.storage_of) if sif else None, current_stream()),
-              "gsl_fused_raster_fwd")
+        hits = self.hits if self.record_hits else None
+        own_sort = dict(sort_bins=self.bins, bin_cap=self.bin_cap, n_isects=self.n_is, flags=self.flags,
+                        storage_of=self.storage_of) if sif else {}
+        stages.fused_raster_fwd(*self._frame(), self.row0, self.row1, Qh=self.Qh,
+                                binned_ws=self.ws if self.bins is not None else None, isect_hits=hits,
+                                isect_hit_counts=self.hit_counts if hits is not None else None,
+                                long_min=self.long_min, **own_sort)
         if not sif:  # (sorting forward: the counters stay set until the backward clears them)
             self._counters_dirty = False
-        self._hits_valid = self.record_hits and self.hits is not None
+        self._hits_valid = hits is not None
         if self.long_min:
-            check(self.lib.gsl_long_raster_fwd(ptr(self.Q0), ptr(self.Q1), ptr(self.Q2), self.D, int(self.ed), self.W,
-                                               self.H, self.tw, self.th, self.ty0, self.ty1, ptr(self.offs),
-                                               ptr(self.flatten_ids), self.capacity, ptr(self.render), ptr(self.alphas),
-                                               ptr(self.last_ids), self.row0, self.row1, ptr(self.Qh),
-                                               ptr(self.hits) if (self.record_hits and self.hits is not None) else None,
-                                               self.long_min, ptr(self.long_ws), self.long_ws_bytes, self.max_seg,
-                                               int(self.bins is not None), current_stream()), "gsl_long_raster_fwd")
+            stages.long_raster_fwd(*self._frame(), self.row0, self.row1, self.long_min, self.long_ws, self.max_seg,
+                                   int(self.bins is not None), Qh=self.Qh, isect_hits=hits)
 
     def _raster_bwd(self, v_render: Tensor, v_alphas: Tensor, tracking_loss=None) -> None:
-        common = (ptr(self.Q0), ptr(self.Q1), ptr(self.Q2), self.D, int(self.ed), self.W, self.H, self.tw, self.th,
-                  self.ty0, self.ty1, ptr(self.offs), ptr(self.flatten_ids), self.capacity, ptr(self.render),
-                  ptr(self.alphas), ptr(self.last_ids), ptr(v_render), ptr(v_alphas))
+        common = self._frame() + (v_render, v_alphas)
         clear = self.sorts_in_forward() and self._counters_dirty  # the sorting forward left the tile counters set
+        clear_ws = self.ws if clear else None
+        hits = self.hits if self._hits_valid else None
         if self.tiny:
-            loss = tracking_loss if tracking_loss is not None else (None, 0.0, 0.0, None)
-            check(self.lib.gsl_tiny_raster_bwd(*common, ptr(self.trec), ptr(self.vcT), self.row0, self.row1,
-                                               ptr(self.flags), self.long_min, ptr(loss[0]), float(loss[1]),
-                                               float(loss[2]), ptr(loss[3]), ptr(self.ws) if clear else None,
-                                               current_stream()), "gsl_tiny_raster_bwd")
+            depth_gt, depth_lambda, edge_lambda, partials = tracking_loss if tracking_loss is not None else (None, 0, 0, None)
+            stages.tiny_raster_bwd(*common, self.trec, self.vcT, self.row0, self.row1, flags=self.flags,
+                                   long_min=self.long_min, loss_depth_gt=depth_gt, depth_lambda=float(depth_lambda),
+                                   edge_lambda=float(edge_lambda), loss_partials=partials, clear_ws=clear_ws)
             # (pass 2, the fold of the slabs into gradient rows, runs inside the projection backward)
         else:
-            check(self.lib.gsl_fused_raster_bwd(*common, ptr(self.vacc), self.row0, self.row1, ptr(self.Qh),
-                                                ptr(self.vrow), ptr(self.hits) if self._hits_valid else None,
-                                                ptr(self.hit_counts) if self._hits_valid else None, self.long_min,
-                                                ptr(self.ws) if clear else None, current_stream()),
-                  "gsl_fused_raster_bwd")
+            stages.fused_raster_bwd(*common, self.vacc, self.row0, self.row1, Qh=self.Qh, vrow=self.vrow, isect_hits=hits,
+                                    isect_hit_counts=self.hit_counts if self._hits_valid else None,
+                                    long_min=self.long_min, clear_ws=clear_ws)
         if clear:
             self._counters_dirty = False
         if self.long_min:  # the segments of the long tiles: rows added to vacc
-            check(self.lib.gsl_long_raster_bwd(*common, ptr(self.vacc), self.row0, self.row1, ptr(self.Qh),
-                                               ptr(self.hits) if self._hits_valid else None,
-                                               self.long_min, ptr(self.long_ws), self.max_seg, current_stream()),
-                  "gsl_long_raster_bwd")
+            stages.long_raster_bwd(*common, self.vacc, self.row0, self.row1, self.long_min, self.long_ws, self.max_seg,
+                                   Qh=self.Qh, isect_hits=hits)
 
     def _project_bwd(self, full: bool, reduce: bool = True) -> None:
         means, quats, scales, opacities, colors, viewmat, K = self._inputs
-        if self.vrow is not None and not self.tiny:  # deterministic general backward: rows per intersection
-            det = (ptr(self.vrow), ptr(self.keys), ptr(self.offs), ptr(self.Q0), self.tw, self.th, self.ty0, self.ty1,
-                   self.capacity)
-        else:  # (the tiny-splat backward has no atomics to begin with)
-            det = (None, None, None, None, 0, 0, 0, 0, 0)
-        tiny = (ptr(self.trec), ptr(self.vcT)) if self.tiny else (None, None)
-        if tiny[0] is not None:  # the projection backward folds the slabs itself: it needs the records
-            det = (None, None, None, ptr(self.Q0), 0, 0, 0, 0, 0)
-        check(self.lib.gsl_fused_project_bwd(
-            ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(colors) if self.rgb else None, self.sh_degree,
-            self.K_sh, ptr(viewmat), ptr(K), self.N, self.W, self.H, self.eps2d, int(self.antialiased), self.D,
-            ptr(self.radii), ptr(self.Q1), ptr(self.comps),
-            ptr(self.vacc) if (not self.tiny or self.long_min) else None,
-            ptr(self.v_means) if full else None, ptr(self.v_quats) if full else None,
-            ptr(self.v_scales) if full else None, ptr(self.v_opacities) if full else None,
-            ptr(self.v_colors) if (full and self.rgb) else None, ptr(self.v_viewmat), ptr(self.ws), self.ws_bytes,
-            self.n_tiles, *det, *tiny, int(reduce), ptr(self.vc_state) if (full and self.rgb) else None,
-            current_stream()), "gsl_fused_project_bwd")
+        mode = {}
+        if self.tiny:  # no atomics to begin with; the projection backward folds the slabs itself: it needs the records
+            mode = dict(Q0=self.Q0, tiny_trec=self.trec, tiny_vcT=self.vcT)
+        elif self.vrow is not None:  # deterministic general backward: rows per intersection
+            mode = dict(vrow=self.vrow, sorted_keys=self.keys, tile_offsets=self.offs, Q0=self.Q0, tile_w=self.tw,
+                        tile_h=self.th, ty0=self.ty0, ty1=self.ty1, capacity=self.capacity)
+        grads = (self.v_means, self.v_quats, self.v_scales, self.v_opacities) if full else (None, None, None, None)
+        stages.fused_project_bwd(means, quats, scales, opacities, colors if self.rgb else None, self.sh_degree, self.K_sh,
+                                 viewmat, K, self.N, self.W, self.H, self.eps2d, int(self.antialiased), self.D, self.radii,
+                                 self.Q1, self.comps, self.vacc if (not self.tiny or self.long_min) else None, *grads,
+                                 self.v_colors if (full and self.rgb) else None, self.v_viewmat, self.ws, self.n_tiles,
+                                 int(reduce), v_colors_state=self.vc_state if (full and self.rgb) else None, **mode)
 
     # ------------------------------------------------------------------ forward / backward
     def forward(self, means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor, colors: Optional[Tensor],

@@ -10,139 +10,184 @@ a strip of tile rows (screen-tile parallelism, ``gsplatloc_amd.parallel``).
 """
 from __future__ import annotations
 
-import math
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
 
-from ._lib import check, current_stream, load_library, ptr
-
-MAX_STRIP_TILES = 8192
-_MODES = {"RGB": (3, False), "D": (1, False), "ED": (1, True), "RGB+D": (4, False), "RGB+ED": (4, True)}
-
-
-def tile_n_bits(n_tiles: int) -> int:
-    return int(math.floor(math.log2(n_tiles))) + 1
+from . import stages
+from ._lib import load_library
+from .stages import _MODES, MAX_STRIP_TILES, alloc_records, tile_n_bits
 
 
-def alloc_records(lib, N: int, rgb: bool, dev, zero: bool = False):
-    """The per-Gaussian record arrays Q0, Q1, Q2 ([N,4] each; Q2 None without colours)."""
-    make = torch.zeros if zero else torch.empty
-    Q0 = make(N, 4, dtype=torch.float32, device=dev)
-    Q1 = make(N, 4, dtype=torch.float32, device=dev)
-    Q2 = make(N, 4, dtype=torch.float32, device=dev) if rgb else None
-    return Q0, Q1, Q2
+class FusedCfg(NamedTuple):
+    """What one allocate-per-call render depends on besides its tensors.  Whole frame: (ty0, ty1) = (0, tile rows)."""
+    width: int
+    height: int
+    sh_degree: int  # -1: colours are RGB
+    mode: str
+    eps2d: float
+    near_plane: float
+    far_plane: float
+    radius_clip: float
+    antialiased: bool
+    ty0: int
+    ty1: int
+    want_isect_ids: bool
+
+
+def _make_cfg(width, height, sh_degree, render_mode, eps2d, near_plane, far_plane, radius_clip, antialiased, tile_rows,
+              want_isect_ids) -> FusedCfg:
+    ty0, ty1 = tile_rows if tile_rows is not None else (0, (height + 15) // 16)
+    assert 0 <= ty0 <= ty1 <= (height + 15) // 16, (ty0, ty1, height)
+    return FusedCfg(int(width), int(height), -1 if sh_degree is None else int(sh_degree), render_mode, float(eps2d),
+                    float(near_plane), float(far_plane), float(radius_clip), bool(antialiased), int(ty0), int(ty1),
+                    bool(want_isect_ids))
+
+
+def _geometry(cfg: FusedCfg):
+    """(channels, ed, colours?, tile columns, tile rows) of a configuration."""
+    D, ed = _MODES[cfg.mode]
+    return D, ed, D >= 3, (cfg.width + 15) // 16, (cfg.height + 15) // 16
+
+
+def prep(t, name):
+    assert t.is_cuda, f"{name} must live on the GPU (got {t.device}); there is no CPU path"
+    assert t.dtype == torch.float32, f"{name} must be float32 (got {t.dtype})"
+    return t.contiguous()
+
+
+def _gsplat_meta(width, height, s, means2d=None) -> Dict:
+    """gsplat's meta dict ([1,N,...] views) from the arrays of a render: s maps radii, Q0, Q1, tiles_per_gauss,
+    flatten_ids, tile_offsets and, where they are produced, isect_ids."""
+    tw, th = (width + 15) // 16, (height + 15) // 16
+    Q0, Q1 = s["Q0"], s["Q1"]
+    return {
+        "camera_ids": None, "gaussian_ids": None,
+        "radii": s["radii"][None], "means2d": Q0[None, :, 0:2] if means2d is None else means2d, "depths": Q0[None, :, 2],
+        "conics": Q1[None, :, 0:3], "opacities": Q0[None, :, 3],
+        "tile_width": tw, "tile_height": th, "tiles_per_gauss": s["tiles_per_gauss"][None],
+        "isect_ids": s.get("isect_ids"), "flatten_ids": s["flatten_ids"],
+        "isect_offsets": s["tile_offsets"][:-1].reshape(1, th, tw), "width": width, "height": height,
+        "tile_size": 16, "n_cameras": 1,
+    }
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The steps of the allocate-per-call path, once each.  `s` is the state of one render: cfg, N, K_sh, n_isects and the arrays
+# projection and binning left.  _FusedRasterization keeps them with save_for_backward; the absgrad nodes share `s` itself.
+_SCALARS = ("cfg", "N", "K_sh", "n_isects")
+_ARRAYS = ("radii", "Q0", "Q1", "Q2", "comps", "tile_offsets", "flatten_ids", "ws")  # what a backward reads
+
+
+def _project_and_bin(means, quats, scales, opacities, colors, viewmat, K, cfg: FusedCfg) -> Dict:
+    """Records, gsl_fused_project, the intersection count read back, lists, gsl_fused_bin."""
+    _, _, rgb, tw, th = _geometry(cfg)
+    N, dev, n_tiles = means.shape[0], means.device, tw * th
+    f32, i32 = torch.float32, torch.int32
+    radii = torch.empty(N, dtype=i32, device=dev)
+    Q0, Q1, Q2 = alloc_records(N, rgb, dev)
+    comps = torch.empty(N, dtype=f32, device=dev) if cfg.antialiased else None
+    tpg = torch.empty(N, dtype=i32, device=dev)
+    offs = torch.empty(n_tiles + 1, dtype=i32, device=dev)
+    n_is = torch.empty(1, dtype=i32, device=dev)
+    ws = torch.empty(load_library().gsl_fused_ws_bytes(N, n_tiles), dtype=torch.uint8, device=dev)
+    K_sh = colors.shape[1] if (rgb and cfg.sh_degree >= 0) else 0
+    # two-pass binning (no bins): tile sizes are not known in advance
+    stages.fused_project(means, quats, scales, opacities, colors if rgb else None, cfg.sh_degree, K_sh, viewmat, K, N,
+                         cfg.width, cfg.height, cfg.eps2d, cfg.near_plane, cfg.far_plane, cfg.radius_clip,
+                         int(cfg.antialiased), tw, th, cfg.ty0, cfg.ty1, radii, Q0, Q1, Q2, comps, tpg, offs, n_is, ws)
+    n_isects = int(n_is.item())  # output sizes depend on it (gsplat syncs at the same point)
+    keys = torch.empty(max(n_isects, 1), dtype=torch.int64, device=dev)
+    flatten_ids = torch.empty(n_isects, dtype=i32, device=dev)
+    isect_ids = torch.empty(n_isects, dtype=torch.int64, device=dev) if cfg.want_isect_ids else None
+    stages.fused_bin(Q0, radii, N, tw, th, cfg.ty0, cfg.ty1, tile_n_bits(n_tiles), offs, n_isects, keys,
+                     flatten_ids if n_isects else None, ws, isect_ids=isect_ids if n_isects else None)
+    return dict(cfg=cfg, N=N, K_sh=K_sh, n_isects=n_isects, radii=radii, Q0=Q0, Q1=Q1, Q2=Q2, comps=comps,
+                tiles_per_gauss=tpg, tile_offsets=offs, flatten_ids=flatten_ids, isect_ids=isect_ids, ws=ws)
+
+
+def _composite_fwd(s):
+    """Outputs, hit lists and gsl_fused_raster_fwd: (render, alphas, last_ids, hits, hit_counts)."""
+    cfg, n_isects = s["cfg"], s["n_isects"]
+    D, ed, _, tw, th = _geometry(cfg)
+    W, H, dev, f32, i32 = cfg.width, cfg.height, s["Q0"].device, torch.float32, torch.int32
+    make = torch.empty if (cfg.ty0, cfg.ty1) == (0, th) else torch.zeros  # (a strip writes its own tile rows only)
+    render = make(H, W, D, dtype=f32, device=dev)
+    alphas = make(H, W, 1, dtype=f32, device=dev)
+    last_ids = torch.zeros(H, W, dtype=i32, device=dev)
+    # per tile and quadrant: the entries it composited (a hit word holds the list index in 28 bits: none beyond that,
+    # the backward then tests the blocks geometrically)
+    hits = torch.empty(4 * max(n_isects, 1), dtype=i32, device=dev) if max(n_isects, 1) < (1 << 28) else None
+    hit_counts = torch.empty(4 * tw * th + 1, dtype=i32, device=dev) if hits is not None else None
+    stages.fused_raster_fwd(s["Q0"], s["Q1"], s["Q2"], D, int(ed), W, H, tw, th, cfg.ty0, cfg.ty1, s["tile_offsets"],
+                            s["flatten_ids"] if n_isects else None, n_isects, render, alphas, last_ids, 0, H,
+                            isect_hits=hits, isect_hit_counts=hit_counts)
+    return render, alphas, last_ids, hits, hit_counts
+
+
+def _composite_bwd(s, outputs, v_render, v_alphas, want_absgrad: bool = False):
+    """gsl_fused_raster_bwd into a fresh vacc [N,16] and, asked for, gsl_fused_absgrad into a fresh [N,2]: (vacc,
+    absgrad or None).  outputs: what _composite_fwd returned."""
+    cfg, n_isects = s["cfg"], s["n_isects"]
+    D, ed, _, tw, th = _geometry(cfg)
+    render, alphas, last_ids, hits, hit_counts = outputs
+    v_render, v_alphas = v_render.contiguous(), v_alphas.contiguous()
+    lists = (s["tile_offsets"], s["flatten_ids"] if n_isects else None, n_isects, render, alphas, last_ids, v_render,
+             v_alphas)
+    vacc = torch.zeros(s["N"], 16, dtype=torch.float32, device=render.device)
+    stages.fused_raster_bwd(s["Q0"], s["Q1"], s["Q2"], D, int(ed), cfg.width, cfg.height, tw, th, cfg.ty0, cfg.ty1,
+                            *lists, vacc, 0, cfg.height, isect_hits=hits, isect_hit_counts=hit_counts)
+    absgrad = None
+    if want_absgrad:
+        absgrad = torch.zeros(s["N"], 2, dtype=torch.float32, device=render.device)
+        stages.fused_absgrad(s["Q0"], s["Q1"], s["Q2"], D, int(ed), cfg.width, cfg.height, tw, th, *lists, absgrad,
+                             isect_hits=hits, isect_hit_counts=hit_counts)
+    return vacc, absgrad
+
+
+def _project_bwd(s, inputs, vacc, ni):
+    """Gradient tensors, gsl_fused_project_bwd (it consumes vacc), and the needs_input_grad filter: what the backward
+    of a node with the inputs (means, quats, scales, opacities, colors, viewmat, K, cfg, state) returns."""
+    cfg, N = s["cfg"], s["N"]
+    D, _, rgb, tw, th = _geometry(cfg)
+    means, quats, scales, opacities, colors, viewmat, K = inputs
+    dev, f32 = means.device, torch.float32
+    v_means = v_quats = v_scales = v_opac = v_colors = None
+    if any(ni[:5]):
+        v_means = torch.empty(N, 3, dtype=f32, device=dev)
+        v_quats = torch.empty(N, 4, dtype=f32, device=dev)
+        v_scales = torch.empty(N, 3, dtype=f32, device=dev)
+        v_opac = torch.empty(N, dtype=f32, device=dev)
+        if rgb:
+            v_colors = torch.empty_like(colors)
+    v_viewmat = torch.empty(4, 4, dtype=f32, device=dev) if ni[5] else None
+    stages.fused_project_bwd(means, quats, scales, opacities, colors if rgb else None, cfg.sh_degree, s["K_sh"], viewmat,
+                             K, N, cfg.width, cfg.height, cfg.eps2d, int(cfg.antialiased), D, s["radii"], s["Q1"],
+                             s["comps"], vacc, v_means, v_quats, v_scales, v_opac, v_colors, v_viewmat, s["ws"], tw * th, 1)
+    return (v_means if ni[0] else None, v_quats if ni[1] else None, v_scales if ni[2] else None,
+            v_opac if ni[3] else None, v_colors if (ni[4] and rgb) else None, v_viewmat, None, None, None)
 
 
 class _FusedRasterization(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, scales, opacities, colors, viewmat, K, cfg, meta):
-        lib = load_library()
-        (W, H, sh_degree, mode, eps2d, near, far, radius_clip, antialiased, ty0, ty1, want_isect_ids) = cfg
-        D, ed = _MODES[mode]
-        rgb = D >= 3
-        N = means.shape[0]
-        dev = means.device
-        tw, th = (W + 15) // 16, (H + 15) // 16
-        n_tiles = tw * th
-        f32, i32 = torch.float32, torch.int32
-        radii = torch.empty(N, dtype=i32, device=dev)
-        Q0, Q1, Q2 = alloc_records(lib, N, rgb, dev)
-        comps = torch.empty(N, dtype=f32, device=dev) if antialiased else None
-        tpg = torch.empty(N, dtype=i32, device=dev)
-        offs = torch.empty(n_tiles + 1, dtype=i32, device=dev)
-        n_is = torch.empty(1, dtype=i32, device=dev)
-        ws_bytes = lib.gsl_fused_ws_bytes(N, n_tiles)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        st = current_stream()
-        K_sh = colors.shape[1] if (rgb and sh_degree >= 0) else 0
-        check(lib.gsl_fused_project(
-            ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(colors) if rgb else None, sh_degree, K_sh,
-            ptr(viewmat), ptr(K), N, W, H, eps2d, near, far, radius_clip, int(antialiased), tw, th, ty0, ty1,
-            ptr(radii), ptr(Q0), ptr(Q1), ptr(Q2), ptr(comps), ptr(tpg), ptr(offs), ptr(n_is), ptr(ws), ws_bytes,
-            None, None, 0, None, None, st), "gsl_fused_project")  # two-pass binning: tile sizes are not known in advance
-        n_isects = int(n_is.item())  # output sizes depend on it (gsplat syncs at the same point)
-        cap = max(n_isects, 1)
-        keys = torch.empty(cap, dtype=torch.int64, device=dev)
-        flatten_ids = torch.empty(n_isects, dtype=i32, device=dev)
-        isect_ids = torch.empty(n_isects, dtype=torch.int64, device=dev) if want_isect_ids else None
-        check(lib.gsl_fused_bin(ptr(Q0), ptr(radii), N, tw, th, ty0, ty1, tile_n_bits(n_tiles), ptr(offs), n_isects,
-                                ptr(keys), ptr(flatten_ids) if n_isects else None,
-                                ptr(isect_ids) if (want_isect_ids and n_isects) else None, ptr(ws), ws_bytes, 0, None, 0,
-                                None, None, 0, None, None, st), "gsl_fused_bin")
-        render = torch.zeros(H, W, D, dtype=f32, device=dev) if (ty0, ty1) != (0, th) else \
-            torch.empty(H, W, D, dtype=f32, device=dev)
-        alphas = torch.zeros(H, W, 1, dtype=f32, device=dev) if (ty0, ty1) != (0, th) else \
-            torch.empty(H, W, 1, dtype=f32, device=dev)
-        last_ids = torch.zeros(H, W, dtype=i32, device=dev)
-        # per tile and quadrant: the entries it composited (a hit word holds the list index in 28 bits: none beyond that,
-        # the backward then tests the blocks geometrically)
-        hits = torch.empty(4 * cap, dtype=torch.int32, device=dev) if cap < (1 << 28) else None
-        hit_counts = torch.empty(4 * n_tiles + 1, dtype=i32, device=dev) if hits is not None else None
-        check(lib.gsl_fused_raster_fwd(ptr(Q0), ptr(Q1), ptr(Q2), D, int(ed), W, H, tw, th, ty0, ty1, ptr(offs),
-                                       ptr(flatten_ids) if n_isects else None, n_isects, ptr(render), ptr(alphas),
-                                       ptr(last_ids), 0, H, None, None, ptr(hits), ptr(hit_counts), 0, None, 0, None, None,
-                                       None, st),
-              "gsl_fused_raster_fwd")
-        ctx.save_for_backward(means, quats, scales, opacities, colors if rgb else torch.empty(0, device=dev),
-                              viewmat, K, radii, Q0, Q1, Q2 if rgb else torch.empty(0, device=dev),
-                              comps if antialiased else torch.empty(0, device=dev), offs, flatten_ids, render,
-                              alphas, last_ids, ws, hits, hit_counts)
-        ctx.cfg = cfg
-        ctx.n_isects = n_isects
-        ctx.K_sh = K_sh
+        s = _project_and_bin(means, quats, scales, opacities, colors, viewmat, K, cfg)
+        outputs = _composite_fwd(s)
+        ctx.save_for_backward(means, quats, scales, opacities, colors if _geometry(cfg)[2] else None, viewmat, K,
+                              *(s[k] for k in _ARRAYS), *outputs)
+        ctx.scalars = {k: s[k] for k in _SCALARS}
         if meta is not None:
-            meta.update(radii=radii, Q0=Q0, Q1=Q1, Q2=Q2, compensations=comps, tiles_per_gauss=tpg,
-                        tile_offsets=offs, flatten_ids=flatten_ids, isect_ids=isect_ids, n_isects=n_isects,
-                        last_ids=last_ids)
-        ctx.mark_non_differentiable(last_ids)
-        return render, alphas, last_ids
+            meta.update(s, last_ids=outputs[2])
+        ctx.mark_non_differentiable(outputs[2])
+        return outputs[:3]
 
     @staticmethod
     def backward(ctx, v_render, v_alphas, _v_last):
-        lib = load_library()
-        (means, quats, scales, opacities, colors, viewmat, K, radii, Q0, Q1, Q2, comps, offs, flatten_ids, render,
-         alphas, last_ids, ws, hits, hit_counts) = ctx.saved_tensors
-        (W, H, sh_degree, mode, eps2d, near, far, radius_clip, antialiased, ty0, ty1, _) = ctx.cfg
-        D, ed = _MODES[mode]
-        rgb = D >= 3
-        N = means.shape[0]
-        dev = means.device
-        tw, th = (W + 15) // 16, (H + 15) // 16
-        n_tiles = tw * th
-        st = current_stream()
-        f32 = torch.float32
-        v_render = v_render.contiguous()
-        v_alphas = v_alphas.contiguous()
-        vacc = torch.zeros(N, 16, dtype=f32, device=dev)
-        n_isects = ctx.n_isects
-        check(lib.gsl_fused_raster_bwd(ptr(Q0), ptr(Q1), ptr(Q2) if rgb else None, D, int(ed), W, H, tw, th, ty0,
-                                       ty1, ptr(offs), ptr(flatten_ids) if n_isects else None, n_isects,
-                                       ptr(render), ptr(alphas), ptr(last_ids), ptr(v_render), ptr(v_alphas),
-                                       ptr(vacc), 0, H, None, None, ptr(hits), ptr(hit_counts), 0, None, st),
-              "gsl_fused_raster_bwd")
-        ni = ctx.needs_input_grad
-        full = any(ni[:5])
-        v_means = v_quats = v_scales = v_opac = v_colors = None
-        if full:
-            v_means = torch.empty(N, 3, dtype=f32, device=dev)
-            v_quats = torch.empty(N, 4, dtype=f32, device=dev)
-            v_scales = torch.empty(N, 3, dtype=f32, device=dev)
-            v_opac = torch.empty(N, dtype=f32, device=dev)
-            if rgb:
-                v_colors = torch.empty_like(colors)
-        v_viewmat = torch.empty(4, 4, dtype=f32, device=dev) if ni[5] else None
-        ws_bytes = ws.numel()
-        check(lib.gsl_fused_project_bwd(
-            ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(colors) if rgb else None, sh_degree, ctx.K_sh,
-            ptr(viewmat), ptr(K), N, W, H, eps2d, int(antialiased), D, ptr(radii), ptr(Q1),
-            ptr(comps) if antialiased else None, ptr(vacc), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_opac),
-            ptr(v_colors), ptr(v_viewmat), ptr(ws), ws_bytes, n_tiles, None, None, None, None, 0, 0, 0, 0, 0, None, None, 1, None,
-            st),
-            "gsl_fused_project_bwd")
-        return (v_means if ni[0] else None, v_quats if ni[1] else None, v_scales if ni[2] else None,
-                v_opac if ni[3] else None, v_colors if (ni[4] and rgb) else None, v_viewmat, None, None, None)
+        saved = ctx.saved_tensors
+        s = dict(ctx.scalars, **dict(zip(_ARRAYS, saved[7:-5])))
+        vacc, _ = _composite_bwd(s, saved[-5:], v_render, v_alphas)
+        return _project_bwd(s, saved[:7], vacc, ctx.needs_input_grad)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -156,143 +201,39 @@ class _FusedRasterization(torch.autograd.Function):
 class _FusedProjectNode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, scales, opacities, colors, viewmat, K, cfg, state):
-        lib = load_library()
-        (W, H, sh_degree, mode, eps2d, near, far, radius_clip, antialiased, want_isect_ids) = cfg
-        D, _ = _MODES[mode]
-        rgb = D >= 3
-        N = means.shape[0]
-        dev = means.device
-        tw, th = (W + 15) // 16, (H + 15) // 16
-        n_tiles = tw * th
-        f32, i32 = torch.float32, torch.int32
-        radii = torch.empty(N, dtype=i32, device=dev)
-        Q0, Q1, Q2 = alloc_records(lib, N, rgb, dev)
-        comps = torch.empty(N, dtype=f32, device=dev) if antialiased else None
-        tpg = torch.empty(N, dtype=i32, device=dev)
-        offs = torch.empty(n_tiles + 1, dtype=i32, device=dev)
-        n_is = torch.empty(1, dtype=i32, device=dev)
-        ws_bytes = lib.gsl_fused_ws_bytes(N, n_tiles)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        st = current_stream()
-        K_sh = colors.shape[1] if (rgb and sh_degree >= 0) else 0
-        check(lib.gsl_fused_project(
-            ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(colors) if rgb else None, sh_degree, K_sh,
-            ptr(viewmat), ptr(K), N, W, H, eps2d, near, far, radius_clip, int(antialiased), tw, th, 0, th,
-            ptr(radii), ptr(Q0), ptr(Q1), ptr(Q2), ptr(comps), ptr(tpg), ptr(offs), ptr(n_is), ptr(ws), ws_bytes,
-            None, None, 0, None, None, st), "gsl_fused_project")
-        n_isects = int(n_is.item())
-        cap = max(n_isects, 1)
-        keys = torch.empty(cap, dtype=torch.int64, device=dev)
-        flatten_ids = torch.empty(n_isects, dtype=i32, device=dev)
-        isect_ids = torch.empty(n_isects, dtype=torch.int64, device=dev) if want_isect_ids else None
-        check(lib.gsl_fused_bin(ptr(Q0), ptr(radii), N, tw, th, 0, th, tile_n_bits(n_tiles), ptr(offs), n_isects,
-                                ptr(keys), ptr(flatten_ids) if n_isects else None,
-                                ptr(isect_ids) if (want_isect_ids and n_isects) else None, ptr(ws), ws_bytes, 0, None, 0,
-                                None, None, 0, None, None, st), "gsl_fused_bin")
-        state.update(cfg=cfg, N=N, D=D, tw=tw, th=th, n_isects=n_isects, K_sh=K_sh, radii=radii, Q0=Q0, Q1=Q1, Q2=Q2,
-                     comps=comps, tiles_per_gauss=tpg, tile_offsets=offs, flatten_ids=flatten_ids, isect_ids=isect_ids,
-                     ws=ws, vacc=None)
-        ctx.save_for_backward(means, quats, scales, opacities, colors if rgb else torch.empty(0, device=dev), viewmat, K)
+        _, _, rgb, _, th = _geometry(cfg)
+        assert (cfg.ty0, cfg.ty1) == (0, th), "absgrad renders whole frames only (gsl_fused_absgrad)"
+        state.update(_project_and_bin(means, quats, scales, opacities, colors, viewmat, K, cfg), vacc=None)
+        ctx.save_for_backward(means, quats, scales, opacities, colors if rgb else None, viewmat, K)
         ctx.state = state
-        return Q0[None, :, 0:2].clone()
+        return state["Q0"][None, :, 0:2].clone()
 
     @staticmethod
     def backward(ctx, v_means2d):
-        lib = load_library()
         s = ctx.state
-        means, quats, scales, opacities, colors, viewmat, K = ctx.saved_tensors
-        (W, H, sh_degree, mode, eps2d, _, _, _, antialiased, _) = s["cfg"]
-        D, N = s["D"], s["N"]
-        rgb = D >= 3
-        dev = means.device
-        f32 = torch.float32
-        vacc = s["vacc"]
-        s["vacc"] = None
+        vacc, s["vacc"] = s["vacc"], None
         if vacc is None:  # (nothing was composited into the loss: means2d is all the gradient there is)
-            vacc = torch.zeros(N, 16, dtype=f32, device=dev)
+            vacc = torch.zeros(s["N"], 16, dtype=torch.float32, device=v_means2d.device)
         vacc[:, 0:2].copy_(v_means2d[0])
-        ni = ctx.needs_input_grad
-        full = any(ni[:5])
-        v_means = v_quats = v_scales = v_opac = v_colors = None
-        if full:
-            v_means = torch.empty(N, 3, dtype=f32, device=dev)
-            v_quats = torch.empty(N, 4, dtype=f32, device=dev)
-            v_scales = torch.empty(N, 3, dtype=f32, device=dev)
-            v_opac = torch.empty(N, dtype=f32, device=dev)
-            if rgb:
-                v_colors = torch.empty_like(colors)
-        v_viewmat = torch.empty(4, 4, dtype=f32, device=dev) if ni[5] else None
-        ws = s["ws"]
-        comps = s["comps"]
-        check(lib.gsl_fused_project_bwd(
-            ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(colors) if rgb else None, sh_degree, s["K_sh"],
-            ptr(viewmat), ptr(K), N, W, H, eps2d, int(antialiased), D, ptr(s["radii"]), ptr(s["Q1"]),
-            ptr(comps) if antialiased else None, ptr(vacc), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_opac),
-            ptr(v_colors), ptr(v_viewmat), ptr(ws), ws.numel(), s["tw"] * s["th"], None, None, None, None, 0, 0, 0, 0, 0,
-            None, None, 1, None, current_stream()),
-            "gsl_fused_project_bwd")
-        return (v_means if ni[0] else None, v_quats if ni[1] else None, v_scales if ni[2] else None,
-                v_opac if ni[3] else None, v_colors if (ni[4] and rgb) else None, v_viewmat, None, None, None)
+        return _project_bwd(s, ctx.saved_tensors, vacc, ctx.needs_input_grad)
 
 
 class _FusedCompositeNode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2d, state):
-        lib = load_library()
-        s = state
-        (W, H, _, mode, _, _, _, _, _, _) = s["cfg"]
-        D, ed = _MODES[mode]
-        tw, th = s["tw"], s["th"]
-        n_isects = s["n_isects"]
-        dev = means2d.device
-        f32, i32 = torch.float32, torch.int32
-        cap = max(n_isects, 1)
-        render = torch.empty(H, W, D, dtype=f32, device=dev)
-        alphas = torch.empty(H, W, 1, dtype=f32, device=dev)
-        last_ids = torch.zeros(H, W, dtype=i32, device=dev)
-        hits = torch.empty(4 * cap, dtype=torch.int32, device=dev) if cap < (1 << 28) else None
-        hit_counts = torch.empty(4 * tw * th + 1, dtype=i32, device=dev) if hits is not None else None
-        flatten_ids = s["flatten_ids"]
-        check(lib.gsl_fused_raster_fwd(ptr(s["Q0"]), ptr(s["Q1"]), ptr(s["Q2"]), D, int(ed), W, H, tw, th, 0, th,
-                                       ptr(s["tile_offsets"]), ptr(flatten_ids) if n_isects else None, n_isects,
-                                       ptr(render), ptr(alphas), ptr(last_ids), 0, H, None, None, ptr(hits),
-                                       ptr(hit_counts), 0, None, 0, None, None, None, current_stream()),
-              "gsl_fused_raster_fwd")
-        s["last_ids"] = last_ids
-        ctx.save_for_backward(means2d, render, alphas, last_ids, hits, hit_counts)
+        outputs = _composite_fwd(state)
+        state["last_ids"] = outputs[2]
+        ctx.save_for_backward(means2d, *outputs)
         ctx.state = state
-        ctx.mark_non_differentiable(last_ids)
-        return render, alphas, last_ids
+        ctx.mark_non_differentiable(outputs[2])
+        return outputs[:3]
 
     @staticmethod
     def backward(ctx, v_render, v_alphas, _v_last):
-        lib = load_library()
-        s = ctx.state
-        means2d, render, alphas, last_ids, hits, hit_counts = ctx.saved_tensors
-        (W, H, _, mode, _, _, _, _, _, _) = s["cfg"]
-        D, ed = _MODES[mode]
-        rgb = D >= 3
-        N, tw, th, n_isects = s["N"], s["tw"], s["th"], s["n_isects"]
-        dev = means2d.device
-        st = current_stream()
-        v_render = v_render.contiguous()
-        v_alphas = v_alphas.contiguous()
-        Q0, Q1, Q2 = s["Q0"], s["Q1"], s["Q2"] if rgb else None
-        offs, flatten_ids = s["tile_offsets"], s["flatten_ids"]
-        vacc = torch.zeros(N, 16, dtype=torch.float32, device=dev)
-        check(lib.gsl_fused_raster_bwd(ptr(Q0), ptr(Q1), ptr(Q2), D, int(ed), W, H, tw, th, 0, th, ptr(offs),
-                                       ptr(flatten_ids) if n_isects else None, n_isects, ptr(render), ptr(alphas),
-                                       ptr(last_ids), ptr(v_render), ptr(v_alphas), ptr(vacc), 0, H, None, None,
-                                       ptr(hits), ptr(hit_counts), 0, None, st),
-              "gsl_fused_raster_bwd")
-        absgrad = torch.zeros(N, 2, dtype=torch.float32, device=dev)
-        check(lib.gsl_fused_absgrad(ptr(Q0), ptr(Q1), ptr(Q2), D, int(ed), W, H, tw, th, ptr(offs),
-                                    ptr(flatten_ids) if n_isects else None, n_isects, ptr(render), ptr(alphas),
-                                    ptr(last_ids), ptr(v_render), ptr(v_alphas), ptr(hits), ptr(hit_counts),
-                                    ptr(absgrad), st),
-              "gsl_fused_absgrad")
+        means2d, *outputs = ctx.saved_tensors
+        vacc, absgrad = _composite_bwd(ctx.state, outputs, v_render, v_alphas, want_absgrad=True)
         means2d.absgrad = absgrad[None]  # assigned by every backward, as gsplat does
-        s["vacc"] = vacc  # the projection node's backward consumes it
+        ctx.state["vacc"] = vacc  # the projection node's backward consumes it
         return vacc[None, :, 0:2].clone(), None
 
 
@@ -304,28 +245,12 @@ def fused_absgrad_rasterization(
 ) -> Tuple[Tensor, Tensor, Dict]:
     """fused_rasterization (whole frame) with meta["means2d"] [1,N,2] in the autograd graph between projection and
     compositing: after a backward it carries ``.absgrad`` (and ``.grad`` when retained), as gsplat's absgrad=True."""
-    def prep(t, name):
-        assert t.is_cuda, f"{name} must live on the GPU (got {t.device}); there is no CPU path"
-        assert t.dtype == torch.float32, f"{name} must be float32 (got {t.dtype})"
-        return t.contiguous()
-
-    cfg = (int(width), int(height), -1 if sh_degree is None else int(sh_degree), render_mode, float(eps2d),
-           float(near_plane), float(far_plane), float(radius_clip), bool(antialiased), bool(want_isect_ids))
+    cfg = _make_cfg(width, height, sh_degree, render_mode, eps2d, near_plane, far_plane, radius_clip, antialiased, None,
+                    want_isect_ids)
     render, alphas, means2d, s = fused_absgrad_apply(
         prep(means, "means"), prep(quats, "quats"), prep(scales, "scales"), prep(opacities, "opacities"),
         prep(colors, "colors"), prep(viewmat, "viewmats"), prep(K, "Ks"), cfg)
-    tw, th = s["tw"], s["th"]
-    Q0, Q1 = s["Q0"], s["Q1"]
-    meta = {
-        "camera_ids": None, "gaussian_ids": None,
-        "radii": s["radii"][None], "means2d": means2d, "depths": Q0[None, :, 2],
-        "conics": Q1[None, :, 0:3], "opacities": Q0[None, :, 3],
-        "tile_width": tw, "tile_height": th, "tiles_per_gauss": s["tiles_per_gauss"][None],
-        "isect_ids": s["isect_ids"], "flatten_ids": s["flatten_ids"],
-        "isect_offsets": s["tile_offsets"][:-1].reshape(1, th, tw), "width": width, "height": height,
-        "tile_size": 16, "n_cameras": 1,
-    }
-    return render, alphas, meta
+    return render, alphas, _gsplat_meta(width, height, s, means2d)
 
 
 def fused_absgrad_apply(means, quats, scales, opacities, colors, viewmat, K, cfg):
@@ -388,8 +313,9 @@ class _CachedRasterization(torch.autograd.Function):
         ctx.save_for_backward(means, quats, scales, opacities, colors if rc.rgb else torch.empty(0, device=dev), viewmat, K,
                               rc.render, rc.alphas, rc.last_ids)
         if meta is not None:
-            meta.update(radii=rc.radii, Q0=rc.Q0, Q1=rc.Q1, offs=rc.offs, flatten_ids=rc.flatten_ids[:rc.last_n_isects],
-                        n_isects=rc.last_n_isects, last_ids=rc.last_ids, tiles_per_gauss=rc.tiles_per_gauss)
+            meta.update(radii=rc.radii, Q0=rc.Q0, Q1=rc.Q1, tile_offsets=rc.offs, n_isects=rc.last_n_isects,
+                        flatten_ids=rc.flatten_ids[:rc.last_n_isects], last_ids=rc.last_ids,
+                        tiles_per_gauss=rc.tiles_per_gauss)
         ctx.mark_non_differentiable(rc.last_ids)
         return rc.render, rc.alphas, rc.last_ids
 
@@ -434,11 +360,6 @@ def cached_rasterization(means, quats, scales, opacities, colors, viewmat, K, wi
     call with the same signature (GsplatLoc never reads them); isect_ids is not produced."""
     from .context import RenderContext
 
-    def prep(t, name):
-        assert t.is_cuda, f"{name} must live on the GPU (got {t.device}); there is no CPU path"
-        assert t.dtype == torch.float32, f"{name} must be float32 (got {t.dtype})"
-        return t.contiguous()
-
     N = means.shape[0]
     D, _ = _MODES[render_mode]
     rgb = D >= 3
@@ -461,18 +382,7 @@ def cached_rasterization(means, quats, scales, opacities, colors, viewmat, K, wi
     render, alphas, _ = _CachedRasterization.apply(
         prep(means, "means"), prep(quats, "quats"), prep(scales, "scales"), prep(opacities, "opacities"),
         prep(colors, "colors") if rgb else colors, prep(viewmat, "viewmats"), prep(K, "Ks"), rc, raw)
-    tw, th = rc.tw, rc.th
-    Q0, Q1 = raw["Q0"], raw["Q1"]
-    meta = {
-        "camera_ids": None, "gaussian_ids": None,
-        "radii": raw["radii"][None], "means2d": Q0[None, :, 0:2], "depths": Q0[None, :, 2],
-        "conics": Q1[None, :, 0:3], "opacities": Q0[None, :, 3],
-        "tile_width": tw, "tile_height": th, "tiles_per_gauss": raw["tiles_per_gauss"][None],
-        "isect_ids": None, "flatten_ids": raw["flatten_ids"],
-        "isect_offsets": raw["offs"][:-1].reshape(1, th, tw), "width": width, "height": height,
-        "tile_size": 16, "n_cameras": 1,
-    }
-    return render, alphas, meta
+    return render, alphas, _gsplat_meta(width, height, raw)
 
 
 def fused_supported(N: int, C: int, colors: Tensor, sh_degree: Optional[int], width: int, height: int,
@@ -497,29 +407,10 @@ def fused_rasterization(
     tile_rows: Optional[Tuple[int, int]] = None, want_isect_ids: bool = True,
 ) -> Tuple[Tensor, Tensor, Dict]:
     """One camera.  Returns render [H,W,X], alphas [H,W,1], meta (gsplat keys, [1,N,...] views)."""
-    def prep(t, name):
-        assert t.is_cuda, f"{name} must live on the GPU (got {t.device}); there is no CPU path"
-        assert t.dtype == torch.float32, f"{name} must be float32 (got {t.dtype})"
-        return t.contiguous()
-
-    tw, th = (width + 15) // 16, (height + 15) // 16
-    ty0, ty1 = tile_rows if tile_rows is not None else (0, th)
-    assert 0 <= ty0 <= ty1 <= th, (ty0, ty1, th)
-    cfg = (int(width), int(height), -1 if sh_degree is None else int(sh_degree), render_mode, float(eps2d),
-           float(near_plane), float(far_plane), float(radius_clip), bool(antialiased), int(ty0), int(ty1),
-           bool(want_isect_ids))
+    cfg = _make_cfg(width, height, sh_degree, render_mode, eps2d, near_plane, far_plane, radius_clip, antialiased,
+                    tile_rows, want_isect_ids)
     raw: Dict = {}
     render, alphas, _ = _FusedRasterization.apply(
         prep(means, "means"), prep(quats, "quats"), prep(scales, "scales"), prep(opacities, "opacities"),
         prep(colors, "colors"), prep(viewmat, "viewmats"), prep(K, "Ks"), cfg, raw)
-    Q0, Q1 = raw["Q0"], raw["Q1"]
-    meta = {
-        "camera_ids": None, "gaussian_ids": None,
-        "radii": raw["radii"][None], "means2d": Q0[None, :, 0:2], "depths": Q0[None, :, 2],
-        "conics": Q1[None, :, 0:3], "opacities": Q0[None, :, 3],
-        "tile_width": tw, "tile_height": th, "tiles_per_gauss": raw["tiles_per_gauss"][None],
-        "isect_ids": raw["isect_ids"], "flatten_ids": raw["flatten_ids"],
-        "isect_offsets": raw["tile_offsets"][:-1].reshape(1, th, tw), "width": width, "height": height,
-        "tile_size": 16, "n_cameras": 1,
-    }
-    return render, alphas, meta
+    return render, alphas, _gsplat_meta(width, height, raw)

@@ -13,8 +13,46 @@ def _declared(repo_root):
     return sorted(set(re.findall(r"\b(gsl_[a-z_0-9]+)\s*\(", txt)))
 
 
+def prototypes(repo_root):
+    """Every prototype of include/gsloc_hip.h: {name: (return type, [(parameter type, parameter name), ...])}, the types
+    as C text without the parameter's name (``const float*``, ``int64_t``)."""
+    txt = open(os.path.join(repo_root, "include", "gsloc_hip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"^\s*#.*$", "", txt, flags=re.M)
+    out = {}
+    for stmt in txt.split(";"):
+        m = re.search(r"([\w\s\*]+?)\b(gsl_[a-z_0-9]+)\s*\((.*)\)\s*$", stmt.split("{")[-1], flags=re.S)
+        if not m:
+            continue
+        params = [] if m.group(3).strip() == "void" else [
+            re.fullmatch(r"\s*(.*?)\s*(\w+)\s*", p, flags=re.S).groups() for p in m.group(3).split(",")]
+        out[m.group(2)] = (" ".join(m.group(1).split()), [(" ".join(t.split()), n) for t, n in params])
+    return out
+
+
+def _ctype(c_type):
+    """The ctypes type the binding uses for a C type of the header: every pointer travels as void* (a returned string
+    as char*), scalars as themselves."""
+    import ctypes
+
+    if "*" in c_type:
+        return ctypes.c_char_p if "char" in c_type else ctypes.c_void_p
+    return {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+            "double": ctypes.c_double, "uint32_t": ctypes.c_uint32}[c_type]
+
+
 def test_header_and_binding_agree(repo_root):
+    """_lib._SIGNATURES against the header: the same functions, and for each the same return type and the same
+    parameter types in the same number and order."""
     assert _declared(repo_root) == _lib.exported_symbols()
+    protos = prototypes(repo_root)
+    assert sorted(protos) == _lib.exported_symbols()
+    for name, (ret, params) in protos.items():
+        res, args = _lib._SIGNATURES[name]
+        assert res is _ctype(ret), (name, ret, res)
+        assert len(args) == len(params), (name, len(args), len(params))
+        for i, ((c_type, pname), arg) in enumerate(zip(params, args)):
+            assert arg is _ctype(c_type), (name, i, pname, c_type, arg)
 
 
 def test_headers_are_plain_c(repo_root):

@@ -92,6 +92,7 @@ def _scene(N, W, H):
 def test_fused_absgrad_nodes_marshal(mode, sh_degree, monkeypatch):
     """The two autograd nodes of rendering.rasterization(absgrad=True) on the fused path, forward and backward."""
     import gsplatloc_amd.fused as F
+    import gsplatloc_amd.stages as ST
 
     calls = []
 
@@ -99,8 +100,8 @@ def test_fused_absgrad_nodes_marshal(mode, sh_degree, monkeypatch):
         calls.append(what)
         assert status in (0, -3), (what, status)
 
-    monkeypatch.setattr(F, "check", refused)
-    monkeypatch.setattr(F, "current_stream", lambda: None)
+    monkeypatch.setattr(ST, "check", refused)
+    monkeypatch.setattr(ST, "current_stream", lambda: None)
     monkeypatch.setattr(torch, "empty", torch.zeros)  # the intersection count is read back from an output buffer
     N, W, H = 300, 64, 48
     sc, V = _scene(N, W, H)
@@ -108,7 +109,9 @@ def test_fused_absgrad_nodes_marshal(mode, sh_degree, monkeypatch):
     ins = [sc[k].clone().requires_grad_() for k in ("means", "quats", "scales", "opacities")]
     col = colors.clone().requires_grad_()
     V = V.requires_grad_()
-    cfg = (W, H, -1 if sh_degree is None else sh_degree, mode, 0.3, 0.01, 1e10, 0.0, False, True)
+    cfg = F.FusedCfg(width=W, height=H, sh_degree=-1 if sh_degree is None else sh_degree, mode=mode, eps2d=0.3,
+                     near_plane=0.01, far_plane=1e10, radius_clip=0.0, antialiased=False, ty0=0, ty1=3,
+                     want_isect_ids=True)
     render, alphas, means2d, state = F.fused_absgrad_apply(*ins, col, V, sc["K"].contiguous(), cfg)
     assert render.shape == (H, W, F._MODES[mode][0]) and alphas.shape == (H, W, 1)
     assert means2d.shape == (1, N, 2) and means2d.requires_grad and means2d.grad_fn is not None
@@ -125,16 +128,18 @@ def test_fused_absgrad_nodes_marshal(mode, sh_degree, monkeypatch):
 @no_gpu
 def test_fused_absgrad_nodes_under_no_grad(monkeypatch):
     import gsplatloc_amd.fused as F
+    import gsplatloc_amd.stages as ST
 
-    monkeypatch.setattr(F, "check", lambda status, what: None)
-    monkeypatch.setattr(F, "current_stream", lambda: None)
+    monkeypatch.setattr(ST, "check", lambda status, what: None)
+    monkeypatch.setattr(ST, "current_stream", lambda: None)
     monkeypatch.setattr(torch, "empty", torch.zeros)
     N, W, H = 100, 32, 32
     sc, V = _scene(N, W, H)
+    cfg = F.FusedCfg(width=W, height=H, sh_degree=-1, mode="RGB", eps2d=0.3, near_plane=0.01, far_plane=1e10,
+                     radius_clip=0.0, antialiased=False, ty0=0, ty1=2, want_isect_ids=True)
     with torch.no_grad():
         render, alphas, means2d, _ = F.fused_absgrad_apply(sc["means"], sc["quats"], sc["scales"], sc["opacities"],
-                                                           torch.rand(N, 3), V, sc["K"].contiguous(),
-                                                           (W, H, -1, "RGB", 0.3, 0.01, 1e10, 0.0, False, True))
+                                                           torch.rand(N, 3), V, sc["K"].contiguous(), cfg)
     assert not means2d.requires_grad and not hasattr(means2d, "absgrad")
 
 

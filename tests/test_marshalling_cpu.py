@@ -19,9 +19,10 @@ def _expect_hip_refusal(fn, what):
                                                        ("RGB+ED", True, True, (15, 48)), ("RGB", True, False, (16, 33))])
 def test_render_context_stage_calls_marshal(mode, full, tiny, pixel_rows, monkeypatch):
     import gsplatloc_amd.context as CX
+    import gsplatloc_amd.stages as ST
     from gsplatloc_amd.synthetic import perturbed_pose, random_scene
 
-    monkeypatch.setattr(CX, "current_stream", lambda: None)
+    monkeypatch.setattr(ST, "current_stream", lambda: None)
     N, W, H = 500, 64, 48
     rows = (0, 3) if pixel_rows == (15, 48) else (1, 3)
     ctx = CX.RenderContext(N, W, H, mode, sh_degree=1, K_sh=4, device="cpu", full_grads=full, tile_rows=rows,
@@ -87,8 +88,8 @@ def test_tracker_kernel_calls_marshal():
 def test_graph_tracker_iteration_marshals_every_call(monkeypatch):
     """GraphTracker.load_frame() and one _iteration() on host tensors: every C call is reached (the status check
     is relaxed to 'refused by the HIP runtime') and none is rejected by ctypes or by argument validation."""
-    import gsplatloc_amd.context as CX
     import gsplatloc_amd.graph_tracker as GT
+    import gsplatloc_amd.stages as ST
     from gsplatloc_amd.my_gsplat import TrackerConfig
     from gsplatloc_amd.synthetic import frame_pair
 
@@ -102,9 +103,9 @@ def test_graph_tracker_iteration_marshals_every_call(monkeypatch):
         def __init__(self, *a, **k):
             pass
 
-    monkeypatch.setattr(CX, "current_stream", lambda: None)
+    monkeypatch.setattr(ST, "current_stream", lambda: None)
     monkeypatch.setattr(GT, "current_stream", lambda: None)
-    monkeypatch.setattr(CX, "check", refused)
+    monkeypatch.setattr(ST, "check", refused)
     monkeypatch.setattr(GT, "check", refused)
     monkeypatch.setattr(torch.cuda, "Stream", _Stream)
     W, H = 64, 48
@@ -135,6 +136,7 @@ def test_graph_tracker_iteration_marshals_every_call(monkeypatch):
 def test_fused_autograd_function_marshals(mode, sh_degree, monkeypatch):
     """The gsplat-compatible entry's autograd function (fused.py), forward and backward, on host tensors."""
     import gsplatloc_amd.fused as F
+    import gsplatloc_amd.stages as ST
     from gsplatloc_amd.synthetic import perturbed_pose, random_scene
 
     calls = []
@@ -143,8 +145,8 @@ def test_fused_autograd_function_marshals(mode, sh_degree, monkeypatch):
         calls.append(what)
         assert status in (0, -3), (what, status)
 
-    monkeypatch.setattr(F, "check", refused)
-    monkeypatch.setattr(F, "current_stream", lambda: None)
+    monkeypatch.setattr(ST, "check", refused)
+    monkeypatch.setattr(ST, "current_stream", lambda: None)
     monkeypatch.setattr(torch, "empty", torch.zeros)  # the intersection count is read back from an output buffer
     N, W, H = 300, 64, 48
     sc = random_scene(N, W, H, sigma_px=1.0)
@@ -152,7 +154,9 @@ def test_fused_autograd_function_marshals(mode, sh_degree, monkeypatch):
     ins = [sc[k].clone().requires_grad_() for k in ("means", "quats", "scales", "opacities")]
     col = colors.clone().requires_grad_()
     V = torch.linalg.inv(perturbed_pose()).contiguous().requires_grad_()
-    cfg = (W, H, -1 if sh_degree is None else sh_degree, mode, 0.3, 0.01, 1e10, 0.0, False, 0, 3, True)
+    cfg = F.FusedCfg(width=W, height=H, sh_degree=-1 if sh_degree is None else sh_degree, mode=mode, eps2d=0.3,
+                     near_plane=0.01, far_plane=1e10, radius_clip=0.0, antialiased=False, ty0=0, ty1=3,
+                     want_isect_ids=True)
     raw = {}
     render, alphas, last = F._FusedRasterization.apply(*ins, col, V, sc["K"].contiguous(), cfg, raw)
     assert render.shape == (H, W, F._MODES[mode][0]) and alphas.shape == (H, W, 1) and last.shape == (H, W)
@@ -171,9 +175,9 @@ def test_sequence_evaluation_cli_on_host_tensors(tmp_path, monkeypatch, capsys):
     import functools
     import json
 
-    import gsplatloc_amd.context as CX
     import gsplatloc_amd.eval as EV
     import gsplatloc_amd.graph_tracker as GT
+    import gsplatloc_amd.stages as ST
     from gsplatloc_amd.data import Parser
     from tests.test_data import write_replica
 
@@ -184,9 +188,9 @@ def test_sequence_evaluation_cli_on_host_tensors(tmp_path, monkeypatch, capsys):
         def __init__(self, *a, **k):
             pass
 
-    monkeypatch.setattr(CX, "current_stream", lambda: None)
+    monkeypatch.setattr(ST, "current_stream", lambda: None)
     monkeypatch.setattr(GT, "current_stream", lambda: None)
-    monkeypatch.setattr(CX, "check", refused)
+    monkeypatch.setattr(ST, "check", refused)
     monkeypatch.setattr(GT, "check", refused)
     monkeypatch.setattr(torch.cuda, "Stream", _Stream)
     monkeypatch.setattr(EV, "Parser", functools.partial(Parser, device="cpu"))
@@ -204,8 +208,8 @@ GROUP_RANK = r"""
 import os, sys
 sys.path.insert(0, sys.argv[1])
 import torch, torch.distributed as dist
-import gsplatloc_amd.context as CX
 import gsplatloc_amd.graph_tracker as GT
+import gsplatloc_amd.stages as ST
 from gsplatloc_amd.my_gsplat import TrackerConfig
 from gsplatloc_amd.my_gsplat.geometry import depth_to_points
 from gsplatloc_amd.synthetic import frame_pair
@@ -216,8 +220,8 @@ def refused(status, what):
     assert status in (0, -3), (what, status)
 class _Stream:
     def __init__(self, *a, **k): pass
-CX.current_stream = GT.current_stream = lambda: None
-CX.check = GT.check = refused
+ST.current_stream = GT.current_stream = lambda: None
+ST.check = GT.check = refused
 torch.cuda.Stream = _Stream
 dist.init_process_group("gloo")
 rank, world = dist.get_rank(), dist.get_world_size()
