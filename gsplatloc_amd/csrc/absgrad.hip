@@ -21,7 +21,7 @@
 // evaluates alpha with the operations of the fused forward (raster_px.hip); the staged one reads the SoA arrays of
 // gsl_rasterize_fwd (any channel count it supports, backgrounds) with that forward's operations (raster.hip).  Both
 // take the forward's alpha >= 1/255 decision for every (pixel, entry) pair.
-#include "gsloc_common.h"
+#include "gsloc_internal.h"
 
 namespace gsl {
 
@@ -73,11 +73,10 @@ __global__ __launch_bounds__(256) void k_absgrad(
   const float Aimg = inside ? alphas[pid] : 0.f;
   const float T_final = 1.f - Aimg;
   float va = inside ? v_alphas[pid] : 0.f;
-  if (FUSED && ED && inside) {  // expected depth: d/d(depth sum) = v / alpha, and -v ed / alpha on alpha
-    const float dn = render[pid * D + (D - 1)];
-    const float vd = vc[D - 1];
-    if (Aimg >= 1e-10f) va += -vd * dn / Aimg;
-    vc[D - 1] = vd / fmaxf(Aimg, 1e-10f);
+  if (FUSED && ED && inside) {
+    const EdGrad g = ed_backward(Aimg, render[pid * D + (D - 1)], va, vc[D - 1]);
+    va = g.va;
+    vc[D - 1] = g.vd;
   }
   float Bp = -T_final * va;  // v_alpha = T c.v - (buf.v + this) / (1 - alpha): the alpha and background terms
   if (!FUSED && backgrounds) {
@@ -224,9 +223,8 @@ extern "C" int gsl_fused_absgrad(const float* Q0, const float* Q1, const float* 
                                  const int32_t* last_ids, const float* v_render, const float* v_alphas,
                                  const uint32_t* isect_hits, const int32_t* isect_hit_counts, float* absgrad,
                                  void* stream) {
+  if (!gsl::frame_ok(width, height, tile_w, tile_h, 0, tile_h, capacity, 0, height)) return GSL_ERR_BAD_ARG;  // (whole frame)
   if (!(channels == 1 || channels == 3 || channels == 4) || (ed && channels == 3)) return GSL_ERR_BAD_ARG;
-  if (width <= 0 || height <= 0 || tile_w <= 0 || tile_h <= 0 || capacity < 0) return GSL_ERR_BAD_ARG;
-  if (tile_w * 16 < width || tile_h * 16 < height) return GSL_ERR_BAD_ARG;
   if (!tile_offsets || !alphas || !last_ids || !v_render || !v_alphas || !absgrad) return GSL_ERR_BAD_ARG;
   if (ed && !render) return GSL_ERR_BAD_ARG;
   if ((isect_hits == nullptr) != (isect_hit_counts == nullptr)) return GSL_ERR_BAD_ARG;
@@ -239,9 +237,7 @@ extern "C" int gsl_fused_absgrad(const float* Q0, const float* Q1, const float* 
                      (const float4*)Q1, (const float4*)Q2, nullptr, nullptr, nullptr, nullptr, nullptr, width, height, \
                      tile_w, tile_offsets, flatten_ids, (long long)capacity, render, alphas, last_ids, v_render,      \
                      v_alphas, isect_hits, isect_hit_counts, absgrad)
-  if (channels == 1) { if (ed) CALL_AB(1, true); else CALL_AB(1, false); }
-  else if (channels == 3) CALL_AB(3, false);
-  else { if (ed) CALL_AB(4, true); else CALL_AB(4, false); }
+  GSL_DISPATCH_CH_ED(channels, ed, CALL_AB)
 #undef CALL_AB
   GSL_CHECK_LAUNCH();
   return GSL_OK;
@@ -253,13 +249,12 @@ extern "C" int gsl_rasterize_absgrad(const float* means2d, const float* conics, 
                                      const int32_t* flatten_ids, int64_t capacity, const float* render_alphas,
                                      const int32_t* last_ids, const float* v_render_colors,
                                      const float* v_render_alphas, float* absgrad, void* stream) {
+  if (!gsl::frame_ok(width, height, tile_w, tile_h, 0, tile_h, capacity, 0, height)) return GSL_ERR_BAD_ARG;  // (whole frame)
   if (tile_size != 16) return GSL_ERR_BAD_ARG;
   switch (channels) {
     case 1: case 2: case 3: case 4: case 5: case 8: case 16: case 32: break;
     default: return GSL_ERR_BAD_ARG;
   }
-  if (width <= 0 || height <= 0 || tile_w <= 0 || tile_h <= 0 || capacity < 0) return GSL_ERR_BAD_ARG;
-  if (tile_w * 16 < width || tile_h * 16 < height) return GSL_ERR_BAD_ARG;
   if (!tile_offsets || !render_alphas || !last_ids || !v_render_colors || !v_render_alphas || !absgrad)
     return GSL_ERR_BAD_ARG;
   if (capacity > 0 && (!means2d || !conics || !colors || !opacities || !flatten_ids)) return GSL_ERR_BAD_ARG;

@@ -12,8 +12,10 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
-#include "gsloc_common.h"
+#include "gsloc_internal.h"
+#include "long_dev.h"
 #include "sort_dev.h"
+#include "tile_dev.h"
 
 namespace gsl {
 
@@ -291,7 +293,7 @@ __device__ __forceinline__ void bitonic_sort_lds(uint64_t* a, int n, int tid) {
       }
     }
     if (k > S) __syncthreads();
-    else { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+    else wave_lds_fence();
     for (int lj = lk - 2; lj >= 0; --lj) {  // distance j = 2^lj
       int j = 1 << lj;
       if (work) {
@@ -308,7 +310,7 @@ __device__ __forceinline__ void bitonic_sort_lds(uint64_t* a, int n, int tid) {
       // a barrier is needed whenever this or the next sub-step crosses wave segments
       bool cross = (2 * j > S) || (j > 1 ? (j > S) : (2 * k > S));
       if (cross) __syncthreads();
-      else { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+      else wave_lds_fence();
     }
   }
   __syncthreads();
@@ -553,7 +555,6 @@ __global__ __launch_bounds__(256) void k_isect_offsets(const int64_t* __restrict
   }
 }
 
-
 // ------------------------------------------------------------------------------------------------
 // Sort of a LONG tile list by several workgroups (binned mode).  One workgroup sorted such a list block-wise in 1.6 ms
 // (23 k keys: the pile of invalid TUM points) -- after the compositing of that list had been split
@@ -664,7 +665,6 @@ __global__ __launch_bounds__(64) void k_long_merge(const int32_t* __restrict__ t
     if (last) flatten_ids[s + pair_start + o + d] = list_id(storage_of, v);
   }
 }
-
 
 // Same contract as k_tile_sort (offsets from the counters in binned mode, overflow flags, long lists left to
 // gsl_long_sort), one tile per workgroup.
@@ -791,12 +791,6 @@ extern "C" int gsl_isect_fill(const float* means2d, const int32_t* radii, const 
                        cam_enc, stream);
 }
 
-extern "C" int gsl_tile_sort_keys(int32_t* tile_offsets, int tile_begin, int n_strip_tiles, int64_t capacity,
-                                  uint64_t* sort_keys, int32_t* flatten_ids, int64_t* isect_ids, int64_t cam_enc,
-                                  int write_sorted_keys, uint64_t* bins, int bin_cap, const int32_t* counts,
-                                  int32_t* n_isects, int32_t* flags, int long_min, int occupied_tiles,
-                                  const int32_t* storage_of, void* stream);
-
 namespace gsl {
 // launches of k_tile_sort<4>, k_tile_sort<5>, k_tile_sort_wg issued by this process (host-side diagnostics for the
 // tests: which tile-sort kernel a call ran; gsl_dev_tile_sort_launches)
@@ -814,17 +808,14 @@ extern "C" int gsl_tile_sort(const int32_t* tile_offsets, int tile_begin, int n_
   if (!tile_offsets || tile_begin < 0 || n_strip_tiles < 0 || capacity < 0) return GSL_ERR_BAD_ARG;
   if (n_strip_tiles == 0 || capacity == 0) return GSL_OK;
   if (!sort_keys || !flatten_ids) return GSL_ERR_BAD_ARG;
-  return gsl_tile_sort_keys(const_cast<int32_t*>(tile_offsets), tile_begin, n_strip_tiles, capacity, sort_keys, flatten_ids,
-                            isect_ids, cam_enc, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
+  return gsl::tile_sort_keys(const_cast<int32_t*>(tile_offsets), tile_begin, n_strip_tiles, capacity, sort_keys, flatten_ids,
+                             isect_ids, cam_enc, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
 }
 
-// gsl_tile_sort that can also leave the sorted (depth bits, id) keys in sort_keys and read the unsorted keys from
-// fixed-capacity per-tile bins instead of sort_keys (internal: gsl_fused_bin)
-extern "C" int gsl_tile_sort_keys(int32_t* tile_offsets, int tile_begin, int n_strip_tiles, int64_t capacity,
-                                  uint64_t* sort_keys, int32_t* flatten_ids, int64_t* isect_ids, int64_t cam_enc,
-                                  int write_sorted_keys, uint64_t* bins, int bin_cap, const int32_t* counts,
-                                  int32_t* n_isects, int32_t* flags, int long_min, int occupied_tiles,
-                                  const int32_t* storage_of, void* stream) {
+int gsl::tile_sort_keys(int32_t* tile_offsets, int tile_begin, int n_strip_tiles, int64_t capacity, uint64_t* sort_keys,
+                        int32_t* flatten_ids, int64_t* isect_ids, int64_t cam_enc, int write_sorted_keys, uint64_t* bins,
+                        int bin_cap, const int32_t* counts, int32_t* n_isects, int32_t* flags, int long_min,
+                        int occupied_tiles, const int32_t* storage_of, void* stream) {
   if (!tile_offsets || tile_begin < 0 || n_strip_tiles < 0 || capacity < 0) return GSL_ERR_BAD_ARG;
   if (counts && (!bins || tile_begin != 0)) return GSL_ERR_BAD_ARG;  // the scan runs over all tiles, bins only
   if (n_strip_tiles == 0 || (capacity == 0 && !counts)) return GSL_OK;
@@ -903,8 +894,8 @@ extern "C" int gsl_long_sort(const int32_t* tile_offsets, int tile_w, int tile_h
   if (ty0 == ty1 || capacity == 0) return GSL_OK;
   hipStream_t st = (hipStream_t)stream;
   gsl::LongWs w = gsl::long_ws_views(long_ws, max_seg);
-  hipLaunchKernelGGL(gsl::k_long_map, dim3(1), dim3(1024), 0, st, tile_offsets, ty0 * tile_w, (ty1 - ty0) * tile_w,
-                     (long long)capacity, long_min, max_seg, GSL_SORT_SEG << passes, w);
+  gsl::launch_long_map(st, tile_offsets, ty0 * tile_w, (ty1 - ty0) * tile_w, (long long)capacity, long_min, max_seg,
+                       GSL_SORT_SEG << passes, w);
   hipLaunchKernelGGL(gsl::k_long_sort_seg, dim3(max_seg), dim3(64), 0, st, tile_offsets, (long long)capacity, bins,
                      bin_cap, sort_keys, w);
   for (int p = 0; p < passes; ++p)

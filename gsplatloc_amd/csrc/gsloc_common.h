@@ -19,9 +19,6 @@
 
 namespace gsl {
 
-// misc.hip: zero n dwords with a kernel of the library (never hipMemsetAsync: see the note there)
-int zero_u32(void* p, size_t n_dwords, hipStream_t st);
-
 struct M3 {  // row-major 3x3
   float m[9];
   __device__ __forceinline__ float& operator()(int r, int c) { return m[r * 3 + c]; }
@@ -194,6 +191,12 @@ __device__ __forceinline__ float dpp_get(float v) {
       float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, true));
 }
 
+// LDS written by some lanes of a wave is read by other lanes of the same wave: orders the accesses without a barrier.
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
 // Sum over the 64 lanes of a wave in 6 DPP adds (quad swaps, row mirrors, row broadcasts);
 // the total comes back wave-uniform (scalar register) from lane 63.  Fixed order => deterministic.
 __device__ __forceinline__ float wave_sum(float v) {
@@ -204,6 +207,25 @@ __device__ __forceinline__ float wave_sum(float v) {
   v += dpp_get<0x142, 0xA>(v);  // row_bcast15 into rows 1,3
   v += dpp_get<0x143, 0xC>(v);  // row_bcast31 into rows 2,3
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+
+// Lane select driven by a 64-bit scalar mask: t in the lanes of m, f elsewhere (v_cndmask_b32_e64 with an SGPR pair).
+// Measured on MI355X: the VOP2 form that reads VCC issues ~5x slower than this form (9.5 vs 1.8 ns per
+// wave-instruction per SIMD), and hipcc picks the VCC form for plain ?: selects -- so the hot loops keep their
+// predicates as scalar masks (__ballot, lane-constant literals) and select through this helper.
+#define GSL_SEL_ASM(r, m, t, f) asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(t), "s"(m))
+__device__ __forceinline__ float sel(unsigned long long m, float t, float f) { float r; GSL_SEL_ASM(r, m, t, f); return r; }
+__device__ __forceinline__ unsigned sel(unsigned long long m, unsigned t, unsigned f) { unsigned r; GSL_SEL_ASM(r, m, t, f); return r; }
+__device__ __forceinline__ int sel(unsigned long long m, int t, int f) { int r; GSL_SEL_ASM(r, m, t, f); return r; }
+
+// Expected depth ("ED"): the forward divides the depth channel's sum by the pixel's alpha, guarded at GSL_ED_ALPHA_MIN.
+// The backward kernels undo that once per pixel, before the walk: vd (upstream gradient of the expected depth dn)
+// becomes the gradient of the depth sum, vd / alpha, and the alpha gradient gains -vd dn / alpha.
+#define GSL_ED_ALPHA_MIN 1e-10f
+struct EdGrad { float va, vd; };
+__device__ __forceinline__ EdGrad ed_backward(float Aimg, float dn, float va, float vd) {
+  if (Aimg >= GSL_ED_ALPHA_MIN) va += -vd * dn / Aimg;
+  return {va, vd / fmaxf(Aimg, GSL_ED_ALPHA_MIN)};
 }
 
 // Inverse of the rotation block and the camera position -R^-1 t (what torch.inverse(viewmat)[:3,3] is).
@@ -225,330 +247,5 @@ __device__ __forceinline__ void cam_inverse(const Cam& cam, M3& Ri, float cp[3])
   for (int k = 0; k < 3; ++k) cp[k] = -(Ri(k, 0) * cam.t[0] + Ri(k, 1) * cam.t[1] + Ri(k, 2) * cam.t[2]);
 }
 
-// Thread t < 16 of a workgroup: entry t of v_viewmat from the 15 summed rows [v_R 9 | v_t 3 | v_campos 3] (the SH view
-// direction chained through the camera position, campos = -R^-1 t; row 3 = 0: that row is constant).
-__device__ __forceinline__ float viewmat_from_totals(const float* tot, const float* __restrict__ V,
-                                                     const float* __restrict__ Kmat) {
-  float v = 0.f;
-  if (threadIdx.x < 16) {
-    int r = threadIdx.x >> 2, c = threadIdx.x & 3;
-    if (r < 3) {
-      Cam cam = load_cam(V, Kmat);
-      M3 Ri;
-      float cp[3];
-      cam_inverse(cam, Ri, cp);
-      // w = R^-T v_campos
-      float w = Ri(0, r) * tot[12] + Ri(1, r) * tot[13] + Ri(2, r) * tot[14];
-      if (c < 3) v = tot[r * 3 + c] - w * cp[c];
-      else v = tot[9 + r] - w;
-    }
-  }
-  return v;
-}
-
-// The pose gradient leaves the projection backward as one row of 15 sums per workgroup
-// ([v_R 9 | v_t 3 | v_campos 3], 16 floats apart).  Fixed-order sum of the rows by a 256-thread workgroup, chain of
-// the SH view direction through the camera position (campos = -R^-1 t): thread t < 16 returns v_viewmat[t]
-// (row 3 = 0: that row is constant).  Used by k_freduce_viewmat and, to save its launch, by the tracker's pose step.
-__device__ __forceinline__ float reduce_viewmat_rows(const float* __restrict__ partials, int nb,
-                                                     const float* __restrict__ V, const float* __restrict__ Kmat,
-                                                     float (*red)[15], float* tot) {
-  // thread (row r0 = tid >> 2, quarter q = tid & 3) adds quarter q of rows r0, r0 + 64, ...: 16-byte coalesced loads,
-  // four rows in flight; then lanes of equal q are folded (xor 4 .. 32) and the four waves summed in wave order
-  int q = threadIdx.x & 3;
-  const float4* rows = reinterpret_cast<const float4*>(partials) + q;
-  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
-  int b = threadIdx.x >> 2;
-  for (; b + 192 < nb; b += 256) {
-    float4 x0 = rows[(size_t)b * 4], x1 = rows[(size_t)(b + 64) * 4], x2 = rows[(size_t)(b + 128) * 4],
-           x3 = rows[(size_t)(b + 192) * 4];
-    a0.x += x0.x; a0.y += x0.y; a0.z += x0.z; a0.w += x0.w;
-    a1.x += x1.x; a1.y += x1.y; a1.z += x1.z; a1.w += x1.w;
-    a2.x += x2.x; a2.y += x2.y; a2.z += x2.z; a2.w += x2.w;
-    a3.x += x3.x; a3.y += x3.y; a3.z += x3.z; a3.w += x3.w;
-  }
-  for (; b < nb; b += 64) {
-    float4 x0 = rows[(size_t)b * 4];
-    a0.x += x0.x; a0.y += x0.y; a0.z += x0.z; a0.w += x0.w;
-  }
-  float v4[4] = {(a0.x + a1.x) + (a2.x + a3.x), (a0.y + a1.y) + (a2.y + a3.y), (a0.z + a1.z) + (a2.z + a3.z),
-                 (a0.w + a1.w) + (a2.w + a3.w)};
-  int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    float x = v4[c];
-#pragma unroll
-    for (int o = 4; o < 64; o <<= 1) x += __shfl_xor(x, o, 64);
-    if (lane < 4 && 4 * q + c < 15) red[wv][4 * q + c] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < 15) tot[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-  __syncthreads();
-  return viewmat_from_totals(tot, V, Kmat);
-}
-
-// The same reduction by a 1024-thread workgroup (k_freduce_viewmat: 3 907 rows at 1 M Gaussians; with 256 threads the
-// launch was 9.5 us of dependent L2 round trips, 15 rounds of 4 loads in flight per thread).  Its own fixed order:
-// thread (row mod 256, quarter), four rows in flight, lanes of equal quarter folded, the 16 waves summed in wave order.
-__device__ __forceinline__ float reduce_viewmat_rows_wide(const float* __restrict__ partials, int nb,
-                                                          const float* __restrict__ V, const float* __restrict__ Kmat,
-                                                          float (*red)[15], float* tot) {
-  int q = threadIdx.x & 3;
-  const float4* rows = reinterpret_cast<const float4*>(partials) + q;
-  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
-  int b = threadIdx.x >> 2;
-  for (; b + 768 < nb; b += 1024) {
-    float4 x0 = rows[(size_t)b * 4], x1 = rows[(size_t)(b + 256) * 4], x2 = rows[(size_t)(b + 512) * 4],
-           x3 = rows[(size_t)(b + 768) * 4];
-    a0.x += x0.x; a0.y += x0.y; a0.z += x0.z; a0.w += x0.w;
-    a1.x += x1.x; a1.y += x1.y; a1.z += x1.z; a1.w += x1.w;
-    a2.x += x2.x; a2.y += x2.y; a2.z += x2.z; a2.w += x2.w;
-    a3.x += x3.x; a3.y += x3.y; a3.z += x3.z; a3.w += x3.w;
-  }
-  for (; b < nb; b += 256) {
-    float4 x0 = rows[(size_t)b * 4];
-    a0.x += x0.x; a0.y += x0.y; a0.z += x0.z; a0.w += x0.w;
-  }
-  float v4[4] = {(a0.x + a1.x) + (a2.x + a3.x), (a0.y + a1.y) + (a2.y + a3.y), (a0.z + a1.z) + (a2.z + a3.z),
-                 (a0.w + a1.w) + (a2.w + a3.w)};
-  int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    float x = v4[c];
-#pragma unroll
-    for (int o = 4; o < 64; o <<= 1) x += __shfl_xor(x, o, 64);
-    if (lane < 4 && 4 * q + c < 15) red[wv][4 * q + c] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < 15) {
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) s += red[w][threadIdx.x];
-    tot[threadIdx.x] = s;
-  }
-  __syncthreads();
-  return viewmat_from_totals(tot, V, Kmat);
-}
-
-// ---- tiny-splat backward, pass 2 (csrc/raster_px.hip has pass 1 and the story) ---------------------------------------
-__device__ __forceinline__ int tiny_origin(float centre, float r) {  // first pixel index within r of centre
-  return (int)ceilf(centre - r - 0.5f);
-}
-
-// Lane r (0..3) of a quad folds row r of Gaussian gid's 4x4 slab of (w, alpha*T) records into the gradient row
-// [v_xy 2 | v_conic 3 | v_opacity 1 | v_colour D] (dx, dy rebuilt from the Gaussian's own record), clears the slab row,
-// and the quad's four partial rows are added up: every lane of the quad returns the Gaussian's total.
-// Split in two (round 4): tiny_slab_load issues every load that does not depend on another one -- radius, the slab row,
-// both records -- and tiny_slab_fold works on them; the caller loads two items, consumes all loads at once (empty asm) and
-// folds.  Written as one function called four times in a rolled loop, a thread went through radius -> slab -> records ->
-// upstream pixels four times in a row: sixteen dependent memory round trips, half of the projection backward's 16 us in a
-// tracker iteration at 102 k Gaussians.
-struct TinySlabIn {
-  int rad;
-  float4 lo, hi, q0, qc;
-};
-__device__ __forceinline__ TinySlabIn tiny_slab_load(const int32_t* __restrict__ radii, const float4* __restrict__ Q0,
-                                                     const float4* __restrict__ Q1, const float4* __restrict__ trec,
-                                                     int gid, int r, int N) {
-  TinySlabIn in;
-  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-  in.rad = 0; in.lo = z; in.hi = z; in.q0 = z; in.qc = z;
-  if (gid < N) {
-    const float4* row = trec + (size_t)gid * 8 + 2 * r;  // slab = 16 float2 = 8 float4; row r = float4 2r, 2r+1
-    in.rad = radii[gid];
-    in.lo = row[0];
-    in.hi = row[1];
-    in.q0 = Q0[gid];
-    in.qc = Q1[gid];
-  }
-  return in;
-}
-#define GSL_TINY_SLAB_PIN(in)                                                                                         \
-  asm volatile("" : "+v"((in).rad), "+v"((in).lo.x), "+v"((in).lo.y), "+v"((in).lo.z), "+v"((in).lo.w), "+v"((in).hi.x), \
-               "+v"((in).hi.y), "+v"((in).hi.z), "+v"((in).hi.w), "+v"((in).q0.x), "+v"((in).q0.y), "+v"((in).q0.z),    \
-               "+v"((in).q0.w), "+v"((in).qc.x), "+v"((in).qc.y), "+v"((in).qc.z), "+v"((in).qc.w)                       \
-               :                                                                                                      \
-               : "memory")
-template <int D>
-__device__ __forceinline__ void tiny_slab_fold(const TinySlabIn& in, int W, int H, float4* __restrict__ trec,
-                                               const float* __restrict__ vcT, int gid, int r, float (&v)[6 + D]) {
-  constexpr int A = 6 + D;
-#pragma unroll
-  for (int k = 0; k < A; ++k) v[k] = 0.f;
-  if (in.rad > 0) {
-    float4* row = trec + (size_t)gid * 8 + 2 * r;
-    const float4 lo = in.lo, hi = in.hi;
-    float w[4] = {lo.x, lo.z, hi.x, hi.z}, f[4] = {lo.y, lo.w, hi.y, hi.w};
-    bool any = false;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) any = any || (w[c] != 0.f) || (f[c] != 0.f);
-    if (any) {
-      float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-      row[0] = z;
-      row[1] = z;
-      const float4 q0 = in.q0, qc = in.qc;
-      int pcol0 = tiny_origin(q0.x, qc.w), prow = tiny_origin(q0.y, qc.w) + r;
-      float dy = q0.y - ((float)prow + 0.5f);
-      bool row_in = (unsigned)prow < (unsigned)H;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        if (w[c] != 0.f || f[c] != 0.f) {
-          int pcol = pcol0 + c;
-          float dx = q0.x - ((float)pcol + 0.5f);
-          float gx = qc.x * dx + qc.y * dy, gy = qc.y * dx + qc.z * dy;
-          float v_sigma = -q0.w * w[c], hs = 0.5f * v_sigma;
-          v[0] += v_sigma * gx; v[1] += v_sigma * gy;
-          v[2] += hs * dx * dx; v[3] += v_sigma * dx * dy; v[4] += hs * dy * dy;
-          v[5] += w[c];
-          if (f[c] != 0.f && row_in && (unsigned)pcol < (unsigned)W) {
-            size_t pid = (size_t)prow * W + pcol;
-#pragma unroll
-            for (int k = 0; k < D; ++k) v[6 + k] += f[c] * vcT[pid * D + k];
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < A; ++k) {
-    float x = v[k];
-    x += dpp_get<0xB1>(x);  // quad_perm [1,0,3,2]
-    x += dpp_get<0x4E>(x);  // quad_perm [2,3,0,1]: every lane of the quad holds the Gaussian's total
-    v[k] = x;
-  }
-}
-
-// ---- long tile lists split over workgroups (raster_px.hip: forward; raster_g16.hip: backward) -----------------------------
-// GSL_SEG: entries per compositing segment (the walk of a segment is serial per pixel, so its length is the latency of
-// a pile frame: 512 -> 256 -> 128 took the pile frame's compositing from 0.50 to 0.37 to ... ms); GSL_SORT_SEG: keys per
-// sorted run of the long-list sort (a multiple of GSL_SEG: 8 keys per lane in registers).
-#ifndef GSL_SEG_LOG2
-#define GSL_SEG_LOG2 7
-#endif
-#define GSL_SEG (1 << GSL_SEG_LOG2)
-#define GSL_SORT_SEG_LOG2 9
-#define GSL_SORT_SEG (1 << GSL_SORT_SEG_LOG2)
-
-struct LongWs {  // views into the caller's long_ws (sized by gsl_long_ws_bytes)
-  int32_t* n_seg;     // [4]: segments of this frame, max_seg overflow flag, -, -
-  int32_t* seg_tile;  // [max_seg]
-  int32_t* seg_idx;   // [max_seg]  segment number inside its tile
-  int32_t* seg_cnt;   // [max_seg]  segments of that tile
-  int32_t* seg_qcnt;  // [max_seg][4] length of the segment's hit list per quadrant (written by the forward's pass B)
-  float* P;           // [max_seg][256]
-  float* Tend;        // [max_seg][256]
-  int32_t* last;      // [max_seg][256]
-  float* C;           // [max_seg][256][4]
-};
-__host__ __device__ __forceinline__ LongWs long_ws_views(void* ws, int max_seg) {
-  LongWs w;
-  char* p = (char*)ws;
-  w.n_seg = (int32_t*)p; p += 16;
-  w.seg_tile = (int32_t*)p; p += (size_t)max_seg * 4;
-  w.seg_idx = (int32_t*)p; p += (size_t)max_seg * 4;
-  w.seg_cnt = (int32_t*)p; p += (size_t)max_seg * 4;
-  w.seg_qcnt = (int32_t*)p; p += (size_t)max_seg * 16;
-  p = (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-  w.P = (float*)p; p += (size_t)max_seg * 256 * 4;
-  w.Tend = (float*)p; p += (size_t)max_seg * 256 * 4;
-  w.last = (int32_t*)p; p += (size_t)max_seg * 256 * 4;
-  w.C = (float*)p;
-  return w;
-}
-
-// One workgroup: the (tile, segment) pairs of every tile of the strip whose list is longer than long_min.
-static __global__ __launch_bounds__(1024) void k_long_map(const int32_t* __restrict__ tile_offsets, int tile_begin, int n_strip_tiles,
-                                                   long long capacity, int long_min, int max_seg, int max_list, LongWs w) {
-  __shared__ int wsum[16];
-  __shared__ int carry_s, n_long_s;
-  __shared__ int lt_tile[32], lt_first[32], lt_nseg[32];
-  int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if (tid == 0) {
-    carry_s = 0;
-    n_long_s = 0;
-  }
-  __syncthreads();
-  for (int base = 0; base < n_strip_tiles; base += 1024) {
-    int q = base + tid;
-    int nseg = 0, tile = tile_begin + q;
-    if (q < n_strip_tiles) {
-      long long rs = tile_offsets[tile], re = tile_offsets[tile + 1];
-      if (re > capacity) re = capacity;
-      long long len = re - rs;
-      if (len > long_min) nseg = (int)((len + GSL_SEG - 1) / GSL_SEG);
-      if (max_list > 0 && len > long_min && len > max_list) w.n_seg[2] = (int)len;  // longer than the merge passes cover
-    }
-    int x = nseg;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      int y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wv] = x;
-    __syncthreads();
-    int woff = 0;
-    for (int k = 0; k < wv; ++k) woff += wsum[k];
-    int first = carry_s + woff + x - nseg;
-    // A tile is mapped with ALL its segments or not at all: the combine and the backward index a tile's segments
-    // first .. first + nseg - 1, which must exist.  Slots of a tile that does not fit get tile -1 (every kernel that walks
-    // the map returns on it); n_seg[1] then tells the host how many segments the frame needed.
-    const bool fits = first + nseg <= max_seg;
-    // the long tiles of this round (a handful at most) are noted in LDS and their slots written by all threads together
-    // (one thread writing its tile's 180 slots alone was 7 us of a pile frame)
-    if (nseg > 0) {
-      int k = atomicAdd(&n_long_s, 1);
-      if (k < 32) {
-        lt_tile[k] = fits ? tile : -1;
-        lt_first[k] = first;
-        lt_nseg[k] = nseg;
-      } else {  // (more long tiles than notes: this thread writes its own)
-        for (int sgm = 0; sgm < nseg; ++sgm) {
-          int g = first + sgm;
-          if (g < max_seg) {
-            w.seg_tile[g] = fits ? tile : -1;
-            w.seg_idx[g] = fits ? sgm : -1;
-            w.seg_cnt[g] = fits ? nseg : 0;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    int nl = min(n_long_s, 32);
-    for (int k = 0; k < nl; ++k) {
-      int t = lt_tile[k], f = lt_first[k], c = lt_nseg[k];
-      for (int sgm = tid; sgm < c; sgm += 1024) {
-        int g = f + sgm;
-        if (g < max_seg) {
-          w.seg_tile[g] = t;
-          w.seg_idx[g] = t >= 0 ? sgm : -1;
-          w.seg_cnt[g] = t >= 0 ? c : 0;
-        }
-      }
-    }
-    __syncthreads();
-    if (tid == 1023) {
-      carry_s = carry_s + woff + x;
-      n_long_s = 0;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    w.n_seg[0] = min(carry_s, max_seg);
-    if (carry_s > max_seg) w.n_seg[1] = carry_s;  // sticky: more segments than the workspace holds (host polls)
-  }
-}
-
-// Tile rectangle of a projected Gaussian: [xmin,xmax) x [ymin,ymax) in tiles.
-__device__ __forceinline__ void tile_rect(float mx, float my, int radius, int tile_size, int tile_w,
-                                          int tile_h, int& xmin, int& ymin, int& xmax, int& ymax) {
-  float ts = (float)tile_size;
-  float tr = (float)radius / ts;
-  float tx = mx / ts, ty = my / ts;
-  // clamp in float first: (uint32_t)floor(negative) saturates to 0 in the reference kernel
-  xmin = (int)fminf(fmaxf(floorf(tx - tr), 0.f), (float)tile_w);
-  ymin = (int)fminf(fmaxf(floorf(ty - tr), 0.f), (float)tile_h);
-  xmax = (int)fminf(fmaxf(ceilf(tx + tr), 0.f), (float)tile_w);
-  ymax = (int)fminf(fmaxf(ceilf(ty + tr), 0.f), (float)tile_h);
-}
-
 }  // namespace gsl
+

@@ -7,7 +7,7 @@
 // thread per query point scans shells of cells around its own cell and keeps the k smallest squared
 // distances in registers.  The result is exact: the search radius grows until the k-th distance is not
 // larger than the distance to the nearest unsearched cell face.
-#include "gsloc_common.h"
+#include "gsloc_internal.h"
 
 namespace gsl {
 

@@ -1,5 +1,5 @@
 // Library identification and status strings.
-#include "gsloc_common.h"
+#include "gsloc_internal.h"
 
 extern "C" const char* gsl_version(void) { return "gsloc_hip 0.1.0 gfx950"; }
 

@@ -5,6 +5,7 @@
 // read as consecutive dwords per lane: a wave touches one contiguous 768/1024-byte span,
 // so every fetched cache line is fully used.  Camera constants are wave-uniform and live
 // in scalar registers.  HBM-bound: 40 B read + 28 B written per Gaussian (fwd).
+#include "gsloc_internal.h"
 #include "project_dev.h"
 
 namespace gsl {

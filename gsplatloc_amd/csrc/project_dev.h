@@ -1,5 +1,5 @@
 // Device-side projection math shared by the stage kernels (project.hip) and the fused
-// pipeline (fused.hip).  Formulas: SURVEY.md A.1 / A.5 (gsplat fully_fused_projection fwd/bwd).
+// pipeline (fused_project.hip, fused_project_bwd.hip).  Formulas: SURVEY.md A.1 / A.5 (gsplat fully_fused_projection fwd/bwd).
 #pragma once
 #include "gsloc_common.h"
 

@@ -23,6 +23,7 @@
 //
 // Row gather (k_gather_rows) and its vjp (k_scatter_rows, k_scatter_add_rows): x[gaussian_ids] / x[camera_ids] for the
 // opacities, colours, means and camera positions the packed pipeline reads per row.
+#include "gsloc_internal.h"
 #include "project_dev.h"
 
 namespace gsl {

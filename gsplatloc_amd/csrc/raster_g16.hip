@@ -1,5 +1,5 @@
 // Compositing backward, 16-lane groups ("G16"): the vjp of gsplat.rasterize_to_pixels (IDX:14279)
-// for the fused pipeline.  Replaces the quadrant walk of fused.hip (k_mraster_bwd) on the non-deterministic path.
+// for the fused pipeline.  The default path; the deterministic mode keeps the quadrant walk of raster_det.hip (k_mraster_bwd).
 //
 // Why.  k_mraster_bwd lets all 64 lanes of a wave (an 8x8 pixel quadrant) evaluate one splat per trip; a sigma ~ 1 px
 // splat reaches ~11 of those 64 pixels, 27 % of the trips find none (profiles/r02_pmc_sq_counters.txt), and the
@@ -25,18 +25,10 @@
 //      [v_xy | v_conic | v_opacity | v_colour] (the splat's own centre, conic and opacity), and the rows leave as
 //      packed 64-byte global atomics, one per (quadrant, entry) with a composited pixel.
 // A row list longer than LCAP entries in one batch is walked in rounds of LCAP trips.
-#include <stdlib.h>
-#include <string.h>
-
-#include "gsloc_common.h"
+#include "gsloc_internal.h"
+#include "long_dev.h"
 
 namespace gsl {
-
-__device__ __forceinline__ float g16_sel(unsigned long long m, float t, float f) {
-  float r;
-  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(t), "s"(m));
-  return r;
-}
 
 // lane-constant row masks (bit = lane; p = lane & 15)
 #define G16_M_LO8 0x00FF00FF00FF00FFull  // p < 8
@@ -79,7 +71,7 @@ __device__ __forceinline__ float row_scatter8(const float (&v)[8]) {
       "v_add_f32_dpp %5, %3, %3 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
       : "=&v"(n0), "=&v"(n1), "=&v"(n2), "=&v"(n3), "=&v"(m0), "=&v"(m1)
       : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]));
-  float keep = g16_sel(G16_M_B1, m0, m1), send = g16_sel(G16_M_B1, m1, m0);
+  float keep = sel(G16_M_B1, m0, m1), send = sel(G16_M_B1, m1, m0);
   float r = keep + dpp_get<0x4E>(send);  // quad_perm [2,3,0,1]
   r += dpp_get<0xB1>(r);                 // quad_perm [1,0,3,2]
   return r;
@@ -90,21 +82,21 @@ __device__ __forceinline__ float row_scatter16(const float (&v)[16]) {
   float a[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    float keep = g16_sel(G16_M_LO8, v[i], v[i + 8]), send = g16_sel(G16_M_LO8, v[i + 8], v[i]);
+    float keep = sel(G16_M_LO8, v[i], v[i + 8]), send = sel(G16_M_LO8, v[i + 8], v[i]);
     a[i] = keep + dpp_get<0x140>(send);
   }
   float n[4], m[2];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    float keep = g16_sel(G16_M_B2, a[i], a[i + 4]), send = g16_sel(G16_M_B2, a[i + 4], a[i]);
+    float keep = sel(G16_M_B2, a[i], a[i + 4]), send = sel(G16_M_B2, a[i + 4], a[i]);
     n[i] = keep + dpp_get<0x141>(send);
   }
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    float keep = g16_sel(G16_M_B1, n[i], n[i + 2]), send = g16_sel(G16_M_B1, n[i + 2], n[i]);
+    float keep = sel(G16_M_B1, n[i], n[i + 2]), send = sel(G16_M_B1, n[i + 2], n[i]);
     m[i] = keep + dpp_get<0x4E>(send);
   }
-  float keep = g16_sel(G16_M_B0, m[0], m[1]), send = g16_sel(G16_M_B0, m[1], m[0]);
+  float keep = sel(G16_M_B0, m[0], m[1]), send = sel(G16_M_B0, m[1], m[0]);
   return keep + dpp_get<0xB1>(send);
 }
 
@@ -137,7 +129,7 @@ __device__ __forceinline__ void half_scatter16(const float (&v)[16], float4& lo,
   float a[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    float keep = g16_sel(G16_M_B2, v[i], v[i + 8]), send = g16_sel(G16_M_B2, v[i + 8], v[i]);
+    float keep = sel(G16_M_B2, v[i], v[i + 8]), send = sel(G16_M_B2, v[i + 8], v[i]);
     a[i] = keep + dpp_get<0x141>(send);
   }
 #pragma unroll
@@ -357,7 +349,7 @@ __device__ __forceinline__ void qraster_bwd_body(
 #endif
         G16_STAT(5, __popcll(validm));
         unsigned long long capm = __ballot(opv <= GSL_ALPHA_MAX);
-        float am = g16_sel(validm, alpha, 0.f);
+        float am = sel(validm, alpha, 0.f);
         float ra = __builtin_amdgcn_rcpf(1.f - am);
         T *= ra;
         float fac = am * T;
@@ -374,7 +366,7 @@ __device__ __forceinline__ void qraster_bwd_body(
         }
         float v_alpha = T * cdot - ra * Bp;
         Bp += fac * cdot;
-        float w = g16_sel(validm & capm, vis, 0.f) * v_alpha;
+        float w = sel(validm & capm, vis, 0.f) * v_alpha;
         float val[NS];
         val[0] = w; val[1] = w * lx; val[2] = w * ly; val[3] = w * lxx; val[4] = w * lxy; val[5] = w * lyy;
         if (CG == D) {
@@ -595,10 +587,9 @@ __device__ __forceinline__ void qraster_bwd_item(
   float T_final = 1.f - Aimg;
   float va = inside ? v_alphas[pid] : 0.f;
   if (ED && inside) {
-    float dn = render[pid * D + (D - 1)];
-    float vd = vc[D - 1];
-    if (Aimg >= 1e-10f) va += -vd * dn / Aimg;
-    vc[D - 1] = vd / fmaxf(Aimg, 1e-10f);
+    const EdGrad g = ed_backward(Aimg, render[pid * D + (D - 1)], va, vc[D - 1]);
+    va = g.va;
+    vc[D - 1] = g.vd;
   }
   float T_init = T_final, Bp_init = -T_final * va;
   if (LONG) {
@@ -696,17 +687,13 @@ extern "C" int gsl_g16_stats(unsigned long long* host_out, int reset) {
 }
 #endif
 
-extern "C" int32_t* gsl_fused_bin_state(void* ws, int n_tiles);  // fused.hip: the state word inside ws
-
-// Launch of the G16 backward (called by gsl_fused_raster_bwd in fused.hip for the non-deterministic path).
-extern "C" int gsl_g16_raster_bwd_launch(const float* Q0, const float* Q1, const float* Q2, int channels, int ed, int width,
-                                         int height, int tile_w, int ty0, int ty1, const int32_t* tile_offsets,
-                                         const int32_t* flatten_ids, int64_t capacity, const float* render,
-                                         const float* alphas, const int32_t* last_ids, const float* v_render,
-                                         const float* v_alphas, float* vacc, int row0, int row1, const void* Qh,
-                                         const uint32_t* isect_hits, const int32_t* isect_hit_counts, int long_min,
-                                         void* long_ws, int max_seg, int rgb_flag_index, void* clear_ws,
-                                         void* stream) {
+static int g16_raster_bwd_launch(const float* Q0, const float* Q1, const float* Q2, int channels, int ed, int width,
+                                 int height, int tile_w, int ty0, int ty1, const int32_t* tile_offsets,
+                                 const int32_t* flatten_ids, int64_t capacity, const float* render,
+                                 const float* alphas, const int32_t* last_ids, const float* v_render,
+                                 const float* v_alphas, float* vacc, int row0, int row1, const void* Qh,
+                                 const uint32_t* isect_hits, const int32_t* isect_hit_counts, int long_min,
+                                 void* long_ws, int max_seg, int rgb_flag_index, void* clear_ws, void* stream) {
   // long_ws == NULL: the tiles of the strip (those longer than long_min, if > 0, are skipped);
   // long_ws != NULL: only the (tile, segment) pairs the forward's long-list pass listed there
   hipStream_t st = (hipStream_t)stream;
@@ -716,30 +703,74 @@ extern "C" int gsl_g16_raster_bwd_launch(const float* Q0, const float* Q1, const
   // (the flag sits behind the 4 n_tiles hit-list lengths; the long-list launches, which have no lengths array, go without)
   int32_t* rgb_flag = isect_hit_counts ? const_cast<int32_t*>(isect_hit_counts) + rgb_flag_index : nullptr;
   int32_t* clear_counts = (int32_t*)clear_ws;
-  int32_t* clear_state = clear_ws ? gsl_fused_bin_state(clear_ws, rgb_flag_index / 4) : nullptr;  // (4 n_tiles)
-#define CALL_Q(DD, EE, CC)                                                                                   \
-  do {                                                                                                       \
-    const int n_items = 4 * nblk;                                                                            \
-    const int grid = ((DD) == 4 && (CC) == 4 && rgb_flag && n_items > 2048) ? 2048 : n_items;                \
-    if (lng)                                                                                                 \
-      hipLaunchKernelGGL((gsl::k_qraster_bwd<DD, EE, CC, true>), dim3(grid), dim3(64), 0, st, (const float4*)Q0, \
-                         (const float4*)Q1, (const float4*)Q2, width, height, tile_w, ty0, tile_offsets,     \
-                         flatten_ids, (long long)capacity, render, alphas, last_ids, v_render, v_alphas, vacc, \
-                         row0, row1, (const uint4*)Qh, isect_hits, const_cast<int32_t*>(isect_hit_counts), long_min, lw, rgb_flag, clear_counts, clear_state, n_items);                   \
-    else                                                                                                     \
-      hipLaunchKernelGGL((gsl::k_qraster_bwd<DD, EE, CC, false>), dim3(grid), dim3(64), 0, st, (const float4*)Q0, \
-                         (const float4*)Q1, (const float4*)Q2, width, height, tile_w, ty0, tile_offsets,     \
-                         flatten_ids, (long long)capacity, render, alphas, last_ids, v_render, v_alphas, vacc, \
-                         row0, row1, (const uint4*)Qh, isect_hits, const_cast<int32_t*>(isect_hit_counts), long_min, lw, rgb_flag, clear_counts, clear_state, n_items);                   \
+  int32_t* clear_state = gsl::fused_bin_state(clear_ws, rgb_flag_index / 4);  // (4 n_tiles)
+#define CALL_QL(DD, EE, CC, LL)                                                                                  \
+  hipLaunchKernelGGL((gsl::k_qraster_bwd<DD, EE, CC, LL>), dim3(grid), dim3(64), 0, st, (const float4*)Q0,       \
+                     (const float4*)Q1, (const float4*)Q2, width, height, tile_w, ty0, tile_offsets, flatten_ids, \
+                     (long long)capacity, render, alphas, last_ids, v_render, v_alphas, vacc, row0, row1,         \
+                     (const uint4*)Qh, isect_hits, const_cast<int32_t*>(isect_hit_counts), long_min, lw, rgb_flag, \
+                     clear_counts, clear_state, n_items)
+#define CALL_Q(DD, EE, CC)                                                                    \
+  do {                                                                                        \
+    const int n_items = 4 * nblk;                                                             \
+    const int grid = ((DD) == 4 && (CC) == 4 && rgb_flag && n_items > 2048) ? 2048 : n_items; \
+    if (lng) CALL_QL(DD, EE, CC, true); else CALL_QL(DD, EE, CC, false);                      \
   } while (0)
-  if (channels == 1) { if (ed) CALL_Q(1, true, 1); else CALL_Q(1, false, 1); }
-  else if (channels == 3) { CALL_Q(3, false, 3); }
-  else if (channels == 4) {
-    if (ed) { CALL_Q(4, true, 1); CALL_Q(4, true, 4); }
-    else { CALL_Q(4, false, 1); CALL_Q(4, false, 4); }
-  }
-  else return GSL_ERR_BAD_ARG;
+  // "RGB+ED" takes two launches: the depth-only kernel (CG = 1), then the full-colour one for the quadrants it left
+#define CALL_QD(DD, EE) do { CALL_Q(DD, EE, ((DD) == 4 ? 1 : (DD))); if ((DD) == 4) CALL_Q(DD, EE, DD); } while (0)
+  GSL_DISPATCH_CH_ED(channels, ed, CALL_QD)
+#undef CALL_QD
 #undef CALL_Q
+#undef CALL_QL
   GSL_CHECK_LAUNCH();
   return GSL_OK;
+}
+
+// Compositing backward of the fused pipeline: adds a gradient row per Gaussian into vacc (k_qraster_bwd above), or with
+// vrow stores one row per intersection, deterministically (k_mraster_bwd, raster_det.hip).
+// Pixel rows outside [row0, row1) are not touched (strip rendering with a one-pixel halo).
+extern "C" int gsl_fused_raster_bwd(const float* Q0, const float* Q1, const float* Q2, int channels, int ed,
+                                   int width, int height, int tile_w, int tile_h, int ty0, int ty1,
+                                   const int32_t* tile_offsets, const int32_t* flatten_ids, int64_t capacity,
+                                   const float* render, const float* alphas, const int32_t* last_ids,
+                                   const float* v_render, const float* v_alphas, float* vacc, int row0, int row1,
+                                   const void* Qh, float* vrow, const uint32_t* isect_hits,
+                                   const int32_t* isect_hit_counts, int long_min, void* clear_ws, void* stream) {
+  if (!gsl::frame_ok(width, height, tile_w, tile_h, ty0, ty1, capacity, row0, row1)) return GSL_ERR_BAD_ARG;
+  if (!tile_offsets || !render || !alphas || !last_ids || !v_render || !v_alphas) return GSL_ERR_BAD_ARG;
+  if (ed && channels == 3) return GSL_ERR_BAD_ARG;
+  if (capacity == 0 || ty0 == ty1 || row0 == row1) return GSL_OK;
+  if (!flatten_ids || (!vacc && !vrow)) return GSL_ERR_BAD_ARG;
+  if (isect_hits && !isect_hit_counts) return GSL_ERR_BAD_ARG;
+  if (!Qh && (!Q0 || !Q1 || (channels >= 3 && !Q2))) return GSL_ERR_BAD_ARG;
+  if (vrow && clear_ws) return GSL_ERR_BAD_ARG;  // (the deterministic mode keeps the separate sort launch)
+  if (vrow)  // deterministic mode: one row per intersection, plain stores, no atomics anywhere
+    return gsl::launch_mraster_bwd(Q0, Q1, Q2, channels, ed, width, height, tile_w, ty0, ty1, tile_offsets, flatten_ids,
+                                   capacity, render, alphas, last_ids, v_render, v_alphas, vrow, row0, row1, Qh,
+                                   (hipStream_t)stream);
+  // non-deterministic path: 16-lane groups, one workgroup per quadrant
+  return g16_raster_bwd_launch(Q0, Q1, Q2, channels, ed, width, height, tile_w, ty0, ty1, tile_offsets, flatten_ids,
+                               capacity, render, alphas, last_ids, v_render, v_alphas, vacc, row0, row1, Qh,
+                               isect_hits, isect_hit_counts, long_min, nullptr, 0, 4 * tile_w * tile_h, clear_ws,
+                                   stream);
+}
+
+// Compositing backward of the long tile lists (the segments gsl_long_raster_fwd listed in long_ws): adds into vacc.
+extern "C" int gsl_long_raster_bwd(const float* Q0, const float* Q1, const float* Q2, int channels, int ed, int width,
+                                   int height, int tile_w, int tile_h, int ty0, int ty1, const int32_t* tile_offsets,
+                                   const int32_t* flatten_ids, int64_t capacity, const float* render,
+                                   const float* alphas, const int32_t* last_ids, const float* v_render,
+                                   const float* v_alphas, float* vacc, int row0, int row1, const void* Qh,
+                                   const uint32_t* isect_hits, int long_min, void* long_ws, int max_seg,
+                                   void* stream) {
+  if (!gsl::frame_ok(width, height, tile_w, tile_h, ty0, ty1, capacity, row0, row1, false) || long_min <= 0 ||
+      max_seg <= 0 || !long_ws)
+    return GSL_ERR_BAD_ARG;
+  if (!tile_offsets || !render || !alphas || !last_ids || !v_render || !v_alphas || !vacc) return GSL_ERR_BAD_ARG;
+  if (ed && channels == 3) return GSL_ERR_BAD_ARG;
+  if (capacity == 0 || ty0 == ty1 || row0 == row1) return GSL_OK;
+  if (!flatten_ids || (!Qh && (!Q0 || !Q1 || (channels >= 3 && !Q2)))) return GSL_ERR_BAD_ARG;
+  return g16_raster_bwd_launch(Q0, Q1, Q2, channels, ed, width, height, tile_w, ty0, ty1, tile_offsets, flatten_ids,
+                               capacity, render, alphas, last_ids, v_render, v_alphas, vacc, row0, row1, Qh,
+                               isect_hits, nullptr, long_min, long_ws, max_seg, 0, nullptr, stream);
 }

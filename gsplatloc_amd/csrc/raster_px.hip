@@ -17,13 +17,15 @@
 //      (~3 for the reference's splats instead of ~22 wave-wide trips).
 //   5. backward: every lane adds its contribution to the splat's LDS accumulator row with ds_add_f32
 //      (lanes work on different splats, so there is nothing to reduce across the wave); rows are flushed
-//      per batch as packed 64-byte global atomics exactly as in fused.hip.
+//      per batch as packed 64-byte global atomics: 16 consecutive lanes add one Gaussian's row.
 //
 // Skipped candidates are exactly those the reference loop would `continue` over (alpha < 1/255), so the
 // per-pixel sequence of composited splats -- and therefore every output -- is unchanged.
-#include "gsloc_common.h"
+#include "gsloc_internal.h"
+#include "long_dev.h"
 #include "loss_dev.h"
 #include "sort_dev.h"
+#include "tiny_dev.h"
 
 namespace gsl {
 
@@ -146,18 +148,6 @@ __device__ __forceinline__ unsigned group_or(unsigned v) {
   return v;
 }
 
-// t in the lanes of the scalar mask m, f elsewhere (v_cndmask_b32_e64 on an SGPR pair; no VCC round trip).
-__device__ __forceinline__ unsigned sel_u32(unsigned long long m, unsigned t, unsigned f) {
-  unsigned r;
-  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(t), "s"(m));
-  return r;
-}
-__device__ __forceinline__ float sel_f32(unsigned long long m, float t, float f) {
-  float r;
-  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(t), "s"(m));
-  return r;
-}
-
 // Index of the lowest set bit; 0xFFFFFFFF for 0 (v_ffbl_b32 as it is: __builtin_ctz(0) is undefined and __ffs costs two more
 // four-cycle instructions for the zero case, which the trips below do not need).
 __device__ __forceinline__ int ffbl_raw(unsigned v) {
@@ -262,13 +252,13 @@ __device__ __forceinline__ void praster_walk(
       }
       unsigned mlo, mhi;
       pixel_masks<true>(lox, hix, loy, hiy, lane, mlo, mhi);
-      mlo = sel_u32(DONE, 0u, mlo);
-      mhi = sel_u32(DONE, 0u, mhi);
+      mlo = sel(DONE, 0u, mlo);
+      mhi = sel(DONE, 0u, mhi);
       unsigned cm[2] = {0u, 0u};  // candidates of this chunk this pixel composited
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         unsigned m = half ? mhi : mlo;
-        if (half) m = sel_u32(DONE, 0u, m);  // (a pixel that stopped in the first half; inside the loop only m is cleared)
+        if (half) m = sel(DONE, 0u, m);  // (a pixel that stopped in the first half; inside the loop only m is cleared)
         const uint16_t* const ql = &sb.qlist[wv][c + half * 32];
         // Straight-line trips under a wave-uniform loop: a lane that has run out of candidates goes through the
         // arithmetic with alpha 0.  No divergent region, so none of the copies the structurizer makes of the nine values
@@ -301,8 +291,8 @@ __device__ __forceinline__ void praster_walk(
           const unsigned long long OK0 = ACT & __ballot(sg0 >= 0.f) & __ballot(al0 >= GSL_ALPHA_MIN);
           const unsigned long long OK1 = TWO & __ballot(sg1 >= 0.f) & __ballot(al1 >= GSL_ALPHA_MIN);
           if (MODE == 1) {
-            T *= 1.f - sel_f32(OK0, al0, 0.f);
-            T *= 1.f - sel_f32(OK1, al1, 0.f);
+            T *= 1.f - sel(OK0, al0, 0.f);
+            T *= 1.f - sel(OK1, al1, 0.f);
             ACT = __ballot(m != 0);
             continue;
           }
@@ -312,13 +302,13 @@ __device__ __forceinline__ void praster_walk(
           // selects on vis and T would (two 2-cycle ops for two 4-cycle selects per candidate).
           const unsigned long long S0R = __ballot(T * (1.f - al0) <= GSL_T_STOP);  // candidate 0 would stop the pixel
           const unsigned long long STOP0 = OK0 & S0R, EFF0 = OK0 & ~S0R;
-          const float a0 = sel_f32(EFF0, al0, 0.f);
+          const float a0 = sel(EFF0, al0, 0.f);
           const float vis0 = a0 * T;
           const float T1 = T * (1.f - a0);
           const unsigned long long LIVE1 = OK1 & ~STOP0;
           const unsigned long long S1R = __ballot(T1 * (1.f - al1) <= GSL_T_STOP);
           const unsigned long long STOP1 = LIVE1 & S1R, EFF1 = LIVE1 & ~S1R;
-          const float a1 = sel_f32(EFF1, al1, 0.f);
+          const float a1 = sel(EFF1, al1, 0.f);
           const float vis1 = a1 * T1;
           T = T1 * (1.f - a1);
           if (RGB) {
@@ -334,10 +324,10 @@ __device__ __forceinline__ void praster_walk(
           }
           // composited <=> alpha >= 1/255 and the pixel did not stop on this entry (alpha T > 0 then: T > 1e-4): the
           // masks the alphas were selected under
-          cm[half] |= sel_u32(EFF0, b0, 0u) | sel_u32(EFF1, b1, 0u);
+          cm[half] |= sel(EFF0, b0, 0u) | sel(EFF1, b1, 0u);
           const unsigned long long STOPPED = STOP0 | STOP1;
           DONE |= STOPPED;
-          m = sel_u32(STOPPED, 0u, m);
+          m = sel(STOPPED, 0u, m);
           ACT = __ballot(m != 0);
         } while (ACT);
       }
@@ -360,7 +350,7 @@ __device__ __forceinline__ void praster_walk(
           unsigned glo = (unsigned)__builtin_amdgcn_readlane((int)rlo, (64 / GSL_NG) * g);
           unsigned ghi = (unsigned)__builtin_amdgcn_readlane((int)rhi, (64 / GSL_NG) * g);
           unsigned long long gm = ((unsigned long long)ghi << 32) | glo;
-          nib |= sel_u32(gm, 1u << g, 0u);
+          nib |= sel(gm, 1u << g, 0u);
           Rm |= gm;
         }
         // (a set bit implies e < n)
@@ -505,7 +495,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SORT == 3 ?
     size_t pid = (size_t)i * W + j;
     float A = 1.f - T;
     alphas[pid] = A;
-    if (ED) pix[D - 1] = pix[D - 1] / fmaxf(A, 1e-10f);
+    if (ED) pix[D - 1] = pix[D - 1] / fmaxf(A, GSL_ED_ALPHA_MIN);
 #pragma unroll
     for (int k = 0; k < D; ++k) render[pid * D + k] = pix[k];
     last_ids[pid] = cur_idx;
@@ -532,6 +522,94 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SORT == 3 ?
 // product changes ((P_0 P_1) x ... instead of one running product), a last-bit effect.  The backward
 // (raster_g16.hip, k_long_bwd) restarts each segment from the stored T and the colour partials of the later segments.
 // ---------------------------------------------------------------------------------------------------
+// One workgroup: the (tile, segment) pairs of every tile of the strip whose list is longer than long_min.
+__global__ __launch_bounds__(1024) void k_long_map(const int32_t* __restrict__ tile_offsets, int tile_begin,
+                                                   int n_strip_tiles, long long capacity, int long_min, int max_seg, int max_list, LongWs w) {
+  __shared__ int wsum[16];
+  __shared__ int carry_s, n_long_s;
+  __shared__ int lt_tile[32], lt_first[32], lt_nseg[32];
+  int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid == 0) {
+    carry_s = 0;
+    n_long_s = 0;
+  }
+  __syncthreads();
+  for (int base = 0; base < n_strip_tiles; base += 1024) {
+    int q = base + tid;
+    int nseg = 0, tile = tile_begin + q;
+    if (q < n_strip_tiles) {
+      long long rs = tile_offsets[tile], re = tile_offsets[tile + 1];
+      if (re > capacity) re = capacity;
+      long long len = re - rs;
+      if (len > long_min) nseg = (int)((len + GSL_SEG - 1) / GSL_SEG);
+      if (max_list > 0 && len > long_min && len > max_list) w.n_seg[2] = (int)len;  // longer than the merge passes cover
+    }
+    int x = nseg;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      int y = __shfl_up(x, o, 64);
+      if (lane >= o) x += y;
+    }
+    if (lane == 63) wsum[wv] = x;
+    __syncthreads();
+    int woff = 0;
+    for (int k = 0; k < wv; ++k) woff += wsum[k];
+    int first = carry_s + woff + x - nseg;
+    // A tile is mapped with ALL its segments or not at all: the combine and the backward index a tile's segments
+    // first .. first + nseg - 1, which must exist.  Slots of a tile that does not fit get tile -1 (every kernel that walks
+    // the map returns on it); n_seg[1] then tells the host how many segments the frame needed.
+    const bool fits = first + nseg <= max_seg;
+    // the long tiles of this round (a handful at most) are noted in LDS and their slots written by all threads together
+    // (one thread writing its tile's 180 slots alone was 7 us of a pile frame)
+    if (nseg > 0) {
+      int k = atomicAdd(&n_long_s, 1);
+      if (k < 32) {
+        lt_tile[k] = fits ? tile : -1;
+        lt_first[k] = first;
+        lt_nseg[k] = nseg;
+      } else {  // (more long tiles than notes: this thread writes its own)
+        for (int sgm = 0; sgm < nseg; ++sgm) {
+          int g = first + sgm;
+          if (g < max_seg) {
+            w.seg_tile[g] = fits ? tile : -1;
+            w.seg_idx[g] = fits ? sgm : -1;
+            w.seg_cnt[g] = fits ? nseg : 0;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    int nl = min(n_long_s, 32);
+    for (int k = 0; k < nl; ++k) {
+      int t = lt_tile[k], f = lt_first[k], c = lt_nseg[k];
+      for (int sgm = tid; sgm < c; sgm += 1024) {
+        int g = f + sgm;
+        if (g < max_seg) {
+          w.seg_tile[g] = t;
+          w.seg_idx[g] = t >= 0 ? sgm : -1;
+          w.seg_cnt[g] = t >= 0 ? c : 0;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid == 1023) {
+      carry_s = carry_s + woff + x;
+      n_long_s = 0;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    w.n_seg[0] = min(carry_s, max_seg);
+    if (carry_s > max_seg) w.n_seg[1] = carry_s;  // sticky: more segments than the workspace holds (host polls)
+  }
+}
+
+void launch_long_map(hipStream_t st, const int32_t* tile_offsets, int tile_begin, int n_strip_tiles, long long capacity,
+                     int long_min, int max_seg, int max_list, const LongWs& w) {
+  hipLaunchKernelGGL(k_long_map, dim3(1), dim3(1024), 0, st, tile_offsets, tile_begin, n_strip_tiles, capacity, long_min,
+                     max_seg, max_list, w);
+}
+
 template <int D, int PASS>
 __global__ __launch_bounds__(256) void k_long_fwd(
     const float4* __restrict__ Q0, const float4* __restrict__ Q1, const float4* __restrict__ Q2, int W, int H,
@@ -662,7 +740,7 @@ __global__ __launch_bounds__(1024) void k_long_combine(int W, int H, int tile_w,
   size_t pid = (size_t)i * W + j;
   float A = 1.f - T;
   alphas[pid] = A;
-  if (ED) pix[D - 1] = pix[D - 1] / fmaxf(A, 1e-10f);
+  if (ED) pix[D - 1] = pix[D - 1] / fmaxf(A, GSL_ED_ALPHA_MIN);
 #pragma unroll
   for (int k = 0; k < D; ++k) render[pid * D + k] = pix[k];
   last_ids[pid] = last;
@@ -675,7 +753,7 @@ __global__ __launch_bounds__(1024) void k_long_combine(int W, int H, int tile_w,
 // (pixel, splat) it stores  (w, fac) = (vis * v_alpha [0 when alpha is clamped], alpha * T)  into the
 // splat's own 4x4 slab  trec[g][row - r0][col - c0]  (plain 8-byte stores, no atomics, no reduction), and
 // every pixel leaves its (expected-depth-chained) upstream gradient in vcT[H,W,D].
-// Pass 2 runs inside the projection backward (k_fproject_bwd, tiny_slab_load + tiny_slab_fold in gsloc_common.h): four lanes per
+// Pass 2 runs inside the projection backward (k_fproject_bwd, tiny_slab_load + tiny_slab_fold in tiny_dev.h): four lanes per
 // Gaussian read its slab, rebuild dx, dy from the Gaussian's own record and sum the 16 slots into its gradient row,
 // which never leaves LDS.
 // ---------------------------------------------------------------------------------------------------
@@ -761,10 +839,9 @@ __global__ __launch_bounds__(256) void k_tiny_bwd(
     for (int k = 0; k < D; ++k) vc[k] = inside ? v_render[pid * D + k] : 0.f;
   }
   if (ED && inside) {
-    float dn = render[pid * D + (D - 1)];
-    float vd = vc[D - 1];
-    if (Aimg >= 1e-10f) va += -vd * dn / Aimg;
-    vc[D - 1] = vd / fmaxf(Aimg, 1e-10f);
+    const EdGrad g = ed_backward(Aimg, render[pid * D + (D - 1)], va, vc[D - 1]);
+    va = g.va;
+    vc[D - 1] = g.vd;
   }
   if (inside) {
 #pragma unroll
@@ -861,7 +938,7 @@ __global__ __launch_bounds__(256) void k_tiny_bwd(
             cd1 = q21.x * vc[0] + q21.y * vc[1] + q21.z * vc[2];
           }
           if (DEPTH) { cd0 += p0.z * vc[D - 1]; cd1 += u0.z * vc[D - 1]; }
-          const float a0 = sel_f32(OK0, al0, 0.f), a1 = sel_f32(OK1, al1, 0.f);
+          const float a0 = sel(OK0, al0, 0.f), a1 = sel(OK1, al1, 0.f);
           const float ra0 = __builtin_amdgcn_rcpf(1.f - a0), ra1 = __builtin_amdgcn_rcpf(1.f - a1);  // (alpha 0: exactly 1)
           const float T0 = T * ra0;
           const float fac0 = a0 * T0;
@@ -895,10 +972,7 @@ __global__ __launch_bounds__(256) void k_tiny_bwd(
   }
 }
 
-
 }  // namespace gsl
-
-extern "C" int32_t* gsl_fused_bin_state(void* ws, int n_tiles);  // fused.hip: the state word inside ws
 
 extern "C" int gsl_tiny_raster_bwd(const float* Q0, const float* Q1, const float* Q2, int channels, int ed, int width,
                                    int height, int tile_w, int tile_h, int ty0, int ty1, const int32_t* tile_offsets,
@@ -907,10 +981,7 @@ extern "C" int gsl_tiny_raster_bwd(const float* Q0, const float* Q1, const float
                                    const float* v_alphas, float* trec, float* vcT, int row0, int row1,
                                    int32_t* flags, int long_min, const float* loss_depth_gt, float depth_lambda,
                                    float edge_lambda, float* loss_partials, void* clear_ws, void* stream) {
-  if (width <= 0 || height <= 0 || tile_w <= 0 || tile_h <= 0 || ty0 < 0 || ty1 > tile_h || ty0 > ty1 ||
-      capacity < 0 || row0 < 0 || row0 > row1)
-    return GSL_ERR_BAD_ARG;
-  if (tile_w * 16 < width || tile_h * 16 < height) return GSL_ERR_BAD_ARG;
+  if (!gsl::frame_ok(width, height, tile_w, tile_h, ty0, ty1, capacity, row0, row1)) return GSL_ERR_BAD_ARG;
   if (!tile_offsets || !render || !alphas || !last_ids || !v_render || !v_alphas || !trec || !vcT)
     return GSL_ERR_BAD_ARG;
   if (ed && channels == 3) return GSL_ERR_BAD_ARG;
@@ -931,24 +1002,15 @@ extern "C" int gsl_tiny_raster_bwd(const float* Q0, const float* Q1, const float
                      (const float4*)Q1, (const float4*)Q2, width, height, tile_w, ty0, tile_offsets,         \
                      flatten_ids, (long long)capacity, render, alphas, last_ids, v_render, v_alphas,         \
                      (float2*)trec, vcT, row0, row1, flags, long_min, tl, (int32_t*)clear_ws,                \
-                     clear_ws ? gsl_fused_bin_state(clear_ws, tile_w * tile_h) : (int32_t*)nullptr)
-#define CALL_TL(DD, EE) do { if (loss) CALL_TB(DD, EE, true); else CALL_TB(DD, EE, false); } while (0)
-  if (channels == 1) { if (ed) CALL_TL(1, true); else CALL_TL(1, false); }
-  else if (channels == 3) { CALL_TB(3, false, false); }
-  else if (channels == 4) { if (ed) CALL_TL(4, true); else CALL_TL(4, false); }
-  else return GSL_ERR_BAD_ARG;
+                     gsl::fused_bin_state(clear_ws, tile_w * tile_h))
+  // (the loss variant exists where there is a depth channel: loss with three channels was refused above)
+#define CALL_TL(DD, EE) do { if (loss && (DD) != 3) CALL_TB(DD, EE, ((DD) != 3)); else CALL_TB(DD, EE, false); } while (0)
+  GSL_DISPATCH_CH_ED(channels, ed, CALL_TL)
 #undef CALL_TL
 #undef CALL_TB
   GSL_CHECK_LAUNCH();
   return GSL_OK;
 }
-
-
-#define GSL_P_DISPATCH(D, ED, CALL)                                \
-  if (D == 1) { if (ED) CALL(1, true); else CALL(1, false); }      \
-  else if (D == 3) { CALL(3, false); }                             \
-  else if (D == 4) { if (ED) CALL(4, true); else CALL(4, false); } \
-  else return GSL_ERR_BAD_ARG;
 
 // Compositing forward (k_praster_fwd).  Pixel rows outside [row0, row1) are not touched.
 // sort_bins != NULL (binned projection, whole frame, bin_cap <= 2048, long_min == 0): the kernel also does gsl_fused_bin's
@@ -961,10 +1023,7 @@ extern "C" int gsl_fused_raster_fwd(const float* Q0, const float* Q1, const floa
                                  uint32_t* isect_hits, int32_t* isect_hit_counts, int long_min, void* sort_bins,
                                  int bin_cap, int32_t* n_isects, int32_t* flags, const int32_t* storage_of,
                                  void* stream) {
-  if (width <= 0 || height <= 0 || tile_w <= 0 || tile_h <= 0 || ty0 < 0 || ty1 > tile_h || ty0 > ty1 ||
-      capacity < 0 || row0 < 0 || row0 > row1)
-    return GSL_ERR_BAD_ARG;
-  if (tile_w * 16 < width || tile_h * 16 < height) return GSL_ERR_BAD_ARG;
+  if (!gsl::frame_ok(width, height, tile_w, tile_h, ty0, ty1, capacity, row0, row1)) return GSL_ERR_BAD_ARG;
   if (!tile_offsets || !render || !alphas || !last_ids) return GSL_ERR_BAD_ARG;
   if (capacity > 0 && !flatten_ids) return GSL_ERR_BAD_ARG;
   if (capacity > 0 && !Qh && (!Q0 || !Q1 || (channels >= 3 && !Q2))) return GSL_ERR_BAD_ARG;
@@ -982,18 +1041,16 @@ extern "C" int gsl_fused_raster_fwd(const float* Q0, const float* Q1, const floa
                   const_cast<int32_t*>(flatten_ids), n_isects, flags, bin_cap, storage_of};
   // (sorting variant: the counters are still being added up by other workgroups -- the backward clears them)
   int32_t* clear_counts = sort ? nullptr : (int32_t*)binned_ws;
-  int32_t* clear_state = sort ? nullptr : gsl_fused_bin_state(binned_ws, tile_w * tile_h);
+  int32_t* clear_state = sort ? nullptr : gsl::fused_bin_state(binned_ws, tile_w * tile_h);
   const int lk = !sort ? 0 : (bin_cap <= 1024 ? 2 : 3);
 #define CALL_PF3(DD, EE, SS)                                                                                  \
   hipLaunchKernelGGL((gsl::k_praster_fwd<DD, EE, SS>), dim3(nblk), dim3(256), 0, st, (const float4*)Q0,      \
                      (const float4*)Q1, (const float4*)Q2, width, height, tile_w, ty0, tile_offsets,          \
                      flatten_ids, (long long)capacity, render, alphas, last_ids, row0, row1, (const uint4*)Qh,     \
                      clear_counts, clear_state, isect_hits, isect_hit_counts, long_min, tile_w * tile_h, fs)
-#define CALL_PF(DD, EE)                                                                          \
-  do {                                                                                           \
-    if (lk == 0) CALL_PF3(DD, EE, 0); else if (lk == 2) CALL_PF3(DD, EE, 2); else CALL_PF3(DD, EE, 3); \
-  } while (0)
-  GSL_P_DISPATCH(channels, ed, CALL_PF)
+#define CALL_PF(DD, EE) \
+  do { if (lk == 0) CALL_PF3(DD, EE, 0); else if (lk == 2) CALL_PF3(DD, EE, 2); else CALL_PF3(DD, EE, 3); } while (0)
+  GSL_DISPATCH_CH_ED(channels, ed, CALL_PF)
 #undef CALL_PF
 #undef CALL_PF3
   GSL_CHECK_LAUNCH();
@@ -1016,8 +1073,7 @@ extern "C" int gsl_long_raster_fwd(const float* Q0, const float* Q1, const float
                                    int32_t* last_ids, int row0, int row1, const void* Qh, uint32_t* isect_hits,
                                    int long_min, void* long_ws, size_t long_ws_bytes, int max_seg, int map_ready,
                                    void* stream) {
-  if (width <= 0 || height <= 0 || tile_w <= 0 || tile_h <= 0 || ty0 < 0 || ty1 > tile_h || ty0 > ty1 ||
-      capacity < 0 || row0 < 0 || row0 > row1 || long_min <= 0 || max_seg <= 0)
+  if (!gsl::frame_ok(width, height, tile_w, tile_h, ty0, ty1, capacity, row0, row1, false) || long_min <= 0 || max_seg <= 0)
     return GSL_ERR_BAD_ARG;
   if (!tile_offsets || !render || !alphas || !last_ids || !long_ws) return GSL_ERR_BAD_ARG;
   if (long_ws_bytes < gsl_long_ws_bytes(max_seg)) return GSL_ERR_WORKSPACE;
@@ -1027,8 +1083,7 @@ extern "C" int gsl_long_raster_fwd(const float* Q0, const float* Q1, const float
   hipStream_t st = (hipStream_t)stream;
   gsl::LongWs w = gsl::long_ws_views(long_ws, max_seg);
   if (!map_ready) {  // (gsl_long_sort of the same frame, strip and long_min has listed the segments already)
-    hipLaunchKernelGGL(gsl::k_long_map, dim3(1), dim3(1024), 0, st, tile_offsets, ty0 * tile_w, (ty1 - ty0) * tile_w,
-                       (long long)capacity, long_min, max_seg, 0, w);
+    gsl::launch_long_map(st, tile_offsets, ty0 * tile_w, (ty1 - ty0) * tile_w, (long long)capacity, long_min, max_seg, 0, w);
     GSL_CHECK_LAUNCH();
   }
 #define CALL_LF(DD, EE)                                                                                          \
@@ -1042,7 +1097,7 @@ extern "C" int gsl_long_raster_fwd(const float* Q0, const float* Q1, const float
     hipLaunchKernelGGL((gsl::k_long_combine<DD, EE>), dim3(max_seg), dim3(1024), 0, st, width, height, tile_w,   \
                        render, alphas, last_ids, row0, row1, w);                                                 \
   } while (0)
-  GSL_P_DISPATCH(channels, ed, CALL_LF)
+  GSL_DISPATCH_CH_ED(channels, ed, CALL_LF)
 #undef CALL_LF
   GSL_CHECK_LAUNCH();
   return GSL_OK;

@@ -1,4 +1,4 @@
-// Real spherical-harmonics basis (degree 0..3) and its gradient, shared by sh.hip and fused.hip.
+// Real spherical-harmonics basis (degree 0..3) and its gradient, shared by sh.hip and the fused projection (fused_project*.hip).
 #pragma once
 #include "gsloc_common.h"
 

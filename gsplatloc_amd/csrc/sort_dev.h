@@ -12,16 +12,6 @@ __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int mask) {
   hi = (unsigned)__shfl_xor((int)hi, mask, 64);
   return ((uint64_t)hi << 32) | lo;
 }
-// 32-bit select on a 64-bit scalar mask (v_cndmask_b32_e64 with an SGPR pair).  Written with ?: the compiler sends every
-// compare of the network through VCC: v_cmp_lt -> s_nop -> two v_cndmask (VCC) -> v_cmp_gt -> s_nop -> two v_cndmask per
-// compare-exchange -- two compares where one decides both outputs, and a hazard bubble per compare (round 4 found ~640 s_nop
-// and 2 x 480 v_cmp_u64 in one 1024-key sort).  With the outcome as a ballot every compare-exchange is ONE v_cmp into its
-// own SGPR pair and four selects, and consecutive compares do not wait for each other.
-__device__ __forceinline__ unsigned sort_sel(unsigned long long m, unsigned t, unsigned f) {
-  unsigned r;
-  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(t), "s"(m));
-  return r;
-}
 // Compare-exchange of two keys held in one lane: a <- min, b <- max.
 // A key is (depth bits << 32) | Gaussian index with the depth a POSITIVE FINITE float (every projection of this library
 // culls z <= 0 and z > far_plane), so its 64 bits read as a double are a positive finite double, and positive doubles
@@ -39,11 +29,16 @@ __device__ __forceinline__ void cswap(uint64_t& a, uint64_t& b) {
   a = (uint64_t)__double_as_longlong(lo);
   b = (uint64_t)__double_as_longlong(hi);
 }
-// keep_min_mask: ballot of the lanes that keep the smaller key of (a, partner's o)
+// keep_min_mask: ballot of the lanes that keep the smaller key of (a, partner's o).  The outcome is a ballot and the
+// halves go through gsl::sel: written with ?: the compiler sends every compare of the network through VCC, v_cmp_lt ->
+// s_nop -> two v_cndmask (VCC) -> v_cmp_gt -> s_nop -> two v_cndmask per compare-exchange -- two compares where one
+// decides both outputs, and a hazard bubble per compare (round 4 found ~640 s_nop and 2 x 480 v_cmp_u64 in one 1024-key
+// sort).  This way every compare-exchange is ONE v_cmp into its own SGPR pair and four selects, and consecutive compares
+// do not wait for each other.
 __device__ __forceinline__ uint64_t pick(uint64_t a, uint64_t o, unsigned long long keep_min_mask) {
   const unsigned long long take = ~(__ballot(o < a) ^ keep_min_mask);  // take the partner's key where (o < a) == keep_min
-  return ((uint64_t)sort_sel(take, (unsigned)(o >> 32), (unsigned)(a >> 32)) << 32) |
-         sort_sel(take, (unsigned)o, (unsigned)a);
+  return ((uint64_t)sel(take, (unsigned)(o >> 32), (unsigned)(a >> 32)) << 32) |
+         sel(take, (unsigned)o, (unsigned)a);
 }
 
 // Lane exchanges of the network.  Round 4: the sort kernel's waves spent a quarter of their cycles waiting to ISSUE an LDS

@@ -8,6 +8,7 @@
 //   S(x)  = sqrt(gx^2 + gy^2 + 1e-6), gx/gy = 3x3 Sobel / 8 with replicate padding (kornia.filters.sobel).
 #include "gsloc_common.h"
 #include "loss_dev.h"
+#include "pose_dev.h"
 
 namespace gsl {
 

@@ -1,4 +1,5 @@
-"""Fused single-camera render (host side of csrc/fused.hip).
+"""Fused single-camera render (host side of csrc/fused_project.hip, fused_project_bwd.hip, raster_px.hip,
+raster_g16.hip and raster_det.hip: one file per stage).
 
 ``fused_rasterization`` runs ``gsplat.rasterization``'s whole forward in five
 launches and its backward in three, for the configuration GsplatLoc uses

@@ -131,7 +131,7 @@ def rasterization(
                 f"absgrad with {n_feat} feature channels: they are composited in chunks of {min(int(channel_chunk), 32)} "
                 "and the sum over pixels of |v_means2d| over all channels is not the sum of the per-chunk ones")
 
-    # Hot path: one camera, no background -> the fused five-launch pipeline (csrc/fused.hip).
+    # Hot path: one camera, no background -> the fused five-launch pipeline (csrc/fused_project.hip and the raster_*.hip stages).
     if fused and absgrad:
         # the same kernels with means2d in the graph between projection and compositing (fused.py): it gets .absgrad
         render, alphas, meta = fused_absgrad_rasterization(

@@ -74,6 +74,16 @@ def test_library_exports_every_symbol(repo_root):
     lib = _lib.load_library()
     for name in _declared(repo_root):
         assert hasattr(lib, name), name
+    # ... and nothing else under the library's prefix: a function one source file defines for another is not part of the
+    # ABI and must not be reachable as if it were (a C symbol links against any prototype, right or wrong)
+    import subprocess
+
+    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+    res = subprocess.run([readelf, "--dyn-syms", "--wide", _lib.library_path()], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    defined = {ln.split()[-1] for ln in res.stdout.splitlines() if len(ln.split()) == 8 and ln.split()[6] != "UND"}
+    exported = sorted(n for n in defined if n.startswith("gsl_"))
+    assert exported == _declared(repo_root), sorted(set(exported) ^ set(_declared(repo_root)))
     assert lib.gsl_version().decode().startswith("gsloc_hip")
     assert lib.gsl_status_string(-2).decode() == "workspace too small"
 
