@@ -106,7 +106,14 @@ class RenderContext:
         self.render = torch.zeros(self.H, self.W, self.D, dtype=f32, device=dev)
         self.alphas = torch.zeros(self.H, self.W, 1, dtype=f32, device=dev)
         self.last_ids = torch.zeros(self.H, self.W, dtype=i32, device=dev)
-        self.vacc = torch.zeros(N, 16, dtype=f32, device=dev)  # cleared by the projection backward
+        # the gradient rows: zero whenever a compositing backward starts.  Restored by the projection backward that read
+        # them, or -- sort_clears_rows() -- by the sort launch of the next forward.  _sort_cleared: the last forward's sort
+        # launch did clear them (only the backward of such a forward leaves them to the next one); _rows_dirty: a
+        # projection backward has left them standing and no sort has cleared them since (the next backward then clears
+        # them first)
+        self.vacc = torch.zeros(N, 16, dtype=f32, device=dev)
+        self._rows_dirty = False
+        self._sort_cleared = False
         self.v_viewmat = torch.zeros(4, 4, dtype=f32, device=dev)
         if self.full_grads:
             self.v_means = torch.zeros(N, 3, dtype=f32, device=dev)
@@ -356,6 +363,16 @@ class RenderContext:
                     and 0 < self.bin_cap <= (2048 if mode == "force" else 1024) and self.long_min == 0
                     and not self.deterministic and self.ty0 == 0 and self.ty1 == self.th)
 
+    def sort_clears_rows(self) -> bool:
+        """The gradient rows are cleared by the sort launch of the next forward (gsl_fused_bin_clear) instead of by the
+        projection backward that read them (gsl_fused_project_bwd_keep), which runs at what the memory system gives
+        and so pays for every byte of zeros it stores: general non-deterministic backward with a sort launch of the
+        context's own.  The tiny-splat contexts, the sorting forward and the deterministic mode keep the projection
+        backward that clears what it read.  Read per call, like the other switches: GSLOC_SORT_CLEARS_ROWS=0 is the
+        earlier behaviour everywhere."""
+        return bool(os.environ.get("GSLOC_SORT_CLEARS_ROWS", "1") != "0" and self.vacc is not None and not self.tiny
+                    and not self.deterministic and not self.sorts_in_forward())
+
     def _screen_coherent_order(self) -> bool:
         """Do consecutive Gaussians land in the same or a neighbouring tile (a back-projected depth frame in pixel
         order: the reference's only input, /root/reference/src/my_gsplat/geometry.py:138-161)?  The tiny-splat backward
@@ -414,13 +431,20 @@ class RenderContext:
                              bins=self.bins, bin_cap=self.bin_cap, flags=self.flags, order_ids=self.order_ids)
 
     def _bin(self) -> None:
+        self._sort_cleared = False
         if self.sorts_in_forward():
             return  # (the compositing forward sorts its own tile's bin)
-        stages.fused_bin(self.Q0, self.radii, self.N, self.tw, self.th, self.ty0, self.ty1, tile_n_bits(self.n_tiles),
-                         self.offs, self.capacity, self.keys, self.flatten_ids, self.ws,
-                         write_sorted_keys=int(self.deterministic), bins=self.bins, bin_cap=self.bin_cap,
-                         n_isects=self.n_is, flags=self.flags, long_min=self.long_min if self.bins is not None else 0,
-                         order_ids=self.order_ids, storage_of=self.storage_of)
+        args = (self.Q0, self.radii, self.N, self.tw, self.th, self.ty0, self.ty1, tile_n_bits(self.n_tiles), self.offs,
+                self.capacity, self.keys, self.flatten_ids, self.ws)
+        modes = dict(write_sorted_keys=int(self.deterministic), bins=self.bins, bin_cap=self.bin_cap, n_isects=self.n_is,
+                     flags=self.flags, long_min=self.long_min if self.bins is not None else 0, order_ids=self.order_ids,
+                     storage_of=self.storage_of)
+        if self.sort_clears_rows():
+            stages.fused_bin_clear(*args, self.vacc, **modes)
+            # (behind the call: one that was refused or failed has cleared nothing)
+            self._rows_dirty, self._sort_cleared = False, True
+        else:
+            stages.fused_bin(*args, **modes)
         if self.long_min and self.bins is not None:  # the long lists: sorted by several workgroups
             stages.long_sort(self.offs, self.tw, self.th, self.ty0, self.ty1, self.capacity, self.bins, self.bin_cap,
                              self.keys, self.flatten_ids, self.long_min, self.long_ws, self.max_seg, self.long_passes,
@@ -452,6 +476,9 @@ class RenderContext:
         clear = self.sorts_in_forward() and self._counters_dirty  # the sorting forward left the tile counters set
         clear_ws = self.ws if clear else None
         hits = self.hits if self._hits_valid else None
+        if self._rows_dirty:  # a second backward after one forward: no sort has cleared what the first one left standing
+            stages.fused_clear_rows(self.vacc, self.N)
+            self._rows_dirty = False
         if self.tiny:
             depth_gt, depth_lambda, edge_lambda, partials = tracking_loss if tracking_loss is not None else (None, 0, 0, None)
             stages.tiny_raster_bwd(*common, self.trec, self.vcT, self.row0, self.row1, flags=self.flags,
@@ -477,11 +504,16 @@ class RenderContext:
             mode = dict(vrow=self.vrow, sorted_keys=self.keys, tile_offsets=self.offs, Q0=self.Q0, tile_w=self.tw,
                         tile_h=self.th, ty0=self.ty0, ty1=self.ty1, capacity=self.capacity)
         grads = (self.v_means, self.v_quats, self.v_scales, self.v_opacities) if full else (None, None, None, None)
-        stages.fused_project_bwd(means, quats, scales, opacities, colors if self.rgb else None, self.sh_degree, self.K_sh,
-                                 viewmat, K, self.N, self.W, self.H, self.eps2d, int(self.antialiased), self.D, self.radii,
-                                 self.Q1, self.comps, self.vacc if (not self.tiny or self.long_min) else None, *grads,
-                                 self.v_colors if (full and self.rgb) else None, self.v_viewmat, self.ws, self.n_tiles,
-                                 int(reduce), v_colors_state=self.vc_state if (full and self.rgb) else None, **mode)
+        project_bwd = stages.fused_project_bwd
+        # (only behind a forward whose sort did clear them: a context whose sort launches clear is what the rows are left to)
+        if self._sort_cleared and self.sort_clears_rows():
+            project_bwd = stages.fused_project_bwd_keep
+            self._rows_dirty = True  # (in front of the call: whatever becomes of it, the rows are not known to be zero)
+        project_bwd(means, quats, scales, opacities, colors if self.rgb else None, self.sh_degree, self.K_sh, viewmat, K,
+                    self.N, self.W, self.H, self.eps2d, int(self.antialiased), self.D, self.radii, self.Q1, self.comps,
+                    self.vacc if (not self.tiny or self.long_min) else None, *grads,
+                    self.v_colors if (full and self.rgb) else None, self.v_viewmat, self.ws, self.n_tiles, int(reduce),
+                    v_colors_state=self.vc_state if (full and self.rgb) else None, **mode)
 
     # ------------------------------------------------------------------ forward / backward
     def forward(self, means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor, colors: Optional[Tensor],

@@ -367,12 +367,15 @@ template <int LK>
 __device__ __forceinline__ void wave_sort_tile(const uint64_t* __restrict__ src, int n, long long s, int t, int lane,
                                                uint64_t* __restrict__ keys_out, int32_t* __restrict__ flatten_ids,
                                                int64_t* __restrict__ isect_ids, int64_t cam_enc,
-                                               const int32_t* __restrict__ storage_of, int32_t* ids_lds) {
+                                               const int32_t* __restrict__ storage_of, int32_t* ids_lds,
+                                               const RowClear clr, int clr_part) {
   constexpr int KPT = 1 << LK;
   uint64_t k[KPT];
   int e0 = lane * KPT;
 #pragma unroll
   for (int r = 0; r < KPT; ++r) k[r] = (r * 64 + lane < n) ? src[r * 64 + lane] : GSL_SORT_PAD;
+  keys_arrived();
+  if (clr.rows) clr.run(clr_part, lane, 64);  // (this wave's part of the gradient rows: see RowClear)
   wave_sort_regs<LK>(k, lane);
   if (LK <= 4 && !isect_ids && !keys_out) {  // (32 keys per lane: the ids' registers would cost the instance a wave per SIMD)
 #pragma unroll
@@ -412,6 +415,9 @@ __device__ __forceinline__ void wave_sort_tile(const uint64_t* __restrict__ src,
 // sort below.  The 32-keys-per-lane network is what sets the kernel's register count (141 VGPR once every compare is a
 // ballot: three waves per SIMD, one fewer than a frame of 3 225 tiles needs to be resident at once), so frames whose lists
 // are expected to stay below 1024 keys run the instance without it (gsl_tile_sort_keys).
+// clr (gsl_fused_bin_clear): the launch also zeroes the gradient rows, one part per wave, whatever the wave does with its
+// tile -- behind its key loads when it sorts one in registers (RowClear), at once when its tile is empty, past the strip
+// or left to the workgroup's long-list sort.
 template <int MAXLK>
 __global__ __launch_bounds__(256) void k_tile_sort(int32_t* __restrict__ tile_offsets, int tile_begin,
                                                    int n_strip_tiles, long long capacity,
@@ -420,7 +426,7 @@ __global__ __launch_bounds__(256) void k_tile_sort(int32_t* __restrict__ tile_of
                                                    int write_sorted_keys, uint64_t* __restrict__ bins, int bin_cap,
                                                    const int32_t* __restrict__ counts, int32_t* __restrict__ n_isects,
                                                    int32_t* __restrict__ flags, int long_min,
-                                                   const int32_t* __restrict__ storage_of) {
+                                                   const int32_t* __restrict__ storage_of, const RowClear clr) {
   __shared__ uint64_t skeys[GSL_SORT_LDS_CAP];
   __shared__ int s_scan[8];
   int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -460,6 +466,8 @@ __global__ __launch_bounds__(256) void k_tile_sort(int32_t* __restrict__ tile_of
     }
   };
   int local = blockIdx.x * 4 + wv;
+  const int clr_part = __builtin_amdgcn_readfirstlane(local);
+  bool cleared = false;
   if (local < n_strip_tiles) {
     int t = tile_begin + local;
     long long s, e;
@@ -473,12 +481,14 @@ __global__ __launch_bounds__(256) void k_tile_sort(int32_t* __restrict__ tile_of
     uint64_t* kout = write_sorted_keys ? keys : nullptr;
     int32_t* const ids_lds = reinterpret_cast<int32_t*>(skeys) + wv * 2048;  // (this wave's quarter of the LDS block)
     if (n > 0 && n <= (64 << MAXLK)) {
-      if (n <= 256) wave_sort_tile<2>(src, n, s, t, lane, kout, flatten_ids, isect_ids, cam_enc, storage_of, ids_lds);
-      else if (n <= 512) wave_sort_tile<3>(src, n, s, t, lane, kout, flatten_ids, isect_ids, cam_enc, storage_of, ids_lds);
-      else if (MAXLK == 4 || n <= 1024) wave_sort_tile<4>(src, n, s, t, lane, kout, flatten_ids, isect_ids, cam_enc, storage_of, ids_lds);
-      else wave_sort_tile<(MAXLK > 4 ? 5 : 4)>(src, n, s, t, lane, kout, flatten_ids, isect_ids, cam_enc, storage_of, ids_lds);
+      cleared = true;
+      if (n <= 256) wave_sort_tile<2>(src, n, s, t, lane, kout, flatten_ids, isect_ids, cam_enc, storage_of, ids_lds, clr, clr_part);
+      else if (n <= 512) wave_sort_tile<3>(src, n, s, t, lane, kout, flatten_ids, isect_ids, cam_enc, storage_of, ids_lds, clr, clr_part);
+      else if (MAXLK == 4 || n <= 1024) wave_sort_tile<4>(src, n, s, t, lane, kout, flatten_ids, isect_ids, cam_enc, storage_of, ids_lds, clr, clr_part);
+      else wave_sort_tile<(MAXLK > 4 ? 5 : 4)>(src, n, s, t, lane, kout, flatten_ids, isect_ids, cam_enc, storage_of, ids_lds, clr, clr_part);
     }
   }
+  if (clr.rows && !cleared) clr.run(clr_part, lane, 64);
   // rare: lists too long for one wave, sorted in place by the whole workgroup, one after the other
   for (int q = 0; q < 4; ++q) {
     int lq = blockIdx.x * 4 + q;
@@ -667,7 +677,7 @@ __global__ __launch_bounds__(64) void k_long_merge(const int32_t* __restrict__ t
 }
 
 // Same contract as k_tile_sort (offsets from the counters in binned mode, overflow flags, long lists left to
-// gsl_long_sort), one tile per workgroup.
+// gsl_long_sort, the gradient rows cleared: one part per workgroup), one tile per workgroup.
 __global__ __launch_bounds__(256) void k_tile_sort_wg(int32_t* __restrict__ tile_offsets, int tile_begin,
                                                       int n_strip_tiles, long long capacity,
                                                       uint64_t* __restrict__ keys, int32_t* __restrict__ flatten_ids,
@@ -675,7 +685,7 @@ __global__ __launch_bounds__(256) void k_tile_sort_wg(int32_t* __restrict__ tile
                                                       int write_sorted_keys, uint64_t* __restrict__ bins, int bin_cap,
                                                       const int32_t* __restrict__ counts, int32_t* __restrict__ n_isects,
                                                       int32_t* __restrict__ flags, int long_min,
-                                                      const int32_t* __restrict__ storage_of) {
+                                                      const int32_t* __restrict__ storage_of, const RowClear clr) {
   __shared__ uint64_t skeys[GSL_SORT_LDS_CAP];
   __shared__ int s_scan[5];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -708,13 +718,14 @@ __global__ __launch_bounds__(256) void k_tile_sort_wg(int32_t* __restrict__ tile
   if (e > capacity) e = capacity;
   int n = (int)max(e - s, (long long)0);
   if (bins && n > bin_cap) n = bin_cap;
+  if (clr.rows && (n == 0 || n > 2048)) clr.run(blockIdx.x, tid, 256);  // (no register sort to put the stores behind)
   if (n == 0) return;
   uint64_t* src = bins ? bins + (size_t)t * (size_t)bin_cap : keys + s;
   uint64_t* kout = write_sorted_keys ? keys : nullptr;
   if (n <= 1024) {
-    wg_sort_tile<2>(src, n, s, t, tid, skeys, kout, flatten_ids, isect_ids, cam_enc, storage_of);
+    wg_sort_tile<2, true>(src, n, s, t, tid, skeys, kout, flatten_ids, isect_ids, cam_enc, storage_of, clr, blockIdx.x);
   } else if (n <= 2048) {
-    wg_sort_tile<3>(src, n, s, t, tid, skeys, kout, flatten_ids, isect_ids, cam_enc, storage_of);
+    wg_sort_tile<3, true>(src, n, s, t, tid, skeys, kout, flatten_ids, isect_ids, cam_enc, storage_of, clr, blockIdx.x);
   } else {
     if (long_min > 0 && bins && n > long_min) return;  // sorted by several workgroups: gsl_long_sort
     bitonic_sort_long(src, n, skeys, tid);
@@ -809,16 +820,19 @@ extern "C" int gsl_tile_sort(const int32_t* tile_offsets, int tile_begin, int n_
   if (n_strip_tiles == 0 || capacity == 0) return GSL_OK;
   if (!sort_keys || !flatten_ids) return GSL_ERR_BAD_ARG;
   return gsl::tile_sort_keys(const_cast<int32_t*>(tile_offsets), tile_begin, n_strip_tiles, capacity, sort_keys, flatten_ids,
-                             isect_ids, cam_enc, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, stream);
+                             isect_ids, cam_enc, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, stream);
 }
 
 int gsl::tile_sort_keys(int32_t* tile_offsets, int tile_begin, int n_strip_tiles, int64_t capacity, uint64_t* sort_keys,
                         int32_t* flatten_ids, int64_t* isect_ids, int64_t cam_enc, int write_sorted_keys, uint64_t* bins,
                         int bin_cap, const int32_t* counts, int32_t* n_isects, int32_t* flags, int long_min,
-                        int occupied_tiles, const int32_t* storage_of, void* stream) {
+                        int occupied_tiles, const int32_t* storage_of, float* clear_rows, int clear_n, void* stream) {
   if (!tile_offsets || tile_begin < 0 || n_strip_tiles < 0 || capacity < 0) return GSL_ERR_BAD_ARG;
   if (counts && (!bins || tile_begin != 0)) return GSL_ERR_BAD_ARG;  // the scan runs over all tiles, bins only
-  if (n_strip_tiles == 0 || (capacity == 0 && !counts)) return GSL_OK;
+  if (clear_n < 0 || clear_n > GSL_MAX_GAUSSIANS || (clear_n > 0 && !clear_rows)) return GSL_ERR_BAD_ARG;
+  if (clear_n == 0) clear_rows = nullptr;
+  if (n_strip_tiles == 0 || (capacity == 0 && !counts))  // no sort launch: the rows are still the caller's to find zero
+    return clear_rows ? gsl::zero_u32(clear_rows, (size_t)16 * (size_t)clear_n, (hipStream_t)stream) : GSL_OK;
   if (capacity > 0 && (!sort_keys || !flatten_ids)) return GSL_ERR_BAD_ARG;
   // lists of several hundred keys: one tile per workgroup (waves sort quarters, merged in LDS); short lists: one per wave
   // (occupied_tiles: the tiles that can hold entries -- a strip's, when the launch runs over all tiles of the image)
@@ -839,18 +853,23 @@ int gsl::tile_sort_keys(int32_t* tile_offsets, int tile_begin, int n_strip_tiles
   // (capacity carries ~1.3 x head-room: a mean list of <= ~880 keys, whose longest lists stay below 1024 in a frame of
   // evenly spread splats; a tile that does exceed 1024 takes the workgroup's LDS sort -- slower, never wrong)
   else variant = mean_list <= 1150 ? 0 : 1;
+  // the gradient rows, 4 float4 each, in one part per workgroup (k_tile_sort_wg) or per wave: a multiple of the part's
+  // width, so that every store instruction but a part's last writes one full run
+  const int parts = variant == 2 ? n_strip_tiles : (n_strip_tiles + 3) / 4 * 4, width = variant == 2 ? 256 : 64;
+  const int n4 = 4 * clear_n;
+  const gsl::RowClear clr{(float4*)clear_rows, n4, ((n4 + parts - 1) / parts + width - 1) / width * width};
   if (variant == 2)
     hipLaunchKernelGGL(gsl::k_tile_sort_wg, dim3(n_strip_tiles), dim3(256), 0, (hipStream_t)stream, tile_offsets,
                        tile_begin, n_strip_tiles, (long long)capacity, sort_keys, flatten_ids, isect_ids, cam_enc,
-                       write_sorted_keys, bins, bin_cap, counts, n_isects, flags, long_min, storage_of);
+                       write_sorted_keys, bins, bin_cap, counts, n_isects, flags, long_min, storage_of, clr);
   else if (variant == 0)
     hipLaunchKernelGGL((gsl::k_tile_sort<4>), dim3((n_strip_tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, tile_offsets,
                        tile_begin, n_strip_tiles, (long long)capacity, sort_keys, flatten_ids, isect_ids, cam_enc,
-                       write_sorted_keys, bins, bin_cap, counts, n_isects, flags, long_min, storage_of);
+                       write_sorted_keys, bins, bin_cap, counts, n_isects, flags, long_min, storage_of, clr);
   else
     hipLaunchKernelGGL((gsl::k_tile_sort<5>), dim3((n_strip_tiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, tile_offsets,
                        tile_begin, n_strip_tiles, (long long)capacity, sort_keys, flatten_ids, isect_ids, cam_enc,
-                       write_sorted_keys, bins, bin_cap, counts, n_isects, flags, long_min, storage_of);
+                       write_sorted_keys, bins, bin_cap, counts, n_isects, flags, long_min, storage_of, clr);
   gsl::g_tile_sort_launches[variant].fetch_add(1, std::memory_order_relaxed);
   GSL_CHECK_LAUNCH();
   return GSL_OK;

@@ -393,13 +393,18 @@ extern "C" int gsl_fused_project(const float* means, const float* quats, const f
   return GSL_OK;
 }
 
-extern "C" int gsl_fused_bin(const float* Q0, const int32_t* radii, int N, int tile_w, int tile_h, int ty0, int ty1,
-                             int tile_n_bits, int32_t* tile_offsets, int64_t capacity, uint64_t* sort_keys,
-                             int32_t* flatten_ids, int64_t* isect_ids, void* ws, size_t ws_bytes,
-                             int write_sorted_keys, void* bins, int bin_cap, int32_t* n_isects, int32_t* flags,
-                             int long_min, const int32_t* order_ids, const int32_t* storage_of, void* stream) {
+namespace gsl {
+// gsl_fused_bin and gsl_fused_bin_clear (clear: the latter; rows: its N gradient rows, zeroed whichever way the call ends)
+static int fused_bin(const float* Q0, const int32_t* radii, int N, int tile_w, int tile_h, int ty0, int ty1,
+                     int32_t* tile_offsets, int64_t capacity, uint64_t* sort_keys, int32_t* flatten_ids,
+                     int64_t* isect_ids, void* ws, size_t ws_bytes, int write_sorted_keys, void* bins, int bin_cap,
+                     int32_t* n_isects, int32_t* flags, int long_min, const int32_t* order_ids,
+                     const int32_t* storage_of, bool clear, float* rows, void* stream) {
   if (N < 0 || tile_w <= 0 || tile_h <= 0 || ty0 < 0 || ty1 > tile_h || ty0 > ty1 || capacity < 0)
     return GSL_ERR_BAD_ARG;
+  if (clear && (N > GSL_MAX_GAUSSIANS || (N > 0 && !rows))) return GSL_ERR_BAD_ARG;
+  if (!clear || N == 0) rows = nullptr;
+  const int n_rows = rows ? N : 0;
   int n_tiles = tile_w * tile_h, nst = (ty1 - ty0) * tile_w;
   if (nst > GSL_F_MAX_STRIP_TILES || !tile_offsets) return GSL_ERR_BAD_ARG;
   if (bins) {
@@ -410,9 +415,10 @@ extern "C" int gsl_fused_bin(const float* Q0, const int32_t* radii, int N, int t
     if (capacity > 0 && (!sort_keys || !flatten_ids)) return GSL_ERR_BAD_ARG;
     return gsl::tile_sort_keys(tile_offsets, 0, n_tiles, capacity, sort_keys, flatten_ids, isect_ids, 0,
                                write_sorted_keys, (uint64_t*)bins, bin_cap, (const int32_t*)ws, n_isects, flags,
-                               write_sorted_keys ? 0 : long_min, nst, storage_of, stream);
+                               write_sorted_keys ? 0 : long_min, nst, storage_of, rows, n_rows, stream);
   }
-  if (N == 0 || capacity == 0 || nst == 0) return GSL_OK;
+  if (N == 0 || capacity == 0 || nst == 0)  // no launch of the sort: the rows get one of their own
+    return rows ? gsl::zero_u32(rows, (size_t)16 * (size_t)N, (hipStream_t)stream) : GSL_OK;
   if (!Q0 || !radii || !sort_keys || !flatten_ids) return GSL_ERR_BAD_ARG;
   if (!ws || ws_bytes < gsl_fused_ws_bytes(N, n_tiles)) return GSL_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -422,5 +428,35 @@ extern "C" int gsl_fused_bin(const float* Q0, const int32_t* radii, int N, int t
                      tile_offsets, cursors, (long long)capacity, sort_keys, order_ids);
   GSL_CHECK_LAUNCH();
   return gsl::tile_sort_keys(tile_offsets, ty0 * tile_w, nst, capacity, sort_keys, flatten_ids, isect_ids, 0,
-                             write_sorted_keys, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, storage_of, stream);
+                             write_sorted_keys, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, storage_of, rows, n_rows,
+                             stream);
+}
+}  // namespace gsl
+
+extern "C" int gsl_fused_bin(const float* Q0, const int32_t* radii, int N, int tile_w, int tile_h, int ty0, int ty1,
+                             int tile_n_bits, int32_t* tile_offsets, int64_t capacity, uint64_t* sort_keys,
+                             int32_t* flatten_ids, int64_t* isect_ids, void* ws, size_t ws_bytes,
+                             int write_sorted_keys, void* bins, int bin_cap, int32_t* n_isects, int32_t* flags,
+                             int long_min, const int32_t* order_ids, const int32_t* storage_of, void* stream) {
+  (void)tile_n_bits;
+  return gsl::fused_bin(Q0, radii, N, tile_w, tile_h, ty0, ty1, tile_offsets, capacity, sort_keys, flatten_ids, isect_ids,
+                        ws, ws_bytes, write_sorted_keys, bins, bin_cap, n_isects, flags, long_min, order_ids, storage_of,
+                        false, nullptr, stream);
+}
+
+extern "C" int gsl_fused_bin_clear(const float* Q0, const int32_t* radii, int N, int tile_w, int tile_h, int ty0, int ty1,
+                                   int tile_n_bits, int32_t* tile_offsets, int64_t capacity, uint64_t* sort_keys,
+                                   int32_t* flatten_ids, int64_t* isect_ids, void* ws, size_t ws_bytes,
+                                   int write_sorted_keys, void* bins, int bin_cap, int32_t* n_isects, int32_t* flags,
+                                   int long_min, const int32_t* order_ids, const int32_t* storage_of, float* rows,
+                                   void* stream) {
+  (void)tile_n_bits;
+  return gsl::fused_bin(Q0, radii, N, tile_w, tile_h, ty0, ty1, tile_offsets, capacity, sort_keys, flatten_ids, isect_ids,
+                        ws, ws_bytes, write_sorted_keys, bins, bin_cap, n_isects, flags, long_min, order_ids, storage_of,
+                        true, rows, stream);
+}
+
+extern "C" int gsl_fused_clear_rows(float* rows, int N, void* stream) {
+  if (N < 0 || (N > 0 && !rows)) return GSL_ERR_BAD_ARG;
+  return gsl::zero_u32(rows, (size_t)16 * (size_t)N, (hipStream_t)stream);
 }

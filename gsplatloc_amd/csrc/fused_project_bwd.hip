@@ -13,8 +13,11 @@ namespace gsl {
 // ------------------------------------------------------------------------------------------------
 // Backward 2: per-Gaussian vjp of projection + colour, and the pose reduction.
 // Reads (and clears) the 64-byte gradient rows.  partial rows: [v_R 9][v_t 3][v_campos 3].
+// KEEP (gsl_fused_project_bwd_keep, general path only): the rows are read and left as they are -- the sort launch of
+// the next forward clears them (gsl_fused_bin_clear), and this kernel, which runs at what the memory system gives,
+// writes 48 bytes of zeros per Gaussian less.
 // ------------------------------------------------------------------------------------------------
-template <bool FULL, int D>
+template <bool FULL, int D, bool KEEP>
 __global__ __launch_bounds__(256) void k_fproject_bwd(
     const float* __restrict__ means, const float* __restrict__ quats, const float* __restrict__ scales,
     const float* __restrict__ opacities, const float* __restrict__ colors, int sh_degree, int K_sh,
@@ -114,7 +117,7 @@ __global__ __launch_bounds__(256) void k_fproject_bwd(
       }
     } else {
       r0 = vacc[4 * (size_t)i]; r1 = vacc[4 * (size_t)i + 1]; r2 = vacc[4 * (size_t)i + 2];
-      vacc[4 * (size_t)i] = z; vacc[4 * (size_t)i + 1] = z; vacc[4 * (size_t)i + 2] = z;
+      if (!KEEP) { vacc[4 * (size_t)i] = z; vacc[4 * (size_t)i + 1] = z; vacc[4 * (size_t)i + 2] = z; }
     }
     // row = [vx vy | va vb vc | vop | col0 col1 col2 col3 ...]
     float vm2x = r0.x, vm2y = r0.y, v_ca = r0.z, v_cb = r0.w, v_cc = r1.x, vop_eff = r1.y;
@@ -266,18 +269,19 @@ __global__ __launch_bounds__(1024) void k_freduce_viewmat(const float* __restric
   if (vc_state && threadIdx.x == 0) *vc_state = (*vc_state == 2) ? 0 : 1;
 }
 
-}  // namespace gsl
-extern "C" int gsl_fused_project_bwd(const float* means, const float* quats, const float* scales,
-                                     const float* opacities, const float* colors, int sh_degree, int K_sh,
-                                     const float* viewmat, const float* K, int N, int width, int height,
-                                     float eps2d, int antialiased, int channels, const int32_t* radii,
-                                     const float* Q1, const float* compensations, float* vacc, float* v_means,
-                                     float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
-                                     float* v_viewmat, void* ws, size_t ws_bytes, int n_tiles, const float* vrow,
-                                     const uint64_t* sorted_keys, const int32_t* tile_offsets, const float* Q0,
-                                     int tile_w, int tile_h, int ty0, int ty1, int64_t capacity, float* tiny_trec,
-                                     const float* tiny_vcT, int reduce_viewmat, int32_t* v_colors_state, void* stream) {
+// gsl_fused_project_bwd and gsl_fused_project_bwd_keep (keep: the latter -- the rows of vacc, which it must be given
+// and which are the only source it takes, are left as read)
+static int fused_project_bwd(const float* means, const float* quats, const float* scales, const float* opacities,
+                             const float* colors, int sh_degree, int K_sh, const float* viewmat, const float* K, int N,
+                             int width, int height, float eps2d, int antialiased, int channels, const int32_t* radii,
+                             const float* Q1, const float* compensations, float* vacc, float* v_means, float* v_quats,
+                             float* v_scales, float* v_opacities, float* v_colors, float* v_viewmat, void* ws,
+                             size_t ws_bytes, int n_tiles, const float* vrow, const uint64_t* sorted_keys,
+                             const int32_t* tile_offsets, const float* Q0, int tile_w, int tile_h, int ty0, int ty1,
+                             int64_t capacity, float* tiny_trec, const float* tiny_vcT, int reduce_viewmat,
+                             int32_t* v_colors_state, bool keep, void* stream) {
   if (N < 0 || width <= 0 || height <= 0 || n_tiles <= 0) return GSL_ERR_BAD_ARG;
+  if (keep && (vrow || tiny_trec || (N > 0 && !vacc))) return GSL_ERR_BAD_ARG;
   if (reduce_viewmat && !v_viewmat) return GSL_ERR_BAD_ARG;
   if (channels != 1 && channels != 3 && channels != 4) return GSL_ERR_BAD_ARG;
   bool full = v_means != nullptr;
@@ -302,12 +306,15 @@ extern "C" int gsl_fused_project_bwd(const float* means, const float* quats, con
   float* partials = (float*)((char*)ws + gsl::fused_vm_rows_offset(n_tiles));
   int grid = (N + 255) / 256;
   int32_t* vcs = (full && channels >= 3) ? v_colors_state : nullptr;
-#define CALL_PB(FF, DD)                                                                                          \
-  hipLaunchKernelGGL((gsl::k_fproject_bwd<FF, DD>), dim3(grid), dim3(256), 0, st, means, quats, scales, opacities, \
-                     colors, sh_degree, K_sh, viewmat, K, N, width, height, eps2d, antialiased, radii,             \
-                     (const float4*)Q1, compensations, (float4*)vacc, v_means, v_quats, v_scales, v_opacities,    \
-                     v_colors, partials, (const float4*)vrow, sorted_keys, tile_offsets, (const float4*)Q0, tile_w,   \
-                     tile_h, ty0, ty1, (long long)capacity, (float4*)tiny_trec, tiny_vcT, vcs)
+#define CALL_PB(FF, DD)                                                                                               \
+  do {                                                                                                                \
+    auto kern = keep ? gsl::k_fproject_bwd<FF, DD, true> : gsl::k_fproject_bwd<FF, DD, false>;                        \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, means, quats, scales, opacities, colors, sh_degree, K_sh,  \
+                       viewmat, K, N, width, height, eps2d, antialiased, radii, (const float4*)Q1, compensations,     \
+                       (float4*)vacc, v_means, v_quats, v_scales, v_opacities, v_colors, partials,                    \
+                       (const float4*)vrow, sorted_keys, tile_offsets, (const float4*)Q0, tile_w, tile_h, ty0, ty1,   \
+                       (long long)capacity, (float4*)tiny_trec, tiny_vcT, vcs);                                       \
+  } while (0)
   if (full) {
     if (channels == 1) CALL_PB(true, 1); else if (channels == 3) CALL_PB(true, 3); else CALL_PB(true, 4);
   } else {
@@ -327,3 +334,26 @@ extern "C" int gsl_fused_project_bwd(const float* means, const float* quats, con
   }
   return GSL_OK;
 }
+}  // namespace gsl
+
+#define GSL_PROJECT_BWD_PARAMS                                                                                         \
+  const float *means, const float *quats, const float *scales, const float *opacities, const float *colors,           \
+      int sh_degree, int K_sh, const float *viewmat, const float *K, int N, int width, int height, float eps2d,       \
+      int antialiased, int channels, const int32_t *radii, const float *Q1, const float *compensations, float *vacc,  \
+      float *v_means, float *v_quats, float *v_scales, float *v_opacities, float *v_colors, float *v_viewmat,         \
+      void *ws, size_t ws_bytes, int n_tiles, const float *vrow, const uint64_t *sorted_keys,                         \
+      const int32_t *tile_offsets, const float *Q0, int tile_w, int tile_h, int ty0, int ty1, int64_t capacity,       \
+      float *tiny_trec, const float *tiny_vcT, int reduce_viewmat, int32_t *v_colors_state, void *stream
+#define GSL_PROJECT_BWD_ARGS(KEEP)                                                                                    \
+  means, quats, scales, opacities, colors, sh_degree, K_sh, viewmat, K, N, width, height, eps2d, antialiased,         \
+      channels, radii, Q1, compensations, vacc, v_means, v_quats, v_scales, v_opacities, v_colors, v_viewmat, ws,     \
+      ws_bytes, n_tiles, vrow, sorted_keys, tile_offsets, Q0, tile_w, tile_h, ty0, ty1, capacity, tiny_trec,          \
+      tiny_vcT, reduce_viewmat, v_colors_state, KEEP, stream
+extern "C" int gsl_fused_project_bwd(GSL_PROJECT_BWD_PARAMS) {
+  return gsl::fused_project_bwd(GSL_PROJECT_BWD_ARGS(false));
+}
+extern "C" int gsl_fused_project_bwd_keep(GSL_PROJECT_BWD_PARAMS) {
+  return gsl::fused_project_bwd(GSL_PROJECT_BWD_ARGS(true));
+}
+#undef GSL_PROJECT_BWD_PARAMS
+#undef GSL_PROJECT_BWD_ARGS

@@ -12,11 +12,12 @@ struct LongWs;  // long_dev.h
 int zero_u32(void* p, size_t n_dwords, hipStream_t st);
 
 // binning.hip: gsl_tile_sort that can also leave the sorted (depth bits, id) keys in sort_keys and read the unsorted keys
-// from fixed-capacity per-tile bins instead of sort_keys (gsl_fused_bin)
+// from fixed-capacity per-tile bins instead of sort_keys (gsl_fused_bin), and zero clear_n 64-byte gradient rows at
+// clear_rows along the way (gsl_fused_bin_clear; NULL / 0: none) -- with a launch of their own where no sort launches
 int tile_sort_keys(int32_t* tile_offsets, int tile_begin, int n_strip_tiles, int64_t capacity, uint64_t* sort_keys,
                    int32_t* flatten_ids, int64_t* isect_ids, int64_t cam_enc, int write_sorted_keys, uint64_t* bins,
                    int bin_cap, const int32_t* counts, int32_t* n_isects, int32_t* flags, int long_min, int occupied_tiles,
-                   const int32_t* storage_of, void* stream);
+                   const int32_t* storage_of, float* clear_rows, int clear_n, void* stream);
 
 // raster_px.hip: launch of k_long_map (one workgroup lists the (tile, segment) pairs of the strip's long tiles in w);
 // the caller checks the launch

@@ -157,6 +157,28 @@ __device__ __forceinline__ int prefix_count_share(const int32_t* __restrict__ co
   return acc;
 }
 
+// The gradient rows a sort launch clears for the compositing backward that follows (gsl_fused_bin_clear): n4 float4 from
+// `rows`, cut into parts of `per` float4 (a multiple of the width; the host sizes it so that the launch's parts cover
+// n4).  Part `part` is zeroed by `width` threads -- a wave (64) or a workgroup (256) -- one contiguous run of 16 x width
+// bytes per store instruction.  rows == nullptr: nothing to clear.
+// Where the stores sit: on gfx950 loads and stores share vmcnt, and the compiler counts them in issue order, so stores
+// issued between the key loads and the network would put their acknowledgements in front of the network's first
+// instruction.  The sorts therefore call keys_arrived() -- the wait that first instruction needs anyway -- and issue the
+// stores behind it: nothing in the network waits for vector memory again, and they drain while it runs.  The wait stands
+// in front of the `if (clr.rows)`, not inside it: the compiler places its own waits for the state in which the two
+// paths join, and with keys still in flight on the path without stores it put `s_waitcnt vmcnt(6) .. vmcnt(0)` into the
+// first compare-exchanges of the network -- where the path with stores then waited for every one of them.
+struct RowClear {
+  float4* rows;
+  int n4, per;
+  __device__ __forceinline__ void run(int part, int t, int width) const {
+    const int b = part * per, e = min(n4, b + per);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = b + t; i < e; i += width) rows[i] = z;
+  }
+};
+__device__ __forceinline__ void keys_arrived() { __builtin_amdgcn_s_waitcnt(0x0F70); }  // s_waitcnt vmcnt(0)
+
 // smallest ia in [lo, hi] such that the first d merged elements take ia from A (keys are unique)
 __device__ __forceinline__ int merge_diag(const uint64_t* __restrict__ A, int lenA, const uint64_t* __restrict__ B, int lenB,
                                           int d) {
@@ -176,17 +198,24 @@ __device__ __forceinline__ int merge_diag(const uint64_t* __restrict__ A, int le
 // (wave_sort_regs), the four runs go to LDS and two merge-path passes (every thread merges its 2^LK outputs) finish the
 // job: a third of the compare-exchanges, a quarter of the critical path.  Same result: the keys are unique.
 // ------------------------------------------------------------------------------------------------
-template <int LK>
+// CLR: the instance that may be handed rows to clear (k_tile_sort_wg); the compositing forward that sorts its own bin
+// keeps the instance without the wait.
+template <int LK, bool CLR = false>
 __device__ __forceinline__ void wg_sort_tile(const uint64_t* __restrict__ src, int n, long long s, int t, int tid,
                                              uint64_t* __restrict__ lds, uint64_t* __restrict__ keys_out,
                                              int32_t* __restrict__ flatten_ids, int64_t* __restrict__ isect_ids,
-                                             int64_t cam_enc, const int32_t* __restrict__ storage_of = nullptr) {
+                                             int64_t cam_enc, const int32_t* __restrict__ storage_of = nullptr,
+                                             const RowClear clr = RowClear{nullptr, 0, 0}, int clr_part = 0) {
   constexpr int KPT = 1 << LK, RUN = 64 * KPT;
   const int lane = tid & 63, wv = tid >> 6;
   uint64_t k[KPT];
   const int e0 = wv * RUN + lane * KPT;
 #pragma unroll
   for (int r = 0; r < KPT; ++r) k[r] = (e0 + r < n) ? src[e0 + r] : GSL_SORT_PAD;
+  if (CLR) {  // (this workgroup's part of the gradient rows: see RowClear)
+    keys_arrived();
+    if (clr.rows) clr.run(clr_part, tid, 256);
+  }
   wave_sort_regs<LK>(k, lane);
   uint64_t* bufA = lds;
   uint64_t* bufB = lds + 4 * RUN;

@@ -4,7 +4,8 @@ Each carries the header's parameter names in the header's order, takes tensors, 
 launches on torch's current stream.  What the header documents as NULL / 0 for a mode that is off (fp16 staging, bins,
 deterministic rows, hit lists, long lists, placement, tiny slabs, the fused loss) is keyword-only and defaults to off.
 What the header never lets be NULL is read with ``.data_ptr()`` directly, the rest through ``ptr()``: a call per argument
-adds up on the eager drop-in path.  No other module calls these ten; tests/test_stages_cpu.py pins them to the header.
+adds up on the eager drop-in path.  No other module calls these; tests/test_stages_cpu.py and
+tests/test_rows_cleared_by_sort_cpu.py pin them to the header.
 """
 from __future__ import annotations
 
@@ -48,6 +49,21 @@ def fused_bin(Q0, radii, N, tile_w, tile_h, ty0, ty1, tile_n_bits, tile_offsets,
         Q0.data_ptr(), radii.data_ptr(), N, tile_w, tile_h, ty0, ty1, tile_n_bits, tile_offsets.data_ptr(), capacity,
         sort_keys.data_ptr(), ptr(flatten_ids), ptr(isect_ids), ws.data_ptr(), ws.numel(), write_sorted_keys, ptr(bins),
         bin_cap, ptr(n_isects), ptr(flags), long_min, ptr(order_ids), ptr(storage_of), current_stream()), "gsl_fused_bin")
+
+
+def fused_bin_clear(Q0, radii, N, tile_w, tile_h, ty0, ty1, tile_n_bits, tile_offsets, capacity, sort_keys, flatten_ids, ws,
+                    rows, *, isect_ids=None, write_sorted_keys=0, bins=None, bin_cap=0, n_isects=None, flags=None,
+                    long_min=0, order_ids=None, storage_of=None):
+    """fused_bin whose sort launch also zeroes the N gradient rows."""
+    check(load_library().gsl_fused_bin_clear(
+        Q0.data_ptr(), radii.data_ptr(), N, tile_w, tile_h, ty0, ty1, tile_n_bits, tile_offsets.data_ptr(), capacity,
+        sort_keys.data_ptr(), ptr(flatten_ids), ptr(isect_ids), ws.data_ptr(), ws.numel(), write_sorted_keys, ptr(bins),
+        bin_cap, ptr(n_isects), ptr(flags), long_min, ptr(order_ids), ptr(storage_of), ptr(rows), current_stream()),
+        "gsl_fused_bin_clear")
+
+
+def fused_clear_rows(rows, N):
+    check(load_library().gsl_fused_clear_rows(ptr(rows), N, current_stream()), "gsl_fused_clear_rows")
 
 
 def fused_raster_fwd(Q0, Q1, Q2, channels, ed, width, height, tile_w, tile_h, ty0, ty1, tile_offsets, flatten_ids, capacity,
@@ -119,6 +135,21 @@ def fused_project_bwd(means, quats, scales, opacities, colors, sh_degree, K_sh, 
         ptr(v_viewmat), ws.data_ptr(), ws.numel(), n_tiles, ptr(vrow), ptr(sorted_keys), ptr(tile_offsets), ptr(Q0), tile_w,
         tile_h, ty0, ty1, capacity, ptr(tiny_trec), ptr(tiny_vcT), reduce_viewmat, ptr(v_colors_state), current_stream()),
         "gsl_fused_project_bwd")
+
+
+def fused_project_bwd_keep(means, quats, scales, opacities, colors, sh_degree, K_sh, viewmat, K, N, width, height, eps2d,
+                           antialiased, channels, radii, Q1, compensations, vacc, v_means, v_quats, v_scales, v_opacities,
+                           v_colors, v_viewmat, ws, n_tiles, reduce_viewmat, *, vrow=None, sorted_keys=None,
+                           tile_offsets=None, Q0=None, tile_w=0, tile_h=0, ty0=0, ty1=0, capacity=0, tiny_trec=None,
+                           tiny_vcT=None, v_colors_state=None):
+    """fused_project_bwd (general path) that reads the gradient rows and leaves them standing."""
+    check(load_library().gsl_fused_project_bwd_keep(
+        means.data_ptr(), quats.data_ptr(), scales.data_ptr(), opacities.data_ptr(), ptr(colors), sh_degree, K_sh,
+        viewmat.data_ptr(), K.data_ptr(), N, width, height, eps2d, antialiased, channels, radii.data_ptr(), Q1.data_ptr(),
+        ptr(compensations), ptr(vacc), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_opacities), ptr(v_colors),
+        ptr(v_viewmat), ws.data_ptr(), ws.numel(), n_tiles, ptr(vrow), ptr(sorted_keys), ptr(tile_offsets), ptr(Q0), tile_w,
+        tile_h, ty0, ty1, capacity, ptr(tiny_trec), ptr(tiny_vcT), reduce_viewmat, ptr(v_colors_state), current_stream()),
+        "gsl_fused_project_bwd_keep")
 
 
 def fused_absgrad(Q0, Q1, Q2, channels, ed, width, height, tile_w, tile_h, tile_offsets, flatten_ids, capacity, render,

@@ -285,7 +285,7 @@ int gsl_vacc_unpack(const float* vacc, int n_gaussians, int channels, float* v_m
  *                     ValueError for a visible Gaussian with a negative, -0.0 or NaN depth).
  * Limits: N <= 2^26 Gaussians per call (gsl_fused_project returns GSL_ERR_BAD_ARG beyond: the compositing backward
  *                     addresses the 64-byte gradient rows of vacc by 32-bit byte offsets).
- * gsl_fused_project_bwd : consumes AND CLEARS vacc; v_means/v_quats/v_scales/v_opacities (and
+ * gsl_fused_project_bwd : consumes AND CLEARS vacc (gsl_fused_project_bwd_keep: consumes it and leaves it); v_means/v_quats/v_scales/v_opacities (and
  *                     v_colors, shaped like colors) may be NULL together (pose-only);
  *                     v_viewmat[16] is overwritten (row 3 = 0).  tiny_trec / tiny_vcT (may be NULL): the slabs
  *                     gsl_tiny_raster_bwd filled; the kernel then folds them itself (pass 2 of the tiny-splat
@@ -309,6 +309,30 @@ int gsl_fused_bin(const float* Q0, const int32_t* radii, int N, int tile_w, int 
                   uint64_t* sort_keys, int32_t* flatten_ids, int64_t* isect_ids, void* ws,
                   size_t ws_bytes, int write_sorted_keys, void* bins, int bin_cap, int32_t* n_isects,
                   int32_t* flags, int long_min, const int32_t* order_ids, const int32_t* storage_of, void* stream);
+/* Who clears the gradient rows.  The compositing backward adds into vacc and must find it zero.  By default
+ * gsl_fused_project_bwd restores that: it clears every row it has read -- 48 bytes of zero stores per visible Gaussian
+ * in the one kernel of the step that runs at what the memory system gives.  A caller that renders again and again (a
+ * context with preallocated buffers) can move the clearing into the sort launch of the NEXT forward, whose memory pipes
+ * are idle while its waves run their sorting networks:
+ *   gsl_fused_bin_clear        = gsl_fused_bin, and the same launch zeroes rows[N][16] (all of it, contiguously, split
+ *                                over the launch's waves / workgroups whatever their number; every kernel behind the
+ *                                sort, binned or two-pass, whole frame or strip).  rows must not be NULL when N > 0.
+ *                                Where gsl_fused_bin would return without a sort launch (capacity 0, an empty strip)
+ *                                the rows are zeroed by a launch of their own: after GSL_OK they are zero.
+ *   gsl_fused_project_bwd_keep = gsl_fused_project_bwd on the general path (vacc required; vrow and tiny_trec must be
+ *                                NULL), reading the rows and leaving them as they are.
+ *   gsl_fused_clear_rows       : zeroes rows[N][16] with a kernel of the library (not a memset node: see
+ *                                csrc/misc.hip) -- for the caller that runs a second backward after one forward and
+ *                                so finds the rows of a _keep call still standing.
+ * The invariant is unchanged -- zero rows when a compositing backward starts -- and the caller keeps track of who owes
+ * the clearing (gsplatloc_amd/context.py: RenderContext._rows_dirty). */
+int gsl_fused_bin_clear(const float* Q0, const int32_t* radii, int N, int tile_w, int tile_h, int ty0,
+                        int ty1, int tile_n_bits, int32_t* tile_offsets, int64_t capacity,
+                        uint64_t* sort_keys, int32_t* flatten_ids, int64_t* isect_ids, void* ws,
+                        size_t ws_bytes, int write_sorted_keys, void* bins, int bin_cap, int32_t* n_isects,
+                        int32_t* flags, int long_min, const int32_t* order_ids, const int32_t* storage_of,
+                        float* rows, void* stream);
+int gsl_fused_clear_rows(float* rows, int N, void* stream);
 int gsl_fused_raster_fwd(const float* Q0, const float* Q1, const float* Q2, int channels, int ed,
                          int width, int height, int tile_w, int tile_h, int ty0, int ty1,
                          const int32_t* tile_offsets, const int32_t* flatten_ids, int64_t capacity,
@@ -373,6 +397,16 @@ int gsl_fused_project_bwd(const float* means, const float* quats, const float* s
                           const uint64_t* sorted_keys, const int32_t* tile_offsets, const float* Q0, int tile_w,
                           int tile_h, int ty0, int ty1, int64_t capacity, float* tiny_trec, const float* tiny_vcT,
                           int reduce_viewmat, int32_t* v_colors_state, void* stream);
+int gsl_fused_project_bwd_keep(const float* means, const float* quats, const float* scales,
+                               const float* opacities, const float* colors, int sh_degree, int K_sh,
+                               const float* viewmat, const float* K, int N, int width, int height,
+                               float eps2d, int antialiased, int channels, const int32_t* radii,
+                               const float* Q1, const float* compensations, float* vacc, float* v_means,
+                               float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
+                               float* v_viewmat, void* ws, size_t ws_bytes, int n_tiles, const float* vrow,
+                               const uint64_t* sorted_keys, const int32_t* tile_offsets, const float* Q0, int tile_w,
+                               int tile_h, int ty0, int ty1, int64_t capacity, float* tiny_trec, const float* tiny_vcT,
+                               int reduce_viewmat, int32_t* v_colors_state, void* stream);
 /* v_colors_state (int32[1], may be NULL): the caller's promise that v_colors is the SAME buffer in every call that is
  * given this state word; initialise it to 1 together with a zero-filled v_colors (or to 0 for a buffer of unknown
  * content).  While it reads 1 a Gaussian whose colour gradient is zero -- all of them under a depth-only loss,
