@@ -274,19 +274,23 @@ class RenderContext:
         hr = max(headroom, 1.5)
         seg = float(self.lib.gsl_long_segment())
         segs = int(torch.ceil(near.double() * hr / seg).sum()) + 3 * int(math.ceil(float(near.max()) * hr / seg)) + 8
+        self._size_long(long_min, segs, float(near.max()))
+
+    def _size_long(self, long_min: int, segs: int, longest: float) -> None:
+        """The long-list state for lists above long_min entries, a workspace of `segs` segments and a longest list of
+        `longest` keys.  Merge passes of the long-list sort: runs of one sort segment doubled until they cover 1.5 x the
+        longest list."""
         self.long_min, self.max_seg = long_min, segs
-        # merge passes of the long-list sort: runs of one sort segment doubled until they cover 1.5 x the longest list
-        self.long_passes = max(1, math.ceil(math.log2(max(2.0, 1.5 * float(near.max()) / self.lib.gsl_long_sort_segment()))))
+        self.long_passes = math.ceil(math.log2(max(2.0, 1.5 * longest / self.lib.gsl_long_sort_segment())))
         self.long_ws_bytes = self.lib.gsl_long_ws_bytes(segs)
         self.long_ws = torch.zeros(self.long_ws_bytes, dtype=torch.uint8, device=self.device)
 
     def grow_long(self, needed: int) -> None:
         """Recovery after long_overflowed(): a workspace for 1.5 x the segments the frame needed."""
-        self.long_min, self.max_seg = max(self.long_min, LONG_MIN), max(self.max_seg, int(needed * 1.5) + 8)
-        runs = needed * self.lib.gsl_long_segment() / self.lib.gsl_long_sort_segment()
-        self.long_passes = max(self.long_passes, math.ceil(math.log2(max(2.0, 1.5 * runs))))
-        self.long_ws_bytes = self.lib.gsl_long_ws_bytes(self.max_seg)
-        self.long_ws = torch.zeros(self.long_ws_bytes, dtype=torch.uint8, device=self.device)
+        passes = self.long_passes
+        self._size_long(max(self.long_min, LONG_MIN), max(self.max_seg, int(needed * 1.5) + 8),
+                        needed * self.lib.gsl_long_segment())
+        self.long_passes = max(passes, self.long_passes)
 
     def long_overflowed(self) -> int:
         """Host sync: 0, or the number of (tile, segment) pairs a frame needed beyond the long-list workspace."""
@@ -331,11 +335,7 @@ class RenderContext:
             long_min = max(LONG_MIN, int(4.0 * self._mean_list))
             if longest > int(long_min * 0.75):
                 seg = float(self.lib.gsl_long_segment())
-                segs = 4 * int(math.ceil(longest * 1.5 / seg)) + 8
-                self.long_min, self.max_seg = long_min, segs
-                self.long_passes = max(1, math.ceil(math.log2(max(2.0, 1.5 * longest / self.lib.gsl_long_sort_segment()))))
-                self.long_ws_bytes = self.lib.gsl_long_ws_bytes(segs)
-                self.long_ws = torch.zeros(self.long_ws_bytes, dtype=torch.uint8, device=self.device)
+                self._size_long(long_min, 4 * int(math.ceil(longest * 1.5 / seg)) + 8, longest)
 
     def _choose_backward(self) -> None:
         """Tiny-splat backward (per-splat 4x4 record slabs, no reduction, no atomics) when no splat reaches

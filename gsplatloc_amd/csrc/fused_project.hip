@@ -1,5 +1,6 @@
 // Fused single-camera render pipeline for GsplatLoc's pose-tracking loop (the hot path):
-//   forward : project + SH colour + pack + tile histogram  -> scan -> scatter -> per-tile LDS sort      (this file)
+//   forward : project + SH colour + pack + tile histogram                                                (this file)
+//             -> scan -> scatter (binning.hip) -> per-tile sort (tile_sort.hip)
 //             -> composite (expected-depth normalisation fused)                                          (raster_px.hip)
 //   backward: composite vjp (packed 64-byte gradient rows)            (raster_g16.hip; deterministic: raster_det.hip)
 //             -> projection/SH vjp + pose reduction                                                      (fused_project_bwd.hip)
@@ -19,11 +20,6 @@
 #include "tile_dev.h"
 
 namespace gsl {
-
-#ifndef GSL_F_BIN_THREADS
-#define GSL_F_BIN_THREADS 512
-#endif
-#define GSL_F_MAX_STRIP_TILES 8192
 
 // Radius of the smallest disc around the centre that holds the whole alpha >= 1/255 ellipse {sigma <= tau}:
 // sqrt(2 tau / lambda_min(conic)).  (Round 2 stored the half-extent of the ellipse's axis-aligned bounding box, which is
@@ -49,7 +45,7 @@ __device__ __forceinline__ float cull_radius(float ca, float cb, float cc, float
 // distinct tile per workgroup, ranks inside the workgroup from LDS) and writes the (depth bits | id) key there: the
 // separate scatter pass and its second read of the records disappear.  tile_counts ends up holding the tile sizes.
 template <bool RGB, bool BINNED>
-__global__ __launch_bounds__(GSL_F_BIN_THREADS) void k_fproject(
+__global__ __launch_bounds__(GSL_BIN_THREADS) void k_fproject(
     const float* __restrict__ means, const float* __restrict__ quats, const float* __restrict__ scales,
     const float* __restrict__ opacities, const float* __restrict__ colors, int sh_degree, int K_sh,
     const float* __restrict__ V, const float* __restrict__ Kmat, int N, int W, int H, float eps2d, float near_plane,
@@ -71,10 +67,10 @@ __global__ __launch_bounds__(GSL_F_BIN_THREADS) void k_fproject(
   // workgroup's 512 touch a band of two or three tile rows, not the frame's 3 225 tiles (the fixed 16-step loops were a
   // quarter of the kernel's VALU instructions).
   int* const s_rng = s_hist + nst;
-  for (int k = threadIdx.x; k < nst; k += GSL_F_BIN_THREADS) s_hist[k] = 0;
+  for (int k = threadIdx.x; k < nst; k += GSL_BIN_THREADS) s_hist[k] = 0;
   if (threadIdx.x == 0) { s_rng[0] = nst; s_rng[1] = -1; }
   __syncthreads();
-  int i = blockIdx.x * GSL_F_BIN_THREADS + threadIdx.x;
+  int i = blockIdx.x * GSL_BIN_THREADS + threadIdx.x;
   Cam cam = load_cam(V, Kmat);
   int xmin = 0, ymin = 0, xmax = 0, ymax = 0;
   uint64_t key = 0;
@@ -174,10 +170,7 @@ __global__ __launch_bounds__(GSL_F_BIN_THREADS) void k_fproject(
     }
     if (Qh) store_half_record(Qh, (size_t)i, o0, o1, make_float4(c0, c1, c2, 0.f));
     if (radius > 0) {
-      tile_rect(o0.x, o0.y, radius, 16, tile_w, tile_h, xmin, ymin, xmax, ymax);
-      ymin = max(ymin, ty0);
-      ymax = min(ymax, ty1);
-      if (ymax < ymin) ymax = ymin;
+      strip_rect(o0.x, o0.y, radius, 16, tile_w, tile_h, ty0, ty1, xmin, ymin, xmax, ymax);
       key = ((uint64_t)__float_as_uint(o0.z) << 32) | (uint32_t)(order_ids ? order_ids[i] : i);
     }
     if (tiles_per_gauss) tiles_per_gauss[i] = (xmax - xmin) * (ymax - ymin);
@@ -197,27 +190,27 @@ __global__ __launch_bounds__(GSL_F_BIN_THREADS) void k_fproject(
   __syncthreads();
   const int k_lo = __builtin_amdgcn_readfirstlane(s_rng[0]), k_hi = __builtin_amdgcn_readfirstlane(s_rng[1]);
   if (!BINNED) {
-    for (int k = k_lo + (int)threadIdx.x; k <= k_hi; k += GSL_F_BIN_THREADS) {
+    for (int k = k_lo + (int)threadIdx.x; k <= k_hi; k += GSL_BIN_THREADS) {
       int c = s_hist[k];
       if (c) atomicAdd(&tile_counts[tbase + k], c);
     }
     return;
   }
   // all of a thread's returning atomics are issued before the first result is consumed
-  int res[GSL_F_MAX_STRIP_TILES / GSL_F_BIN_THREADS];
+  int res[GSL_MAX_STRIP_TILES / GSL_BIN_THREADS];
 #pragma unroll
-  for (int u = 0; u < GSL_F_MAX_STRIP_TILES / GSL_F_BIN_THREADS; ++u) {
+  for (int u = 0; u < GSL_MAX_STRIP_TILES / GSL_BIN_THREADS; ++u) {
     res[u] = 0;
-    if (k_lo + u * GSL_F_BIN_THREADS <= k_hi) {  // (wave-uniform)
-      int k = k_lo + (int)threadIdx.x + u * GSL_F_BIN_THREADS;
+    if (k_lo + u * GSL_BIN_THREADS <= k_hi) {  // (wave-uniform)
+      int k = k_lo + (int)threadIdx.x + u * GSL_BIN_THREADS;
       int c = (k <= k_hi) ? s_hist[k] : 0;
       res[u] = c ? atomicAdd(&tile_counts[tbase + k], c) : 0;
     }
   }
 #pragma unroll
-  for (int u = 0; u < GSL_F_MAX_STRIP_TILES / GSL_F_BIN_THREADS; ++u) {
-    if (k_lo + u * GSL_F_BIN_THREADS <= k_hi) {
-      int k = k_lo + (int)threadIdx.x + u * GSL_F_BIN_THREADS;
+  for (int u = 0; u < GSL_MAX_STRIP_TILES / GSL_BIN_THREADS; ++u) {
+    if (k_lo + u * GSL_BIN_THREADS <= k_hi) {
+      int k = k_lo + (int)threadIdx.x + u * GSL_BIN_THREADS;
       if (k <= k_hi && s_hist[k]) s_hist[k] = res[u];  // first slot of this workgroup's span; ranks count up from it
     }
   }
@@ -227,107 +220,6 @@ __global__ __launch_bounds__(GSL_F_BIN_THREADS) void k_fproject(
       int lt = y * tile_w + x - tbase;
       int slot = atomicAdd(&s_hist[lt], 1);
       if (slot < bin_cap) bins[(size_t)(tbase + lt) * (size_t)bin_cap + slot] = key;
-    }
-}
-
-// Exclusive scan of tile counts (single workgroup) -> offsets[n+1], total, zeroed cursors.  The counts are cleared
-// after they are read (the next projection accumulates into them again).  bin_cap > 0: a tile keeps at most bin_cap
-// entries (what its bin holds); a larger count raises flags[1] and leaves the largest count seen in flags[2].
-__global__ __launch_bounds__(1024) void k_ftile_scan(int32_t* __restrict__ counts, int n,
-                                                     int32_t* __restrict__ offsets, int32_t* __restrict__ n_isects,
-                                                     int32_t* __restrict__ cursors, int bin_cap,
-                                                     int32_t* __restrict__ flags) {
-  __shared__ int wsum[16];
-  __shared__ int carry_s;
-  int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  for (int base = 0; base < n; base += 1024) {
-    int i = base + tid;
-    int v = (i < n) ? counts[i] : 0;
-    if (i < n) counts[i] = 0;
-    if (bin_cap > 0 && v > bin_cap) {
-      if (flags) { flags[1] = 1; atomicMax(&flags[2], v); }
-      v = bin_cap;
-    }
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      int y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wv] = x;
-    __syncthreads();
-    int woff = 0;
-    for (int k = 0; k < wv; ++k) woff += wsum[k];
-    int carry = carry_s;
-    if (i < n) {
-      offsets[i] = carry + woff + x - v;
-      cursors[i] = 0;
-    }
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + woff + x;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    offsets[n] = carry_s;
-    n_isects[0] = carry_s;
-  }
-}
-
-// Forward 2: scatter (depth bits | Gaussian id) keys into the tile buckets.
-__global__ __launch_bounds__(GSL_F_BIN_THREADS) void k_fscatter(
-    const float4* __restrict__ Q0, const int32_t* __restrict__ radii, int N, int tile_w, int tile_h, int ty0, int ty1,
-    const int32_t* __restrict__ tile_offsets, int32_t* __restrict__ cursors, long long capacity,
-    uint64_t* __restrict__ keys, const int32_t* __restrict__ order_ids) {
-  extern __shared__ int s_mem[];
-  int nst = (ty1 - ty0) * tile_w, tbase = ty0 * tile_w;
-  int* s_cnt = s_mem;
-  int* s_base = s_mem + nst;
-  for (int k = threadIdx.x; k < nst; k += GSL_F_BIN_THREADS) s_cnt[k] = 0;
-  __syncthreads();
-  int i = blockIdx.x * GSL_F_BIN_THREADS + threadIdx.x;
-  int xmin = 0, ymin = 0, xmax = 0, ymax = 0;
-  uint64_t key = 0;
-  if (i < N) {
-    int r = radii[i];
-    if (r > 0) {
-      float4 q0 = GSL_Q(Q0, i);
-      tile_rect(q0.x, q0.y, r, 16, tile_w, tile_h, xmin, ymin, xmax, ymax);
-      ymin = max(ymin, ty0);
-      ymax = min(ymax, ty1);
-      if (ymax < ymin) ymax = ymin;
-      key = ((uint64_t)__float_as_uint(q0.z) << 32) | (uint32_t)(order_ids ? order_ids[i] : i);
-    }
-  }
-  for (int y = ymin; y < ymax; ++y)
-    for (int x = xmin; x < xmax; ++x) atomicAdd(&s_cnt[y * tile_w + x - tbase], 1);
-  __syncthreads();
-  // one returning global atomic per distinct tile reserves this workgroup's span of the bucket;
-  // all of a thread's atomics are issued before the first result is consumed
-  {
-    int res[GSL_F_MAX_STRIP_TILES / GSL_F_BIN_THREADS];
-#pragma unroll
-    for (int u = 0; u < GSL_F_MAX_STRIP_TILES / GSL_F_BIN_THREADS; ++u) {
-      int k = threadIdx.x + u * GSL_F_BIN_THREADS;
-      int c = (k < nst) ? s_cnt[k] : 0;
-      res[u] = c ? atomicAdd(&cursors[tbase + k], c) : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < GSL_F_MAX_STRIP_TILES / GSL_F_BIN_THREADS; ++u) {
-      int k = threadIdx.x + u * GSL_F_BIN_THREADS;
-      if (k < nst) {
-        if (s_cnt[k]) s_base[k] = tile_offsets[tbase + k] + res[u];
-        s_cnt[k] = 0;
-      }
-    }
-  }
-  __syncthreads();
-  for (int y = ymin; y < ymax; ++y)
-    for (int x = xmin; x < xmax; ++x) {
-      int lt = y * tile_w + x - tbase;
-      long long pos = (long long)s_base[lt] + atomicAdd(&s_cnt[lt], 1);
-      if (pos < capacity) keys[pos] = key;
     }
 }
 
@@ -358,7 +250,7 @@ extern "C" int gsl_fused_project(const float* means, const float* quats, const f
   if (N > GSL_MAX_GAUSSIANS) return GSL_ERR_BAD_ARG;  // (packed gradient rows are addressed by 32-bit byte offsets)
   if (tile_w * 16 < width || tile_h * 16 < height) return GSL_ERR_BAD_ARG;
   int n_tiles = tile_w * tile_h, nst = (ty1 - ty0) * tile_w;
-  if (nst > GSL_F_MAX_STRIP_TILES) return GSL_ERR_BAD_ARG;
+  if (nst > GSL_MAX_STRIP_TILES) return GSL_ERR_BAD_ARG;
   if (!viewmat || !K || !tile_offsets || !n_isects) return GSL_ERR_BAD_ARG;
   if (N > 0 && (!means || !quats || !scales || !opacities || !radii || !Q0 || !Q1)) return GSL_ERR_BAD_ARG;
   if (Q2 && !colors) return GSL_ERR_BAD_ARG;
@@ -373,7 +265,7 @@ extern "C" int gsl_fused_project(const float* means, const float* quats, const f
   // binned mode relies on the scan leaving the counters cleared (ws zero-filled once by the caller): no clearing launch
   if (!bins && gsl::zero_u32(counts, (size_t)n_tiles, st) != GSL_OK) return GSL_ERR_HIP;
   if (N > 0) {
-    dim3 grid((N + GSL_F_BIN_THREADS - 1) / GSL_F_BIN_THREADS), block(GSL_F_BIN_THREADS);
+    dim3 grid((N + GSL_BIN_THREADS - 1) / GSL_BIN_THREADS), block(GSL_BIN_THREADS);
     size_t lds = (size_t)(nst + 2) * sizeof(int);  // counters + the touched range
 #define CALL_P(RGBV, BINV)                                                                                            \
   hipLaunchKernelGGL((gsl::k_fproject<RGBV, BINV>), grid, block, lds, st, means, quats, scales, opacities, colors,    \
@@ -387,8 +279,7 @@ extern "C" int gsl_fused_project(const float* means, const float* quats, const f
     GSL_CHECK_LAUNCH();
   }
   if (bins) return GSL_OK;  // binned mode: gsl_fused_bin's sort kernel adds up the tile sizes itself
-  hipLaunchKernelGGL(gsl::k_ftile_scan, dim3(1), dim3(1024), 0, st, counts, n_tiles, tile_offsets, n_isects, cursors, 0,
-                     flags);
+  gsl::launch_tile_scan(st, counts, n_tiles, tile_offsets, n_isects, cursors);
   GSL_CHECK_LAUNCH();
   return GSL_OK;
 }
@@ -406,7 +297,7 @@ static int fused_bin(const float* Q0, const int32_t* radii, int N, int tile_w, i
   if (!clear || N == 0) rows = nullptr;
   const int n_rows = rows ? N : 0;
   int n_tiles = tile_w * tile_h, nst = (ty1 - ty0) * tile_w;
-  if (nst > GSL_F_MAX_STRIP_TILES || !tile_offsets) return GSL_ERR_BAD_ARG;
+  if (nst > GSL_MAX_STRIP_TILES || !tile_offsets) return GSL_ERR_BAD_ARG;
   if (bins) {
     // gsl_fused_project already put every key into its tile's bin and left the tile sizes in the counters: the sort
     // kernel runs over ALL tiles, writes tile_offsets[n_tiles + 1] and n_isects itself (sizes outside the strip are 0)
@@ -423,9 +314,8 @@ static int fused_bin(const float* Q0, const int32_t* radii, int N, int tile_w, i
   if (!ws || ws_bytes < gsl_fused_ws_bytes(N, n_tiles)) return GSL_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   int32_t* cursors = (int32_t*)ws + n_tiles;
-  hipLaunchKernelGGL(gsl::k_fscatter, dim3((N + GSL_F_BIN_THREADS - 1) / GSL_F_BIN_THREADS), dim3(GSL_F_BIN_THREADS),
-                     (size_t)2 * nst * sizeof(int), st, (const float4*)Q0, radii, N, tile_w, tile_h, ty0, ty1,
-                     tile_offsets, cursors, (long long)capacity, sort_keys, order_ids);
+  gsl::launch_record_scatter(st, Q0, radii, order_ids, N, tile_w, tile_h, ty0, ty1, tile_offsets, cursors,
+                             (long long)capacity, sort_keys);
   GSL_CHECK_LAUNCH();
   return gsl::tile_sort_keys(tile_offsets, ty0 * tile_w, nst, capacity, sort_keys, flatten_ids, isect_ids, 0,
                              write_sorted_keys, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, storage_of, rows, n_rows,

@@ -11,7 +11,16 @@ struct LongWs;  // long_dev.h
 // misc.hip: zero n dwords with a kernel of the library (never hipMemsetAsync: see the note there)
 int zero_u32(void* p, size_t n_dwords, hipStream_t st);
 
-// binning.hip: gsl_tile_sort that can also leave the sorted (depth bits, id) keys in sort_keys and read the unsorted keys
+// binning.hip: the launches of two-pass binning that the staged API and the fused pipeline share (the caller checks the
+// launch).  The scan of the tile counts -> tile_offsets[n_tiles + 1], total, cursors zeroed, counts cleared; and the
+// scatter of the (depth bits, id) keys of the Q0 records into the tile buckets (order_ids: NULL, or the id of every slot)
+void launch_tile_scan(hipStream_t st, int32_t* counts, int n_tiles, int32_t* tile_offsets, int32_t* n_isects,
+                      int32_t* cursors);
+void launch_record_scatter(hipStream_t st, const float* Q0, const int32_t* radii, const int32_t* order_ids, int N,
+                           int tile_w, int tile_h, int ty0, int ty1, const int32_t* tile_offsets, int32_t* cursors,
+                           long long capacity, uint64_t* keys);
+
+// tile_sort.hip: gsl_tile_sort that can also leave the sorted (depth bits, id) keys in sort_keys and read the unsorted keys
 // from fixed-capacity per-tile bins instead of sort_keys (gsl_fused_bin), and zero clear_n 64-byte gradient rows at
 // clear_rows along the way (gsl_fused_bin_clear; NULL / 0: none) -- with a launch of their own where no sort launches
 int tile_sort_keys(int32_t* tile_offsets, int tile_begin, int n_strip_tiles, int64_t capacity, uint64_t* sort_keys,

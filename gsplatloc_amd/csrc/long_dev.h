@@ -1,4 +1,4 @@
-// Long tile lists split over workgroups: segment sizes and the views into the caller's long_ws (binning.hip: sort;
+// Long tile lists split over workgroups: segment sizes and the views into the caller's long_ws (tile_sort.hip: sort;
 // raster_px.hip: k_long_map and the forward; raster_g16.hip: backward).
 #pragma once
 #include "gsloc_common.h"

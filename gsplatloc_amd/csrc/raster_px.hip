@@ -418,24 +418,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SORT == 3 ?
   long long sorted_rs = 0, sorted_re = 0;
   if constexpr (SORT != 0) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int acc = prefix_count_share(fs.counts, tile, fs.bin_cap, tid);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (lane == 0) s_scan[wv] = acc;
-    if (tid == 0) {
-      int c_own = fs.counts[tile];
-      s_scan[4] = min(c_own, fs.bin_cap);
-      if (c_own > fs.bin_cap && fs.flags) { fs.flags[1] = 1; atomicMax(&fs.flags[2], c_own); }
-    }
-    __syncthreads();
-    long long s0 = s_scan[0] + s_scan[1] + s_scan[2] + s_scan[3], e0 = s0 + s_scan[4];
-    if (tid == 0) {
-      fs.tile_offsets[tile] = (int32_t)s0;
-      if (tile == n_tiles_total - 1) {
-        fs.tile_offsets[tile + 1] = (int32_t)e0;
-        if (fs.n_isects) fs.n_isects[0] = (int32_t)e0;
-      }
-    }
+    long long s0, e0;
+    binned_tile_span(fs.counts, tile, tile == n_tiles_total - 1, fs.bin_cap, fs.tile_offsets, fs.n_isects, fs.flags, s_scan,
+                     tid, s0, e0);
     if (e0 > capacity) e0 = capacity;  // (the total tells the host; what fits is sorted and composited)
     int n = (int)max(e0 - s0, (long long)0);
     if (n > 256) {

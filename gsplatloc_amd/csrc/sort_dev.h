@@ -1,6 +1,6 @@
-// Device-side pieces of the per-tile sort shared by the binning kernels (binning.hip) and by the compositing forward
-// that sorts its own tile's bin (raster_px.hip): the register bitonic network of one wave, the merge-path search, and
-// the one-tile-per-workgroup sort built from them.
+// Device-side pieces of the per-tile sort shared by the sort kernels (tile_sort.hip) and by the compositing forward
+// that sorts its own tile's bin (raster_px.hip): the register bitonic network of one wave, the offsets of a binned tile's
+// list, the write-out of a sorted key, the merge-path search, and the one-tile-per-workgroup sort built from them.
 #pragma once
 #include "gsloc_common.h"
 
@@ -157,6 +157,46 @@ __device__ __forceinline__ int prefix_count_share(const int32_t* __restrict__ co
   return acc;
 }
 
+// Binned projection: the span [s, e) of tile t's list in the packed arrays, from the tile sizes the projection left in
+// `counts` -- the sizes of the tiles before it, added up by the tile's own 256-thread workgroup (every thread calls this;
+// it holds a barrier).  Thread 0 writes tile_offsets[t] and, for the `last` tile, the closing offset and the total; a
+// tile that outgrew its bin keeps bin_cap entries, raises flags[1] and leaves its size in flags[2].  s_scan: 5 ints of
+// LDS.  (k_tile_sort, four tiles per workgroup, has the same steps written out for its four waves.)
+__device__ __forceinline__ void binned_tile_span(const int32_t* counts, int t, bool last, int bin_cap, int32_t* tile_offsets,
+                                                 int32_t* n_isects, int32_t* flags, int* s_scan, int tid, long long& s,
+                                                 long long& e) {
+  const int lane = tid & 63, wv = tid >> 6;
+  int acc = prefix_count_share(counts, t, bin_cap, tid);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if (lane == 0) s_scan[wv] = acc;
+  if (tid == 0) {
+    int c_own = counts[t];
+    s_scan[4] = min(c_own, bin_cap);
+    if (c_own > bin_cap && flags) { flags[1] = 1; atomicMax(&flags[2], c_own); }
+  }
+  __syncthreads();
+  s = s_scan[0] + s_scan[1] + s_scan[2] + s_scan[3];
+  e = s + s_scan[4];
+  if (tid == 0) {
+    tile_offsets[t] = (int32_t)s;
+    if (last) {
+      tile_offsets[t + 1] = (int32_t)e;
+      if (n_isects) n_isects[0] = (int32_t)e;
+    }
+  }
+}
+
+// Entry `pos` of the packed lists of tile t takes the sorted key v: the Gaussian's list id, gsplat's isect id and the key
+// itself, as far as the caller wants them (isect_ids, keys_out: may be NULL).
+__device__ __forceinline__ void write_sorted_key(uint64_t v, long long pos, int t, uint64_t* __restrict__ keys_out,
+                                                 int32_t* __restrict__ flatten_ids, int64_t* __restrict__ isect_ids,
+                                                 int64_t cam_enc, const int32_t* __restrict__ storage_of) {
+  flatten_ids[pos] = list_id(storage_of, v);
+  if (isect_ids) isect_ids[pos] = cam_enc | ((int64_t)t << 32) | (int64_t)(v >> 32);
+  if (keys_out) keys_out[pos] = v;
+}
+
 // The gradient rows a sort launch clears for the compositing backward that follows (gsl_fused_bin_clear): n4 float4 from
 // `rows`, cut into parts of `per` float4 (a multiple of the width; the host sizes it so that the launch's parts cover
 // n4).  Part `part` is zeroed by `width` threads -- a wave (64) or a workgroup (256) -- one contiguous run of 16 x width
@@ -248,11 +288,7 @@ __device__ __forceinline__ void wg_sort_tile(const uint64_t* __restrict__ src, i
         uint64_t v;
         if (ib >= 2 * RUN || (ia < 2 * RUN && A[ia] <= B[ib])) v = A[ia++];
         else v = B[ib++];
-        if (d0 + q < n) {
-          flatten_ids[s + d0 + q] = list_id(storage_of, v);
-          if (isect_ids) isect_ids[s + d0 + q] = cam_enc | ((int64_t)t << 32) | (int64_t)(v >> 32);
-          if (keys_out) keys_out[s + d0 + q] = v;
-        }
+        if (d0 + q < n) write_sorted_key(v, s + d0 + q, t, keys_out, flatten_ids, isect_ids, cam_enc, storage_of);
       }
     }
   }

@@ -123,6 +123,37 @@ def test_binning_bit_exact(shape):
     assert torch.equal(off_g.cpu(), off_o)
 
 
+def _staged_binning_case(tw, th, r_max, n=3000, seed=11):
+    """Projected centres uniform over the frame widened by 32 px on every side, integer radii 0 .. r_max (zeros
+    included), depths in [0.5, 5.5] with every 7th equal to one value: ties that the Gaussian index has to break."""
+    g = torch.Generator().manual_seed(seed)
+    W, H = 16 * tw, 16 * th
+    m2 = torch.rand(1, n, 2, generator=g) * torch.tensor([W + 64.0, H + 64.0]) - 32.0
+    r = torch.randint(0, r_max + 1, (1, n), generator=g, dtype=torch.int32)
+    d = 0.5 + 5.0 * torch.rand(1, n, generator=g)
+    d[:, ::7] = 2.25
+    return m2.contiguous(), r, d
+
+
+# 128 x 65 = 8320 tiles: the smallest grid past the 8192 tiles the LDS count and scatter kernels hold (the global-atomic
+# kernels run, the scan takes nine chunks); 40 x 30 = 1200: the LDS kernels, the scan's carry across its first chunk
+@pytest.mark.parametrize("tw,th,r_max", [(128, 65, 40), (40, 30, 24)])
+def test_staged_binning_bit_exact_on_large_grids(tw, th, r_max):
+    A = _gpu()
+    m2, r, d = _staged_binning_case(tw, th, r_max)
+    for sort in (True, False):
+        tpg_o, ids_o, fl_o = G.isect_tiles(m2, r, d, 16, tw, th, sort=sort)
+        tpg_g, ids_g, fl_g = A.isect_tiles(m2.to(DEV), r.to(DEV), d.to(DEV), 16, tw, th, sort=sort)
+        assert ids_o.numel() > 10000
+        assert torch.equal(tpg_g.cpu(), tpg_o), f"tiles_per_gauss sort={sort}"
+        assert torch.equal(ids_g.cpu(), ids_o), f"isect_ids sort={sort}"
+        assert torch.equal(fl_g.cpu(), fl_o), f"flatten_ids sort={sort}"
+        if sort:
+            off_o = G.isect_offset_encode(ids_o, 1, tw, th)
+            assert int(off_o[0, -1, -1]) < ids_o.numel(), "the last tile's list is not empty"
+            assert torch.equal(A.isect_offset_encode(ids_g, 1, tw, th).cpu(), off_o)
+
+
 def test_binning_multi_camera_and_empty():
     A = _gpu()
     W, H = 96, 64

@@ -51,7 +51,8 @@ def test_compositing_kernels_keep_their_occupancy():
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_sort_and_projection_kernels_stay_in_registers():
     binning = _resources("binning.hip")
-    sort = {k: v for k, v in binning.items() if "k_tile_sort" in k}
+    assert not any("k_tile_sort" in k for k in binning)  # (the sort has its own file)
+    sort = {k: v for k, v in _resources("tile_sort.hip").items() if "k_tile_sort" in k}
     assert len(sort) == 3  # one tile per wave (lists up to 1024 / up to 2048 keys in registers), one tile per workgroup
     for k, s in sort.items():
         # no spills; LDS (32 KB, four workgroups per CU) for the long-list path / the workgroup kernel's merge buffers.  The
@@ -59,7 +60,8 @@ def test_sort_and_projection_kernels_stay_in_registers():
         # frame of 3 225 tiles is then resident at once; the 32-keys-per-lane network costs a wave (141 VGPR)
         assert s["ScratchSize"] == 0 and s["LDS"] <= 32 * 1024 + 64, (k, s)
         assert s["Occupancy"] >= (3 if "k_tile_sortILi5" in k else 4), (k, s)
-    fused = {**_resources("fused_project.hip"), **_resources("fused_project_bwd.hip")}
+    # (the scan of the tile counts, shared with the staged API, is in binning.hip)
+    fused = {**_resources("fused_project.hip"), **_resources("fused_project_bwd.hip"), **binning}
     assert any("k_fproject_bwd" in k for k in fused) and any("k_ftile_scan" in k for k in fused)
     for k, v in fused.items():
         if "k_fproject" in k or "k_ftile_scan" in k:
