@@ -220,6 +220,7 @@ __global__ __launch_bounds__(256) void k_normal_gather(const float* __restrict__
 //   f[21] lr_quat f[22] lr_trans        f[23] best_loss f[24] best_depth f[25] best_edge
 //   f[26] best_eT f[27] best_eR         f[28] last_loss f[29] last_eT f[30] last_eR
 //   f[32] lr_quat f[33] lr_trans at step 0 (f[21], f[22] = these times gamma^step)
+//   f[34] best_rgb_l1 f[35] best (1 - ssim): written with f[23] by gsl_pose_step_photo only (photo.hip)
 //   i[0] step  i[1] counter  i[2] stopped  i[3] best_step
 // c2w / viewmat: the pose to render next; once stopped, the last pose that was rendered (the reference's final pose).
 // ------------------------------------------------------------------------------------------------
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(256) void k_normal_gather(const float* __restrict__
 // which is what a float32 torch.optim.Adam hands to its tensor operations.
 struct PoseHyper {
   double beta1, beta2, gamma;
-  float eps, wd_quat, wd_trans, depth_w, edge_w, normal_w;
+  float eps, wd_quat, wd_trans, depth_w, edge_w, normal_w, rgb_w, ssim_w;
   int width, height, min_step, patience, early_stop, max_steps;
 };
 
@@ -307,6 +308,8 @@ __global__ void k_pose_init(float* __restrict__ f, int* __restrict__ istate, con
 // vm_rows[n_vm][16]: the partial rows the projection backward left (gsl_fused_project_bwd, reduce_viewmat = 0), summed
 // here in a fixed order (saves the launch of the separate reduction); Kmat and the CURRENT viewmat are then read too.
 // partial[nb][2] loss sums of this rank (loss_sums_in != null: already reduced (sum_l1, sum_edge) over ranks).
+// photo_sums != null (gsl_pose_step_photo): the whole frame's (sum m, sum |c - p|, sum S) of gsl_photo_loss, whose term
+// hp.rgb_w * ((1 - hp.ssim_w) l1 + hp.ssim_w (1 - ssim)) joins the total.
 __global__ __launch_bounds__(256) void k_pose_step(float* __restrict__ f, int* __restrict__ istate,
                                                    const float* __restrict__ v_viewmat,
                                                    const float* __restrict__ vm_rows, int n_vm,
@@ -314,6 +317,7 @@ __global__ __launch_bounds__(256) void k_pose_step(float* __restrict__ f, int* _
                                                    const float* __restrict__ partial, int nb,
                                                    const float* __restrict__ loss_sums_in,
                                                    const float* __restrict__ normal_sum,
+                                                   const float* __restrict__ photo_sums,
                                                    const float* __restrict__ gt_c2w, PoseHyper hp,
                                                    float* __restrict__ c2w, float* __restrict__ viewmat,
                                                    float* __restrict__ loss_hist) {
@@ -360,6 +364,13 @@ __global__ __launch_bounds__(256) void k_pose_step(float* __restrict__ f, int* _
     float cs = loss_sums_in ? loss_sums_in[2] : (normal_sum ? normal_sum[0] : 0.f);
     total_d += hp.normal_w * (1.0 - cs / (3.0 * (double)hp.height));
   }
+  double rgb_l1_d = 0.0, dssim_d = 0.0;
+  if (photo_sums) {
+    const double n_windows = 3.0 * (double)(hp.width - 10) * (double)(hp.height - 10);
+    rgb_l1_d = (double)photo_sums[1] / ((double)photo_sums[0] + 1e-8);
+    dssim_d = 1.0 - (double)photo_sums[2] / n_windows;
+    total_d += (double)hp.rgb_w * ((1.0 - (double)hp.ssim_w) * rgb_l1_d + (double)hp.ssim_w * dssim_d);
+  }
   float depth_loss = (float)depth_d, edge_loss = (float)edge_d, total = (float)total_d;
   float q[4] = {sF[0], sF[1], sF[2], sF[3]}, t[3] = {sF[4], sF[5], sF[6]};
   double qd[4] = {q[0], q[1], q[2], q[3]}, td[3] = {t[0], t[1], t[2]};
@@ -383,6 +394,7 @@ __global__ __launch_bounds__(256) void k_pose_step(float* __restrict__ f, int* _
   if (hp.early_stop && step > hp.min_step) {
     if (total < sF[23]) {
       f[23] = total; f[24] = depth_loss; f[25] = edge_loss; f[26] = eT; f[27] = eR;
+      if (photo_sums) { f[34] = (float)rgb_l1_d; f[35] = (float)dssim_d; }
       sI[1] = 0; istate[3] = step;
     } else {
       sI[1] += 1;
@@ -575,25 +587,42 @@ extern "C" int gsl_pose_init(float* pose_f, int* pose_i, const float* init_c2w, 
   return GSL_OK;
 }
 
+extern "C" int gsl_pose_step_photo(float* pose_f, int* pose_i, const float* v_viewmat, const float* vm_rows,
+                                   int n_vm_rows, const float* K, const float* loss_partials, int n_partials,
+                                   const float* loss_sums, const float* normal_sum, const float* gt_c2w, int width,
+                                   int height, float depth_lambda, float edge_lambda, float normal_lambda, double beta1,
+                                   double beta2, float eps, float wd_quat, float wd_trans, double gamma, int min_step,
+                                   int patience, int early_stop, int max_steps, float* c2w, float* viewmat,
+                                   float* loss_hist, void* stream, const float* photo_sums, float rgb_lambda,
+                                   float ssim_lambda) {
+  if (!pose_f || !pose_i || !gt_c2w || !c2w || !viewmat) return GSL_ERR_BAD_ARG;
+  if (!v_viewmat && !vm_rows) return GSL_ERR_BAD_ARG;
+  if (vm_rows && (n_vm_rows < 0 || !K)) return GSL_ERR_BAD_ARG;
+  if (!loss_partials && !loss_sums) return GSL_ERR_BAD_ARG;
+  if (width <= 0 || height <= 0 || n_partials < 0) return GSL_ERR_BAD_ARG;
+  if (photo_sums && (width < 11 || height < 11)) return GSL_ERR_BAD_ARG;
+  gsl::PoseHyper hp;
+  hp.beta1 = beta1; hp.beta2 = beta2; hp.gamma = gamma;
+  hp.eps = eps; hp.wd_quat = wd_quat; hp.wd_trans = wd_trans;
+  hp.depth_w = depth_lambda; hp.edge_w = edge_lambda; hp.normal_w = normal_lambda;
+  hp.rgb_w = rgb_lambda; hp.ssim_w = ssim_lambda;
+  hp.width = width; hp.height = height;
+  hp.min_step = min_step; hp.patience = patience; hp.early_stop = early_stop; hp.max_steps = max_steps;
+  hipLaunchKernelGGL(gsl::k_pose_step, dim3(1), dim3(256), 0, (hipStream_t)stream, pose_f, pose_i, v_viewmat,
+                     vm_rows, n_vm_rows, K, loss_partials, n_partials, loss_sums, normal_sum, photo_sums, gt_c2w, hp, c2w,
+                     viewmat, loss_hist);
+  GSL_CHECK_LAUNCH();
+  return GSL_OK;
+}
+
 extern "C" int gsl_pose_step(float* pose_f, int* pose_i, const float* v_viewmat, const float* vm_rows, int n_vm_rows,
                              const float* K, const float* loss_partials, int n_partials, const float* loss_sums, const float* normal_sum, const float* gt_c2w,
                              int width, int height, float depth_lambda, float edge_lambda, float normal_lambda,
                              double beta1, double beta2, float eps,
                              float wd_quat, float wd_trans, double gamma, int min_step, int patience, int early_stop,
                              int max_steps, float* c2w, float* viewmat, float* loss_hist, void* stream) {
-  if (!pose_f || !pose_i || !gt_c2w || !c2w || !viewmat) return GSL_ERR_BAD_ARG;
-  if (!v_viewmat && !vm_rows) return GSL_ERR_BAD_ARG;
-  if (vm_rows && (n_vm_rows < 0 || !K)) return GSL_ERR_BAD_ARG;
-  if (!loss_partials && !loss_sums) return GSL_ERR_BAD_ARG;
-  if (width <= 0 || height <= 0 || n_partials < 0) return GSL_ERR_BAD_ARG;
-  gsl::PoseHyper hp;
-  hp.beta1 = beta1; hp.beta2 = beta2; hp.gamma = gamma;
-  hp.eps = eps; hp.wd_quat = wd_quat; hp.wd_trans = wd_trans;
-  hp.depth_w = depth_lambda; hp.edge_w = edge_lambda; hp.normal_w = normal_lambda;
-  hp.width = width; hp.height = height;
-  hp.min_step = min_step; hp.patience = patience; hp.early_stop = early_stop; hp.max_steps = max_steps;
-  hipLaunchKernelGGL(gsl::k_pose_step, dim3(1), dim3(256), 0, (hipStream_t)stream, pose_f, pose_i, v_viewmat,
-                     vm_rows, n_vm_rows, K, loss_partials, n_partials, loss_sums, normal_sum, gt_c2w, hp, c2w, viewmat, loss_hist);
-  GSL_CHECK_LAUNCH();
-  return GSL_OK;
+  return gsl_pose_step_photo(pose_f, pose_i, v_viewmat, vm_rows, n_vm_rows, K, loss_partials, n_partials, loss_sums,
+                             normal_sum, gt_c2w, width, height, depth_lambda, edge_lambda, normal_lambda, beta1, beta2, eps,
+                             wd_quat, wd_trans, gamma, min_step, patience, early_stop, max_steps, c2w, viewmat, loss_hist,
+                             stream, NULL, 0.f, 0.f);
 }

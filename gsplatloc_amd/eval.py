@@ -27,12 +27,14 @@ def rmse(values: List[float]) -> float:
 
 
 def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[int] = 1998, verbose: bool = False,
-                  profile: bool = False) -> Dict:
+                  profile: bool = False, rgb_lambda: float = 0.0, ssim_lambda: float = 0.5) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
-    capture + replays + polls) -- `phase_seconds` in the result."""
-    cfg = TrackerConfig(max_steps=num_iters)
+    capture + replays + polls) -- `phase_seconds` in the result.  rgb_lambda != 0 switches the photometric term on
+    (TrackerConfig.rgb_lambda / ssim_lambda): the tracker then renders "RGB+ED" and is given the frame's image."""
+    cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
+    photo = rgb_lambda != 0.0
     phases = {} if profile else None
     parser.phase_seconds = phases
 
@@ -53,12 +55,15 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
             # expected depth only: the reference's loop asks for "RGB+ED" (model.py:195-213) and reads renders[..., 3:4]
             # alone (gs_trainer_total.py:104-123) -- the SH colours, their records and three of four composited channels
             # are work whose result nobody looks at.  Same depth, same loss, same pose; 2 % more
-            # iterations per second at 102 k Gaussians, 20 % at 816 k.  render_mode="RGB+ED" is the literal call.
-            tracker = GraphTracker(d.tar_points.shape[0], W, H, cfg, device=d.tar_points.device, render_mode="ED")
+            # iterations per second at 102 k Gaussians, 20 % at 816 k.  render_mode="RGB+ED" is the literal call, and
+            # what the photometric term needs.
+            tracker = GraphTracker(d.tar_points.shape[0], W, H, cfg, device=d.tar_points.device,
+                                   render_mode="RGB+ED" if photo else "ED")
         ta = tick()
         scales = init_gs_scales(d.tar_points)
         tb = tick()
-        tracker.load_frame(d.tar_points, d.colors, scales, d.src_depth, d.tar_c2w, d.src_c2w, parser.K)
+        tracker.load_frame(d.tar_points, d.colors, scales, d.src_depth, d.tar_c2w, d.src_c2w, parser.K,
+                           pixels=d.pixels if photo else None)
         tc = tick()
         res = tracker.run()
         if profile:
@@ -95,11 +100,15 @@ def main(argv=None):
     ap.add_argument("--no-normalize", action="store_true")
     ap.add_argument("--out", default="res.json")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--rgb-lambda", type=float, default=0.0,
+                    help="weight of the photometric term (RGB L1 + SSIM against the frame's image); 0 = off")
+    ap.add_argument("--ssim-lambda", type=float, default=0.5, help="share of 1 - SSIM inside the photometric term")
     a = ap.parse_args(argv)
     out = {}
     for room in a.rooms:
         parser = Parser(a.dataset, room, normalize=not a.no_normalize, input_folder=a.root)
-        r = evaluate_room(parser, a.num_iters, a.max_frames, a.verbose)
+        r = evaluate_room(parser, a.num_iters, a.max_frames, a.verbose, rgb_lambda=a.rgb_lambda,
+                          ssim_lambda=a.ssim_lambda)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

@@ -27,6 +27,11 @@ Overflow handling: the kernels never drop work silently.  A splat that outgrows 
 sticky device flag, and the intersection count is compared with the buffer capacity; both are read at the
 existing poll of the "stopped" flag, and on either the frame is re-run from its initial pose with the general
 backward / a larger capacity.
+
+Photometric term (``rgb_lambda != 0``, off by default like the normal term; one rank, "RGB+ED"): gsl_photo_loss
+(csrc/photo.hip, two launches) writes the colour channels of the upstream gradient between the depth losses and the
+backward, and gsl_pose_step_photo adds the term to the total.  The loss fused into the tiny backward treats the colour
+gradient as zero, so that iteration always takes the separate loss launch.
 """
 from __future__ import annotations
 
@@ -50,6 +55,17 @@ class GraphTracker:
                  render_mode: str = "RGB+ED", rows: Optional[Tuple[int, int]] = None, group=None,
                  use_graph: bool = True, poll: int = 25, prune: Optional[bool] = None, guard_tiles: int = 1):
         assert render_mode in ("RGB+ED", "ED"), "the tracker's loss reads expected depth"
+        if config.rgb_lambda != 0.0:
+            if render_mode != "RGB+ED":
+                raise ValueError(f"rgb_lambda = {config.rgb_lambda}: the photometric term compares rendered colours, "
+                                 f"which render_mode={render_mode!r} does not produce; use \"RGB+ED\"")
+            if rows is not None or group is not None:
+                raise NotImplementedError("rgb_lambda != 0 with rows= / group=: the photometric term is whole-frame only "
+                                          "(a strip would need a 5-row halo for the 11x11 SSIM window and a fourth "
+                                          "reduced sum in the all-reduce)")
+            if width < 11 or height < 11:
+                raise ValueError(f"rgb_lambda != 0: the 11x11 SSIM window needs a frame of at least 11x11, got "
+                                 f"{width}x{height}")
         self.lib = load_library()
         self.cfg = config
         self.N, self.W, self.H = int(N), int(width), int(height)
@@ -99,6 +115,12 @@ class GraphTracker:
             self.normal_ws_bytes = self.lib.gsl_normal_ws_bytes(self.W, self.H)
             self.normal_ws = torch.zeros(self.normal_ws_bytes, dtype=torch.uint8, device=d)
             self.normal_sum = torch.zeros(1, dtype=f32, device=d)
+        self.pixels = self.photo_sums = self.photo_ws = None
+        if config.rgb_lambda != 0.0:  # the term the reference keeps commented out (gs_trainer_total.py:111-123)
+            self.pixels = torch.zeros(self.H, self.W, 3, dtype=f32, device=d)
+            self.photo_sums = torch.zeros(3, dtype=f32, device=d)
+            self.photo_ws_bytes = self.lib.gsl_photo_ws_bytes(self.W, self.H)
+            self.photo_ws = torch.zeros(self.photo_ws_bytes, dtype=torch.uint8, device=d)
         self._host16 = None
         self._intrinsics = (1.0, 1.0, 0.0, 0.0)
         self.graph = self.graph_tail = None
@@ -160,11 +182,17 @@ class GraphTracker:
 
     # ------------------------------------------------------------------ frame setup
     def load_frame(self, tar_points: Tensor, colors: Tensor, scales: Tensor, src_depth: Tensor, tar_c2w: Tensor,
-                   src_c2w: Tensor, K: Tensor) -> None:
+                   src_c2w: Tensor, K: Tensor, pixels: Optional[Tensor] = None) -> None:
         """Copy one frame pair into the tracker's persistent buffers (shapes fixed at construction):
         Gaussians = tar_points [N,3] with isotropic scales [N,3] and colours [N,3]; target depth
-        src_depth [...,H,W,...]; initial pose tar_c2w; reference pose src_c2w (error read-out only)."""
+        src_depth [...,H,W,...]; initial pose tar_c2w; reference pose src_c2w (error read-out only); target image
+        pixels [...,H,W,3] in 0..1 (read for rgb_lambda != 0 only)."""
         assert tar_points.shape == (self.N, 3), tar_points.shape
+        if self.pixels is not None:
+            if pixels is None:
+                raise ValueError("rgb_lambda != 0: the frame needs its target image (load_frame(..., pixels=))")
+            self.pixels.copy_(pixels.reshape(self.H, self.W, 3))
+            self.pose_f[34:36] = float("inf")  # best rgb_l1 / 1 - ssim: gsl_pose_init knows nothing of them
         self.means.copy_(tar_points)
         self.scales.copy_(scales)
         self.sh.zero_()
@@ -199,7 +227,8 @@ class GraphTracker:
         edge_w = 1.0 - cfg.depth_lambda - cfg.normal_lambda
         # one rank, no normal term, tiny-splat backward: the compositing backward computes the loss of its own tile and
         # its gradient (gsl_tiny_raster_bwd(..., loss_depth_gt, ...)): one launch fewer per iteration
-        fuse = (self.group is None and self.normal_ws is None and self.rc.can_fuse_tracking_loss()
+        # (nor with the photometric term: the loss inside the backward takes the colour gradient as zero)
+        fuse = (self.group is None and self.normal_ws is None and self.photo_ws is None and self.rc.can_fuse_tracking_loss()
                 and os.environ.get("GSLOC_FUSE_LOSS", "1") != "0")
         if fuse:
             self.rc.backward(self.v_render, self.v_alphas, full=False, reduce_viewmat=False,
@@ -213,6 +242,10 @@ class GraphTracker:
                                       self.row1, *self._intrinsics, cfg.normal_lambda, ptr(self.v_render),
                                       ptr(self.normal_sum), ptr(self.normal_ws), self.normal_ws_bytes, st),
                   "gsl_normal_loss")
+        if self.photo_ws is not None:  # colour channels of v_render; the depth channel stays what the two above left
+            check(lib.gsl_photo_loss(ptr(self.rc.render), self.rc.D, ptr(self.pixels), self.W, self.H, cfg.rgb_lambda,
+                                     cfg.ssim_lambda, ptr(self.v_render), ptr(self.photo_sums), ptr(self.photo_ws),
+                                     self.photo_ws_bytes, st), "gsl_photo_loss")
         # the pose gradient stays as partial rows: the pack kernel / the pose step sum them (one launch fewer)
         self.rc.backward(self.v_render, self.v_alphas, full=False, reduce_viewmat=False)
         if self.group is not None:
@@ -232,12 +265,17 @@ class GraphTracker:
         cam = cfg.camera
         edge_w = 1.0 - cfg.depth_lambda - cfg.normal_lambda
         gamma = 0.2 ** (1.0 / cfg.max_steps)
-        check(lib.gsl_pose_step(ptr(self.pose_f), ptr(self.pose_i), v_viewmat, rows, n_rows, ptr(self.K),
-                                ptr(self.partials), self.n_partials, loss_sums, ptr(self.normal_sum), ptr(self.gt_c2w), self.W, self.H,
-                                cfg.depth_lambda, edge_w, cfg.normal_lambda, 0.9, 0.999, 1e-8, cam.quat_opt_reg,
-                                cam.trans_opt_reg, gamma, cfg.min_step,
-                                cfg.patience, int(cfg.early_stop), cfg.max_steps, ptr(self.c2w), ptr(self.viewmat),
-                                ptr(self.loss_hist), current_stream()), "gsl_pose_step")
+        args = (ptr(self.pose_f), ptr(self.pose_i), v_viewmat, rows, n_rows, ptr(self.K),
+                ptr(self.partials), self.n_partials, loss_sums, ptr(self.normal_sum), ptr(self.gt_c2w), self.W, self.H,
+                cfg.depth_lambda, edge_w, cfg.normal_lambda, 0.9, 0.999, 1e-8, cam.quat_opt_reg,
+                cam.trans_opt_reg, gamma, cfg.min_step,
+                cfg.patience, int(cfg.early_stop), cfg.max_steps, ptr(self.c2w), ptr(self.viewmat),
+                ptr(self.loss_hist), current_stream())
+        if self.photo_ws is not None:
+            check(lib.gsl_pose_step_photo(*args, ptr(self.photo_sums), cfg.rgb_lambda, cfg.ssim_lambda),
+                  "gsl_pose_step_photo")
+        else:
+            check(lib.gsl_pose_step(*args), "gsl_pose_step")
 
     def _collective(self) -> None:
         """THE collective of the path: 16 floats summed over the ranks (RCCL on device buffers; the one-GPU
@@ -393,5 +431,7 @@ class GraphTracker:
         res.losses = self.loss_hist[:pi[0]].tolist()
         res.best_loss, res.best_depth_loss, res.best_silhouette_loss = pf[23], pf[24], pf[25]
         res.best_eT, res.best_eR = pf[26], pf[27]
+        if self.photo_ws is not None:
+            res.best_rgb_l1_loss, res.best_ssim_loss = pf[34], pf[35]
         res.final_c2w = self.c2w.clone()
         return res

@@ -20,7 +20,8 @@ import torch
 from torch import Tensor
 
 from ..context import RenderContext
-from .loss import compute_depth_loss, compute_normal_consistency_loss, compute_silhouette_loss
+from .loss import (compute_depth_loss, compute_normal_consistency_loss, compute_rgb_l1_loss, compute_silhouette_loss,
+                   compute_ssim_loss)
 from .model import CameraConfig, CameraOptModule_quat_tans, GsConfig, GSModel
 
 
@@ -45,6 +46,10 @@ class TrackerConfig:
     max_steps: int = 1000
     depth_lambda: float = 0.8
     normal_lambda: float = 0.0
+    # the photometric term the reference writes out and keeps commented (gs_trainer_total.py:111-123): it enters the
+    # total as rgb_lambda * ((1 - ssim_lambda) * rgb_l1 + ssim_lambda * (1 - ssim)), beside the three weights above
+    rgb_lambda: float = 0.0
+    ssim_lambda: float = 0.5  # data/base.py:26
     early_stop: bool = True
     patience: int = 200
     min_step: int = 100  # "if step > 100" (gs_trainer_total.py:171)
@@ -58,6 +63,8 @@ class TrackResult:
     best_loss: float = float("inf")
     best_depth_loss: float = float("inf")
     best_silhouette_loss: float = float("inf")
+    best_rgb_l1_loss: float = float("inf")  # the photometric term's two parts at the best step (rgb_lambda != 0 only)
+    best_ssim_loss: float = float("inf")
     best_eT: float = float("inf")
     best_eR: float = float("inf")
     final_c2w: Optional[Tensor] = None
@@ -70,9 +77,12 @@ class PoseTracker:
         self.config = config
         self.engine = engine
 
-    def tracking_loss(self, depths: Tensor, depths_gt: Tensor, K: Optional[Tensor] = None):
+    def tracking_loss(self, depths: Tensor, depths_gt: Tensor, K: Optional[Tensor] = None,
+                      colors: Optional[Tensor] = None, pixels: Optional[Tensor] = None):
         """gs_trainer_total.py:105-150.  The normal-consistency term is the call the reference keeps commented
-        out (:138-143) behind normal_lambda = 0 (data/base.py:28); it is evaluated only for a non-zero weight."""
+        out (:138-143) behind normal_lambda = 0 (data/base.py:28); it is evaluated only for a non-zero weight.  So is
+        the photometric term (:111-123; rendered ``colors`` and the target image ``pixels``, both [1,H,W,3]): its two
+        parts are left in ``self.last_photo`` = (rgb_l1, 1 - ssim), None when the weight is 0."""
         mask = (depths != 0).float()
         depth_loss = compute_depth_loss(depths * mask, depths_gt * mask, loss_type="l1")
         silhouette_loss = compute_silhouette_loss(depths * mask, depths_gt * mask, loss_type="l1")
@@ -83,14 +93,27 @@ class PoseTracker:
             normal_loss = compute_normal_consistency_loss((depths * mask)[0, :, :, 0], (depths_gt * mask)[0, :, :, 0],
                                                           K=K, loss_type="cosine")
             total = total + normal_loss * self.config.normal_lambda
+        self.last_photo = None
+        if self.config.rgb_lambda != 0.0:
+            if pixels is None or colors is None:
+                raise ValueError("rgb_lambda != 0: the photometric term needs the rendered colours and the target image "
+                                 "(pixels)")
+            rgb_l1 = compute_rgb_l1_loss(colors, pixels, mask)
+            ssim_loss = compute_ssim_loss(colors, pixels, mask)
+            lam = self.config.ssim_lambda
+            total = total + self.config.rgb_lambda * ((1 - lam) * rgb_l1 + lam * ssim_loss)
+            self.last_photo = (rgb_l1, ssim_loss)
         return total, depth_loss, silhouette_loss
 
     def track_frame(self, tar_points: Tensor, colors: Tensor, src_depth: Tensor, tar_c2w: Tensor, src_c2w: Tensor,
                     K: Tensor, width: int, height: int, scales: Optional[Tensor] = None,
-                    verbose: bool = False) -> TrackResult:
+                    verbose: bool = False, pixels: Optional[Tensor] = None) -> TrackResult:
         """One frame pair: Gaussians from the previous frame (``tar_points``), initial pose ``tar_c2w``,
-        target depth ``src_depth`` [1,H,W,1], reference pose ``src_c2w`` for the error read-out."""
+        target depth ``src_depth`` [1,H,W,1], reference pose ``src_c2w`` for the error read-out; ``pixels``
+        [1,H,W,3] in 0..1 is the target image of the photometric term (needed, and read, for rgb_lambda != 0 only)."""
         cfg = self.config
+        if cfg.rgb_lambda != 0.0 and pixels is None:
+            raise ValueError("rgb_lambda != 0: track_frame needs the target image (pixels)")
         max_steps = cfg.max_steps
         Ks = K.unsqueeze(0)
         gs_splats = GSModel(tar_points, colors, config=cfg.gs, scales=scales)
@@ -121,7 +144,7 @@ class PoseTracker:
                 renders = render.unsqueeze(0)
             assert renders.shape[-1] == 4
             depths = renders[..., 3:4]
-            total_loss, depth_loss, silhouette_loss = self.tracking_loss(depths, src_depth, K)
+            total_loss, depth_loss, silhouette_loss = self.tracking_loss(depths, src_depth, K, renders[..., 0:3], pixels)
             total_loss.backward()
             with torch.no_grad():
                 lv = total_loss.item()
@@ -134,6 +157,8 @@ class PoseTracker:
                             res.best_loss = lv
                             res.best_silhouette_loss = silhouette_loss.item()
                             res.best_depth_loss = depth_loss.item()
+                            if self.last_photo is not None:
+                                res.best_rgb_l1_loss, res.best_ssim_loss = (v.item() for v in self.last_photo)
                             res.best_eT, res.best_eR = eT, eR
                             counter = 0
                         else:

@@ -461,7 +461,32 @@ int gsl_tiny_raster_bwd(const float* Q0, const float* Q1, const float* Q2, int c
  *   similarity ALONG EACH IMAGE ROW per component as the reference codes it, loss = 1 - mean.  Adds
  *   normal_lambda * d loss / d depth to v_render[...,channels-1] for rows [row0-1,row1+1) (call it after
  *   gsl_tracking_loss, which writes that channel) and writes the sum of the owned rows' cosines to normal_sum[0].
- *   ws: gsl_normal_ws_bytes. */
+ *   ws: gsl_normal_ws_bytes.
+ * gsl_photo_loss: the photometric term the reference declares and keeps commented out (gs_trainer_total.py:111-123,
+ *   ssim_lambda = 0.5 at data/base.py:26, StructuralSimilarityIndexMeasure(data_range=1.0)) (csrc/photo.hip).  With
+ *   m = (render[...,3] != 0) (no gradient), c = render[...,0:3] m and p = pixels m (pixels [H,W,3] in 0..1):
+ *     l1 = sum |c - p| / (sum m + 1e-8)  (sum m counts pixels),  ssim = mean of S over the 3 (H-10) (W-10) windows
+ *     inside the image, S as torchmetrics computes it for data_range 1 (11x11 window of a sigma 1.5 Gaussian, C1 = 1e-4,
+ *     C2 = 9e-4, variances clamped at 0),  photo = (1 - ssim_lambda) l1 + ssim_lambda (1 - ssim).
+ *   WRITES rgb_lambda * d photo / d render into v_render[...,0:3] of every pixel (exactly 0 where m = 0), leaves
+ *   v_render[...,3] untouched (so it composes with gsl_tracking_loss / gsl_normal_loss in either order) and writes the
+ *   raw sums photo_sums[3] = (sum m, sum |c - p|, sum S).  Whole frame only (a strip would need a 5-row halo), channels
+ *   must be 4 and both sides at least 11 (GSL_ERR_BAD_ARG otherwise).  Two launches, no atomics: two calls give the
+ *   same bits.  ws: gsl_photo_ws_bytes (0 for a frame below 11x11); GSL_ERR_WORKSPACE when shorter.
+ * gsl_pose_step_photo: gsl_pose_step with the photometric term: photo_sums (of gsl_photo_loss; NULL: none) adds
+ *   rgb_lambda * photo, taken in double from the three sums, to the total that goes into loss_hist, the best-loss
+ *   bookkeeping and the early stop; whenever pose_f[23] is written, pose_f[34] gets that step's l1 and pose_f[35] its
+ *   1 - ssim.  gsl_pose_step is this function with NULL, 0, 0. */
+size_t gsl_photo_ws_bytes(int width, int height);
+int gsl_photo_loss(const float* render, int channels, const float* pixels, int width, int height, float rgb_lambda,
+                   float ssim_lambda, float* v_render, float* photo_sums, void* ws, size_t ws_bytes, void* stream);
+int gsl_pose_step_photo(float* pose_f, int* pose_i, const float* v_viewmat, const float* vm_rows, int n_vm_rows,
+                        const float* K, const float* loss_partials, int n_partials, const float* loss_sums,
+                        const float* normal_sum, const float* gt_c2w, int width, int height, float depth_lambda,
+                        float edge_lambda, float normal_lambda, double beta1, double beta2, float eps, float wd_quat,
+                        float wd_trans, double gamma, int min_step, int patience, int early_stop, int max_steps,
+                        float* c2w, float* viewmat, float* loss_hist, void* stream, const float* photo_sums,
+                        float rgb_lambda, float ssim_lambda);
 size_t gsl_loss_ws_bytes(int width, int height);
 int gsl_loss_n_partials(int width, int height, int row0, int row1);
 size_t gsl_normal_ws_bytes(int width, int height);
