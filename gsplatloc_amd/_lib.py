@@ -85,6 +85,9 @@ _SIGNATURES = {
     "gsl_pose_step_photo": (c_int, [P, P, P, P, c_int, P, P, c_int, P, P, P, c_int, c_int, c_float, c_float, c_float,
                                     c_double, c_double, c_float, c_float, c_float, c_double, c_int, c_int, c_int, c_int,
                                     P, P, P, P, P, c_float, c_float]),
+    "gsl_pose_step_best": (c_int, [P, P, P, P, c_int, P, P, c_int, P, P, P, c_int, c_int, c_float, c_float, c_float,
+                                   c_double, c_double, c_float, c_float, c_float, c_double, c_int, c_int, c_int, c_int,
+                                   P, P, P, P, P, c_float, c_float, P]),
     "gsl_knn_ws_bytes": (c_size_t, [c_int]),
     "gsl_knn_cells": (c_int, []),
     "gsl_knn_count": (c_int, [P, c_int, P, P, c_size_t, P]),

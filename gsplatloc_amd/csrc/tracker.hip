@@ -222,6 +222,8 @@ __global__ __launch_bounds__(256) void k_normal_gather(const float* __restrict__
 //   f[32] lr_quat f[33] lr_trans at step 0 (f[21], f[22] = these times gamma^step)
 //   f[34] best_rgb_l1 f[35] best (1 - ssim): written with f[23] by gsl_pose_step_photo only (photo.hip)
 //   i[0] step  i[1] counter  i[2] stopped  i[3] best_step
+// best_pose[24] (gsl_pose_step_best only), written with f[23]: the pose that step rendered with --
+//   [0..3] quat as stored  [4..6] t  [7] the total loss  [8..23] its camera-to-world matrix
 // c2w / viewmat: the pose to render next; once stopped, the last pose that was rendered (the reference's final pose).
 // ------------------------------------------------------------------------------------------------
 // The state is float32.  The lone thread that advances it works in double and rounds once where a value is stored:
@@ -310,6 +312,7 @@ __global__ void k_pose_init(float* __restrict__ f, int* __restrict__ istate, con
 // partial[nb][2] loss sums of this rank (loss_sums_in != null: already reduced (sum_l1, sum_edge) over ranks).
 // photo_sums != null (gsl_pose_step_photo): the whole frame's (sum m, sum |c - p|, sum S) of gsl_photo_loss, whose term
 // hp.rgb_w * ((1 - hp.ssim_w) l1 + hp.ssim_w (1 - ssim)) joins the total.
+// best_pose != null (gsl_pose_step_best): whenever f[23] is written, the pose of that step (before the Adam update).
 __global__ __launch_bounds__(256) void k_pose_step(float* __restrict__ f, int* __restrict__ istate,
                                                    const float* __restrict__ v_viewmat,
                                                    const float* __restrict__ vm_rows, int n_vm,
@@ -320,7 +323,8 @@ __global__ __launch_bounds__(256) void k_pose_step(float* __restrict__ f, int* _
                                                    const float* __restrict__ photo_sums,
                                                    const float* __restrict__ gt_c2w, PoseHyper hp,
                                                    float* __restrict__ c2w, float* __restrict__ viewmat,
-                                                   float* __restrict__ loss_hist) {
+                                                   float* __restrict__ loss_hist,
+                                                   float* __restrict__ best_pose) {
   __shared__ float red[4][2];
   __shared__ float sums[2];
   __shared__ float vred[4][15];
@@ -395,6 +399,16 @@ __global__ __launch_bounds__(256) void k_pose_step(float* __restrict__ f, int* _
     if (total < sF[23]) {
       f[23] = total; f[24] = depth_loss; f[25] = edge_loss; f[26] = eT; f[27] = eR;
       if (photo_sums) { f[34] = (float)rgb_l1_d; f[35] = (float)dssim_d; }
+      if (best_pose) {  // R and td are what write_pose formed c2w from for this step: the same bits
+        for (int k = 0; k < 4; ++k) best_pose[k] = q[k];
+        for (int k = 0; k < 3; ++k) best_pose[4 + k] = t[k];
+        best_pose[7] = total;
+        for (int r = 0; r < 3; ++r) {
+          for (int c = 0; c < 3; ++c) best_pose[8 + r * 4 + c] = (float)R[r * 3 + c];
+          best_pose[8 + r * 4 + 3] = (float)td[r];
+        }
+        for (int c = 0; c < 4; ++c) best_pose[20 + c] = (c == 3) ? 1.f : 0.f;
+      }
       sI[1] = 0; istate[3] = step;
     } else {
       sI[1] += 1;
@@ -587,14 +601,14 @@ extern "C" int gsl_pose_init(float* pose_f, int* pose_i, const float* init_c2w, 
   return GSL_OK;
 }
 
-extern "C" int gsl_pose_step_photo(float* pose_f, int* pose_i, const float* v_viewmat, const float* vm_rows,
-                                   int n_vm_rows, const float* K, const float* loss_partials, int n_partials,
-                                   const float* loss_sums, const float* normal_sum, const float* gt_c2w, int width,
-                                   int height, float depth_lambda, float edge_lambda, float normal_lambda, double beta1,
-                                   double beta2, float eps, float wd_quat, float wd_trans, double gamma, int min_step,
-                                   int patience, int early_stop, int max_steps, float* c2w, float* viewmat,
-                                   float* loss_hist, void* stream, const float* photo_sums, float rgb_lambda,
-                                   float ssim_lambda) {
+// the one launch site of k_pose_step: the three entry points differ in photo_sums / best_pose being null
+static int pose_step_launch(float* pose_f, int* pose_i, const float* v_viewmat, const float* vm_rows, int n_vm_rows,
+                            const float* K, const float* loss_partials, int n_partials, const float* loss_sums,
+                            const float* normal_sum, const float* gt_c2w, int width, int height, float depth_lambda,
+                            float edge_lambda, float normal_lambda, double beta1, double beta2, float eps, float wd_quat,
+                            float wd_trans, double gamma, int min_step, int patience, int early_stop, int max_steps,
+                            float* c2w, float* viewmat, float* loss_hist, void* stream, const float* photo_sums,
+                            float rgb_lambda, float ssim_lambda, float* best_pose) {
   if (!pose_f || !pose_i || !gt_c2w || !c2w || !viewmat) return GSL_ERR_BAD_ARG;
   if (!v_viewmat && !vm_rows) return GSL_ERR_BAD_ARG;
   if (vm_rows && (n_vm_rows < 0 || !K)) return GSL_ERR_BAD_ARG;
@@ -610,9 +624,38 @@ extern "C" int gsl_pose_step_photo(float* pose_f, int* pose_i, const float* v_vi
   hp.min_step = min_step; hp.patience = patience; hp.early_stop = early_stop; hp.max_steps = max_steps;
   hipLaunchKernelGGL(gsl::k_pose_step, dim3(1), dim3(256), 0, (hipStream_t)stream, pose_f, pose_i, v_viewmat,
                      vm_rows, n_vm_rows, K, loss_partials, n_partials, loss_sums, normal_sum, photo_sums, gt_c2w, hp, c2w,
-                     viewmat, loss_hist);
+                     viewmat, loss_hist, best_pose);
   GSL_CHECK_LAUNCH();
   return GSL_OK;
+}
+
+extern "C" int gsl_pose_step_photo(float* pose_f, int* pose_i, const float* v_viewmat, const float* vm_rows,
+                                   int n_vm_rows, const float* K, const float* loss_partials, int n_partials,
+                                   const float* loss_sums, const float* normal_sum, const float* gt_c2w, int width,
+                                   int height, float depth_lambda, float edge_lambda, float normal_lambda, double beta1,
+                                   double beta2, float eps, float wd_quat, float wd_trans, double gamma, int min_step,
+                                   int patience, int early_stop, int max_steps, float* c2w, float* viewmat,
+                                   float* loss_hist, void* stream, const float* photo_sums, float rgb_lambda,
+                                   float ssim_lambda) {
+  return pose_step_launch(pose_f, pose_i, v_viewmat, vm_rows, n_vm_rows, K, loss_partials, n_partials, loss_sums,
+                          normal_sum, gt_c2w, width, height, depth_lambda, edge_lambda, normal_lambda, beta1, beta2, eps,
+                          wd_quat, wd_trans, gamma, min_step, patience, early_stop, max_steps, c2w, viewmat, loss_hist,
+                          stream, photo_sums, rgb_lambda, ssim_lambda, NULL);
+}
+
+extern "C" int gsl_pose_step_best(float* pose_f, int* pose_i, const float* v_viewmat, const float* vm_rows,
+                                  int n_vm_rows, const float* K, const float* loss_partials, int n_partials,
+                                  const float* loss_sums, const float* normal_sum, const float* gt_c2w, int width,
+                                  int height, float depth_lambda, float edge_lambda, float normal_lambda, double beta1,
+                                  double beta2, float eps, float wd_quat, float wd_trans, double gamma, int min_step,
+                                  int patience, int early_stop, int max_steps, float* c2w, float* viewmat,
+                                  float* loss_hist, void* stream, const float* photo_sums, float rgb_lambda,
+                                  float ssim_lambda, float* best_pose) {
+  if (!best_pose) return GSL_ERR_BAD_ARG;
+  return pose_step_launch(pose_f, pose_i, v_viewmat, vm_rows, n_vm_rows, K, loss_partials, n_partials, loss_sums,
+                          normal_sum, gt_c2w, width, height, depth_lambda, edge_lambda, normal_lambda, beta1, beta2, eps,
+                          wd_quat, wd_trans, gamma, min_step, patience, early_stop, max_steps, c2w, viewmat, loss_hist,
+                          stream, photo_sums, rgb_lambda, ssim_lambda, best_pose);
 }
 
 extern "C" int gsl_pose_step(float* pose_f, int* pose_i, const float* v_viewmat, const float* vm_rows, int n_vm_rows,

@@ -7,14 +7,14 @@ import re
 from collections.abc import Sequence
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Literal
+from typing import Literal, Optional
 
 import numpy as np
 import torch
 from torch import Tensor
 
 from ..my_gsplat.geometry import compute_depth_gt, depth_to_points, transform_points
-from .normalize import normalize_pair
+from .normalize import normalize_pair_with_transform
 
 
 def _natural_key(p: Path):
@@ -209,6 +209,7 @@ class AlignData:
     tar_c2w: Tensor
     src_c2w: Tensor
     tar_nums: int
+    norm_T: Optional[Tensor] = None  # [4,4] world -> normalised frame of the pair; None without normalisation
 
 
 def _now(device) -> float:
@@ -216,6 +217,39 @@ def _now(device) -> float:
     if torch.device(device).type == "cuda":
         torch.cuda.synchronize()
     return time.perf_counter()
+
+
+@torch.no_grad()
+def build_pair(t_pts: Tensor, t_col: Tensor, s_pts: Tensor, s_col: Tensor, s_depth: Tensor, s_rgb: Tensor,
+               t_pose: Tensor, s_pose: Tensor, K: Tensor, normalize: bool, ph: Optional[dict] = None,
+               t0: float = 0.0) -> AlignData:
+    """The tracker's inputs from two frames (the body of dataset.py:345-383): camera-frame clouds ``t_pts`` / ``s_pts``
+    [H*W,3] with colours in 0..1, the query frame's depth [H,W] and image [H,W,3] (0..255), the pose ``t_pose`` BOTH
+    clouds are placed with, and ``s_pose``, the query frame's pose for the error read-out.  normalize: the pair is moved
+    to the target cloud's PCA frame (AlignData.norm_T) and the query depth is re-rendered ("ED") from the source cloud
+    at the target pose.  Shared by Parser (ground-truth or given t_pose) and Localizer (estimated t_pose).
+    ``ph`` / ``t0``: the Parser's per-phase wall times and the time the caller started reading."""
+    device = t_pts.device
+    t_pts = transform_points(t_pose, t_pts)
+    s_pts = transform_points(t_pose, s_pts)
+    pca_factor = torch.scalar_tensor(1.0, device=device)
+    norm_T = None
+    if normalize:
+        t_pts, t_pose, s_pts, s_pose, pca_factor, norm_T = normalize_pair_with_transform(t_pts, t_pose, s_pts, s_pose)
+        t1 = _now(device) if ph is not None else 0.0
+        h, w = s_depth.shape
+        s_depth = compute_depth_gt(s_pts, s_col, K.unsqueeze(0), c2w=t_pose.unsqueeze(0), height=h,
+                                   width=w) / pca_factor
+        s_depth = s_depth.reshape(h, w)
+        if ph is not None:
+            t2 = _now(device)
+            ph["read_backproject_normalise"] = ph.get("read_backproject_normalise", 0.0) + (t1 - t0)
+            ph["depth_gt_render"] = ph.get("depth_gt_render", 0.0) + (t2 - t1)
+    elif ph is not None:
+        ph["read_backproject_normalise"] = ph.get("read_backproject_normalise", 0.0) + (_now(device) - t0)
+    return AlignData(pca_factor=pca_factor, colors=t_col, pixels=(s_rgb / 255.0).unsqueeze(0), tar_points=t_pts,
+                     src_points=s_pts, src_depth=s_depth.unsqueeze(-1).unsqueeze(0), tar_c2w=t_pose,
+                     src_c2w=s_pose, tar_nums=t_pts.shape[0], norm_T=norm_T)
 
 
 class Parser:
@@ -261,8 +295,21 @@ class Parser:
             del self._frames[k]
         return out
 
-    @torch.no_grad()
+    def frame(self, index: int):
+        """(depth [H,W] metres, rgb [H,W,3] 0..255, ground-truth c2w [4,4]) of frame ``index`` on the device; the next
+        frame is decoded on the reader thread meanwhile (what a sequential caller asks for next)."""
+        depth, rgb, pose = self._frame(index)[:3]
+        self._prefetch(index + 1)
+        return depth, rgb, pose
+
     def __getitem__(self, index: int) -> AlignData:
+        return self.pair(index)
+
+    @torch.no_grad()
+    def pair(self, index: int, tar_c2w: Optional[Tensor] = None) -> AlignData:
+        """Pair (index, index + 1).  ``tar_c2w`` (4x4) replaces the ground-truth pose of frame ``index`` wherever the pair
+        is built -- the placement of both clouds, the PCA frame, the pose the query depth is re-rendered from and
+        AlignData.tar_c2w; src_c2w stays the ground truth of frame index + 1 (the error read-out).  pair(i) is parser[i]."""
         if index >= len(self) or index < 0:
             raise IndexError(index)
         ph = self.phase_seconds
@@ -270,22 +317,6 @@ class Parser:
         t_depth, t_rgb, t_pose, t_pts, t_col = self._frame(index)
         s_depth, s_rgb, s_pose, s_pts, s_col = self._frame(index + 1)
         self._prefetch(index + 2)  # what pair index + 1 will need; decoded while this pair is being tracked
-        t_pts = transform_points(t_pose, t_pts)
-        s_pts = transform_points(t_pose, s_pts)
-        pca_factor = torch.scalar_tensor(1.0, device=self.device)
-        if self.normalize:
-            t_pts, t_pose, s_pts, s_pose, pca_factor = normalize_pair(t_pts, t_pose, s_pts, s_pose)
-            t1 = _now(self.device) if ph is not None else 0.0
-            h, w = s_depth.shape
-            s_depth = compute_depth_gt(s_pts, s_col, self.K.unsqueeze(0), c2w=t_pose.unsqueeze(0), height=h,
-                                       width=w) / pca_factor
-            s_depth = s_depth.reshape(h, w)
-            if ph is not None:
-                t2 = _now(self.device)
-                ph["read_backproject_normalise"] = ph.get("read_backproject_normalise", 0.0) + (t1 - t0)
-                ph["depth_gt_render"] = ph.get("depth_gt_render", 0.0) + (t2 - t1)
-        elif ph is not None:
-            ph["read_backproject_normalise"] = ph.get("read_backproject_normalise", 0.0) + (_now(self.device) - t0)
-        return AlignData(pca_factor=pca_factor, colors=t_col, pixels=(s_rgb / 255.0).unsqueeze(0), tar_points=t_pts,
-                         src_points=s_pts, src_depth=s_depth.unsqueeze(-1).unsqueeze(0), tar_c2w=t_pose,
-                         src_c2w=s_pose, tar_nums=t_pts.shape[0])
+        if tar_c2w is not None:
+            t_pose = torch.as_tensor(tar_c2w, dtype=torch.float32, device=self.device)
+        return build_pair(t_pts, t_col, s_pts, s_col, s_depth, s_rgb, t_pose, s_pose, self.K, self.normalize, ph, t0)

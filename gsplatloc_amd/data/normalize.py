@@ -35,10 +35,28 @@ def transform_cameras(matrix: Tensor, c2w: Tensor):
 
 
 @torch.no_grad()
-def normalize_pair(tar_points: Tensor, tar_pose: Tensor, src_points: Tensor, src_pose: Tensor):
-    """normalize.py:107-124 (normalize_2C): PCA frame of the target cloud applied to both clouds and poses."""
+def normalize_pair_with_transform(tar_points: Tensor, tar_pose: Tensor, src_points: Tensor, src_pose: Tensor):
+    """normalize_pair and, as a sixth result, the 4x4 world->normalised transform it applied."""
     T = align_principle_axes(tar_points)
     tar_pose_n, scale = transform_cameras(T, tar_pose.unsqueeze(0))
     src_pose_n, _ = transform_cameras(T, src_pose.unsqueeze(0))
     return (transform_points(T, tar_points), tar_pose_n.squeeze(0), transform_points(T, src_points),
-            src_pose_n.squeeze(0), scale)
+            src_pose_n.squeeze(0), scale, T)
+
+
+@torch.no_grad()
+def normalize_pair(tar_points: Tensor, tar_pose: Tensor, src_points: Tensor, src_pose: Tensor):
+    """normalize.py:107-124 (normalize_2C): PCA frame of the target cloud applied to both clouds and poses."""
+    return normalize_pair_with_transform(tar_points, tar_pose, src_points, src_pose)[:5]
+
+
+@torch.no_grad()
+def denormalize_camera(norm_T: Tensor, c2w: Tensor) -> Tensor:
+    """A camera-to-world pose of the normalised frame back in the world: norm_T^-1 @ c2w.  align_principle_axes returns a
+    rigid transform [R | t], so its inverse is [R^T | -R^T t] and the scale is 1; computed in float64, returned as
+    float32."""
+    T = norm_T.to(torch.float64)
+    inv = torch.eye(4, dtype=torch.float64, device=T.device)
+    inv[:3, :3] = T[:3, :3].T
+    inv[:3, 3] = -(T[:3, :3].T @ T[:3, 3])
+    return (inv @ c2w.to(torch.float64)).to(torch.float32)

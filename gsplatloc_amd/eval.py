@@ -5,6 +5,10 @@ ATE := RMSE of the translation errors, AAE := RMSE of the rotation errors (eval/
 res.json layout of /root/reference/docs/res.json.
 
     python -m gsplatloc_amd.eval --dataset Replica --rooms room0 --root /data/Replica --num-iters 200
+
+--sequential: the room is tracked from the ground-truth pose of frame 0 ONLY (gsplatloc_amd.localizer.Localizer): every
+later frame is placed with, and started from, the tracker's own estimates, and the errors reported are the ABSOLUTE
+errors of the estimated trajectory against ground truth (no trajectory alignment), i.e. they include the drift.
 """
 from __future__ import annotations
 
@@ -18,6 +22,7 @@ import torch
 
 from .data import Parser
 from .graph_tracker import GraphTracker
+from .localizer import Localizer
 from .my_gsplat import TrackerConfig, init_gs_scales
 
 
@@ -27,13 +32,17 @@ def rmse(values: List[float]) -> float:
 
 
 def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[int] = 1998, verbose: bool = False,
-                  profile: bool = False, rgb_lambda: float = 0.0, ssim_lambda: float = 0.5) -> Dict:
+                  profile: bool = False, rgb_lambda: float = 0.0, ssim_lambda: float = 0.5, sequential: bool = False,
+                  motion: str = "constant_velocity") -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
     capture + replays + polls) -- `phase_seconds` in the result.  rgb_lambda != 0 switches the photometric term on
-    (TrackerConfig.rgb_lambda / ssim_lambda): the tracker then renders "RGB+ED" and is given the frame's image."""
+    (TrackerConfig.rgb_lambda / ssim_lambda): the tracker then renders "RGB+ED" and is given the frame's image.
+    sequential=True: evaluate_sequential (only frame 0's ground-truth pose is used; ``motion`` is its hand-over)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
+    if sequential:
+        return evaluate_sequential(parser, cfg, max_frames, verbose, motion)
     photo = rgb_lambda != 0.0
     phases = {} if profile else None
     parser.phase_seconds = phases
@@ -90,6 +99,36 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
             **({"phase_seconds": phases} if profile else {})}
 
 
+def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional[int] = 1998, verbose: bool = False,
+                        motion: str = "constant_velocity") -> Dict:
+    """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
+    ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment."""
+    n = len(parser) if max_frames is None else min(len(parser), max_frames)
+    depth, rgb, pose = parser.frame(0)
+    H, W = depth.shape
+    loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device)
+    t0 = time.perf_counter()
+    loc.reset(depth, rgb, pose)
+    eTs, eRs, steps, lost, path, last_t = [], [], [], 0, 0.0, pose[:3, 3]
+    for i in range(1, n + 1):
+        depth, rgb, pose = parser.frame(i)
+        r = loc.track(depth, rgb, gt_c2w=pose)
+        eTs.append(r.eT)
+        eRs.append(r.eR)
+        steps.append(r.steps)
+        lost += int(r.lost)
+        path += float(torch.norm(pose[:3, 3] - last_t))
+        last_t = pose[:3, 3]
+        if verbose:
+            print(f"frame {i}: steps {r.steps} best step {r.best_step} loss {r.best_loss:.3e} eT {r.eT:.3e} "
+                  f"eR {r.eR:.3e}")
+    dt = time.perf_counter() - t0
+    return {"mode": "sequential", "motion": motion, "ATE": rmse(eTs), "AAE": rmse(eRs),
+            "final_eT": eTs[-1] if eTs else float("nan"), "final_eR": eRs[-1] if eRs else float("nan"),
+            "path_length": path, "frames": n, "lost_frames": lost, "mean_steps": sum(steps) / max(len(steps), 1),
+            "seconds": dt, "frames_per_s": n / dt if dt > 0 else None}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="GsplatLoc evaluation on the MI355X rasterizer")
     ap.add_argument("--dataset", choices=["Replica", "TUM"], default="Replica")
@@ -103,12 +142,17 @@ def main(argv=None):
     ap.add_argument("--rgb-lambda", type=float, default=0.0,
                     help="weight of the photometric term (RGB L1 + SSIM against the frame's image); 0 = off")
     ap.add_argument("--ssim-lambda", type=float, default=0.5, help="share of 1 - SSIM inside the photometric term")
+    ap.add_argument("--sequential", action="store_true",
+                    help="track each room from the ground-truth pose of frame 0 only and report the trajectory's drift")
+    ap.add_argument("--motion", choices=["hold", "constant_velocity"], default="constant_velocity",
+                    help="--sequential: where a frame's optimisation starts (the previous estimate, or the "
+                         "constant-velocity prediction of the last two)")
     a = ap.parse_args(argv)
     out = {}
     for room in a.rooms:
         parser = Parser(a.dataset, room, normalize=not a.no_normalize, input_folder=a.root)
         r = evaluate_room(parser, a.num_iters, a.max_frames, a.verbose, rgb_lambda=a.rgb_lambda,
-                          ssim_lambda=a.ssim_lambda)
+                          ssim_lambda=a.ssim_lambda, sequential=a.sequential, motion=a.motion)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

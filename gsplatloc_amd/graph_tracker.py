@@ -32,6 +32,10 @@ Photometric term (``rgb_lambda != 0``, off by default like the normal term; one 
 (csrc/photo.hip, two launches) writes the colour channels of the upstream gradient between the depth losses and the
 backward, and gsl_pose_step_photo adds the term to the total.  The loss fused into the tiny backward treats the colour
 gradient as zero, so that iteration always takes the separate loss launch.
+
+Minimum-loss pose: the pose step is always gsl_pose_step_best, which writes the pose of the iterate that set a new
+minimum into ``best_pose`` (24 floats) at the moment it writes the best loss: TrackResult.best_c2w / best_step.  Same
+launches, same order, every other buffer bit-identical to gsl_pose_step / gsl_pose_step_photo.
 """
 from __future__ import annotations
 
@@ -98,7 +102,10 @@ class GraphTracker:
         self.gt_depth = torch.zeros(self.H, self.W, dtype=f32, device=d)
         self.init_c2w = torch.eye(4, dtype=f32, device=d)
         self.gt_c2w = torch.eye(4, dtype=f32, device=d)
-        self.pose_f = torch.zeros(40, dtype=f32, device=d)
+        # pose state (40 floats) and the minimum-loss pose (24 floats; layout: include/gsloc_hip.h) in ONE allocation:
+        # saving and restoring the state around a capture or a re-run costs no more copies than without the latter
+        self._pose_store = torch.zeros(64, dtype=f32, device=d)
+        self.pose_f, self.best_pose = self._pose_store[:40], self._pose_store[40:]
         self.pose_i = torch.zeros(4, dtype=torch.int32, device=d)
         self.c2w = torch.eye(4, dtype=f32, device=d)
         self.viewmat = torch.eye(4, dtype=f32, device=d)
@@ -271,11 +278,13 @@ class GraphTracker:
                 cam.trans_opt_reg, gamma, cfg.min_step,
                 cfg.patience, int(cfg.early_stop), cfg.max_steps, ptr(self.c2w), ptr(self.viewmat),
                 ptr(self.loss_hist), current_stream())
+        # always the entry point that keeps the minimum-loss pose; the step it takes is gsl_pose_step's, or
+        # gsl_pose_step_photo's with the photometric term, and an error is reported under that name
         if self.photo_ws is not None:
-            check(lib.gsl_pose_step_photo(*args, ptr(self.photo_sums), cfg.rgb_lambda, cfg.ssim_lambda),
-                  "gsl_pose_step_photo")
+            check(lib.gsl_pose_step_best(*args, ptr(self.photo_sums), cfg.rgb_lambda, cfg.ssim_lambda,
+                                         ptr(self.best_pose)), "gsl_pose_step_photo")
         else:
-            check(lib.gsl_pose_step(*args), "gsl_pose_step")
+            check(lib.gsl_pose_step_best(*args, None, 0.0, 0.0, ptr(self.best_pose)), "gsl_pose_step")
 
     def _collective(self) -> None:
         """THE collective of the path: 16 floats summed over the ranks (RCCL on device buffers; the one-GPU
@@ -312,7 +321,7 @@ class GraphTracker:
             self._pose_step()
 
     def _state(self):
-        return (self.pose_f, self.pose_i, self.c2w, self.viewmat, self.loss_hist)
+        return (self._pose_store, self.pose_i, self.c2w, self.viewmat, self.loss_hist)  # (pose_f and best_pose)
 
     def _capture(self) -> None:
         """One HIP graph per iteration.  Several ranks over RCCL: the 16-float all-reduce is captured INSIDE that graph
@@ -434,4 +443,6 @@ class GraphTracker:
         if self.photo_ws is not None:
             res.best_rgb_l1_loss, res.best_ssim_loss = pf[34], pf[35]
         res.final_c2w = self.c2w.clone()
+        res.best_step = pi[3]
+        res.best_c2w = self.best_pose[8:24].reshape(4, 4).clone() if pi[3] >= 0 else res.final_c2w
         return res

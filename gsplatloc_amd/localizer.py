@@ -1,0 +1,147 @@
+"""Sequential localisation: a depth (or RGB-D) sequence tracked from its FIRST pose only.
+
+The evaluation protocol of ``gsplatloc_amd.eval`` places pair (i, i+1) with the ground-truth pose of frame i and starts
+there.  ``Localizer`` hands its own estimates on instead:
+
+  1. the Gaussians come from the PREVIOUS frame's depth and colours, placed with the previous frame's ESTIMATED pose;
+  2. the target depth is the new frame's;
+  3. the optimisation starts from the previous estimate ("hold", and always for the second frame) or from the
+     constant-velocity prediction of the last two estimates (``predict_pose`` -- the hand-over the reference declares as
+     ``update_pose(None)`` / ``predict_next_pose``, /root/reference/src/my_gsplat/model.py, and never calls);
+  4. both are moved into the pair's PCA frame (``AlignData.norm_T``) when ``normalize`` is on;
+  5. ``GraphTracker.load_frame`` / ``run``;
+  6. the frame's estimate is the MINIMUM-LOSS pose the device kept (``TrackResult.best_c2w``), moved back to the world.
+
+The pair is built by ``data.dataset.build_pair``, the function ``Parser`` uses.  One ``GraphTracker`` is kept while the
+number of Gaussians and the image size stay the same.  The host synchronises once per frame anyway (the tracker's poll
+and its calibration pass), so the hand-over is host code.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Callable, List, Optional
+
+import torch
+from torch import Tensor
+
+from .data.dataset import build_pair
+from .data.normalize import denormalize_camera, transform_cameras
+from .my_gsplat.geometry import construct_full_pose, depth_to_points, init_gs_scales
+from .my_gsplat.trainer import TrackerConfig, calculate_rotation_error, calculate_translation_error
+from .my_gsplat.transform import normalize_quaternion, quat_to_rotation_matrix, rotation_matrix_to_quaternion
+
+MOTIONS = ("constant_velocity", "hold")
+
+
+@torch.no_grad()
+def predict_pose(prev_c2w: Tensor, cur_c2w: Tensor) -> Tensor:
+    """Constant velocity in parameter space, on two world poses: q = normalise(q_cur + (q_cur - q_prev)) on wxyz
+    quaternions, t = t_cur + (t_cur - t_prev).  q and -q are the same rotation and two independent conversions may land
+    on opposite hemispheres, so q_prev is negated when its dot product with q_cur is negative (differencing them as they
+    come would extrapolate to a rotation about 180 degrees away)."""
+    q_prev = rotation_matrix_to_quaternion(prev_c2w[:3, :3].contiguous())
+    q_cur = rotation_matrix_to_quaternion(cur_c2w[:3, :3].contiguous())
+    if float((q_prev * q_cur).sum()) < 0.0:
+        q_prev = -q_prev
+    q = normalize_quaternion(q_cur + (q_cur - q_prev))
+    t = cur_c2w[:3, 3] + (cur_c2w[:3, 3] - prev_c2w[:3, 3])
+    return construct_full_pose(quat_to_rotation_matrix(q), t)
+
+
+@dataclass
+class LocalizeResult:
+    c2w: Tensor  # [4,4] the frame's estimate in the world: the minimum-loss pose (the last iterate when lost)
+    init_c2w: Tensor  # [4,4] the pose the optimisation started from, in the world
+    steps: int
+    best_step: int
+    best_loss: float
+    lost: bool  # no minimum was ever recorded (best_step == -1)
+    eT: Optional[float] = None  # metres / degrees against gt_c2w, when one was given
+    eR: Optional[float] = None
+
+
+def _default_factory(N, W, H, config, device, render_mode):
+    from .graph_tracker import GraphTracker
+    return GraphTracker(N, W, H, config, device=device, render_mode=render_mode)
+
+
+class Localizer:
+    """``reset(depth, rgb, c2w)`` with the first frame and its pose, then ``track(depth, rgb)`` per frame.
+    depth [H,W] in metres, rgb [H,W,3] in 0..255 (as the dataset readers deliver them), poses 4x4 camera-to-world.
+    ``tracker_factory(N, W, H, config, device, render_mode)`` returns what is driven through ``load_frame`` / ``run``
+    (default: GraphTracker).  With ``config.rgb_lambda != 0`` every frame needs its image and the tracker renders
+    "RGB+ED" whatever ``render_mode`` says."""
+
+    def __init__(self, K: Tensor, width: int, height: int, config: TrackerConfig = TrackerConfig(),
+                 normalize: bool = True, motion: str = "constant_velocity", device="cuda", render_mode: str = "ED",
+                 tracker_factory: Optional[Callable] = None):
+        if motion not in MOTIONS:
+            raise ValueError(f"unknown motion model {motion!r}: one of {MOTIONS}")
+        self.device = torch.device(device)
+        self.K = torch.as_tensor(K, dtype=torch.float32, device=self.device)
+        self.W, self.H = int(width), int(height)
+        self.cfg = config
+        self.normalize = bool(normalize)
+        self.motion = motion
+        self.photo = config.rgb_lambda != 0.0
+        self.mode = "RGB+ED" if self.photo else render_mode
+        self._factory = tracker_factory if tracker_factory is not None else _default_factory
+        self.tracker = None
+        self._tracker_N = -1
+        self._prev = None  # (camera-frame cloud [H*W,3], colours [H*W,3] in 0..1) of the last frame
+        self._poses: List[Tensor] = []
+
+    def _frame(self, depth, rgb):
+        depth = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
+        if depth.shape != (self.H, self.W):
+            raise ValueError(f"depth is {tuple(depth.shape)}, the localizer was built for {(self.H, self.W)}")
+        if rgb is None:
+            if self.photo:
+                raise ValueError(f"rgb_lambda = {self.cfg.rgb_lambda}: the photometric term needs every frame's image "
+                                 "(rgb=)")
+            rgb = torch.full((self.H, self.W, 3), 127.5, device=self.device)  # colours are not rendered in "ED"
+        rgb = torch.as_tensor(rgb, dtype=torch.float32, device=self.device)[..., :3]
+        return depth, rgb, depth_to_points(depth, self.K), (rgb / 255.0).reshape(-1, 3)
+
+    @property
+    def trajectory(self) -> Tensor:
+        """[n,4,4] the world poses so far, frame 0 included."""
+        return torch.stack(self._poses) if self._poses else torch.zeros(0, 4, 4, device=self.device)
+
+    def reset(self, depth, rgb=None, c2w: Optional[Tensor] = None) -> None:
+        """The first frame and its pose (identity by default); forgets the trajectory so far."""
+        _, _, pts, col = self._frame(depth, rgb)
+        pose = torch.eye(4) if c2w is None else torch.as_tensor(c2w, dtype=torch.float32)
+        self._prev = (pts, col)
+        self._poses = [pose.to(self.device).clone()]
+
+    @torch.no_grad()
+    def track(self, depth, rgb=None, gt_c2w: Optional[Tensor] = None) -> LocalizeResult:
+        if self._prev is None:
+            raise RuntimeError("Localizer.track before reset(): the first frame comes with its pose")
+        depth, rgb, pts, col = self._frame(depth, rgb)
+        placed = self._poses[-1]
+        if self.motion == "hold" or len(self._poses) < 2:
+            init = placed
+        else:
+            init = predict_pose(self._poses[-2], placed)
+        gt = None if gt_c2w is None else torch.as_tensor(gt_c2w, dtype=torch.float32, device=self.device)
+        # the pair's reference pose is the tracker's error read-out only: without ground truth, the starting pose
+        d = build_pair(self._prev[0], self._prev[1], pts, col, depth, rgb, placed, gt if gt is not None else init,
+                       self.K, self.normalize)
+        init_n = transform_cameras(d.norm_T, init.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else init
+        N = d.tar_points.shape[0]
+        if self.tracker is None or self._tracker_N != N:
+            self.tracker, self._tracker_N = self._factory(N, self.W, self.H, self.cfg, self.device, self.mode), N
+        self.tracker.load_frame(d.tar_points, d.colors, init_gs_scales(d.tar_points), d.src_depth, init_n, d.src_c2w,
+                                self.K, pixels=d.pixels if self.photo else None)
+        res = self.tracker.run()
+        best = res.best_c2w.to(self.device)
+        est = denormalize_camera(d.norm_T, best) if d.norm_T is not None else best.clone()
+        self._prev = (pts, col)
+        self._poses.append(est)
+        out = LocalizeResult(c2w=est, init_c2w=init, steps=res.steps, best_step=res.best_step, best_loss=res.best_loss,
+                             lost=res.best_step == -1)
+        if gt is not None:
+            out.eT, out.eR = calculate_translation_error(est, gt), calculate_rotation_error(est, gt)
+        return out

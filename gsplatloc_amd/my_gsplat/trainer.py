@@ -69,6 +69,10 @@ class TrackResult:
     best_eR: float = float("inf")
     final_c2w: Optional[Tensor] = None
     steps: int = 0
+    # the pose of the minimum-loss iterate (the one best_eT / best_eR were read from) and its step; no minimum was ever
+    # recorded (best_step == -1: num_iters <= min_step + 1, or early_stop off): best_c2w is final_c2w
+    best_c2w: Optional[Tensor] = None
+    best_step: int = -1
 
 
 class PoseTracker:
@@ -160,6 +164,7 @@ class PoseTracker:
                             if self.last_photo is not None:
                                 res.best_rgb_l1_loss, res.best_ssim_loss = (v.item() for v in self.last_photo)
                             res.best_eT, res.best_eR = eT, eR
+                            res.best_c2w, res.best_step = cur_c2w.detach().clone(), step
                             counter = 0
                         else:
                             counter += 1
@@ -174,4 +179,6 @@ class PoseTracker:
                 s.step()
         if rc is not None:
             rc.check_capacity()
+        if res.best_step == -1:
+            res.best_c2w = res.final_c2w
         return res

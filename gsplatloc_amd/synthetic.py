@@ -185,6 +185,45 @@ def write_replica_sequence(root, W, H, n):
             f.write(" ".join(f"{v:.12f}" for v in p.reshape(-1)) + "\n")
 
 
+def write_replica_constant_twist(root, W, H, n, rot_deg: float = 0.4, trans: float = 0.01, axis=(0.3, 1.0, -0.2),
+                                 direction=(0.6, 0.1, 0.8)):
+    """The Replica layout of write_replica_sequence for a camera that moves by the SAME twist every frame (rot_deg about
+    ``axis``, ``trans`` metres along ``direction``, both fixed in the camera frame): the sequence a constant-velocity
+    hand-over predicts up to its second-order term.  Returns the n camera-to-world poses [n,4,4] (float64)."""
+    import json
+
+    import numpy as np
+    from PIL import Image
+
+    d = root / "room0" / "results"
+    d.mkdir(parents=True)
+    K = replica_intrinsics(W, H)
+    cam = {"camera": {"w": W, "h": H, "fx": float(K[0, 0]), "fy": float(K[1, 1]), "cx": float(K[0, 2]),
+                      "cy": float(K[1, 2]), "scale": 6553.5}}
+    (root / "cam_params.json").write_text(json.dumps(cam))
+    ax = np.asarray(axis, dtype=np.float64)
+    ax /= np.linalg.norm(ax)
+    th = np.radians(rot_deg)
+    Kx = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+    step = np.eye(4)
+    step[:3, :3] = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * (Kx @ Kx)
+    t = np.asarray(direction, dtype=np.float64)
+    step[:3, 3] = trans * t / np.linalg.norm(t)
+    rng = np.random.default_rng(11)
+    poses, c2w = [], np.eye(4)
+    for i in range(n):
+        if i:
+            c2w = c2w @ step
+        depth = room_depth(W, H, K, torch.from_numpy(c2w).float()).numpy()
+        Image.fromarray(np.round(depth * 6553.5).astype(np.uint16)).save(d / f"depth{i:06d}.png")
+        Image.fromarray(rng.integers(0, 255, (H, W, 3), dtype=np.uint8)).save(d / f"frame{i:06d}.jpg")
+        poses.append(c2w.copy())
+    with open(root / "room0" / "traj.txt", "w") as f:
+        for p in poses:
+            f.write(" ".join(f"{v:.12f}" for v in p.reshape(-1)) + "\n")
+    return torch.from_numpy(np.stack(poses))
+
+
 def write_tum_sequence(root, W, H, n, hole_frac: float = 0.06, crop_edge: int = 8, name: str = "freiburg1_desk"):
     """TUM RGB-D layout (rgbd_dataset_<name>/{rgb/*.png, depth/*.png at scale 5000, rgb.txt, depth.txt, groundtruth.txt
     with `timestamp tx ty tz qx qy qz qw`, cam_params.json with crop_edge}) of the same drifting camera, 15 Hz, the

@@ -476,7 +476,14 @@ int gsl_tiny_raster_bwd(const float* Q0, const float* Q1, const float* Q2, int c
  * gsl_pose_step_photo: gsl_pose_step with the photometric term: photo_sums (of gsl_photo_loss; NULL: none) adds
  *   rgb_lambda * photo, taken in double from the three sums, to the total that goes into loss_hist, the best-loss
  *   bookkeeping and the early stop; whenever pose_f[23] is written, pose_f[34] gets that step's l1 and pose_f[35] its
- *   1 - ssim.  gsl_pose_step is this function with NULL, 0, 0. */
+ *   1 - ssim.  gsl_pose_step is this function with NULL, 0, 0.
+ * gsl_pose_step_best: gsl_pose_step_photo (photo_sums may be NULL: no photometric term) that also keeps the
+ *   minimum-loss POSE: whenever pose_f[23] is written, best_pose[24] (not NULL: GSL_ERR_BAD_ARG) gets the pose that
+ *   iteration rendered with, i.e. before its Adam update --
+ *     best_pose[0..3] the quaternion as stored (wxyz, not normalised), [4..6] the translation, [7] the total loss
+ *     (== pose_f[23]), [8..23] the 4x4 camera-to-world matrix, the bits c2w held during that iteration.
+ *   Nothing else is written to it: "no best yet" is pose_i[3] == -1, and the buffer then holds what the caller left.
+ *   Every other output is bit-identical to gsl_pose_step_photo's. */
 size_t gsl_photo_ws_bytes(int width, int height);
 int gsl_photo_loss(const float* render, int channels, const float* pixels, int width, int height, float rgb_lambda,
                    float ssim_lambda, float* v_render, float* photo_sums, void* ws, size_t ws_bytes, void* stream);
@@ -487,6 +494,13 @@ int gsl_pose_step_photo(float* pose_f, int* pose_i, const float* v_viewmat, cons
                         float wd_trans, double gamma, int min_step, int patience, int early_stop, int max_steps,
                         float* c2w, float* viewmat, float* loss_hist, void* stream, const float* photo_sums,
                         float rgb_lambda, float ssim_lambda);
+int gsl_pose_step_best(float* pose_f, int* pose_i, const float* v_viewmat, const float* vm_rows, int n_vm_rows,
+                       const float* K, const float* loss_partials, int n_partials, const float* loss_sums,
+                       const float* normal_sum, const float* gt_c2w, int width, int height, float depth_lambda,
+                       float edge_lambda, float normal_lambda, double beta1, double beta2, float eps, float wd_quat,
+                       float wd_trans, double gamma, int min_step, int patience, int early_stop, int max_steps,
+                       float* c2w, float* viewmat, float* loss_hist, void* stream, const float* photo_sums,
+                       float rgb_lambda, float ssim_lambda, float* best_pose);
 size_t gsl_loss_ws_bytes(int width, int height);
 int gsl_loss_n_partials(int width, int height, int row0, int row1);
 size_t gsl_normal_ws_bytes(int width, int height);
