@@ -22,5 +22,6 @@ from .ops import (  # noqa: F401
 from .rendering import rasterization  # noqa: F401
 from .legacy import project_gaussians, rasterize_gaussians  # noqa: F401
 from .localizer import LocalizeResult, Localizer, predict_pose  # noqa: F401
+from .mapping import GaussianMap, MapConfig  # noqa: F401
 
 __version__ = "0.1.0"

@@ -39,6 +39,10 @@ _SIGNATURES = {
                                        P, c_int, P, P, P, P, P, c_size_t, P]),
     "gsl_gather_rows": (c_int, [P, c_int64, c_int, P, c_int64, P, P]),
     "gsl_scatter_add_rows": (c_int, [P, P, c_int64, c_int, c_int64, c_int, P, P]),
+    "gsl_map_ws_bytes": (c_size_t, [c_int, c_int]),
+    "gsl_map_select": (c_int, [P, P, P, c_int, c_int, c_float, c_float, P, P, c_size_t, P]),
+    "gsl_map_append": (c_int, [P, P, c_int, c_int, c_float, c_float, c_float, c_float, P, P, P, c_int64, c_int64, P, P,
+                               c_size_t, P]),
     "gsl_sh_fwd": (c_int, [c_int, P, P, P, c_int, c_int, P, P]),
     "gsl_sh_bwd": (c_int, [c_int, P, P, P, c_int, c_int, P, P, P, P]),
     "gsl_isect_ws_bytes": (c_size_t, [c_int]),

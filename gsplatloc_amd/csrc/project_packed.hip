@@ -296,6 +296,10 @@ __global__ __launch_bounds__(256) void k_scatter_add_rows(const float* __restric
   }
 }
 
+void launch_count_scan(hipStream_t st, const uint32_t* counts, int nb, uint32_t* bases, int32_t* total) {
+  hipLaunchKernelGGL(k_packed_scan, dim3(1), dim3(256), 0, st, counts, nb, bases, total);
+}
+
 static inline long long packed_blocks(int C, int N) { return ((long long)C * N + 255) / 256; }
 
 }  // namespace gsl
@@ -336,7 +340,7 @@ extern "C" int gsl_project_packed_count(const float* means, const float* quats, 
                      (const uint32_t*)nullptr, 0ll, (int64_t*)nullptr, (int64_t*)nullptr, (int32_t*)nullptr,
                      (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
   GSL_CHECK_LAUNCH();
-  hipLaunchKernelGGL(gsl::k_packed_scan, dim3(1), dim3(256), 0, st, counts, nb, bases, nnz);
+  gsl::launch_count_scan(st, counts, nb, bases, nnz);
   GSL_CHECK_LAUNCH();
   return GSL_OK;
 }

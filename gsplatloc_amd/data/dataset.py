@@ -222,15 +222,18 @@ def _now(device) -> float:
 @torch.no_grad()
 def build_pair(t_pts: Tensor, t_col: Tensor, s_pts: Tensor, s_col: Tensor, s_depth: Tensor, s_rgb: Tensor,
                t_pose: Tensor, s_pose: Tensor, K: Tensor, normalize: bool, ph: Optional[dict] = None,
-               t0: float = 0.0) -> AlignData:
+               t0: float = 0.0, t_placed: bool = False) -> AlignData:
     """The tracker's inputs from two frames (the body of dataset.py:345-383): camera-frame clouds ``t_pts`` / ``s_pts``
     [H*W,3] with colours in 0..1, the query frame's depth [H,W] and image [H,W,3] (0..255), the pose ``t_pose`` BOTH
     clouds are placed with, and ``s_pose``, the query frame's pose for the error read-out.  normalize: the pair is moved
     to the target cloud's PCA frame (AlignData.norm_T) and the query depth is re-rendered ("ED") from the source cloud
     at the target pose.  Shared by Parser (ground-truth or given t_pose) and Localizer (estimated t_pose).
-    ``ph`` / ``t0``: the Parser's per-phase wall times and the time the caller started reading."""
+    ``ph`` / ``t0``: the Parser's per-phase wall times and the time the caller started reading.
+    ``t_placed``: the target cloud [N,3] is in the world already (a map's points, any N); only the query cloud is placed
+    with ``t_pose``."""
     device = t_pts.device
-    t_pts = transform_points(t_pose, t_pts)
+    if not t_placed:
+        t_pts = transform_points(t_pose, t_pts)
     s_pts = transform_points(t_pose, s_pts)
     pca_factor = torch.scalar_tensor(1.0, device=device)
     norm_T = None

@@ -15,6 +15,9 @@ there.  ``Localizer`` hands its own estimates on instead:
 The pair is built by ``data.dataset.build_pair``, the function ``Parser`` uses.  One ``GraphTracker`` is kept while the
 number of Gaussians and the image size stay the same.  The host synchronises once per frame anyway (the tracker's poll
 and its calibration pass), so the hand-over is host code.
+
+``mode="map"`` replaces step 1: the Gaussians are the live points of a persistent ``GaussianMap`` (mapping.py), already in
+the world, which every tracked frame extends by the pixels the map does not explain.  Steps 2 - 6 are unchanged.
 """
 from __future__ import annotations
 
@@ -26,11 +29,13 @@ from torch import Tensor
 
 from .data.dataset import build_pair
 from .data.normalize import denormalize_camera, transform_cameras
-from .my_gsplat.geometry import construct_full_pose, depth_to_points, init_gs_scales
+from .mapping import GaussianMap, MapConfig
+from .my_gsplat.geometry import construct_full_pose, depth_to_points, init_gs_scales, render_depth_alpha
 from .my_gsplat.trainer import TrackerConfig, calculate_rotation_error, calculate_translation_error
 from .my_gsplat.transform import normalize_quaternion, quat_to_rotation_matrix, rotation_matrix_to_quaternion
 
 MOTIONS = ("constant_velocity", "hold")
+MODES = ("frame", "map")
 
 
 @torch.no_grad()
@@ -58,6 +63,8 @@ class LocalizeResult:
     lost: bool  # no minimum was ever recorded (best_step == -1)
     eT: Optional[float] = None  # metres / degrees against gt_c2w, when one was given
     eR: Optional[float] = None
+    map_size: Optional[int] = None  # mode="map": live map points after this frame, and how many it added
+    added: Optional[int] = None
 
 
 def _default_factory(N, W, H, config, device, render_mode):
@@ -70,13 +77,26 @@ class Localizer:
     depth [H,W] in metres, rgb [H,W,3] in 0..255 (as the dataset readers deliver them), poses 4x4 camera-to-world.
     ``tracker_factory(N, W, H, config, device, render_mode)`` returns what is driven through ``load_frame`` / ``run``
     (default: GraphTracker).  With ``config.rgb_lambda != 0`` every frame needs its image and the tracker renders
-    "RGB+ED" whatever ``render_mode`` says."""
+    "RGB+ED" whatever ``render_mode`` says.
+
+    ``mode="frame"`` (default): frame to frame, as above.  ``mode="map"``: frame to map.  The Gaussians of every frame are
+    the live points of a ``GaussianMap`` (``map_config``; ``map_factory(width, height, config, device)`` builds it), which
+    are in the world already: ``reset`` fills it with every valid pixel of the first frame, and after every frame that
+    is not lost the map is rendered once at the frame's estimate -- in the pair's frame, with the scales the tracker just
+    used, by ``map_renderer(points, scales, Ks, c2w, height, width) -> (depth, alpha)`` (default: render_depth_alpha; the
+    CPU tests use stand-ins for both) -- and the pixels it does not explain are appended (mapping.py).  The tracker is
+    rebuilt when the live count changes.  Everything else -- normalisation, the re-rendered query depth, the scales, the
+    hand-over, ``best_c2w`` -- is the frame mode's."""
 
     def __init__(self, K: Tensor, width: int, height: int, config: TrackerConfig = TrackerConfig(),
                  normalize: bool = True, motion: str = "constant_velocity", device="cuda", render_mode: str = "ED",
-                 tracker_factory: Optional[Callable] = None):
+                 tracker_factory: Optional[Callable] = None, mode: str = "frame",
+                 map_config: Optional[MapConfig] = None, map_factory: Optional[Callable] = None,
+                 map_renderer: Optional[Callable] = None):
         if motion not in MOTIONS:
             raise ValueError(f"unknown motion model {motion!r}: one of {MOTIONS}")
+        if mode not in MODES:
+            raise ValueError(f"unknown mode {mode!r}: one of {MODES}")
         self.device = torch.device(device)
         self.K = torch.as_tensor(K, dtype=torch.float32, device=self.device)
         self.W, self.H = int(width), int(height)
@@ -84,12 +104,18 @@ class Localizer:
         self.normalize = bool(normalize)
         self.motion = motion
         self.photo = config.rgb_lambda != 0.0
-        self.mode = "RGB+ED" if self.photo else render_mode
+        self.render_mode = "RGB+ED" if self.photo else render_mode
         self._factory = tracker_factory if tracker_factory is not None else _default_factory
         self.tracker = None
         self._tracker_N = -1
         self._prev = None  # (camera-frame cloud [H*W,3], colours [H*W,3] in 0..1) of the last frame
         self._poses: List[Tensor] = []
+        self.map_mode = mode == "map"
+        self.map = None
+        if self.map_mode:
+            make = map_factory if map_factory is not None else GaussianMap
+            self.map = make(self.W, self.H, map_config if map_config is not None else MapConfig(), self.device)
+        self._render_map = map_renderer if map_renderer is not None else render_depth_alpha
 
     def _frame(self, depth, rgb):
         depth = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
@@ -110,10 +136,13 @@ class Localizer:
 
     def reset(self, depth, rgb=None, c2w: Optional[Tensor] = None) -> None:
         """The first frame and its pose (identity by default); forgets the trajectory so far."""
-        _, _, pts, col = self._frame(depth, rgb)
+        depth, rgb, pts, col = self._frame(depth, rgb)
         pose = torch.eye(4) if c2w is None else torch.as_tensor(c2w, dtype=torch.float32)
         self._prev = (pts, col)
         self._poses = [pose.to(self.device).clone()]
+        if self.map_mode:
+            self.map.clear()
+            self.map.insert_frame(depth, rgb, self.K, self._poses[0])  # no render yet: every valid pixel
 
     @torch.no_grad()
     def track(self, depth, rgb=None, gt_c2w: Optional[Tensor] = None) -> LocalizeResult:
@@ -127,13 +156,20 @@ class Localizer:
             init = predict_pose(self._poses[-2], placed)
         gt = None if gt_c2w is None else torch.as_tensor(gt_c2w, dtype=torch.float32, device=self.device)
         # the pair's reference pose is the tracker's error read-out only: without ground truth, the starting pose
-        d = build_pair(self._prev[0], self._prev[1], pts, col, depth, rgb, placed, gt if gt is not None else init,
-                       self.K, self.normalize)
+        if self.map_mode:
+            if self.map.n_live == 0:
+                raise RuntimeError("Localizer.track: the map is empty (the first frame had no valid depth)")
+            d = build_pair(self.map.points, self.map.point_colors, pts, col, depth, rgb, placed,
+                           gt if gt is not None else init, self.K, self.normalize, t_placed=True)
+        else:
+            d = build_pair(self._prev[0], self._prev[1], pts, col, depth, rgb, placed, gt if gt is not None else init,
+                           self.K, self.normalize)
         init_n = transform_cameras(d.norm_T, init.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else init
         N = d.tar_points.shape[0]
         if self.tracker is None or self._tracker_N != N:
-            self.tracker, self._tracker_N = self._factory(N, self.W, self.H, self.cfg, self.device, self.mode), N
-        self.tracker.load_frame(d.tar_points, d.colors, init_gs_scales(d.tar_points), d.src_depth, init_n, d.src_c2w,
+            self.tracker, self._tracker_N = self._factory(N, self.W, self.H, self.cfg, self.device, self.render_mode), N
+        scales = init_gs_scales(d.tar_points)
+        self.tracker.load_frame(d.tar_points, d.colors, scales, d.src_depth, init_n, d.src_c2w,
                                 self.K, pixels=d.pixels if self.photo else None)
         res = self.tracker.run()
         best = res.best_c2w.to(self.device)
@@ -142,6 +178,15 @@ class Localizer:
         self._poses.append(est)
         out = LocalizeResult(c2w=est, init_c2w=init, steps=res.steps, best_step=res.best_step, best_loss=res.best_loss,
                              lost=res.best_step == -1)
+        if self.map_mode:
+            out.added = 0
+            if not out.lost:  # a lost frame's pose is a guess: it adds nothing
+                # what the map shows from the estimate, in the pair's frame (a rigid move of the world: depths in metres
+                # up to the pair's scale factor, which build_pair divides the query depth by as well)
+                render, alphas = self._render_map(d.tar_points, scales, self.K.unsqueeze(0), best.unsqueeze(0), self.H,
+                                                  self.W)
+                _, out.added = self.map.insert_frame(depth, rgb, self.K, est, render / d.pca_factor.reshape(()), alphas)
+            out.map_size = self.map.n_live
         if gt is not None:
             out.eT, out.eR = calculate_translation_error(est, gt), calculate_rotation_error(est, gt)
         return out

@@ -1,0 +1,108 @@
+"""A Gaussian map grown on the device: the persistent point cloud ``Localizer(mode="map")`` tracks frames against.
+
+The map is means and colours in the world, ``capacity`` preallocated rows of which the first ``n_live`` are live.  A frame
+adds the back-projection of the pixels the map does not explain yet (csrc/map.hip): pixels with a valid depth where the
+map's render at the frame's pose has alpha below ``alpha_min`` (not covered) or shows a surface more than ``depth_rho``
+behind the observed one (something stands in front).  Pixels without depth never enter.  Scales are not stored: they are
+the reference's construction (``init_gs_scales``) on the cloud that is tracked.
+
+The selection, the raster-order compaction, the back-projection and the append are two entry points and four launches;
+the host reads the two counters back once per frame.  There is no CPU path."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import _lib
+
+
+@dataclass
+class MapConfig:
+    alpha_min: float = 0.5  # a pixel the map renders with less alpha is not covered
+    depth_rho: float = 0.05  # a pixel observed more than this fraction in front of the map's depth is a new surface
+    capacity: Optional[int] = None  # rows; None: 4 * W * H
+
+
+class GaussianMap:
+    """``insert_frame`` per frame; ``points`` / ``point_colors`` are views of the live prefix (no copy)."""
+
+    def __init__(self, width: int, height: int, config: MapConfig = MapConfig(), device="cuda"):
+        self.W, self.H = int(width), int(height)
+        self.cfg = config
+        self.device = torch.device(device)
+        self.capacity = int(config.capacity) if config.capacity is not None else 4 * self.W * self.H
+        if self.capacity <= 0:
+            raise ValueError(f"map capacity {self.capacity}: at least one row")
+        self.means = torch.zeros(self.capacity, 3, device=self.device)
+        self.colors = torch.zeros(self.capacity, 3, device=self.device)
+        self.n_live = 0
+        self.full = False  # some frame's rows were dropped at the capacity
+        # float32 values of the rule, computed here once: the kernel multiplies and compares, nothing else
+        self.alpha_min = float(np.float32(config.alpha_min))
+        self.keep = float(np.float32(1.0) - np.float32(config.depth_rho))
+        self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self._ws = self._alloc_ws()
+
+    def _alloc_ws(self):
+        if self.device.type != "cuda":
+            return None
+        n = _lib.load_library().gsl_map_ws_bytes(self.W, self.H)
+        return torch.empty(n, dtype=torch.uint8, device=self.device)
+
+    @property
+    def points(self) -> Tensor:
+        return self.means[: self.n_live]
+
+    @property
+    def point_colors(self) -> Tensor:
+        return self.colors[: self.n_live]
+
+    def clear(self) -> None:
+        self.n_live, self.full = 0, False
+
+    def _launch(self, depth: Tensor, rgb: Tensor, intr: Tuple[float, float, float, float], c2w: Tensor,
+                render: Optional[Tensor], alphas: Optional[Tensor]) -> Tuple[int, int]:
+        """The two entry points on the current stream and the read-back of (selected, appended)."""
+        assert depth.is_cuda, "GaussianMap.insert_frame: the map is grown by HIP kernels, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        ws = self._ws
+        _lib.check(lib.gsl_map_select(ptr(render), ptr(alphas), ptr(depth), self.W, self.H, self.alpha_min, self.keep,
+                                      ptr(self._counters), ptr(ws), ws.numel(), st), "gsl_map_select")
+        _lib.check(lib.gsl_map_append(ptr(depth), ptr(rgb), self.W, self.H, *intr, ptr(c2w), ptr(self.means),
+                                      ptr(self.colors), self.n_live, self.capacity, ptr(self._counters), ptr(ws),
+                                      ws.numel(), st), "gsl_map_append")
+        selected, appended = self._counters.tolist()  # the frame's one synchronisation
+        return selected, appended
+
+    @torch.no_grad()
+    def insert_frame(self, depth, rgb, K, c2w, render: Optional[Tensor] = None,
+                     alphas: Optional[Tensor] = None) -> Tuple[int, int]:
+        """depth [H,W] metres, rgb [H,W,3] in 0..255, K [3,3], c2w [4,4] the frame's pose in the world; render / alphas
+        [H,W]: the map's expected depth (metres) and alpha at that pose -- both None: every pixel with a valid depth is
+        new (the first frame).  Returns (pixels selected, rows appended); they differ when the map is full."""
+        if (render is None) != (alphas is None):
+            raise ValueError("insert_frame: render and alphas come together (or neither, for the first frame)")
+
+        def image(a, shape, what):
+            a = torch.as_tensor(a, dtype=torch.float32, device=self.device)
+            if a.numel() != shape[0] * shape[1] * (shape[2] if len(shape) > 2 else 1):
+                raise ValueError(f"{what} is {tuple(a.shape)}, the map was built for {shape}")
+            return a.reshape(shape).contiguous()
+
+        hw = (self.H, self.W)
+        depth, rgb = image(depth, hw, "depth"), image(torch.as_tensor(rgb)[..., :3], hw + (3,), "rgb")
+        if render is not None:
+            render, alphas = image(render, hw, "render"), image(alphas, hw, "alphas")
+        Kc = torch.as_tensor(K, dtype=torch.float32).cpu()
+        intr = (float(Kc[0, 0]), float(Kc[1, 1]), float(Kc[0, 2]), float(Kc[1, 2]))
+        c2w = torch.as_tensor(c2w, dtype=torch.float32, device=self.device).contiguous()
+        if c2w.shape != (4, 4):
+            raise ValueError(f"c2w is {tuple(c2w.shape)}, not (4, 4)")
+        selected, appended = self._launch(depth, rgb, intr, c2w, render, alphas)
+        self.n_live += appended
+        self.full = self.full or appended < selected
+        return selected, appended

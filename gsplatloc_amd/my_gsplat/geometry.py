@@ -62,6 +62,22 @@ def compute_depth_gt(points: Tensor, rgbs: Tensor, Ks: Tensor, c2w: Tensor, heig
     return render[0, :, :, 0]
 
 
+@torch.no_grad()
+def render_depth_alpha(points: Tensor, scales: Tensor, Ks: Tensor, c2w: Tensor, height: int,
+                       width: int) -> Tuple[Tensor, Tensor]:
+    """Expected depth [H,W] and alpha [H,W] of the Gaussians the tracker puts on ``points`` [N,3] with ``scales`` [N,3]
+    (identity rotation, opacity 1), seen from ``c2w`` [1,4,4] with ``Ks`` [1,3,3]: one "ED" call.  What a map looks like
+    from a pose -- where alpha is low it does not cover the view."""
+    n, dev = points.shape[0], points.device
+    quats = torch.zeros(n, 4, device=dev)
+    quats[:, 0] = 1.0
+    render, alphas, _ = rasterization(means=points, quats=quats, scales=scales, opacities=torch.ones(n, device=dev),
+                                      colors=torch.zeros(n, 3, device=dev), viewmats=torch.linalg.inv(c2w), Ks=Ks,
+                                      width=width, height=height, far_plane=1e10, near_plane=1e-2, render_mode="ED",
+                                      rasterize_mode="classic", packed=False)
+    return render[0, :, :, 0], alphas[0, :, :, 0]
+
+
 def depth_to_points(depth: Tensor, K: Tensor, include_homogeneous: bool = False) -> Tensor:
     """Back-project a depth image [H,W] through K: pixel (u, v) on the integer grid -> z * K^-1 (u, v, 1),
     row-major [H*W, 3] (or [H*W, 4] with a trailing 1)."""

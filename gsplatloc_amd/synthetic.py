@@ -190,6 +190,49 @@ def write_replica_constant_twist(root, W, H, n, rot_deg: float = 0.4, trans: flo
     """The Replica layout of write_replica_sequence for a camera that moves by the SAME twist every frame (rot_deg about
     ``axis``, ``trans`` metres along ``direction``, both fixed in the camera frame): the sequence a constant-velocity
     hand-over predicts up to its second-order term.  Returns the n camera-to-world poses [n,4,4] (float64)."""
+    import numpy as np
+
+    poses, c2w, step = [], np.eye(4), _twist(rot_deg, trans, axis, direction)
+    for i in range(n):
+        if i:
+            c2w = c2w @ step
+        poses.append(c2w.copy())
+    return _write_replica_poses(root, W, H, poses)
+
+
+def write_replica_there_and_back(root, W, H, n_out, rot_deg: float = 0.4, trans: float = 0.01, axis=(0.3, 1.0, -0.2),
+                                 direction=(0.6, 0.1, 0.8)):
+    """The constant twist of write_replica_constant_twist for n_out steps (poses 0 .. n_out), then the SAME poses back to
+    0: 2 n_out + 1 frames whose last pose is bit for bit the first -- a camera that returns to where it started, seeing
+    on the way back only what it saw on the way out.  Returns the poses [2 n_out + 1,4,4] (float64)."""
+    import numpy as np
+
+    poses, c2w, step = [], np.eye(4), _twist(rot_deg, trans, axis, direction)
+    for i in range(n_out + 1):
+        if i:
+            c2w = c2w @ step
+        poses.append(c2w.copy())
+    return _write_replica_poses(root, W, H, poses + [p.copy() for p in poses[-2::-1]])
+
+
+def _twist(rot_deg, trans, axis, direction):
+    """4x4 step: rot_deg about ``axis``, ``trans`` metres along ``direction`` (float64)."""
+    import numpy as np
+
+    ax = np.asarray(axis, dtype=np.float64)
+    ax /= np.linalg.norm(ax)
+    th = np.radians(rot_deg)
+    Kx = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+    step = np.eye(4)
+    step[:3, :3] = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * (Kx @ Kx)
+    t = np.asarray(direction, dtype=np.float64)
+    step[:3, 3] = trans * t / np.linalg.norm(t)
+    return step
+
+
+def _write_replica_poses(root, W, H, poses):
+    """The room seen from every pose, in the Replica layout (random images, generator seeded with 11); returns the poses
+    [n,4,4] (float64)."""
     import json
 
     import numpy as np
@@ -201,23 +244,11 @@ def write_replica_constant_twist(root, W, H, n, rot_deg: float = 0.4, trans: flo
     cam = {"camera": {"w": W, "h": H, "fx": float(K[0, 0]), "fy": float(K[1, 1]), "cx": float(K[0, 2]),
                       "cy": float(K[1, 2]), "scale": 6553.5}}
     (root / "cam_params.json").write_text(json.dumps(cam))
-    ax = np.asarray(axis, dtype=np.float64)
-    ax /= np.linalg.norm(ax)
-    th = np.radians(rot_deg)
-    Kx = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
-    step = np.eye(4)
-    step[:3, :3] = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * (Kx @ Kx)
-    t = np.asarray(direction, dtype=np.float64)
-    step[:3, 3] = trans * t / np.linalg.norm(t)
     rng = np.random.default_rng(11)
-    poses, c2w = [], np.eye(4)
-    for i in range(n):
-        if i:
-            c2w = c2w @ step
+    for i, c2w in enumerate(poses):
         depth = room_depth(W, H, K, torch.from_numpy(c2w).float()).numpy()
         Image.fromarray(np.round(depth * 6553.5).astype(np.uint16)).save(d / f"depth{i:06d}.png")
         Image.fromarray(rng.integers(0, 255, (H, W, 3), dtype=np.uint8)).save(d / f"frame{i:06d}.jpg")
-        poses.append(c2w.copy())
     with open(root / "room0" / "traj.txt", "w") as f:
         for p in poses:
             f.write(" ".join(f"{v:.12f}" for v in p.reshape(-1)) + "\n")

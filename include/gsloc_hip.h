@@ -127,6 +127,32 @@ int gsl_gather_rows(const float* src, int64_t n_src, int D, const int64_t* ids, 
 int gsl_scatter_add_rows(const float* v_rows, const int64_t* ids, int64_t nnz, int D, int64_t n_dst,
                          int unique, float* v_dst, void* stream);
 
+/* ---- map growth: the pixels of a depth frame that the map does not explain are appended to it ----
+ * Images are [height,width] float32 on the device, row-major: depth (observed, metres), render_depth and alphas (the
+ * map's expected-depth render and its alpha at the frame's pose); rgb[height,width,3] in 0..255.  width * height must
+ * be below 2^31.
+ *
+ * A pixel is selected when depth is finite and > 0 and (alphas < alpha_min or depth < render_depth * keep), evaluated
+ * in float32 exactly as written (one rounded product).  render_depth == NULL and alphas == NULL together ("no render
+ * yet"): every pixel with a finite depth > 0 is selected.
+ *
+ * gsl_map_select: evaluates the rule, leaves one ballot per wave and the row offset of every workgroup in ws
+ *   (gsl_map_ws_bytes(width, height)), writes the number of selected pixels to n_new[0] and 0 to n_new[1].
+ * gsl_map_append: after gsl_map_select with the same depth, size and the same, untouched ws.  The selected pixels
+ *   (u, v), in raster order, become rows n_live, n_live + 1, ... of means[capacity,3] and colors[capacity,3]:
+ *   mean = R p + t with p = ((u - cx) / fx * depth, (v - cy) / fy * depth, depth) and [R | t] the rows of c2w[16]
+ *   (camera-to-world, row-major, on the device), colour = rgb / 255; float32, no fused operations.  Rows at or beyond
+ *   capacity are dropped -- nothing is written there -- and the number of rows written goes to n_new[1].
+ * Both return GSL_ERR_BAD_ARG before any launch for a NULL array, a non-positive size, n_live outside [0, capacity],
+ * only one of render_depth / alphas, or a workspace smaller than gsl_map_ws_bytes. */
+size_t gsl_map_ws_bytes(int width, int height);
+int gsl_map_select(const float* render_depth, const float* alphas, const float* depth, int width,
+                   int height, float alpha_min, float keep, int32_t* n_new, void* ws, size_t ws_bytes,
+                   void* stream);
+int gsl_map_append(const float* depth, const float* rgb, int width, int height, float fx, float fy,
+                   float cx, float cy, const float* c2w, float* means, float* colors, int64_t n_live,
+                   int64_t capacity, int32_t* n_new, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- spherical harmonics: gsplat.spherical_harmonics fwd/bwd (IDX:14306, IDX:14297) ----
  * dirs[M,3], coeffs[M,K,3] with K >= (degree+1)^2, masks[M] (uint8, may be NULL).
  * degree 0..3.  v_dirs may be NULL. */

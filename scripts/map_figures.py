@@ -1,0 +1,90 @@
+"""640x480, 20 synthetic frames: sequential localisation frame to frame beside frame to map, alternating in one process,
+on the random walk, the constant twist and the there-and-back sequence (NOTES.md, "Frame-to-map localisation").  One
+JSON line per configuration (the second pass of each: every buffer warm), then the cost of a frame's map update on the
+there-and-back sequence: wall time, synchronised, of the extra render, of insert_frame (two entry points and the
+read-back) and of building a tracker, per frame, beside the frame's total -- its return half adds nothing, so the
+tracker is kept there.
+
+    python scripts/map_figures.py [--frames 20] [--size 640 480] [--only there_and_back] [--no-cost]"""
+import argparse
+import json
+import os
+import pathlib
+import sys
+import tempfile
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from gsplatloc_amd.data import Parser  # noqa: E402
+from gsplatloc_amd.eval import evaluate_room  # noqa: E402
+from gsplatloc_amd.localizer import Localizer  # noqa: E402
+from gsplatloc_amd.my_gsplat import TrackerConfig  # noqa: E402
+from gsplatloc_amd.synthetic import (write_replica_constant_twist, write_replica_sequence,  # noqa: E402
+                                     write_replica_there_and_back)
+
+
+def timed(fn, sink):
+    def wrapped(*a, **kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn(*a, **kw)
+        torch.cuda.synchronize()
+        sink.append(time.perf_counter() - t0)
+        return out
+    return wrapped
+
+
+def update_cost(root, W, H):
+    parser = Parser("Replica", "room0", normalize=True, input_folder=str(root))
+    for _ in range(2):  # the second pass has every buffer warm
+        depth, rgb, pose = parser.frame(0)
+        loc = Localizer(parser.K, W, H, TrackerConfig(max_steps=2000), mode="map")
+        build, render, insert, frames, added = [], [], [], [], []
+        loc._factory, loc._render_map = timed(loc._factory, build), timed(loc._render_map, render)
+        loc.reset(depth, rgb, pose)
+        loc.map.insert_frame = timed(loc.map.insert_frame, insert)
+        for i in range(1, len(parser) + 1):
+            depth, rgb, pose = parser.frame(i)
+            n_built = len(build)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = loc.track(depth, rgb, gt_c2w=pose)
+            torch.cuda.synchronize()
+            frames.append(time.perf_counter() - t0)
+            added.append(r.added)
+            if len(build) == n_built:
+                build.append(0.0)  # the tracker was kept
+    ms = lambda xs: [round(1e3 * x, 2) for x in xs]  # noqa: E731
+    print("MAP_COST " + json.dumps({"frame_ms": ms(frames), "tracker_build_ms": ms(build), "render_ms": ms(render),
+                                    "insert_ms": ms(insert), "added": added, "map_gaussians": loc.map.n_live}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--size", type=int, nargs=2, default=[640, 480])
+    ap.add_argument("--only", default=None)
+    ap.add_argument("--no-cost", action="store_true")
+    a = ap.parse_args()
+    (W, H), n = a.size, a.frames
+    writers = (("random_walk", lambda root: write_replica_sequence(root, W, H, n)),
+               ("constant_twist", lambda root: write_replica_constant_twist(root, W, H, n)),
+               ("there_and_back", lambda root: write_replica_there_and_back(root, W, H, n // 2)))
+    for name, writer in writers:
+        if a.only not in (None, name):
+            continue
+        root = pathlib.Path(tempfile.mkdtemp())
+        writer(root)
+        for _ in range(2):  # frame mode and map mode alternate; the second pass of each is reported
+            rows = [evaluate_room(Parser("Replica", "room0", normalize=True, input_folder=str(root)), 2000, None,
+                                  sequential=True, map_mode=map_mode) for map_mode in (False, True)]
+        for map_mode, r in zip((False, True), rows):
+            print("MAP_FIG " + json.dumps({"sequence": name, "map": map_mode, **r}), flush=True)
+        if name == "there_and_back" and not a.no_cost:
+            update_cost(root, W, H)
+
+
+if __name__ == "__main__":
+    main()
