@@ -35,17 +35,20 @@ def rmse(values: List[float]) -> float:
 def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[int] = 1998, verbose: bool = False,
                   profile: bool = False, rgb_lambda: float = 0.0, ssim_lambda: float = 0.5, sequential: bool = False,
                   motion: str = "constant_velocity", map_mode: bool = False,
-                  map_capacity: Optional[int] = None) -> Dict:
+                  map_capacity: Optional[int] = None, map_view_guard: Optional[float] = None) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
     capture + replays + polls) -- `phase_seconds` in the result.  rgb_lambda != 0 switches the photometric term on
     (TrackerConfig.rgb_lambda / ssim_lambda): the tracker then renders "RGB+ED" and is given the frame's image.
     sequential=True: evaluate_sequential (only frame 0's ground-truth pose is used; ``motion`` is its hand-over;
-    ``map_mode``: frames are tracked against a map grown on the device, of ``map_capacity`` rows at most)."""
+    ``map_mode``: frames are tracked against a map grown on the device, of ``map_capacity`` rows at most;
+    ``map_view_guard``: against the part of it in view, the image widened by that many pixels)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
+    if map_view_guard is not None and not map_mode:
+        raise ValueError("map_view_guard belongs to the map mode (map_mode=True)")
     if sequential:
-        return evaluate_sequential(parser, cfg, max_frames, verbose, motion, map_mode, map_capacity)
+        return evaluate_sequential(parser, cfg, max_frames, verbose, motion, map_mode, map_capacity, map_view_guard)
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -106,20 +109,23 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
 
 def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional[int] = 1998, verbose: bool = False,
                         motion: str = "constant_velocity", map_mode: bool = False,
-                        map_capacity: Optional[int] = None) -> Dict:
+                        map_capacity: Optional[int] = None, map_view_guard: Optional[float] = None) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
-    map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame and
-    map_full (some frame's points were dropped at map_capacity)."""
+    map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
+    tracked_per_frame (rows the tracker saw) and map_full (some frame's points were dropped at map_capacity).
+    map_view_guard: MapConfig.view_guard_px; the report gains view_violations_per_frame."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
-    extra = dict(mode="map", map_config=MapConfig(capacity=map_capacity)) if map_mode else {}
+    extra = {}
+    if map_mode:
+        extra = dict(mode="map", map_config=MapConfig(capacity=map_capacity, view_guard_px=map_view_guard))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
     eTs, eRs, steps, lost, path, last_t = [], [], [], 0, 0.0, pose[:3, 3]
-    added = []
+    added, tracked, violations = [], [], []
     for i in range(1, n + 1):
         depth, rgb, pose = parser.frame(i)
         r = loc.track(depth, rgb, gt_c2w=pose)
@@ -128,6 +134,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
         steps.append(r.steps)
         lost += int(r.lost)
         added.append(r.added)
+        tracked.append(r.tracked)
+        violations.append(r.view_violations)
         path += float(torch.norm(pose[:3, 3] - last_t))
         last_t = pose[:3, 3]
         if verbose:
@@ -138,7 +146,10 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             "final_eT": eTs[-1] if eTs else float("nan"), "final_eR": eRs[-1] if eRs else float("nan"),
             "path_length": path, "frames": n, "lost_frames": lost, "mean_steps": sum(steps) / max(len(steps), 1),
             "seconds": dt, "frames_per_s": n / dt if dt > 0 else None,
-            **({"map_gaussians": loc.map.n_live, "added_per_frame": added, "map_full": loc.map.full} if map_mode else {})}
+            **({"map_gaussians": loc.map.n_live, "added_per_frame": added, "tracked_per_frame": tracked,
+                "map_full": loc.map.full} if map_mode else {}),
+            **({"view_guard_px": map_view_guard, "view_violations_per_frame": violations}
+               if map_view_guard is not None else {})}
 
 
 def main(argv=None):
@@ -163,15 +174,20 @@ def main(argv=None):
                     help="--sequential: track every frame against a Gaussian map grown on the device (frame to map) "
                          "instead of the previous frame alone")
     ap.add_argument("--map-capacity", type=int, default=None, help="--map: rows of the map (default 4 * W * H)")
+    ap.add_argument("--map-view-guard", type=float, default=None, metavar="PX",
+                    help="--map: track every frame against the map's points in view from its start pose, the image "
+                         "widened by PX pixels on every side (default: against all of them)")
     a = ap.parse_args(argv)
     if a.map and not a.sequential:
         ap.error("--map needs --sequential")
+    if a.map_view_guard is not None and not a.map:
+        ap.error("--map-view-guard needs --map")
     out = {}
     for room in a.rooms:
         parser = Parser(a.dataset, room, normalize=not a.no_normalize, input_folder=a.root)
         r = evaluate_room(parser, a.num_iters, a.max_frames, a.verbose, rgb_lambda=a.rgb_lambda,
                           ssim_lambda=a.ssim_lambda, sequential=a.sequential, motion=a.motion, map_mode=a.map,
-                          map_capacity=a.map_capacity)
+                          map_capacity=a.map_capacity, map_view_guard=a.map_view_guard)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

@@ -18,6 +18,9 @@ and its calibration pass), so the hand-over is host code.
 
 ``mode="map"`` replaces step 1: the Gaussians are the live points of a persistent ``GaussianMap`` (mapping.py), already in
 the world, which every tracked frame extends by the pixels the map does not explain.  Steps 2 - 6 are unchanged.
+With ``MapConfig.view_guard_px`` they are the live points in view from the start pose of step 3, the image widened by
+that guard band; after the frame the band is checked against the estimate (``GaussianMap.view_violations``), and where
+it did not hold the render the new pixels are judged against is made from a selection at the estimate.
 """
 from __future__ import annotations
 
@@ -65,6 +68,8 @@ class LocalizeResult:
     eR: Optional[float] = None
     map_size: Optional[int] = None  # mode="map": live map points after this frame, and how many it added
     added: Optional[int] = None
+    tracked: Optional[int] = None  # mode="map": rows the tracker saw (all live rows, or those in the guarded view)
+    view_violations: Optional[int] = None  # view_guard_px: rows in reach of the view from c2w that were not tracked
 
 
 def _default_factory(N, W, H, config, device, render_mode):
@@ -85,8 +90,11 @@ class Localizer:
     is not lost the map is rendered once at the frame's estimate -- in the pair's frame, with the scales the tracker just
     used, by ``map_renderer(points, scales, Ks, c2w, height, width) -> (depth, alpha)`` (default: render_depth_alpha; the
     CPU tests use stand-ins for both) -- and the pixels it does not explain are appended (mapping.py).  The tracker is
-    rebuilt when the live count changes.  Everything else -- normalisation, the re-rendered query depth, the scales, the
-    hand-over, ``best_c2w`` -- is the frame mode's."""
+    rebuilt when the live count changes.  ``map_config.view_guard_px``: the Gaussians of a frame are the live points in
+    view from its start pose only (``GaussianMap.select_view``; ``LocalizeResult.tracked``), the tracker is keyed on
+    their count, and ``LocalizeResult.view_violations`` says how many rows in reach of the view from the estimate they
+    left out (above 0: the render is made from a selection at the estimate).  Everything else -- normalisation, the
+    re-rendered query depth, the scales, the hand-over, ``best_c2w`` -- is the frame mode's."""
 
     def __init__(self, K: Tensor, width: int, height: int, config: TrackerConfig = TrackerConfig(),
                  normalize: bool = True, motion: str = "constant_velocity", device="cuda", render_mode: str = "ED",
@@ -112,9 +120,12 @@ class Localizer:
         self._poses: List[Tensor] = []
         self.map_mode = mode == "map"
         self.map = None
+        self._view_guard = None  # MapConfig.view_guard_px
         if self.map_mode:
             make = map_factory if map_factory is not None else GaussianMap
-            self.map = make(self.W, self.H, map_config if map_config is not None else MapConfig(), self.device)
+            map_config = map_config if map_config is not None else MapConfig()
+            self.map = make(self.W, self.H, map_config, self.device)
+            self._view_guard = map_config.view_guard_px
         self._render_map = map_renderer if map_renderer is not None else render_depth_alpha
 
     def _frame(self, depth, rgb):
@@ -128,6 +139,25 @@ class Localizer:
             rgb = torch.full((self.H, self.W, 3), 127.5, device=self.device)  # colours are not rendered in "ED"
         rgb = torch.as_tensor(rgb, dtype=torch.float32, device=self.device)[..., :3]
         return depth, rgb, depth_to_points(depth, self.K), (rgb / 255.0).reshape(-1, 3)
+
+    def _map_pair(self, at: Tensor, frame):
+        """The pair of a new frame (its clouds, images, placing and reference pose) and the map: all live points, or --
+        ``view_guard_px`` -- those in view from the world pose ``at``, the image widened by the guard band (an empty
+        selection: all of them)."""
+        t_pts, t_col = self.map.points, self.map.point_colors
+        if self._view_guard is not None:
+            v_pts, v_col, _, n = self.map.select_view(self.K, at, self._view_guard, self.cfg.gs.near_plane,
+                                                      self.cfg.gs.far_plane)
+            if n > 0:
+                t_pts, t_col = v_pts, v_col
+        pts, col, depth, rgb, placed, ref = frame
+        return build_pair(t_pts, t_col, pts, col, depth, rgb, placed, ref, self.K, self.normalize, t_placed=True)
+
+    def _map_render(self, d, scales: Tensor, c2w_n: Tensor):
+        """What the pair's cloud shows from the pose ``c2w_n`` in the pair's frame (a rigid move of the world: depths in
+        metres up to the pair's scale factor, which build_pair divides the query depth by as well)."""
+        render, alphas = self._render_map(d.tar_points, scales, self.K.unsqueeze(0), c2w_n.unsqueeze(0), self.H, self.W)
+        return render / d.pca_factor.reshape(()), alphas
 
     @property
     def trajectory(self) -> Tensor:
@@ -159,8 +189,8 @@ class Localizer:
         if self.map_mode:
             if self.map.n_live == 0:
                 raise RuntimeError("Localizer.track: the map is empty (the first frame had no valid depth)")
-            d = build_pair(self.map.points, self.map.point_colors, pts, col, depth, rgb, placed,
-                           gt if gt is not None else init, self.K, self.normalize, t_placed=True)
+            frame = (pts, col, depth, rgb, placed, gt if gt is not None else init)
+            d = self._map_pair(init, frame)
         else:
             d = build_pair(self._prev[0], self._prev[1], pts, col, depth, rgb, placed, gt if gt is not None else init,
                            self.K, self.normalize)
@@ -179,13 +209,21 @@ class Localizer:
         out = LocalizeResult(c2w=est, init_c2w=init, steps=res.steps, best_step=res.best_step, best_loss=res.best_loss,
                              lost=res.best_step == -1)
         if self.map_mode:
-            out.added = 0
+            out.added, out.tracked = 0, N
             if not out.lost:  # a lost frame's pose is a guess: it adds nothing
-                # what the map shows from the estimate, in the pair's frame (a rigid move of the world: depths in metres
-                # up to the pair's scale factor, which build_pair divides the query depth by as well)
-                render, alphas = self._render_map(d.tar_points, scales, self.K.unsqueeze(0), best.unsqueeze(0), self.H,
-                                                  self.W)
-                _, out.added = self.map.insert_frame(depth, rgb, self.K, est, render / d.pca_factor.reshape(()), alphas)
+                at = best
+                if self._view_guard is not None:
+                    # the band is checked against the estimate, not assumed: rows that reach into the view from there
+                    # and were not tracked would render as an empty border, and insert_frame would add them a second
+                    # time.  Then the insertion render is made from a selection at the estimate (no second tracking)
+                    out.view_violations = self.map.view_violations(self.K, est, self.cfg.gs.near_plane,
+                                                                   self.cfg.gs.far_plane)
+                    if out.view_violations > 0:
+                        d = self._map_pair(est, frame)
+                        scales = init_gs_scales(d.tar_points)
+                        at = transform_cameras(d.norm_T, est.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else est
+                render, alphas = self._map_render(d, scales, at)
+                _, out.added = self.map.insert_frame(depth, rgb, self.K, est, render, alphas)
             out.map_size = self.map.n_live
         if gt is not None:
             out.eT, out.eR = calculate_translation_error(est, gt), calculate_rotation_error(est, gt)

@@ -7,7 +7,12 @@ behind the observed one (something stands in front).  Pixels without depth never
 the reference's construction (``init_gs_scales``) on the cloud that is tracked.
 
 The selection, the raster-order compaction, the back-projection and the append are two entry points and four launches;
-the host reads the two counters back once per frame.  There is no CPU path."""
+the host reads the two counters back once per frame.  There is no CPU path.
+
+The local map (``MapConfig.view_guard_px``, csrc/map_view.hip): ``select_view`` compacts the live rows in view from a
+pose, the image widened by a guard band, in map order into working buffers -- what ``Localizer(mode="map")`` then
+tracks instead of every live row -- and ``view_violations`` counts the rows in reach of the view from another pose that
+this selection left out.  Two more entry points; each of the two calls reads its counters back once."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -25,6 +30,19 @@ class MapConfig:
     alpha_min: float = 0.5  # a pixel the map renders with less alpha is not covered
     depth_rho: float = 0.05  # a pixel observed more than this fraction in front of the map's depth is a new surface
     capacity: Optional[int] = None  # rows; None: 4 * W * H
+    # Localizer(mode="map"): track against the rows in view from the start pose, the image widened by this many pixels
+    # on every side (None: against every live row)
+    view_guard_px: Optional[float] = None
+    # ... and afterwards count the rows in view from the ESTIMATE, the image widened by this, that the tracked set left
+    # out.  A 3 sigma footprint of these clouds is about 7 px wide: a centre up to about 4 px outside still paints inside
+    view_reach_px: float = 4.0
+
+    def __post_init__(self):
+        if not self.view_reach_px >= 0.0:
+            raise ValueError(f"view_reach_px {self.view_reach_px}: not negative")
+        if self.view_guard_px is not None and not self.view_guard_px >= self.view_reach_px:
+            raise ValueError(f"view_guard_px {self.view_guard_px} is below view_reach_px {self.view_reach_px}: the band "
+                             "that is tracked must hold the band that is checked")
 
 
 class GaussianMap:
@@ -46,6 +64,9 @@ class GaussianMap:
         self.keep = float(np.float32(1.0) - np.float32(config.depth_rho))
         self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)
         self._ws = self._alloc_ws()
+        # select_view: capacity-sized working buffers and two workspaces, allocated on first use
+        self._view = None
+        self._view_rows = -1  # n_live at the last select_view: what its ballots describe
 
     def _alloc_ws(self):
         if self.device.type != "cuda":
@@ -63,6 +84,7 @@ class GaussianMap:
 
     def clear(self) -> None:
         self.n_live, self.full = 0, False
+        self._view_rows = -1
 
     def _launch(self, depth: Tensor, rgb: Tensor, intr: Tuple[float, float, float, float], c2w: Tensor,
                 render: Optional[Tensor], alphas: Optional[Tensor]) -> Tuple[int, int]:
@@ -106,3 +128,67 @@ class GaussianMap:
         self.n_live += appended
         self.full = self.full or appended < selected
         return selected, appended
+
+    # ---- the local map: the live rows in view from a pose (csrc/map_view.hip) ---------------------------------------
+    def _view_buffers(self):
+        if self._view is None:
+            cap, dev, ws = self.capacity, self.device, []
+            if dev.type == "cuda":
+                n = _lib.load_library().gsl_map_view_ws_bytes(cap)
+                ws = [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self._view = dict(means=torch.zeros(cap, 3, device=dev), colors=torch.zeros(cap, 3, device=dev),
+                              ids=torch.zeros(cap, dtype=torch.int32, device=dev),
+                              counters=torch.zeros(3, dtype=torch.int32, device=dev), ws=ws)
+        return self._view
+
+    def _view_launch(self, intr: Tuple[float, float, float, float], w2c: Tensor, guard_px: float, near: float,
+                     far: float, check: bool) -> Tuple[int, int, int]:
+        """check False: select the live rows into the first workspace and gather them into the working buffers; True:
+        select into the second workspace against the ballots of the first, no gather.  The read-back of the counters
+        (in view, in view and not in the first workspace's selection, gathered)."""
+        assert self.means.is_cuda, "GaussianMap.select_view: the rows are selected by HIP kernels, no CPU path"
+        lib, st, ptr, v = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._view_buffers()
+        ws, prev = (v["ws"][1], v["ws"][0]) if check else (v["ws"][0], None)
+        _lib.check(lib.gsl_map_view_select(ptr(self.means), self.n_live, ptr(w2c), *intr, self.W, self.H, guard_px, near,
+                                           far, ptr(prev), ptr(v["counters"]), ptr(ws), ws.numel(), st),
+                   "gsl_map_view_select")
+        if not check:
+            _lib.check(lib.gsl_map_view_gather(ptr(self.means), ptr(self.colors), self.n_live, ptr(v["means"]),
+                                               ptr(v["colors"]), ptr(v["ids"]), self.capacity, ptr(v["counters"]),
+                                               ptr(ws), ws.numel(), st), "gsl_map_view_gather")
+        in_view, fresh, gathered = v["counters"].tolist()  # the call's one synchronisation
+        return in_view, fresh, gathered
+
+    def _view_args(self, K, c2w):
+        Kc = torch.as_tensor(K, dtype=torch.float32).cpu()
+        intr = (float(Kc[0, 0]), float(Kc[1, 1]), float(Kc[0, 2]), float(Kc[1, 2]))
+        c2w = torch.as_tensor(c2w).detach().cpu().double().numpy()
+        if c2w.shape != (4, 4):
+            raise ValueError(f"c2w is {c2w.shape}, not (4, 4)")
+        # the float64 inverse, rounded to float32 here: the kernel multiplies and adds, nothing else
+        w2c = torch.from_numpy(np.linalg.inv(c2w).astype(np.float32)).to(self.device).contiguous()
+        return intr, w2c
+
+    @torch.no_grad()
+    def select_view(self, K, c2w, guard_px: float, near: float, far: float) -> Tuple[Tensor, Tensor, Tensor, int]:
+        """The live rows in view from the pose c2w [4,4] -- inside the image widened by guard_px on every side, between
+        the depth planes (the rule: include/gsloc_hip.h) -- in map order.  Returns (points [n,3], colors [n,3],
+        ids [n] int32, n): views of the prefix of capacity-sized working buffers that the next call overwrites."""
+        v = self._view_buffers()
+        n = 0
+        if self.n_live > 0:
+            intr, w2c = self._view_args(K, c2w)
+            n = self._view_launch(intr, w2c, float(guard_px), float(near), float(far), False)[2]
+        self._view_rows = self.n_live
+        return v["means"][:n], v["colors"][:n], v["ids"][:n], n
+
+    @torch.no_grad()
+    def view_violations(self, K, c2w, near: float, far: float) -> int:
+        """How many live rows are in view from c2w, the image widened by ``view_reach_px``, that the last select_view
+        left out: 0 says that selection covers the view from c2w."""
+        if self._view_rows != self.n_live:
+            raise RuntimeError("view_violations: no select_view of the rows that are live now")
+        if self.n_live == 0:
+            return 0
+        intr, w2c = self._view_args(K, c2w)
+        return self._view_launch(intr, w2c, float(self.cfg.view_reach_px), float(near), float(far), True)[1]

@@ -189,7 +189,9 @@ def write_replica_constant_twist(root, W, H, n, rot_deg: float = 0.4, trans: flo
                                  direction=(0.6, 0.1, 0.8)):
     """The Replica layout of write_replica_sequence for a camera that moves by the SAME twist every frame (rot_deg about
     ``axis``, ``trans`` metres along ``direction``, both fixed in the camera frame): the sequence a constant-velocity
-    hand-over predicts up to its second-order term.  Returns the n camera-to-world poses [n,4,4] (float64)."""
+    hand-over predicts up to its second-order term.  With more frames and a larger angle it is the sweep of a camera that
+    keeps turning until the map has outgrown the view (1 degree x 16 frames at 160x120 in the tests of the local map, 2
+    degrees x 24 at 640x480 in scripts/map_figures.py).  Returns the n camera-to-world poses [n,4,4] (float64)."""
     import numpy as np
 
     poses, c2w, step = [], np.eye(4), _twist(rot_deg, trans, axis, direction)

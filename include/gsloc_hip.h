@@ -153,6 +153,33 @@ int gsl_map_append(const float* depth, const float* rgb, int width, int height, 
                    float cx, float cy, const float* c2w, float* means, float* colors, int64_t n_live,
                    int64_t capacity, int32_t* n_new, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- local map: the rows of the map that are in view from a pose, compacted in map order (csrc/map_view.hip) ----
+ * Row i of means[n_rows,3] is IN VIEW when, with w2c[16] (world to camera, row-major, on the device),
+ *   x = ((w0 px + w1 py) + w2 pz) + w3, and y, z likewise from rows 1 and 2 of w2c;  z > near_plane and z < far_plane;
+ *   u = fx x / z + cx and v = fy y / z + cy satisfy -guard_px <= u <= (width - 1) + guard_px and
+ *   -guard_px <= v <= (height - 1) + guard_px;
+ * float32, evaluated exactly as written (no fused operation, correctly rounded division, the two upper limits one
+ * rounded sum each), comparisons false for a NaN.  counters is int32[3].  n_rows must be below 2^31.
+ *
+ * gsl_map_view_select: evaluates the rule, leaves one ballot per wave and the row offset of every workgroup in ws
+ *   (gsl_map_view_ws_bytes(n_rows)); counters[0] = rows in view, counters[1] = rows in view whose bit is CLEAR in the
+ *   ballots of prev_ws -- a workspace an earlier call filled for the same n_rows, only read, not ws -- or 0 when
+ *   prev_ws is NULL; counters[2] = 0.
+ * gsl_map_view_gather: after gsl_map_view_select on the same rows and the same, untouched ws.  The selected rows, in
+ *   ascending row index, become rows 0, 1, ... of out_means / out_colors (bit copies of means / colors [n_rows,3]);
+ *   their indices go to out_ids (may be NULL).  Rows at or beyond out_capacity are dropped -- nothing is written
+ *   there -- and the number of rows written goes to counters[2].
+ * Both return GSL_ERR_BAD_ARG before any launch for a NULL array, n_rows <= 0 or >= 2^31, a non-positive image size,
+ * fx or fy not non-zero, guard_px negative or NaN, near_plane >= far_plane, prev_ws == ws, out_capacity < 0; and
+ * GSL_ERR_WORKSPACE for a workspace smaller than gsl_map_view_ws_bytes. */
+size_t gsl_map_view_ws_bytes(int64_t n_rows);
+int gsl_map_view_select(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx,
+                        float cy, int width, int height, float guard_px, float near_plane, float far_plane,
+                        const void* prev_ws, int32_t* counters, void* ws, size_t ws_bytes, void* stream);
+int gsl_map_view_gather(const float* means, const float* colors, int64_t n_rows, float* out_means,
+                        float* out_colors, int32_t* out_ids, int64_t out_capacity, int32_t* counters, void* ws,
+                        size_t ws_bytes, void* stream);
+
 /* ---- spherical harmonics: gsplat.spherical_harmonics fwd/bwd (IDX:14306, IDX:14297) ----
  * dirs[M,3], coeffs[M,K,3] with K >= (degree+1)^2, masks[M] (uint8, may be NULL).
  * degree 0..3.  v_dirs may be NULL. */

@@ -3,9 +3,11 @@ on the random walk, the constant twist and the there-and-back sequence (NOTES.md
 JSON line per configuration (the second pass of each: every buffer warm), then the cost of a frame's map update on the
 there-and-back sequence: wall time, synchronised, of the extra render, of insert_frame (two entry points and the
 read-back) and of building a tracker, per frame, beside the frame's total -- its return half adds nothing, so the
-tracker is kept there.
+tracker is kept there.  The sweep row ("Local map" in NOTES.md): a camera that keeps turning, map mode against the
+whole map beside map mode against the part in view, and the host cost of the selection and the check.
 
-    python scripts/map_figures.py [--frames 20] [--size 640 480] [--only there_and_back] [--no-cost]"""
+    python scripts/map_figures.py [--frames 20] [--size 640 480] [--only there_and_back | sweep] [--no-cost]
+                                  [--sweep DEG FRAMES GUARD_PX]"""
 import argparse
 import json
 import os
@@ -20,6 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gsplatloc_amd.data import Parser  # noqa: E402
 from gsplatloc_amd.eval import evaluate_room  # noqa: E402
 from gsplatloc_amd.localizer import Localizer  # noqa: E402
+from gsplatloc_amd.mapping import MapConfig  # noqa: E402
 from gsplatloc_amd.my_gsplat import TrackerConfig  # noqa: E402
 from gsplatloc_amd.synthetic import (write_replica_constant_twist, write_replica_sequence,  # noqa: E402
                                      write_replica_there_and_back)
@@ -61,14 +64,52 @@ def update_cost(root, W, H):
                                     "insert_ms": ms(insert), "added": added, "map_gaussians": loc.map.n_live}), flush=True)
 
 
+def sweep(W, H, n, deg, guard, cost=True):
+    """A camera that keeps turning (the constant twist, ``deg`` degrees and 1 cm per frame, ``n`` frames): the map
+    outgrows the view.  Map mode against the whole map beside map mode against the part in view (MapConfig.view_guard_px),
+    alternating in one process, the second pass of each reported; then the per-frame host cost of the selection and of
+    the check (wall time, synchronised on both sides, read-backs included) in a pass of its own."""
+    root = pathlib.Path(tempfile.mkdtemp())
+    write_replica_constant_twist(root, W, H, n, rot_deg=deg, trans=0.01)
+    for _ in range(2):
+        rows = [evaluate_room(Parser("Replica", "room0", normalize=True, input_folder=str(root)), 2000, None,
+                              sequential=True, map_mode=True, map_view_guard=g) for g in (None, guard)]
+    for g, r in zip((None, guard), rows):
+        print("MAP_FIG " + json.dumps({"sequence": f"sweep {deg} deg x {n}", "map": True, "view_guard": g, **r}),
+              flush=True)
+    if not cost:
+        return
+    parser = Parser("Replica", "room0", normalize=True, input_folder=str(root))
+    depth, rgb, pose = parser.frame(0)
+    loc = Localizer(parser.K, W, H, TrackerConfig(max_steps=2000), mode="map", map_config=MapConfig(view_guard_px=guard))
+    select, check, frames, tracked = [], [], [], []
+    loc.map.select_view, loc.map.view_violations = timed(loc.map.select_view, select), timed(loc.map.view_violations, check)
+    loc.reset(depth, rgb, pose)
+    for i in range(1, len(parser) + 1):
+        depth, rgb, pose = parser.frame(i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = loc.track(depth, rgb, gt_c2w=pose)
+        torch.cuda.synchronize()
+        frames.append(time.perf_counter() - t0)
+        tracked.append(r.tracked)
+    ms = lambda xs: [round(1e3 * x, 3) for x in xs]  # noqa: E731
+    print("VIEW_COST " + json.dumps({"frame_ms": ms(frames), "select_view_ms": ms(select), "view_violations_ms": ms(check),
+                                     "tracked": tracked, "map_gaussians": loc.map.n_live}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--size", type=int, nargs=2, default=[640, 480])
     ap.add_argument("--only", default=None)
     ap.add_argument("--no-cost", action="store_true")
+    ap.add_argument("--sweep", type=float, nargs=3, default=[2.0, 24, 8.0], metavar=("DEG", "FRAMES", "GUARD_PX"),
+                    help="the sweep row (--only sweep): degrees per frame, frames, view_guard_px")
     a = ap.parse_args()
     (W, H), n = a.size, a.frames
+    if a.only in (None, "sweep"):
+        sweep(W, H, int(a.sweep[1]), a.sweep[0], a.sweep[2], cost=not a.no_cost)
     writers = (("random_walk", lambda root: write_replica_sequence(root, W, H, n)),
                ("constant_twist", lambda root: write_replica_constant_twist(root, W, H, n)),
                ("there_and_back", lambda root: write_replica_there_and_back(root, W, H, n // 2)))
