@@ -11,8 +11,9 @@ struct LongWs;  // long_dev.h
 // misc.hip: zero n dwords with a kernel of the library (never hipMemsetAsync: see the note there)
 int zero_u32(void* p, size_t n_dwords, hipStream_t st);
 
-// project_packed.hip: launch of k_packed_scan, the single-workgroup exclusive scan of nb workgroup counts -> bases[nb],
-// total -> total[0] (any nb: a thread owns a contiguous chunk); shared with map.hip; the caller checks the launch
+// compact.hip: launch of k_count_scan, the single-workgroup exclusive scan of nb workgroup counts -> bases[nb],
+// total -> total[0] (any nb: a thread owns a contiguous chunk), between the two passes of an ordered compaction
+// (compact_dev.h); the caller checks the launch
 void launch_count_scan(hipStream_t st, const uint32_t* counts, int nb, uint32_t* bases, int32_t* total);
 
 // binning.hip: the launches of two-pass binning that the staged API and the fused pipeline share (the caller checks the

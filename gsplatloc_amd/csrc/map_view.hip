@@ -9,35 +9,28 @@
 // that are false for a NaN: on given inputs the rule has no rounding freedom and the numpy mirror of the tests selects
 // the same rows.  The two upper limits are float32 sums taken on the host.
 //
-// Order-preserving compaction with the structure of map.hip, for the reason written there (no atomics, no workgroup
-// waits for another one, the order is the map's in every run).  One row per thread, 256-thread workgroups:
-//   k_map_view_select  evaluates the rule; one 64-bit ballot per wave, one count per workgroup -- and, given the ballots
-//                      an earlier call left for the same rows (prev), a second count per workgroup: the rows in view
-//                      now whose bit was clear then;
-//   launch_count_scan  (project_packed.hip) exclusive scan of the workgroup counts, total -> counters[0]; a second one
-//                      over the second counts, total -> counters[1] (its bases go to a scratch column of ws);
-//   k_map_view_gather  the lanes whose ballot bit is set copy their mean, colour and index to workgroup base + selected
-//                      lanes of the earlier waves + mbcnt; rows at or beyond out_capacity are dropped, the number
-//                      stored -> counters[2].
+// Order-preserving compaction (compact_dev.h), one row per thread; the order is the map's in every run:
+//   k_map_view_select  evaluates the rule and records it -- and, given the ballots an earlier call left for the same
+//                      rows (prev), a second count per workgroup: the rows in view now whose bit was clear then;
+//   launch_count_scan  over the counts, total -> counters[0]; a second one over the second counts, total ->
+//                      counters[1] (the counts and their bases are the two extra columns of ws; the bases are scratch);
+//   k_map_view_gather  the lanes whose ballot bit is set copy their mean, colour and index to their position; rows at
+//                      or beyond out_capacity are dropped, the number stored -> counters[2].
 // Memory-streaming: 12 B read per row in the first pass, 24 B read and 24 - 28 B written per selected row in the second.
 // The 12-byte rows do not line up with lanes: a lane reads its row with one global_load_dwordx3, a wave's 768 contiguous
 // bytes are six 128-byte lines that this one instruction touches once each ("Map growth": what the ISA
 // shows and why the rows do not go through LDS).
+#include "compact_dev.h"
 #include "gsloc_internal.h"
 
 namespace gsl {
 
-__global__ __launch_bounds__(256) void k_map_view_select(const float* __restrict__ means, long long n_rows,
-                                                         const float* __restrict__ w2c, float fx, float fy, float cx,
-                                                         float cy, float guard_lo, float u_hi, float v_hi,
-                                                         float near_plane, float far_plane,
-                                                         const uint64_t* __restrict__ prev_ballots,
-                                                         uint64_t* __restrict__ ballots,
-                                                         uint32_t* __restrict__ block_counts,
-                                                         uint32_t* __restrict__ block_fresh,
-                                                         int32_t* __restrict__ counters) {
-  const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+__global__ __launch_bounds__(COMPACT_THREADS) void k_map_view_select(
+    const float* __restrict__ means, long long n_rows, const float* __restrict__ w2c, float fx, float fy, float cx,
+    float cy, float guard_lo, float u_hi, float v_hi, float near_plane, float far_plane,
+    const uint64_t* __restrict__ prev_ballots, uint64_t* __restrict__ ballots, uint32_t* __restrict__ block_counts,
+    uint32_t* __restrict__ block_fresh, int32_t* __restrict__ counters) {
+  const long long g = (long long)blockIdx.x * COMPACT_THREADS + threadIdx.x;
   if (g == 0) {  // the scans that follow in the stream write [0] and, with prev, [1]
     if (prev_ballots == nullptr) counters[1] = 0;
     counters[2] = 0;  // nothing gathered yet
@@ -52,40 +45,26 @@ __global__ __launch_bounds__(256) void k_map_view_select(const float* __restrict
     const float u = fx * x / z + cx, v = fy * y / z + cy;
     in_view = z > near_plane && z < far_plane && u >= guard_lo && u <= u_hi && v >= guard_lo && v <= v_hi;
   }
-  const unsigned long long sel = __ballot(in_view);
-  __shared__ uint32_t cnt[4], fresh[4];
-  if (lane == 0) {
-    const size_t slot = (size_t)blockIdx.x * 4 + wv;
-    ballots[slot] = sel;
-    cnt[wv] = (uint32_t)__popcll(sel);
-    fresh[wv] = prev_ballots ? (uint32_t)__popcll(sel & ~prev_ballots[slot]) : 0u;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    block_counts[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-    if (prev_ballots) block_fresh[blockIdx.x] = fresh[0] + fresh[1] + fresh[2] + fresh[3];
+  const unsigned long long sel = compact_ballot(in_view, ballots);
+  // second mask: in view now, bit clear in prev
+  const unsigned long long mask[2] = {sel, prev_ballots ? sel & ~prev_ballots[compact_wave_slot()] : 0ull};
+  uint32_t sum[2];
+  if (compact_block_sums(mask, sum)) {
+    block_counts[blockIdx.x] = sum[0];
+    if (prev_ballots) block_fresh[blockIdx.x] = sum[1];
   }
 }
 
-__global__ __launch_bounds__(256) void k_map_view_gather(const float* __restrict__ means,
-                                                         const float* __restrict__ colors, long long n_rows,
-                                                         const uint64_t* __restrict__ ballots,
-                                                         const uint32_t* __restrict__ block_bases,
-                                                         float* __restrict__ out_means, float* __restrict__ out_colors,
-                                                         int32_t* __restrict__ out_ids, long long out_capacity,
-                                                         int32_t* __restrict__ counters) {
-  const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (g == 0) {
-    const long long selected = counters[0];
-    counters[2] = (int32_t)(selected < out_capacity ? selected : out_capacity);
-  }
-  // position: rows of earlier workgroups, of earlier waves of this one, of lower lanes of this wave
-  const unsigned long long sel = ballots[(size_t)blockIdx.x * 4 + wv];
-  long long pos = block_bases[blockIdx.x];
-  for (int w = 0; w < wv; ++w) pos += __popcll(ballots[(size_t)blockIdx.x * 4 + w]);
-  pos += __builtin_amdgcn_mbcnt_hi((uint32_t)(sel >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sel, 0u));
-  if (g >= n_rows || !((sel >> lane) & 1ull) || pos >= out_capacity) return;
+__global__ __launch_bounds__(COMPACT_THREADS) void k_map_view_gather(
+    const float* __restrict__ means, const float* __restrict__ colors, long long n_rows,
+    const uint64_t* __restrict__ ballots, const uint32_t* __restrict__ block_bases, float* __restrict__ out_means,
+    float* __restrict__ out_colors, int32_t* __restrict__ out_ids, long long out_capacity,
+    int32_t* __restrict__ counters) {
+  const long long g = (long long)blockIdx.x * COMPACT_THREADS + threadIdx.x;
+  compact_store_clamped(counters, out_capacity, counters + 2);
+  if (g >= n_rows) return;
+  const long long pos = compact_position(ballots, block_bases);
+  if (!compact_kept(ballots) || pos >= out_capacity) return;
   const size_t src = 3 * (size_t)g, dst = 3 * (size_t)pos;
   const float m0 = means[src], m1 = means[src + 1], m2 = means[src + 2];
   const float c0 = colors[src], c1 = colors[src + 1], c2 = colors[src + 2];
@@ -98,15 +77,11 @@ __global__ __launch_bounds__(256) void k_map_view_gather(const float* __restrict
   if (out_ids) out_ids[pos] = (int32_t)g;
 }
 
-static inline long long view_blocks(int64_t n_rows) { return ((long long)n_rows + 255) / 256; }
-
 }  // namespace gsl
 
 extern "C" size_t gsl_map_view_ws_bytes(int64_t n_rows) {
-  // [ballots nb x 4 uint64][block counts nb][block bases nb][second counts nb][their bases nb, scratch] (uint32)
-  long long nb = (n_rows > 0 && n_rows < 0x80000000ll) ? gsl::view_blocks(n_rows) : 0;
-  if (nb < 1) nb = 1;
-  return (size_t)nb * (4 * sizeof(uint64_t) + 4 * sizeof(uint32_t));
+  // two extra columns: the second counts and their bases
+  return gsl::compact_ws_bytes(n_rows < 0x80000000ll ? (long long)n_rows : 0, 2);
 }
 
 // Argument checks shared by the two passes.
@@ -125,16 +100,15 @@ extern "C" int gsl_map_view_select(const float* means, int64_t n_rows, const flo
   int rc = view_check(means, n_rows, counters, ws, ws_bytes);
   if (rc != GSL_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int nb = (int)gsl::view_blocks(n_rows);
-  uint64_t* ballots = (uint64_t*)ws;
-  uint32_t* counts = (uint32_t*)(ballots + (size_t)nb * 4);
-  uint32_t *bases = counts + nb, *fresh = bases + nb, *fresh_bases = fresh + nb;
+  const int nb = (int)gsl::compact_blocks(n_rows);
+  const gsl::CompactWs w = gsl::compact_ws(ws, nb);
+  uint32_t *fresh = w.extra, *fresh_bases = w.extra + nb;
   const float u_hi = (float)(width - 1) + guard_px, v_hi = (float)(height - 1) + guard_px;  // one float32 sum each
-  hipLaunchKernelGGL(gsl::k_map_view_select, dim3(nb), dim3(256), 0, st, means, (long long)n_rows, w2c, fx, fy, cx, cy,
-                     -guard_px, u_hi, v_hi, near_plane, far_plane, (const uint64_t*)prev_ws, ballots, counts, fresh,
-                     counters);
+  hipLaunchKernelGGL(gsl::k_map_view_select, dim3(nb), dim3(gsl::COMPACT_THREADS), 0, st, means, (long long)n_rows,
+                     w2c, fx, fy, cx, cy, -guard_px, u_hi, v_hi, near_plane, far_plane, (const uint64_t*)prev_ws,
+                     w.ballots, w.counts, fresh, counters);
   GSL_CHECK_LAUNCH();
-  gsl::launch_count_scan(st, counts, nb, bases, counters);
+  gsl::launch_count_scan(st, w.counts, nb, w.bases, counters);
   GSL_CHECK_LAUNCH();
   if (prev_ws) {
     gsl::launch_count_scan(st, fresh, nb, fresh_bases, counters + 1);
@@ -149,12 +123,11 @@ extern "C" int gsl_map_view_gather(const float* means, const float* colors, int6
   if (!colors || !out_means || !out_colors || out_capacity < 0) return GSL_ERR_BAD_ARG;
   int rc = view_check(means, n_rows, counters, ws, ws_bytes);
   if (rc != GSL_OK) return rc;
-  const int nb = (int)gsl::view_blocks(n_rows);
-  const uint64_t* ballots = (const uint64_t*)ws;
-  const uint32_t* bases = (const uint32_t*)(ballots + (size_t)nb * 4) + nb;
-  hipLaunchKernelGGL(gsl::k_map_view_gather, dim3(nb), dim3(256), 0, (hipStream_t)stream, means, colors,
-                     (long long)n_rows, ballots, bases, out_means, out_colors, out_ids, (long long)out_capacity,
-                     counters);
+  const int nb = (int)gsl::compact_blocks(n_rows);
+  const gsl::CompactWs w = gsl::compact_ws(ws, nb);
+  hipLaunchKernelGGL(gsl::k_map_view_gather, dim3(nb), dim3(gsl::COMPACT_THREADS), 0, (hipStream_t)stream, means,
+                     colors, (long long)n_rows, w.ballots, w.bases, out_means, out_colors, out_ids,
+                     (long long)out_capacity, counters);
   GSL_CHECK_LAUNCH();
   return GSL_OK;
 }

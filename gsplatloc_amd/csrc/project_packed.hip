@@ -3,14 +3,9 @@
 // the cull costs what is visible.  All cameras in one launch; the per-pair arithmetic is project_pair() of
 // project_dev.h, the dense kernel's, so a kept row has the dense row's bits.
 //
-// Order-preserving compaction in two passes over the pairs, one thread per pair, 256-thread blocks:
-//   k_packed_project<false>  evaluates the cull; one 64-bit ballot per wave, one count per workgroup;
-//   k_packed_scan            exclusive scan of the workgroup counts (one workgroup), total -> nnz;
-//   k_packed_project<true>   the lanes whose ballot bit is set evaluate the pair again and store at
-//                            workgroup base + kept lanes of the earlier waves + mbcnt.
-// No workgroup waits for another one (no look-back scan, no "last workgroup" ticket: both need device-scope
-// release/acquire across the eight XCD L2s, NOTES.md round 3).  The fill pass takes its positions from the stored
-// ballots alone, so the two passes cannot disagree about where a row goes.
+// Order-preserving compaction (compact_dev.h) in two passes over the pairs, one thread per pair:
+//   k_packed_project<false>  evaluates the cull and records it; the scan's total -> nnz;
+//   k_packed_project<true>   the lanes whose ballot bit is set evaluate the pair again and store at their position.
 // The camera is loaded per lane (a wave may straddle two cameras when N % 64 != 0); the 25 floats of one camera are
 // one or two cache lines that every lane of the wave hits.  HBM-bound: 40 B read per pair twice, 32 B (+ 16 B of
 // ids) written per kept row.
@@ -23,13 +18,14 @@
 //
 // Row gather (k_gather_rows) and its vjp (k_scatter_rows, k_scatter_add_rows): x[gaussian_ids] / x[camera_ids] for the
 // opacities, colours, means and camera positions the packed pipeline reads per row.
+#include "compact_dev.h"
 #include "gsloc_internal.h"
 #include "project_dev.h"
 
 namespace gsl {
 
 template <bool FILL>
-__global__ __launch_bounds__(256) void k_packed_project(
+__global__ __launch_bounds__(COMPACT_THREADS) void k_packed_project(
     const float* __restrict__ means, const float* __restrict__ quats, const float* __restrict__ scales,
     const float* __restrict__ viewmats, const float* __restrict__ Ks, int C, int N, int W, int H, float eps2d,
     float near_plane, float far_plane, float radius_clip, uint64_t* __restrict__ ballots,
@@ -37,11 +33,9 @@ __global__ __launch_bounds__(256) void k_packed_project(
     int64_t* __restrict__ camera_ids, int64_t* __restrict__ gaussian_ids, int32_t* __restrict__ radii,
     float* __restrict__ means2d, float* __restrict__ depths, float* __restrict__ conics, float* __restrict__ comps) {
   const long long total = (long long)C * N;
-  const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const size_t wave_slot = (size_t)blockIdx.x * 4 + wv;
+  const long long g = (long long)blockIdx.x * COMPACT_THREADS + threadIdx.x;
   bool eval = g < total;
-  if (FILL) eval = eval && ((ballots[wave_slot] >> lane) & 1ull);
+  if (FILL) eval = eval && compact_kept(ballots);
   int cam_id = 0, i = 0;
   ProjOut o;
   o.radius = 0; o.mx = o.my = o.depth = o.ca = o.cb = o.cc = o.comp = 0.f;
@@ -52,20 +46,9 @@ __global__ __launch_bounds__(256) void k_packed_project(
     o = project_pair(means, quats, scales, i, cam, W, H, eps2d, near_plane, far_plane, radius_clip);
   }
   if (!FILL) {
-    unsigned long long kept = __ballot(o.radius > 0);
-    __shared__ uint32_t cnt[4];
-    if (lane == 0) {
-      ballots[wave_slot] = kept;
-      cnt[wv] = (uint32_t)__popcll(kept);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    compact_record(o.radius > 0, ballots, block_counts);
   } else {
-    // position: rows of earlier workgroups, of earlier waves of this one, of lower lanes of this wave
-    unsigned long long kept = ballots[wave_slot];
-    long long pos = block_bases[blockIdx.x];
-    for (int w = 0; w < wv; ++w) pos += __popcll(ballots[(size_t)blockIdx.x * 4 + w]);
-    pos += __builtin_amdgcn_mbcnt_hi((uint32_t)(kept >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)kept, 0u));
+    const long long pos = compact_position(ballots, block_bases);
     if (eval && pos < capacity) {
       camera_ids[pos] = cam_id;
       gaussian_ids[pos] = i;
@@ -78,33 +61,6 @@ __global__ __launch_bounds__(256) void k_packed_project(
       conics[3 * (size_t)pos + 2] = o.cc;
       if (comps) comps[pos] = o.comp;
     }
-  }
-}
-
-// Exclusive scan of counts[nb] -> bases[nb], total -> nnz[0].  One workgroup; thread t owns one contiguous chunk.
-__global__ __launch_bounds__(256) void k_packed_scan(const uint32_t* __restrict__ counts, int nb,
-                                                    uint32_t* __restrict__ bases, int32_t* __restrict__ nnz) {
-  __shared__ uint32_t part[256];
-  const int per = (nb + 255) / 256;
-  const int lo = min(nb, (int)threadIdx.x * per), hi = min(nb, lo + per);
-  uint32_t sum = 0;
-  for (int b = lo; b < hi; ++b) sum += counts[b];
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t run = 0;
-    for (int t = 0; t < 256; ++t) {
-      uint32_t v = part[t];
-      part[t] = run;
-      run += v;
-    }
-    nnz[0] = (int32_t)run;
-  }
-  __syncthreads();
-  uint32_t run = part[threadIdx.x];
-  for (int b = lo; b < hi; ++b) {
-    bases[b] = run;
-    run += counts[b];
   }
 }
 
@@ -296,19 +252,10 @@ __global__ __launch_bounds__(256) void k_scatter_add_rows(const float* __restric
   }
 }
 
-void launch_count_scan(hipStream_t st, const uint32_t* counts, int nb, uint32_t* bases, int32_t* total) {
-  hipLaunchKernelGGL(k_packed_scan, dim3(1), dim3(256), 0, st, counts, nb, bases, total);
-}
-
-static inline long long packed_blocks(int C, int N) { return ((long long)C * N + 255) / 256; }
-
 }  // namespace gsl
 
 extern "C" size_t gsl_project_packed_ws_bytes(int C, int N) {
-  // [ballots nb x 4 uint64][block counts nb uint32][block bases nb uint32]
-  long long nb = (C > 0 && N > 0) ? gsl::packed_blocks(C, N) : 0;
-  if (nb < 1) nb = 1;
-  return (size_t)nb * (4 * sizeof(uint64_t) + 2 * sizeof(uint32_t));
+  return gsl::compact_ws_bytes((C > 0 && N > 0) ? (long long)C * N : 0);
 }
 
 // Argument checks shared by the count and the fill pass.
@@ -330,17 +277,15 @@ extern "C" int gsl_project_packed_count(const float* means, const float* quats, 
   if (rc != GSL_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (N == 0) return gsl::zero_u32(nnz, 1, st);
-  const int nb = (int)gsl::packed_blocks(C, N);
-  uint64_t* ballots = (uint64_t*)ws;
-  uint32_t* counts = (uint32_t*)(ballots + (size_t)nb * 4);
-  uint32_t* bases = counts + nb;
+  const int nb = (int)gsl::compact_blocks((long long)C * N);
+  const gsl::CompactWs w = gsl::compact_ws(ws, nb);
   GSL_CLAMP_DEPTH_WINDOW(near_plane, far_plane);
-  hipLaunchKernelGGL(gsl::k_packed_project<false>, dim3(nb), dim3(256), 0, st, means, quats, scales, viewmats, Ks, C, N,
-                     width, height, eps2d, near_plane, far_plane, radius_clip, ballots, counts,
+  hipLaunchKernelGGL(gsl::k_packed_project<false>, dim3(nb), dim3(gsl::COMPACT_THREADS), 0, st, means, quats, scales,
+                     viewmats, Ks, C, N, width, height, eps2d, near_plane, far_plane, radius_clip, w.ballots, w.counts,
                      (const uint32_t*)nullptr, 0ll, (int64_t*)nullptr, (int64_t*)nullptr, (int32_t*)nullptr,
                      (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
   GSL_CHECK_LAUNCH();
-  gsl::launch_count_scan(st, counts, nb, bases, nnz);
+  gsl::launch_count_scan(st, w.counts, nb, w.bases, nnz);
   GSL_CHECK_LAUNCH();
   return GSL_OK;
 }
@@ -356,15 +301,13 @@ extern "C" int gsl_project_packed_fill(const float* means, const float* quats, c
   if (rc != GSL_OK) return rc;
   if (N == 0 || capacity == 0) return GSL_OK;
   if (!camera_ids || !gaussian_ids || !radii || !means2d || !depths || !conics) return GSL_ERR_BAD_ARG;
-  const int nb = (int)gsl::packed_blocks(C, N);
-  uint64_t* ballots = (uint64_t*)ws;
-  uint32_t* counts = (uint32_t*)(ballots + (size_t)nb * 4);
-  uint32_t* bases = counts + nb;
+  const int nb = (int)gsl::compact_blocks((long long)C * N);
+  const gsl::CompactWs w = gsl::compact_ws(ws, nb);
   GSL_CLAMP_DEPTH_WINDOW(near_plane, far_plane);
-  hipLaunchKernelGGL(gsl::k_packed_project<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, means, quats, scales,
-                     viewmats, Ks, C, N, width, height, eps2d, near_plane, far_plane, radius_clip, ballots, counts,
-                     (const uint32_t*)bases, (long long)capacity, camera_ids, gaussian_ids, radii, means2d, depths,
-                     conics, compensations);
+  hipLaunchKernelGGL(gsl::k_packed_project<true>, dim3(nb), dim3(gsl::COMPACT_THREADS), 0, (hipStream_t)stream, means,
+                     quats, scales, viewmats, Ks, C, N, width, height, eps2d, near_plane, far_plane, radius_clip,
+                     w.ballots, w.counts, w.bases, (long long)capacity, camera_ids, gaussian_ids, radii, means2d,
+                     depths, conics, compensations);
   GSL_CHECK_LAUNCH();
   return GSL_OK;
 }

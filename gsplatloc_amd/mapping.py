@@ -45,6 +45,15 @@ class MapConfig:
                              "that is tracked must hold the band that is checked")
 
 
+def _intr_and_pose(K, c2w) -> Tuple[Tuple[float, float, float, float], Tensor]:
+    """K [3,3] -> (fx, fy, cx, cy); c2w -> a tensor (dtype and device as given), refused unless it is [4,4]."""
+    Kc = torch.as_tensor(K, dtype=torch.float32).cpu()
+    c2w = torch.as_tensor(c2w)
+    if c2w.shape != (4, 4):
+        raise ValueError(f"c2w is {tuple(c2w.shape)}, not (4, 4)")
+    return (float(Kc[0, 0]), float(Kc[1, 1]), float(Kc[0, 2]), float(Kc[1, 2])), c2w
+
+
 class GaussianMap:
     """``insert_frame`` per frame; ``points`` / ``point_colors`` are views of the live prefix (no copy)."""
 
@@ -119,11 +128,8 @@ class GaussianMap:
         depth, rgb = image(depth, hw, "depth"), image(torch.as_tensor(rgb)[..., :3], hw + (3,), "rgb")
         if render is not None:
             render, alphas = image(render, hw, "render"), image(alphas, hw, "alphas")
-        Kc = torch.as_tensor(K, dtype=torch.float32).cpu()
-        intr = (float(Kc[0, 0]), float(Kc[1, 1]), float(Kc[0, 2]), float(Kc[1, 2]))
-        c2w = torch.as_tensor(c2w, dtype=torch.float32, device=self.device).contiguous()
-        if c2w.shape != (4, 4):
-            raise ValueError(f"c2w is {tuple(c2w.shape)}, not (4, 4)")
+        intr, c2w = _intr_and_pose(K, c2w)
+        c2w = c2w.to(device=self.device, dtype=torch.float32).contiguous()
         selected, appended = self._launch(depth, rgb, intr, c2w, render, alphas)
         self.n_live += appended
         self.full = self.full or appended < selected
@@ -160,13 +166,10 @@ class GaussianMap:
         return in_view, fresh, gathered
 
     def _view_args(self, K, c2w):
-        Kc = torch.as_tensor(K, dtype=torch.float32).cpu()
-        intr = (float(Kc[0, 0]), float(Kc[1, 1]), float(Kc[0, 2]), float(Kc[1, 2]))
-        c2w = torch.as_tensor(c2w).detach().cpu().double().numpy()
-        if c2w.shape != (4, 4):
-            raise ValueError(f"c2w is {c2w.shape}, not (4, 4)")
+        intr, c2w = _intr_and_pose(K, c2w)
         # the float64 inverse, rounded to float32 here: the kernel multiplies and adds, nothing else
-        w2c = torch.from_numpy(np.linalg.inv(c2w).astype(np.float32)).to(self.device).contiguous()
+        w2c = np.linalg.inv(c2w.detach().cpu().double().numpy()).astype(np.float32)
+        w2c = torch.from_numpy(w2c).to(self.device).contiguous()
         return intr, w2c
 
     @torch.no_grad()

@@ -2,7 +2,9 @@
 given arrays.
 
 Row counts: 1; 63 / 64 / 65 around one wave; 255 / 256 / 257 around one workgroup; 1000 (four workgroups, the last one
-partial); 4099 (17 workgroup counts, three rows in the last).  Patterns: all rows in view, none (all behind the camera),
+partial); 4099 (17 workgroup counts, three rows in the last); 66 000 (258 workgroup counts: the scan's threads own
+chunks of two, and those from 129 on own nothing -- also under the check against an earlier selection, the one call that
+runs two scans).  Patterns: all rows in view, none (all behind the camera),
 every other row, only lane 0 / only lane 63 of every wave, only the last row -- under a general pose -- and a random
 cloud that straddles the frustum, with rows exactly on the four borders and the two depth planes and NaN / inf rows
 mixed in, under a pose whose float32 arithmetic is exact (a quarter turn and a dyadic translation, power-of-two
@@ -25,7 +27,7 @@ from tests.pose_ref import axis_angle
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 F32 = np.float32
-ROWS = [1, 63, 64, 65, 255, 256, 257, 1000, 4099]
+ROWS = [1, 63, 64, 65, 255, 256, 257, 1000, 4099, 66000]
 PATTERNS = ["all", "none", "every_other", "lane0", "lane63", "last", "random"]
 SENTINEL, GUARD_ROWS = -7.25, 64
 W, H, INTR = 160, 120, (95.3, 88.1, 160 / 2 - 0.3, 120 / 2 + 0.2)  # fx != fy, the principal point off the centre
@@ -164,14 +166,26 @@ def test_the_exact_border_rows_are_where_the_mirror_puts_them():
     assert got["bits"][where].tolist() == [True] * 5 + [False] * 11
 
 
-def test_violations_against_an_earlier_selection():
-    n = 4099
+def _violation_case(n):
+    """(means [n,3] in the world that straddle the frustum of pose A, colors, w2c of pose A, w2c of a pose B nearby)."""
     rng = np.random.default_rng(7)
     z = rng.uniform(0.8, 3.8, n)
     p = np.stack([rng.uniform(-1.3, 1.3, n) * z, rng.uniform(-1.1, 1.1, n) * z, z], axis=-1)  # straddles the frustum
     pose_a, pose_b = _pose(37.0), _pose(39.5, (1.32, -0.79, 2.08))
     means, colors = _world(p, pose_a), rng.uniform(0.0, 1.0, (n, 3)).astype(F32)
-    w2c_a, w2c_b = ref.w2c_of(pose_a), ref.w2c_of(pose_b)
+    return means, colors, ref.w2c_of(pose_a), ref.w2c_of(pose_b)
+
+
+def test_violations_against_an_earlier_selection():
+    _violations_against_an_earlier_selection(4099)
+
+
+def test_violations_against_an_earlier_selection_with_two_counts_per_scan_thread():
+    _violations_against_an_earlier_selection(66000)
+
+
+def _violations_against_an_earlier_selection(n):
+    means, colors, w2c_a, w2c_b = _violation_case(n)
     a = _run(means, colors, w2c_a, INTR, W, H, GUARD, n)
     mask_a = ref.in_view(means, w2c_a, INTR, W, H, GUARD, NEAR, FAR)
     assert np.array_equal(a["bits"], mask_a) and 0.2 < mask_a.mean() < 0.8

@@ -23,7 +23,7 @@ def _resources(src, *extra):
         if m:
             cur = out.setdefault(m.group(1), {})
             continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]|ScratchSize \[bytes/lane\]): (\d+)", line)
+        m = re.search(r"remark:\s+(TotalSGPRs|VGPRs|AGPRs|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]|ScratchSize \[bytes/lane\]): (\d+)", line)
         if m and cur is not None:
             cur[m.group(1).split(" ")[0]] = int(m.group(2))
     return out
@@ -68,6 +68,27 @@ def test_sort_and_projection_kernels_stay_in_registers():
             assert v["ScratchSize"] == 0, (k, v)
         if "k_fprojectILb" in k:   # forward projection (binned or not): 512-thread workgroups must fit twice per CU
             assert v["VGPRs"] <= 128, (k, v)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_compaction_kernels_cost_what_their_hand_written_copies_did():
+    """The record and fill kernels of the three ordered compactions and the scan between them, written on the shared
+    helpers of csrc/compact_dev.h: no more registers (VGPR, SGPR), LDS or scratch than the last commit in which each
+    kernel carried its own copy of the ballot, count and position steps (the numbers are that commit's)."""
+    budget = {  # kernel: (VGPRs, SGPRs, LDS bytes)
+        ("project_packed.hip", "k_packed_projectILb0"): (33, 41, 16),
+        ("project_packed.hip", "k_packed_projectILb1"): (41, 49, 0),
+        ("map.hip", "k_map_select"): (6, 22, 16), ("map.hip", "k_map_append"): (20, 36, 0),
+        ("map_view.hip", "k_map_view_select"): (14, 50, 32), ("map_view.hip", "k_map_view_gather"): (15, 30, 0),
+        ("compact.hip", "k_count_scan"): (26, 20, 1024),
+    }
+    files = {f: _resources(f) for f in sorted({f for f, _ in budget})}
+    for (f, name), (vgprs, sgprs, lds) in budget.items():
+        hit = [v for k, v in files[f].items() if name in k]
+        assert len(hit) == 1, (f, name, list(files[f]))
+        r = hit[0]
+        assert r["VGPRs"] <= vgprs and r["AGPRs"] == 0 and r["TotalSGPRs"] <= sgprs, (name, r)
+        assert r["LDS"] <= lds and r["ScratchSize"] == 0 and r["Occupancy"] == 8, (name, r)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")

@@ -109,6 +109,41 @@ def test_compaction_clamp_and_violation_count():
     assert np.array_equal(ref.w2c_of(c2w)[:3, 3], np.array([-0.5, 1.0, -2.0], F32)) and ref.w2c_of(c2w).dtype == F32
 
 
+def test_the_mirror_carries_the_largest_gpu_cases():
+    """66 000 rows, the largest count of tests/test_gpu_map_view.py (258 workgroups: two counts per thread of the scan,
+    threads from 129 on idle), on the mirror alone: every pattern is what it says, the count stays below the capacity
+    of n + 3 rows the GPU test gives its outputs (so the rows behind it, and the guard rows, keep their sentinels), no
+    selected row holds the sentinel value, and the scene of the violation test has what that test asserts."""
+    from tests import test_gpu_map_view as gpu
+
+    n = max(gpu.ROWS)
+    assert n == 66000 and (n + 255) // 256 == 258
+    for pattern in gpu.PATTERNS:
+        means, c2w, intr, w, h, intended = gpu._case(n, pattern)
+        args = (means, ref.w2c_of(c2w), intr, w, h, gpu.GUARD, gpu.NEAR, gpu.FAR)
+        want = ref.select(*args, out_capacity=n + 3)
+        if intended is not None:
+            assert np.array_equal(want["mask"], intended), pattern
+        else:
+            assert 0.1 < want["mask"].mean() < 0.8, pattern
+        sel, ids = want["counters"][0], want["ids"]
+        assert want["counters"] == (sel, 0, sel) and sel <= n < n + 3, pattern
+        assert ids.dtype == np.int32 and len(ids) == sel and (np.diff(ids) > 0).all() and (sel == 0 or ids[-1] < n)
+        assert not (means[ids] == gpu.SENTINEL).any() and not (ids == -77).any(), pattern
+        assert ref.select(*args, out_capacity=sel // 2)["counters"] == (sel, 0, sel // 2), pattern
+    means, colors, w2c_a, w2c_b = gpu._violation_case(n)
+    assert means.shape == colors.shape == (n, 3) and not (colors == gpu.SENTINEL).any()
+    geom = (gpu.INTR, gpu.W, gpu.H)
+    mask_a = ref.in_view(means, w2c_a, *geom, gpu.GUARD, gpu.NEAR, gpu.FAR)
+    assert 0.2 < mask_a.mean() < 0.8
+    b = ref.select(means, w2c_b, *geom, 4.0, gpu.NEAR, gpu.FAR, prev=mask_a)["counters"]
+    assert 0 < b[1] < b[0] < n
+    same = ref.select(means, w2c_a, *geom, 4.0, gpu.NEAR, gpu.FAR, prev=mask_a)["counters"]
+    assert same[1] == 0 and 0 < same[0] <= int(mask_a.sum())
+    wider = ref.select(means, w2c_a, *geom, 20.0, gpu.NEAR, gpu.FAR, prev=mask_a)["counters"]
+    assert wider[1] == wider[0] - int(mask_a.sum()) > 0
+
+
 # ---- the entry points' argument checks ------------------------------------------------------------------------------
 BAD_ARG, WORKSPACE = -1, -2
 _SELECT = dict(n_rows=1000, fx=50.0, fy=40.0, cx=31.5, cy=23.5, width=64, height=48, guard_px=8.0, near_plane=0.01,

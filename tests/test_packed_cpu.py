@@ -170,12 +170,16 @@ def test_packed_ops_fail_loudly_without_gpu_tensors():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_packed_projection_kernels_stay_in_registers():
-    """ScratchSize 0 for every kernel of csrc/project_packed.hip: both passes of the forward, the scan, the three
-    instances of the backward, the per-camera reduction (register counts and occupancy: DESIGN.md section 4)."""
+    """ScratchSize 0 for every kernel of csrc/project_packed.hip: both passes of the forward, the three instances of
+    the backward, the per-camera reduction -- and for the scan between the two passes, in csrc/compact.hip (register
+    counts and occupancy: DESIGN.md section 4)."""
     res = {k: v for k, v in _resources("project_packed.hip").items() if "k_packed" in k}
     assert sum("k_packed_projectILb" in k for k in res) == 2
     assert sum("k_packed_project_bwd" in k for k in res) == 3
-    assert sum("k_packed_scan" in k for k in res) == 1 and sum("k_packed_reduce_viewmat" in k for k in res) == 1
+    assert sum("k_packed_reduce_viewmat" in k for k in res) == 1
+    scan = {k: v for k, v in _resources("compact.hip").items() if "k_count_scan" in k}
+    assert len(scan) == 1
+    res.update(scan)
     rows = {k: v for k, v in _resources("project_packed.hip").items() if "k_gather_rows" in k or "k_scatter_" in k}
     assert len(rows) == 3  # the gather, its vjp with unique and with repeated ids
     res.update(rows)
