@@ -35,7 +35,8 @@ def rmse(values: List[float]) -> float:
 def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[int] = 1998, verbose: bool = False,
                   profile: bool = False, rgb_lambda: float = 0.0, ssim_lambda: float = 0.5, sequential: bool = False,
                   motion: str = "constant_velocity", map_mode: bool = False,
-                  map_capacity: Optional[int] = None, map_view_guard: Optional[float] = None) -> Dict:
+                  map_capacity: Optional[int] = None, map_view_guard: Optional[float] = None,
+                  map_free_rho: Optional[float] = None, map_free_window: int = 1) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -43,12 +44,16 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     (TrackerConfig.rgb_lambda / ssim_lambda): the tracker then renders "RGB+ED" and is given the frame's image.
     sequential=True: evaluate_sequential (only frame 0's ground-truth pose is used; ``motion`` is its hand-over;
     ``map_mode``: frames are tracked against a map grown on the device, of ``map_capacity`` rows at most;
-    ``map_view_guard``: against the part of it in view, the image widened by that many pixels)."""
+    ``map_view_guard``: against the part of it in view, the image widened by that many pixels; ``map_free_rho`` /
+    ``map_free_window``: MapConfig.free_rho / free_window_px, the rows a frame sees through are removed)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
     if map_view_guard is not None and not map_mode:
         raise ValueError("map_view_guard belongs to the map mode (map_mode=True)")
+    if map_free_rho is not None and not map_mode:
+        raise ValueError("map_free_rho belongs to the map mode (map_mode=True)")
     if sequential:
-        return evaluate_sequential(parser, cfg, max_frames, verbose, motion, map_mode, map_capacity, map_view_guard)
+        return evaluate_sequential(parser, cfg, max_frames, verbose, motion, map_mode, map_capacity, map_view_guard,
+                                   map_free_rho, map_free_window)
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -109,23 +114,26 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
 
 def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional[int] = 1998, verbose: bool = False,
                         motion: str = "constant_velocity", map_mode: bool = False,
-                        map_capacity: Optional[int] = None, map_view_guard: Optional[float] = None) -> Dict:
+                        map_capacity: Optional[int] = None, map_view_guard: Optional[float] = None,
+                        map_free_rho: Optional[float] = None, map_free_window: int = 1) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
     map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
     tracked_per_frame (rows the tracker saw) and map_full (some frame's points were dropped at map_capacity).
-    map_view_guard: MapConfig.view_guard_px; the report gains view_violations_per_frame."""
+    map_view_guard: MapConfig.view_guard_px; the report gains view_violations_per_frame.  map_free_rho /
+    map_free_window: MapConfig.free_rho / free_window_px; the report gains removed_per_frame."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
     extra = {}
     if map_mode:
-        extra = dict(mode="map", map_config=MapConfig(capacity=map_capacity, view_guard_px=map_view_guard))
+        extra = dict(mode="map", map_config=MapConfig(capacity=map_capacity, view_guard_px=map_view_guard,
+                                                       free_rho=map_free_rho, free_window_px=map_free_window))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
     eTs, eRs, steps, lost, path, last_t = [], [], [], 0, 0.0, pose[:3, 3]
-    added, tracked, violations = [], [], []
+    added, tracked, violations, removed = [], [], [], []
     for i in range(1, n + 1):
         depth, rgb, pose = parser.frame(i)
         r = loc.track(depth, rgb, gt_c2w=pose)
@@ -136,6 +144,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
         added.append(r.added)
         tracked.append(r.tracked)
         violations.append(r.view_violations)
+        removed.append(r.removed)
         path += float(torch.norm(pose[:3, 3] - last_t))
         last_t = pose[:3, 3]
         if verbose:
@@ -149,7 +158,9 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             **({"map_gaussians": loc.map.n_live, "added_per_frame": added, "tracked_per_frame": tracked,
                 "map_full": loc.map.full} if map_mode else {}),
             **({"view_guard_px": map_view_guard, "view_violations_per_frame": violations}
-               if map_view_guard is not None else {})}
+               if map_view_guard is not None else {}),
+            **({"free_rho": map_free_rho, "free_window_px": map_free_window, "removed_per_frame": removed}
+               if map_free_rho is not None else {})}
 
 
 def main(argv=None):
@@ -177,17 +188,28 @@ def main(argv=None):
     ap.add_argument("--map-view-guard", type=float, default=None, metavar="PX",
                     help="--map: track every frame against the map's points in view from its start pose, the image "
                          "widened by PX pixels on every side (default: against all of them)")
+    ap.add_argument("--map-free-rho", type=float, default=None, metavar="RHO",
+                    help="--map: after every frame's insertion remove the map's points that the frame sees through, "
+                         "those more than this fraction in front of everything it observes around their pixel "
+                         "(default: the map only grows)")
+    ap.add_argument("--map-free-window", type=int, default=1, metavar="PX",
+                    help="--map-free-rho: the pixels around a point's pixel that must all lie behind it (0 .. 3)")
     a = ap.parse_args(argv)
     if a.map and not a.sequential:
         ap.error("--map needs --sequential")
     if a.map_view_guard is not None and not a.map:
         ap.error("--map-view-guard needs --map")
+    if a.map_free_rho is not None and not a.map:
+        ap.error("--map-free-rho needs --map")
+    if a.map_free_window != 1 and not a.map:
+        ap.error("--map-free-window needs --map")
     out = {}
     for room in a.rooms:
         parser = Parser(a.dataset, room, normalize=not a.no_normalize, input_folder=a.root)
         r = evaluate_room(parser, a.num_iters, a.max_frames, a.verbose, rgb_lambda=a.rgb_lambda,
                           ssim_lambda=a.ssim_lambda, sequential=a.sequential, motion=a.motion, map_mode=a.map,
-                          map_capacity=a.map_capacity, map_view_guard=a.map_view_guard)
+                          map_capacity=a.map_capacity, map_view_guard=a.map_view_guard,
+                          map_free_rho=a.map_free_rho, map_free_window=a.map_free_window)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

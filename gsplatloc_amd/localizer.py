@@ -21,6 +21,9 @@ the world, which every tracked frame extends by the pixels the map does not expl
 With ``MapConfig.view_guard_px`` they are the live points in view from the start pose of step 3, the image widened by
 that guard band; after the frame the band is checked against the estimate (``GaussianMap.view_violations``), and where
 it did not hold the render the new pixels are judged against is made from a selection at the estimate.
+With ``MapConfig.free_rho`` the map also shrinks: after the insertion of a frame that is not lost, the live rows that
+frame sees through -- in front of everything it observes around their pixel -- are removed
+(``GaussianMap.remove_seen_through``).  The hole a removed ghost leaves is filled by the NEXT frame's insertion.
 """
 from __future__ import annotations
 
@@ -70,6 +73,7 @@ class LocalizeResult:
     added: Optional[int] = None
     tracked: Optional[int] = None  # mode="map": rows the tracker saw (all live rows, or those in the guarded view)
     view_violations: Optional[int] = None  # view_guard_px: rows in reach of the view from c2w that were not tracked
+    removed: Optional[int] = None  # free_rho: live rows this frame saw through, removed after its insertion
 
 
 def _default_factory(N, W, H, config, device, render_mode):
@@ -93,8 +97,13 @@ class Localizer:
     rebuilt when the live count changes.  ``map_config.view_guard_px``: the Gaussians of a frame are the live points in
     view from its start pose only (``GaussianMap.select_view``; ``LocalizeResult.tracked``), the tracker is keyed on
     their count, and ``LocalizeResult.view_violations`` says how many rows in reach of the view from the estimate they
-    left out (above 0: the render is made from a selection at the estimate).  Everything else -- normalisation, the
-    re-rendered query depth, the scales, the hand-over, ``best_c2w`` -- is the frame mode's."""
+    left out (above 0: the render is made from a selection at the estimate).  ``map_config.free_rho``: after the
+    insertion (insert first, then remove: the insertion render is of the cloud that was tracked, and the rows just
+    appended sit at their own pixel's observed depth and cannot go) the rows the frame sees through are removed,
+    ``LocalizeResult.removed`` counts them and ``map_size`` is the count after the removal; the pixels behind a removed
+    ghost are uncovered only now, so it is the next frame's insertion that fills the hole.  A lost frame removes
+    nothing.  Everything else -- normalisation, the re-rendered query depth, the scales, the hand-over, ``best_c2w`` --
+    is the frame mode's."""
 
     def __init__(self, K: Tensor, width: int, height: int, config: TrackerConfig = TrackerConfig(),
                  normalize: bool = True, motion: str = "constant_velocity", device="cuda", render_mode: str = "ED",
@@ -121,11 +130,13 @@ class Localizer:
         self.map_mode = mode == "map"
         self.map = None
         self._view_guard = None  # MapConfig.view_guard_px
+        self._free = False  # MapConfig.free_rho is set
         if self.map_mode:
             make = map_factory if map_factory is not None else GaussianMap
             map_config = map_config if map_config is not None else MapConfig()
             self.map = make(self.W, self.H, map_config, self.device)
             self._view_guard = map_config.view_guard_px
+            self._free = map_config.free_rho is not None
         self._render_map = map_renderer if map_renderer is not None else render_depth_alpha
 
     def _frame(self, depth, rgb):
@@ -210,6 +221,7 @@ class Localizer:
                              lost=res.best_step == -1)
         if self.map_mode:
             out.added, out.tracked = 0, N
+            out.removed = 0 if self._free else None
             if not out.lost:  # a lost frame's pose is a guess: it adds nothing
                 at = best
                 if self._view_guard is not None:
@@ -224,6 +236,10 @@ class Localizer:
                         at = transform_cameras(d.norm_T, est.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else est
                 render, alphas = self._map_render(d, scales, at)
                 _, out.added = self.map.insert_frame(depth, rgb, self.K, est, render, alphas)
+                if self._free:
+                    # insert first, then remove: the insertion render was made from the cloud that was tracked, and
+                    # the rows just appended sit at their own pixel's observed depth
+                    out.removed, _ = self.map.remove_seen_through(depth, self.K, est, self.cfg.gs.near_plane)
             out.map_size = self.map.n_live
         if gt is not None:
             out.eT, out.eR = calculate_translation_error(est, gt), calculate_rotation_error(est, gt)

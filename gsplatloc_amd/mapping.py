@@ -12,7 +12,12 @@ the host reads the two counters back once per frame.  There is no CPU path.
 The local map (``MapConfig.view_guard_px``, csrc/map_view.hip): ``select_view`` compacts the live rows in view from a
 pose, the image widened by a guard band, in map order into working buffers -- what ``Localizer(mode="map")`` then
 tracks instead of every live row -- and ``view_violations`` counts the rows in reach of the view from another pose that
-this selection left out.  Two more entry points; each of the two calls reads its counters back once."""
+this selection left out.  Two more entry points; each of the two calls reads its counters back once.
+
+Free space (``MapConfig.free_rho``, csrc/map_free.hip): ``remove_seen_through`` removes the live rows a depth frame sees
+through -- rows that project into the image and lie more than ``free_rho`` in front of everything the frame observes in
+a window of ``free_window_px`` pixels around their pixel -- and compacts the survivors, in map order, into a spare pair
+of buffers that then becomes the map.  One more entry point and the local map's gather; one read-back."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -36,8 +41,18 @@ class MapConfig:
     # ... and afterwards count the rows in view from the ESTIMATE, the image widened by this, that the tracked set left
     # out.  A 3 sigma footprint of these clouds is about 7 px wide: a centre up to about 4 px outside still paints inside
     view_reach_px: float = 4.0
+    # Localizer(mode="map"): after a frame's insertion, remove the live rows that project into the frame and lie more
+    # than this fraction in front of every observed depth within free_window_px pixels of their pixel (None: a map only
+    # grows).  The window is what keeps the edge of a surface that is still there when the pose is a little off
+    free_rho: Optional[float] = None
+    free_window_px: int = 1
 
     def __post_init__(self):
+        if self.free_rho is not None and not 0.0 < self.free_rho < 1.0:
+            raise ValueError(f"free_rho {self.free_rho}: a fraction of the observed depth, inside (0, 1)")
+        if isinstance(self.free_window_px, bool) or not isinstance(self.free_window_px, int) \
+                or not 0 <= self.free_window_px <= 3:
+            raise ValueError(f"free_window_px {self.free_window_px}: a whole number of pixels, 0 .. 3")
         if not self.view_reach_px >= 0.0:
             raise ValueError(f"view_reach_px {self.view_reach_px}: not negative")
         if self.view_guard_px is not None and not self.view_guard_px >= self.view_reach_px:
@@ -55,7 +70,8 @@ def _intr_and_pose(K, c2w) -> Tuple[Tuple[float, float, float, float], Tensor]:
 
 
 class GaussianMap:
-    """``insert_frame`` per frame; ``points`` / ``point_colors`` are views of the live prefix (no copy)."""
+    """``insert_frame`` per frame; ``points`` / ``point_colors`` are views of the live prefix (no copy).  A removal
+    (``remove_seen_through``) that removes something swaps the buffers behind them: views taken before it are stale."""
 
     def __init__(self, width: int, height: int, config: MapConfig = MapConfig(), device="cuda"):
         self.W, self.H = int(width), int(height)
@@ -76,6 +92,10 @@ class GaussianMap:
         # select_view: capacity-sized working buffers and two workspaces, allocated on first use
         self._view = None
         self._view_rows = -1  # n_live at the last select_view: what its ballots describe
+        # remove_seen_through: the spare pair of buffers, the ids and a workspace, allocated on first use
+        self._free = None
+        self._free_keep = None if config.free_rho is None else float(np.float32(1.0) - np.float32(config.free_rho))
+        self._n_survivors = 0
 
     def _alloc_ws(self):
         if self.device.type != "cuda":
@@ -91,9 +111,18 @@ class GaussianMap:
     def point_colors(self) -> Tensor:
         return self.colors[: self.n_live]
 
+    @property
+    def survivors(self) -> Tensor:
+        """int32: the old row of every row that was live after the last ``remove_seen_through`` (empty before the first
+        one); a view that the next call overwrites."""
+        if self._free is None:
+            return torch.zeros(0, dtype=torch.int32, device=self.device)
+        return self._free["ids"][: self._n_survivors]
+
     def clear(self) -> None:
         self.n_live, self.full = 0, False
         self._view_rows = -1
+        self._n_survivors = 0
 
     def _launch(self, depth: Tensor, rgb: Tensor, intr: Tuple[float, float, float, float], c2w: Tensor,
                 render: Optional[Tensor], alphas: Optional[Tensor]) -> Tuple[int, int]:
@@ -195,3 +224,59 @@ class GaussianMap:
             return 0
         intr, w2c = self._view_args(K, c2w)
         return self._view_launch(intr, w2c, float(self.cfg.view_reach_px), float(near), float(far), True)[1]
+
+    # ---- free space: the live rows a depth frame sees through are removed (csrc/map_free.hip) ------------------------
+    def _free_buffers(self):
+        if self._free is None:
+            cap, dev, ws = self.capacity, self.device, None
+            if dev.type == "cuda":
+                ws = torch.empty(_lib.load_library().gsl_map_view_ws_bytes(cap), dtype=torch.uint8, device=dev)
+            self._free = dict(means=torch.zeros(cap, 3, device=dev), colors=torch.zeros(cap, 3, device=dev),
+                              ids=torch.zeros(cap, dtype=torch.int32, device=dev),
+                              counters=torch.zeros(3, dtype=torch.int32, device=dev), ws=ws)
+        return self._free
+
+    def _free_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, keep: float,
+                     window: int, near: float) -> Tuple[int, int]:
+        """The rule over the live rows and the gather of those that stay into the spare buffers (means, colours, old
+        rows); the read-back of (rows that stay, rows stored)."""
+        assert depth.is_cuda, "GaussianMap.remove_seen_through: the rows are judged and moved by HIP kernels, no CPU path"
+        lib, st, ptr, f = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._free_buffers()
+        ws = f["ws"]
+        _lib.check(lib.gsl_map_free_select(ptr(self.means), self.n_live, ptr(w2c), *intr, ptr(depth), self.W, self.H,
+                                           keep, window, near, ptr(f["counters"]), ptr(ws), ws.numel(), st),
+                   "gsl_map_free_select")
+        _lib.check(lib.gsl_map_view_gather(ptr(self.means), ptr(self.colors), self.n_live, ptr(f["means"]),
+                                           ptr(f["colors"]), ptr(f["ids"]), self.capacity, ptr(f["counters"]),
+                                           ptr(ws), ws.numel(), st), "gsl_map_view_gather")
+        stay, _, stored = f["counters"].tolist()  # the call's one synchronisation
+        return stay, stored
+
+    @torch.no_grad()
+    def remove_seen_through(self, depth, K, c2w, near: float) -> Tuple[int, int]:
+        """Removes the live rows that the depth frame [H,W] (metres) at the pose c2w [4,4] sees through (the rule:
+        include/gsloc_hip.h, with ``free_rho`` and ``free_window_px``); the rows that stay keep their order.  Returns
+        (removed, kept).  When something was removed the survivors were compacted into a spare pair of buffers that
+        are ``means`` / ``colors`` from now on (a swap, not a copy -- compacting in place would let a workgroup
+        overwrite rows another has not read yet): views taken from ``points`` / ``point_colors`` before the call are
+        stale, ``survivors`` holds the old row of every live row, and the next ``view_violations`` needs a fresh
+        ``select_view``.  When nothing was removed nothing changes."""
+        if self._free_keep is None:
+            raise RuntimeError("remove_seen_through: MapConfig.free_rho is None, the map only grows")
+        if self.n_live == 0:
+            return 0, 0
+        depth = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
+        if depth.numel() != self.H * self.W:
+            raise ValueError(f"depth is {tuple(depth.shape)}, the map was built for {(self.H, self.W)}")
+        depth = depth.reshape(self.H, self.W).contiguous()
+        intr, w2c = self._view_args(K, c2w)
+        stay, stored = self._free_launch(depth, intr, w2c, self._free_keep, int(self.cfg.free_window_px), float(near))
+        assert stored == stay <= self.n_live, (stay, stored, self.n_live)  # the spare buffers hold the capacity
+        removed, self._n_survivors = self.n_live - stay, stay
+        if removed > 0:
+            f = self._free
+            self.means, f["means"] = f["means"], self.means
+            self.colors, f["colors"] = f["colors"], self.colors
+            self.n_live = stay
+            self._view_rows = -1  # the view ballots describe other rows
+        return removed, stay

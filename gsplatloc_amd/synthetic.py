@@ -92,6 +92,24 @@ def room_depth(W: int, H: int, K: torch.Tensor, c2w: torch.Tensor, half=(2.5, 1.
     return t_best.float()  # ray parameter with d_cam.z = 1 == depth along the optical axis
 
 
+def panel_depth(W: int, H: int, K: torch.Tensor, c2w: torch.Tensor, center=(0.0, 0.0), size=(0.4, 0.3), z: float = 1.5,
+                half=(2.5, 1.5, 3.0)) -> torch.Tensor:
+    """``room_depth`` with a rectangular panel in the room: |x - center[0]| <= size[0] / 2, |y - center[1]| <= size[1] / 2
+    on the plane z = const of the world; the minimum of the two depths where a pixel's ray meets the panel in front of
+    the camera."""
+    dt = torch.float64
+    Kd, Td = K.to(dt), c2w.to(dt)
+    v, u = torch.meshgrid(torch.arange(H, dtype=dt), torch.arange(W, dtype=dt), indexing="ij")
+    d_cam = torch.stack([(u - Kd[0, 2]) / Kd[0, 0], (v - Kd[1, 2]) / Kd[1, 1], torch.ones_like(u)], -1)  # z = 1
+    d_w = d_cam @ Td[:3, :3].T
+    o = Td[:3, 3]
+    t = (z - o[2]) / d_w[..., 2]
+    hit = o[:2] + t[..., None] * d_w[..., :2]
+    on = (t > 1e-6) & ((hit[..., 0] - center[0]).abs() <= size[0] / 2) & ((hit[..., 1] - center[1]).abs() <= size[1] / 2)
+    t = torch.where(on, t, torch.full_like(t, float("inf")))
+    return torch.minimum(room_depth(W, H, K, c2w, half), t.float())
+
+
 def frame_pair(W: int = 160, H: int = 120, rot_deg: float = 0.5, trans: float = 0.01, seed: int = 7) -> Dict:
     """Synthetic GsplatLoc frame pair (/root/reference/src/data/dataset.py:345-383 in miniature):
     target cloud = back-projection of frame 0's depth (pose = identity), query depth = frame 1's depth,
@@ -217,6 +235,26 @@ def write_replica_there_and_back(root, W, H, n_out, rot_deg: float = 0.4, trans:
     return _write_replica_poses(root, W, H, poses + [p.copy() for p in poses[-2::-1]])
 
 
+def write_replica_vanishing_panel(root, W, H, n, n_with, rot_deg: float = 1.0, trans: float = 0.01,
+                                  axis=(0.3, 1.0, -0.2), direction=(0.6, 0.1, 0.8), center=(0.0, 0.0), size=(0.4, 0.3),
+                                  z: float = 1.5):
+    """The constant twist of write_replica_constant_twist, n frames, in a room with a panel (``panel_depth``) that the
+    first ``n_with`` frames show and the others do not: an object that is taken away while the camera looks on.  What it
+    left in a map is in front of everything the later frames observe.  Returns the poses [n,4,4] (float64)."""
+    import numpy as np
+
+    poses, c2w, step = [], np.eye(4), _twist(rot_deg, trans, axis, direction)
+    for i in range(n):
+        if i:
+            c2w = c2w @ step
+        poses.append(c2w.copy())
+
+    def depth_of(i, K, pose):
+        return panel_depth(W, H, K, pose, center, size, z) if i < n_with else room_depth(W, H, K, pose)
+
+    return _write_replica_poses(root, W, H, poses, depth_of)
+
+
 def _twist(rot_deg, trans, axis, direction):
     """4x4 step: rot_deg about ``axis``, ``trans`` metres along ``direction`` (float64)."""
     import numpy as np
@@ -232,9 +270,9 @@ def _twist(rot_deg, trans, axis, direction):
     return step
 
 
-def _write_replica_poses(root, W, H, poses):
+def _write_replica_poses(root, W, H, poses, depth_of=None):
     """The room seen from every pose, in the Replica layout (random images, generator seeded with 11); returns the poses
-    [n,4,4] (float64)."""
+    [n,4,4] (float64).  ``depth_of(i, K, c2w)``: frame i's depth image instead of the empty room's."""
     import json
 
     import numpy as np
@@ -248,7 +286,8 @@ def _write_replica_poses(root, W, H, poses):
     (root / "cam_params.json").write_text(json.dumps(cam))
     rng = np.random.default_rng(11)
     for i, c2w in enumerate(poses):
-        depth = room_depth(W, H, K, torch.from_numpy(c2w).float()).numpy()
+        pose = torch.from_numpy(c2w).float()
+        depth = (room_depth(W, H, K, pose) if depth_of is None else depth_of(i, K, pose)).numpy()
         Image.fromarray(np.round(depth * 6553.5).astype(np.uint16)).save(d / f"depth{i:06d}.png")
         Image.fromarray(rng.integers(0, 255, (H, W, 3), dtype=np.uint8)).save(d / f"frame{i:06d}.jpg")
     with open(root / "room0" / "traj.txt", "w") as f:

@@ -180,6 +180,33 @@ int gsl_map_view_gather(const float* means, const float* colors, int64_t n_rows,
                         float* out_colors, int32_t* out_ids, int64_t out_capacity, int32_t* counters, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ---- free space: the rows of the map that a depth frame sees through are removed (csrc/map_free.hip) ----
+ * depth[height,width] float32 on the device, row-major: the observed depth, metres.  Row i of means[n_rows,3], with
+ * w2c[16] (world to camera, row-major, on the device):
+ *   x = ((w0 px + w1 py) + w2 pz) + w3, and y, z likewise from rows 1 and 2 of w2c;
+ *   u = fx x / z + cx, v = fy y / z + cy;  uf = rintf(u), vf = rintf(v) (round half to even);
+ *   TESTED  when z > near_plane and 0 <= uf <= width - 1 and 0 <= vf <= height - 1 (float comparisons, then the
+ *           conversion to int; uf = -0 passes and is column 0);
+ *   BLOCKED when some pixel (uf + du, vf + dv), |du|, |dv| <= window_px, that lies inside the image has a depth d
+ *           that is not (finite and > 0), or not (z < d * keep); pixels of the window outside the image are skipped;
+ *   REMOVED when tested and not blocked.
+ * float32, evaluated exactly as written (no fused operation, correctly rounded division, d * keep one rounded
+ * product), comparisons false for a NaN: NaN / inf rows, rows behind near_plane and rows outside the image are kept,
+ * and so is a row with a pixel without depth in its window.  keep is 1 - rho, the float32 difference taken by the
+ * caller.  counters is int32[3].
+ *
+ * gsl_map_free_select: evaluates the rule and leaves, in ws (gsl_map_view_ws_bytes(n_rows), the layout of
+ *   gsl_map_view_select), one ballot per wave of the rows that STAY and the row offset of every workgroup;
+ *   counters[0] = rows that stay, counters[1] = counters[2] = 0.  gsl_map_view_gather on the same rows and the same,
+ *   untouched ws then moves the survivors, in ascending row index, into another buffer (out_ids: the old row of every
+ *   survivor; counters[2]: rows stored).  Not in place: a workgroup would overwrite rows another has not read yet.
+ * Returns GSL_ERR_BAD_ARG before any launch for a NULL means, w2c, depth, counters or ws, n_rows <= 0 or >= 2^31,
+ * width or height <= 0 or width * height > 2^31 - 1, fx or fy not non-zero, keep outside (0, 1], window_px outside
+ * 0..3; and GSL_ERR_WORKSPACE for a workspace smaller than gsl_map_view_ws_bytes. */
+int gsl_map_free_select(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx, float cy,
+                        const float* depth, int width, int height, float keep, int window_px, float near_plane,
+                        int32_t* counters, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- spherical harmonics: gsplat.spherical_harmonics fwd/bwd (IDX:14306, IDX:14297) ----
  * dirs[M,3], coeffs[M,K,3] with K >= (degree+1)^2, masks[M] (uint8, may be NULL).
  * degree 0..3.  v_dirs may be NULL. */

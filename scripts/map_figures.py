@@ -4,10 +4,12 @@ JSON line per configuration (the second pass of each: every buffer warm), then t
 there-and-back sequence: wall time, synchronised, of the extra render, of insert_frame (two entry points and the
 read-back) and of building a tracker, per frame, beside the frame's total -- its return half adds nothing, so the
 tracker is kept there.  The sweep row ("Local map" in NOTES.md): a camera that keeps turning, map mode against the
-whole map beside map mode against the part in view, and the host cost of the selection and the check.
+whole map beside map mode against the part in view, and the host cost of the selection and the check.  The vanish row
+("Free space" in NOTES.md): a panel that is taken away while the camera looks on, map mode without and with the removal
+of the rows a frame sees through (MapConfig.free_rho), and the host cost of the removal.
 
-    python scripts/map_figures.py [--frames 20] [--size 640 480] [--only there_and_back | sweep] [--no-cost]
-                                  [--sweep DEG FRAMES GUARD_PX]"""
+    python scripts/map_figures.py [--frames 20] [--size 640 480] [--only there_and_back | sweep | vanish] [--no-cost]
+                                  [--sweep DEG FRAMES GUARD_PX] [--vanish FRAMES WITH RHO WINDOW_PX]"""
 import argparse
 import json
 import os
@@ -20,12 +22,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gsplatloc_amd.data import Parser  # noqa: E402
-from gsplatloc_amd.eval import evaluate_room  # noqa: E402
+from gsplatloc_amd.eval import evaluate_room, rmse  # noqa: E402
 from gsplatloc_amd.localizer import Localizer  # noqa: E402
 from gsplatloc_amd.mapping import MapConfig  # noqa: E402
 from gsplatloc_amd.my_gsplat import TrackerConfig  # noqa: E402
 from gsplatloc_amd.synthetic import (write_replica_constant_twist, write_replica_sequence,  # noqa: E402
-                                     write_replica_there_and_back)
+                                     write_replica_there_and_back, write_replica_vanishing_panel)
 
 
 def timed(fn, sink):
@@ -98,6 +100,52 @@ def sweep(W, H, n, deg, guard, cost=True):
                                      "tracked": tracked, "map_gaussians": loc.map.n_live}), flush=True)
 
 
+def vanish(W, H, n, n_with, rho, window, cost=True):
+    """A panel 0.4 x 0.3 m at z = 1.5 m that the first ``n_with`` of ``n`` frames show (the constant twist, 1 degree and
+    1 cm per frame): map mode without removal beside map mode with ``free_rho``, alternating in one process, the second
+    pass of each reported -- ATE / AAE, the error, the rows added and removed per frame, and the ghost rows (within 1 cm
+    of the panel's plane, inside its rectangle widened by 1 cm) left in the map at the end; then the per-frame host cost
+    of remove_seen_through (wall time, synchronised on both sides, the read-back included) in a pass of its own."""
+    root = pathlib.Path(tempfile.mkdtemp())
+    write_replica_vanishing_panel(root, W, H, n, n_with)
+    parser = Parser("Replica", "room0", normalize=True, input_folder=str(root))
+
+    def run(free_rho, sink=None):
+        depth, rgb, pose = parser.frame(0)
+        loc = Localizer(parser.K, W, H, TrackerConfig(max_steps=2000), mode="map",
+                        map_config=MapConfig(free_rho=free_rho, free_window_px=window))
+        if sink is not None:
+            loc.map.remove_seen_through = timed(loc.map.remove_seen_through, sink)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        loc.reset(depth, rgb, pose)
+        res = []
+        for i in range(1, len(parser) + 1):
+            depth, rgb, pose = parser.frame(i)
+            res.append(loc.track(depth, rgb, gt_c2w=pose))
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        p = loc.map.points
+        ghosts = int(((p[:, 2] - 1.5).abs() <= 0.01).logical_and(p[:, 0].abs() <= 0.21).logical_and(p[:, 1].abs() <= 0.16)
+                     .sum())
+        return {"free_rho": free_rho, "free_window_px": window, "ATE": rmse([r.eT for r in res]),
+                "AAE": rmse([r.eR for r in res]), "eT_per_frame": [float("%.3e" % r.eT) for r in res],
+                "added_per_frame": [r.added for r in res], "removed_per_frame": [r.removed for r in res],
+                "steps": [r.steps for r in res], "lost_frames": sum(r.lost for r in res), "ghost_rows_left": ghosts,
+                "map_gaussians": loc.map.n_live, "frames": len(res), "seconds": dt, "frames_per_s": len(res) / dt}
+
+    for _ in range(2):
+        rows = [run(r) for r in (None, rho)]
+    for r in rows:
+        print("MAP_FIG " + json.dumps({"sequence": f"vanish {n_with} of {n}", "map": True, **r}), flush=True)
+    if cost:
+        sink = []
+        r = run(rho, sink)
+        print("FREE_COST " + json.dumps({"remove_seen_through_ms": [round(1e3 * x, 3) for x in sink],
+                                         "removed": r["removed_per_frame"], "map_gaussians": r["map_gaussians"]}),
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20)
@@ -106,8 +154,14 @@ def main():
     ap.add_argument("--no-cost", action="store_true")
     ap.add_argument("--sweep", type=float, nargs=3, default=[2.0, 24, 8.0], metavar=("DEG", "FRAMES", "GUARD_PX"),
                     help="the sweep row (--only sweep): degrees per frame, frames, view_guard_px")
+    ap.add_argument("--vanish", type=float, nargs=4, default=[12, 4, 0.05, 1],
+                    metavar=("FRAMES", "WITH", "RHO", "WINDOW_PX"),
+                    help="the vanish row (--only vanish): frames, how many of them show the panel, free_rho, "
+                         "free_window_px")
     a = ap.parse_args()
     (W, H), n = a.size, a.frames
+    if a.only in (None, "vanish"):
+        vanish(W, H, int(a.vanish[0]), int(a.vanish[1]), a.vanish[2], int(a.vanish[3]), cost=not a.no_cost)
     if a.only in (None, "sweep"):
         sweep(W, H, int(a.sweep[1]), a.sweep[0], a.sweep[2], cost=not a.no_cost)
     writers = (("random_walk", lambda root: write_replica_sequence(root, W, H, n)),
