@@ -20,8 +20,10 @@
 // 4, the depth channel's colour is Q0.z, "ED" folded into the upstream gradient as gsl_fused_raster_bwd does) and
 // evaluates alpha with the operations of the fused forward (raster_px.hip); the staged one reads the SoA arrays of
 // gsl_rasterize_fwd (any channel count it supports, backgrounds) with that forward's operations (raster.hip).  Both
-// take the forward's alpha >= 1/255 decision for every (pixel, entry) pair.
+// take the forward's alpha >= 1/255 decision for every (pixel, entry) pair -- FUSED through the functions the fused forward
+// itself calls (composite_dev.h: stage_conic, sigma_log2e), which also holds the kernel's opening steps.
 #include "gsloc_internal.h"
+#include "composite_dev.h"
 
 namespace gsl {
 
@@ -51,61 +53,45 @@ __global__ __launch_bounds__(256) void k_absgrad(
     const float* __restrict__ v_render, const float* __restrict__ v_alphas, const uint32_t* __restrict__ isect_hits,
     const int32_t* __restrict__ isect_hit_counts, float* __restrict__ absgrad) {
   constexpr bool RGB = FUSED && D >= 3;
-  constexpr bool DEPTH = FUSED && (D == 1 || D == 4);
   __shared__ AbStage<D, FUSED> sb;
   const int tile = (int)blockIdx.x;
-  const int tyi = tile / tile_w, txi = tile - tyi * tile_w;
   const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int j = txi * 16 + (wv & 1) * 8 + (lane & 7), i = tyi * 16 + (wv >> 1) * 8 + (lane >> 3);
-  const float px = (float)j + 0.5f, py = (float)i + 0.5f;
-  const bool inside = (i < H) && (j < W);
+  const TilePixel tp = quadrant_pixel<false>(tile, tile_w, wv, lane);
+  const bool inside = pixel_inside(tp, W, H, 0, H);
 
-  long long rs = tile_offsets[tile], re = tile_offsets[tile + 1];
-  if (re > capacity) re = capacity;
-  if (rs >= re) return;
+  ListSpan sp = tile_span(tile_offsets, tile, capacity);
+  if (sp.rs >= sp.re) return;
 
-  // per pixel: the backward's starting state (raster_g16.hip qraster_bwd_item / raster.hip k_raster_bwd)
-  const size_t pid = inside ? ((size_t)i * W + j) : 0;
-  const int bin_final = inside ? last_ids[pid] : -1;
+  // per pixel: the backward's starting state
+  const size_t pid = pixel_index(tp, W, inside);
+  const int bin_final = last_composited(last_ids, pid, inside);
   float vc[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) vc[k] = inside ? v_render[pid * D + k] : 0.f;
-  const float Aimg = inside ? alphas[pid] : 0.f;
-  const float T_final = 1.f - Aimg;
-  float va = inside ? v_alphas[pid] : 0.f;
-  if (FUSED && ED && inside) {
-    const EdGrad g = ed_backward(Aimg, render[pid * D + (D - 1)], va, vc[D - 1]);
-    va = g.va;
-    vc[D - 1] = g.vd;
-  }
-  float Bp = -T_final * va;  // v_alpha = T c.v - (buf.v + this) / (1 - alpha): the alpha and background terms
-  if (!FUSED && backgrounds) {
+  load_upstream<D>(v_render, pid, inside, vc);
+  const BwdStart st = bwd_start<D, FUSED && ED>(alphas, render, v_alphas, pid, inside, vc);
+  float Bp = st.Bp();
+  if (!FUSED && backgrounds) {  // (the staged forward's background term)
     float bg_dot = 0.f;
 #pragma unroll
     for (int k = 0; k < D; ++k) bg_dot += backgrounds[k] * vc[k];
-    Bp += T_final * bg_dot;
+    Bp += st.T_final * bg_dot;
   }
-  float T = T_final;
+  float T = st.T_final;
 
-  // nothing behind the last entry a pixel of the tile composited
-  int qfin = bin_final;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) qfin = max(qfin, __shfl_xor(qfin, o, 64));
+  const int qfin = wave_max(bin_final);
   if (lane == 0) sb.fin[wv] = qfin;
   // this quadrant's hit list (gsl_fused_raster_fwd): entries in list order, at 4 start + quadrant x length
   const uint32_t* qh = nullptr;
   int hp = 0;
   if (FUSED && isect_hits) {
-    qh = isect_hits + 4 * rs + (long long)wv * (re - rs);
+    qh = isect_hits + 4 * sp.rs + (long long)wv * (sp.re - sp.rs);
     hp = isect_hit_counts[tile * 4 + wv];
   }
   __syncthreads();
-  const int tfin = max(max(sb.fin[0], sb.fin[1]), max(sb.fin[2], sb.fin[3]));
-  if ((long long)tfin + 1 < re) re = (long long)tfin + 1;
+  block_last_trim(sb.fin, sp);  // nothing behind the last entry a pixel of the tile composited
 
   const unsigned long long lt = (1ull << lane) - 1ull;
-  for (long long hi = re; hi > rs; hi -= GSL_AB_CH) {
-    const long long lo = max(hi - (long long)GSL_AB_CH, rs);
+  for (long long hi = sp.re; hi > sp.rs; hi -= GSL_AB_CH) {
+    const long long lo = max(hi - (long long)GSL_AB_CH, sp.rs);
     const int n = (int)(hi - lo);
     __syncthreads();  // (the previous chunk's flush has read id / acc)
     if (tid < n) {  // slot t <-> list index lo + t
@@ -128,11 +114,11 @@ __global__ __launch_bounds__(256) void k_absgrad(
     // one (quadrant, entry) trip: this lane's pixel's contribution, reduced over the wave when any lane has one
     auto trip = [&](int t) {
       const float4 c0 = sb.s0[t], c1 = sb.s1[t];
-      const float dx = c0.x - px, dy = c0.y - py;
+      const float dx = c0.x - tp.px, dy = c0.y - tp.py;
       float sigma, vis, opv;
-      if (FUSED) {  // the fused forward's expression: conic times log2 e, diagonal halved, exp2
-        const float ca = c1.x * (0.5f * GSL_LOG2E), cb = c1.y * GSL_LOG2E, cc = c1.z * (0.5f * GSL_LOG2E);
-        sigma = fmaf(cb * dx, dy, fmaf(ca * dx, dx, cc * dy * dy));
+      if (FUSED) {  // the fused forward's
+        const float3 cn = stage_conic(c1);
+        sigma = sigma_log2e(cn.x, cn.y, cn.z, dx, dy);
         vis = __builtin_amdgcn_exp2f(-sigma);
         opv = c0.w * vis;
       } else {  // gsl_rasterize_fwd's
@@ -150,11 +136,7 @@ __global__ __launch_bounds__(256) void k_absgrad(
         const float fac = alpha * T;
         float cdot = 0.f;
         if (FUSED) {
-          if (RGB) {
-            const float4 q2 = sb.s2[t];
-            cdot = q2.x * vc[0] + q2.y * vc[1] + q2.z * vc[2];
-          }
-          if (DEPTH) cdot += c0.z * vc[D - 1];
+          cdot = colour_dot<D>(sb.s2, t, c0.z, vc);
         } else {
 #pragma unroll
           for (int k = 0; k < D; ++k) cdot += sb.col[t * D + k] * vc[k];
@@ -224,12 +206,12 @@ extern "C" int gsl_fused_absgrad(const float* Q0, const float* Q1, const float* 
                                  const uint32_t* isect_hits, const int32_t* isect_hit_counts, float* absgrad,
                                  void* stream) {
   if (!gsl::frame_ok(width, height, tile_w, tile_h, 0, tile_h, capacity, 0, height)) return GSL_ERR_BAD_ARG;  // (whole frame)
-  if (!(channels == 1 || channels == 3 || channels == 4) || (ed && channels == 3)) return GSL_ERR_BAD_ARG;
+  if (!(channels == 1 || channels == 3 || channels == 4) || !gsl::ed_ok(channels, ed)) return GSL_ERR_BAD_ARG;
   if (!tile_offsets || !alphas || !last_ids || !v_render || !v_alphas || !absgrad) return GSL_ERR_BAD_ARG;
   if (ed && !render) return GSL_ERR_BAD_ARG;
   if ((isect_hits == nullptr) != (isect_hit_counts == nullptr)) return GSL_ERR_BAD_ARG;
   if (isect_hits && capacity >= ((int64_t)1 << GSL_HIT_SHIFT)) return GSL_ERR_BAD_ARG;
-  if (capacity > 0 && (!Q0 || !Q1 || !flatten_ids || (channels >= 3 && !Q2))) return GSL_ERR_BAD_ARG;
+  if (capacity > 0 && (!flatten_ids || !gsl::records_ok(nullptr, Q0, Q1, Q2, channels))) return GSL_ERR_BAD_ARG;
   if (capacity == 0) return GSL_OK;
   hipStream_t st = (hipStream_t)stream;
 #define CALL_AB(DD, EE)                                                                                               \

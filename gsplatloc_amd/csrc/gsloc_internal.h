@@ -66,6 +66,13 @@ static inline bool frame_ok(int width, int height, int tile_w, int tile_h, int t
     return false;
   return !cover || (tile_w * 16 >= width && tile_h * 16 >= height);
 }
+// The records of this channel count are there (the fp16-staged array Qh, or Q0 / Q1 and Q2 where there are colours), and
+// no expected depth without a depth channel.  Two calls, because the entry points place them on either side of their
+// early "nothing to do" returns, and the status of every bad argument is pinned (tests/test_entry_checks_cpu.py).
+static inline bool records_ok(const void* Qh, const float* Q0, const float* Q1, const float* Q2, int channels) {
+  return Qh || (Q0 && Q1 && (channels < 3 || Q2));
+}
+static inline bool ed_ok(int channels, int ed) { return !(ed && channels == 3); }
 
 }  // namespace gsl
 

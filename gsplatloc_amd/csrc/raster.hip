@@ -9,7 +9,9 @@
 // bounding box of the alpha >= 1/255 ellipse) and then walks only the set bits.  Skipped
 // splats are exactly those the reference loop would `continue` over, so results are
 // unchanged.  Termination (T <= 1e-4) is tracked per lane and voted per wave and per block.
-#include "gsloc_common.h"
+// List span, lane -> pixel and the backward's starting state and list trim: composite_dev.h (no expected depth here, and
+// the background term is added in these kernels).
+#include "composite_dev.h"
 
 namespace gsl {
 
@@ -46,19 +48,17 @@ __global__ __launch_bounds__(256) void k_raster_fwd(
     float* __restrict__ render_colors, float* __restrict__ render_alphas, int32_t* __restrict__ last_ids) {
   __shared__ Batch<D> sb;
   int tile = ty0 * tile_w + blockIdx.x;
-  int tyi = tile / tile_w, txi = tile - tyi * tile_w;
-  int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int qx = txi * 16 + (wv & 1) * 8, qy = tyi * 16 + (wv >> 1) * 8;  // quadrant origin
-  int j = qx + (lane & 7), i = qy + (lane >> 3);
-  float px = (float)j + 0.5f, py = (float)i + 0.5f;
-  bool inside = (i < H) && (j < W);
+  int tid = threadIdx.x, lane = tid & 63;
+  const TilePixel tp = quadrant_pixel<false>(tile, tile_w, tid >> 6, lane);
+  const int qx = tp.qx, qy = tp.qy;
+  const float px = tp.px, py = tp.py;
+  bool inside = pixel_inside(tp, W, H, 0, H);
   bool done = !inside;
   // quadrant bounds in pixel-centre coordinates
   float qx0 = (float)qx + 0.5f, qx1 = (float)qx + 7.5f, qy0 = (float)qy + 0.5f, qy1 = (float)qy + 7.5f;
 
-  long long rs = tile_offsets[tile], re = tile_offsets[tile + 1];
-  if (re > capacity) re = capacity;
-  if (rs > re) rs = re;
+  const ListSpan sp = tile_span(tile_offsets, tile, capacity);
+  const long long rs = min(sp.rs, sp.re), re = sp.re;
   int nb = (int)((re - rs + 255) / 256);
 
   float T = 1.f;
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void k_raster_fwd(
     }
   }
   if (inside) {
-    size_t pid = (size_t)i * W + j;
+    size_t pid = pixel_index(tp, W, true);
     render_alphas[pid] = 1.f - T;
 #pragma unroll
     for (int k = 0; k < D; ++k)
@@ -159,41 +159,36 @@ __global__ __launch_bounds__(256) void k_raster_bwd(
   constexpr int AS = vacc_stride(D);
   __shared__ BatchB<D> sb;
   int tile = ty0 * tile_w + blockIdx.x;
-  int tyi = tile / tile_w, txi = tile - tyi * tile_w;
   int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int qx = txi * 16 + (wv & 1) * 8, qy = tyi * 16 + (wv >> 1) * 8;
-  int j = qx + (lane & 7), i = qy + (lane >> 3);
-  float px = (float)j + 0.5f, py = (float)i + 0.5f;
-  bool inside = (i < H) && (j < W);
+  const TilePixel tp = quadrant_pixel<false>(tile, tile_w, wv, lane);
+  const int qx = tp.qx, qy = tp.qy;
+  const float px = tp.px, py = tp.py;
+  bool inside = pixel_inside(tp, W, H, 0, H);
   float qx0 = (float)qx + 0.5f, qx1 = (float)qx + 7.5f, qy0 = (float)qy + 0.5f, qy1 = (float)qy + 7.5f;
 
-  long long rs = tile_offsets[tile], re = tile_offsets[tile + 1];
-  if (re > capacity) re = capacity;
-  if (rs >= re) return;
+  ListSpan sp = tile_span(tile_offsets, tile, capacity);
+  if (sp.rs >= sp.re) return;
 
-  size_t pid = inside ? ((size_t)i * W + j) : 0;
-  float T_final = inside ? (1.f - render_alphas[pid]) : 1.f;
-  float T = T_final;
-  int bin_final = inside ? last_ids[pid] : -1;
+  size_t pid = pixel_index(tp, W, inside);
+  int bin_final = last_composited(last_ids, pid, inside);
   float vc[D], buf[D];
-  float va = inside ? v_render_alphas[pid] : 0.f;
-  float bg_dot = 0.f;
+  load_upstream<D>(v_render_colors, pid, inside, vc);
+  const BwdStart st = bwd_start<D, false>(render_alphas, nullptr, v_render_alphas, pid, inside, vc);
+  const float T_final = st.T_final, va = st.va;
+  float T = T_final;
+  float bg_dot = 0.f;  // the background term is this kernel's own
 #pragma unroll
   for (int k = 0; k < D; ++k) {
-    vc[k] = inside ? v_render_colors[pid * D + k] : 0.f;
     buf[k] = 0.f;
     if (backgrounds) bg_dot += backgrounds[k] * vc[k];
   }
   // the deepest splat any pixel of the quadrant / tile composited bounds the work
-  int wave_final = bin_final;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) wave_final = max(wave_final, __shfl_xor(wave_final, o, 64));
+  int wave_final = wave_max(bin_final);
   __shared__ int s_block_final[4];
   if (lane == 0) s_block_final[wv] = wave_final;
   __syncthreads();
-  int block_final = max(max(s_block_final[0], s_block_final[1]), max(s_block_final[2], s_block_final[3]));
-  // nothing behind block_final was composited by any pixel: start there
-  if ((long long)block_final + 1 < re) re = max((long long)block_final + 1, rs);
+  block_last_trim(s_block_final, sp);
+  const long long rs = sp.rs, re = sp.re;
   if (rs >= re) return;
   int nb = (int)((re - rs + 255) / 256);
 

@@ -17,8 +17,10 @@
 // own) and stores it in the row of its INTERSECTION, vrow[capacity][16] (zero rows included; rows of entries that are
 // not walked are zeroed up front).  No atomic anywhere: the projection backward (fused_project_bwd.hip) finds a Gaussian's
 // rows by binary search in the sorted tile lists and adds them in tile order.  The matrix pipe runs beside the vector
-// pipe, so the reduction costs the walk ~2 LDS stores per splat.
+// pipe, so the reduction costs the walk ~2 LDS stores per splat.  The kernel's opening (list span, lane -> pixel, starting
+// state, trim to the tile's last composited entry) is composite_dev.h's; alpha here is the __expf form.
 #include "gsloc_internal.h"
+#include "composite_dev.h"
 
 namespace gsl {
 
@@ -86,7 +88,6 @@ __device__ __forceinline__ void mraster_bwd_body(
     long long re, int nb, int tid, float px, float py, float qcx, float qcy, float tcx, float tcy, bool inside,
     int bin_final, int wave_final, float T_final, const float (&vc)[D], float va) {
   constexpr bool RGB = D >= 3;
-  constexpr bool DEPTH = (D == 1) || (D == 4);
   constexpr int A = FStageM<D>::A;
   constexpr int AP = FStageM<D>::AP;
   constexpr int NW = FStageM<D>::NW;
@@ -203,17 +204,7 @@ __device__ __forceinline__ void mraster_bwd_body(
           float ra = __builtin_amdgcn_rcpf(1.f - am);
           T *= ra;
           float fac = am * T;
-          float cdot;
-          if (CG == D) {
-            cdot = 0.f;
-            if (RGB) {
-              float4 q2 = sb.s2[t];
-              cdot = q2.x * vc[0] + q2.y * vc[1] + q2.z * vc[2];
-            }
-            if (DEPTH) cdot += q0.z * vc[D - 1];
-          } else {
-            cdot = q0.z * vc[D - 1];
-          }
+          const float cdot = (CG == D) ? colour_dot<D>(sb.s2, t, q0.z, vc) : q0.z * vc[D - 1];
           float v_alpha = T * cdot - ra * Bp;
           Bp += fac * cdot;
           float vism = sel(validm & capm, vis, 0.f);  // alpha clamped at 0.999 => no geometric gradient
@@ -296,43 +287,29 @@ __global__ __launch_bounds__(256) void k_mraster_bwd(
   __shared__ FStageM<D> sb;
   __shared__ int s_final[4];
   int tile = ty0 * tile_w + GSL_TILE_OF_BLOCK();
-  int tyi = tile / tile_w, txi = tile - tyi * tile_w;
   int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int qx = txi * 16 + (wv & 1) * 8, qy = tyi * 16 + (wv >> 1) * 8;
-  int j = qx + (lane & 7), i = qy + (lane >> 3);
-  float px = (float)j + 0.5f, py = (float)i + 0.5f;
-  bool inside = (i < H) && (j < W) && (i >= row0) && (i < row1);
-  float qcx = (float)qx + 4.f, qcy = (float)qy + 4.f;
-  float tcx = (float)(txi * 16) + 8.f, tcy = (float)(tyi * 16) + 8.f;
+  const TilePixel tp = quadrant_pixel<false>(tile, tile_w, wv, lane);
+  bool inside = pixel_inside(tp, W, H, row0, row1);
+  float qcx = (float)tp.qx + 4.f, qcy = (float)tp.qy + 4.f;
+  float tcx = (float)(tp.txi * 16) + 8.f, tcy = (float)(tp.tyi * 16) + 8.f;
 
-  long long rs = tile_offsets[tile], re = tile_offsets[tile + 1];
-  if (re > capacity) re = capacity;
-  if (rs >= re) return;
+  ListSpan sp = tile_span(tile_offsets, tile, capacity);
+  if (sp.rs >= sp.re) return;
 
-  size_t pid = inside ? ((size_t)i * W + j) : 0;
-  float Aimg = inside ? alphas[pid] : 0.f;
-  float T_final = 1.f - Aimg;
-  int bin_final = inside ? last_ids[pid] : -1;
+  size_t pid = pixel_index(tp, W, inside);
+  int bin_final = last_composited(last_ids, pid, inside);
   float vc[D];
-  float va = inside ? v_alphas[pid] : 0.f;
-#pragma unroll
-  for (int k = 0; k < D; ++k) vc[k] = inside ? v_render[pid * D + k] : 0.f;
-  if (ED && inside) {
-    const EdGrad g = ed_backward(Aimg, render[pid * D + (D - 1)], va, vc[D - 1]);
-    va = g.va;
-    vc[D - 1] = g.vd;
-  }
-  int wave_final = bin_final;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) wave_final = max(wave_final, __shfl_xor(wave_final, o, 64));
+  load_upstream<D>(v_render, pid, inside, vc);
+  const BwdStart st = bwd_start<D, ED>(alphas, render, v_alphas, pid, inside, vc);
+  int wave_final = wave_max(bin_final);
   if (lane == 0) s_final[wv] = wave_final;
   bool rgb_grad = false;
   if (D == 4) rgb_grad = (vc[0] != 0.f) || (vc[1] != 0.f) || (vc[2] != 0.f);
-  int any_rgb = __syncthreads_or(rgb_grad);
-  int block_final = max(max(s_final[0], s_final[1]), max(s_final[2], s_final[3]));
-  // nothing behind block_final was composited by any pixel of the tile: start there
-  long long re_all = re;
-  if ((long long)block_final + 1 < re) re = max((long long)block_final + 1, rs);
+  int any_rgb = __syncthreads_or(rgb_grad);  // (also the barrier in front of block_last_trim)
+  // nothing behind the tile's last composited entry is walked
+  const long long re_all = sp.re;
+  block_last_trim(s_final, sp);
+  const long long rs = sp.rs, re = sp.re;
   {  // rows of the entries that are not walked are zero
     float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     for (long long q = 4 * re + tid; q < 4 * re_all; q += 256) reinterpret_cast<float4*>(vacc)[q] = z;
@@ -340,11 +317,11 @@ __global__ __launch_bounds__(256) void k_mraster_bwd(
   if (rs >= re) return;
   int nb = (int)((re - rs + GSL_MB - 1) / GSL_MB);
   if (D == 4 && !any_rgb)
-    mraster_bwd_body<D, 1>(sb, Q0, Q1, Q2, Qh, flatten_ids, vacc, rs, re, nb, tid, px, py, qcx, qcy, tcx, tcy, inside,
-                           bin_final, wave_final, T_final, vc, va);
+    mraster_bwd_body<D, 1>(sb, Q0, Q1, Q2, Qh, flatten_ids, vacc, rs, re, nb, tid, tp.px, tp.py, qcx, qcy, tcx, tcy, inside,
+                           bin_final, wave_final, st.T_final, vc, st.va);
   else
-    mraster_bwd_body<D, D>(sb, Q0, Q1, Q2, Qh, flatten_ids, vacc, rs, re, nb, tid, px, py, qcx, qcy, tcx, tcy, inside,
-                           bin_final, wave_final, T_final, vc, va);
+    mraster_bwd_body<D, D>(sb, Q0, Q1, Q2, Qh, flatten_ids, vacc, rs, re, nb, tid, tp.px, tp.py, qcx, qcy, tcx, tcy, inside,
+                           bin_final, wave_final, st.T_final, vc, st.va);
 }
 
 int launch_mraster_bwd(const float* Q0, const float* Q1, const float* Q2, int channels, int ed, int width, int height,

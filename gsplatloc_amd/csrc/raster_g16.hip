@@ -25,7 +25,10 @@
 //      [v_xy | v_conic | v_opacity | v_colour] (the splat's own centre, conic and opacity), and the rows leave as
 //      packed 64-byte global atomics, one per (quadrant, entry) with a composited pixel.
 // A row list longer than LCAP entries in one batch is walked in rounds of LCAP trips.
+// An item's opening (list span, the forward's lane -> pixel map, starting state, trim to the quadrant's last composited
+// entry) and the forward's alpha expression (stage_conic, sigma_log2e) are composite_dev.h's.
 #include "gsloc_internal.h"
+#include "composite_dev.h"
 #include "long_dev.h"
 
 namespace gsl {
@@ -189,7 +192,6 @@ __device__ __forceinline__ void qraster_bwd_body(
     long long re, int lane, int quad, float px, float py, float tx0, float ty0, int bin_final, float T_init,
     float Bp_init, const float (&vc)[D], const uint32_t* __restrict__ qhits, int n_qhits) {
   constexpr bool RGB = D >= 3;
-  constexpr bool DEPTH = (D == 1) || (D == 4);
   constexpr int NV = QStage<D, CG>::NV;
   constexpr int NS = QStage<D, CG>::NS;
   constexpr int A = QStage<D, CG>::A;
@@ -294,11 +296,8 @@ __device__ __forceinline__ void qraster_bwd_body(
       if (__builtin_amdgcn_inverse_ballot_w64(R)) {
         sb.id[slot] = gid;
         sb.s0[slot] = r0;
-        // the conic as the FORWARD stages it (times log2 e, diagonal halved: raster_px.hip praster_walk), so that a trip
-        // evaluates alpha with the forward's very operations and both sides take the same alpha >= 1/255 decision for
-        // every (pixel, entry) pair; the flush scales back
-        sb.s1[slot] = make_float4(r1.x * (0.5f * GSL_LOG2E), r1.y * GSL_LOG2E, r1.z * (0.5f * GSL_LOG2E),
-                                  __int_as_float((int)idx));
+        const float3 cn = stage_conic(r1);  // (the flush scales back)
+        sb.s1[slot] = make_float4(cn.x, cn.y, cn.z, __int_as_float((int)idx));
         if (RGB && CG == D) sb.s2[slot] = r2;
 #pragma unroll
         for (int w = 0; w < NG / 4; ++w) sb.posn[w][slot] = pack[w];
@@ -329,7 +328,7 @@ __device__ __forceinline__ void qraster_bwd_body(
     // = what this lane stores of them.
     auto trip = [&](int t, const float4& c0, const float4& c1, float4& r, float4& r2) {
       float dx = c0.x - px, dy = c0.y - py;
-      float sigma = fmaf(c1.y * dx, dy, fmaf(c1.x * dx, dx, c1.z * dy * dy));  // log2(e) sigma, the forward's expression
+      float sigma = sigma_log2e(c1.x, c1.y, c1.z, dx, dy);
       float vis = __builtin_amdgcn_exp2f(-sigma);
       float opv = c0.w * vis;
       float alpha = fminf(GSL_ALPHA_MAX, opv);
@@ -353,17 +352,7 @@ __device__ __forceinline__ void qraster_bwd_body(
         float ra = __builtin_amdgcn_rcpf(1.f - am);
         T *= ra;
         float fac = am * T;
-        float cdot;
-        if (CG == D) {
-          cdot = 0.f;
-          if (RGB) {
-            float4 q2 = sb.s2[t];
-            cdot = q2.x * vc[0] + q2.y * vc[1] + q2.z * vc[2];
-          }
-          if (DEPTH) cdot += c0.z * vc[D - 1];
-        } else {
-          cdot = c0.z * vc[D - 1];
-        }
+        const float cdot = (CG == D) ? colour_dot<D>(sb.s2, t, c0.z, vc) : c0.z * vc[D - 1];
         float v_alpha = T * cdot - ra * Bp;
         Bp += fac * cdot;
         float w = sel(validm & capm, vis, 0.f) * v_alpha;
@@ -531,6 +520,7 @@ __device__ __forceinline__ void qraster_bwd_item(
     int32_t* __restrict__ rgb_flag, int32_t* __restrict__ clear_counts, int32_t* __restrict__ clear_state) {
   // (a forward that sorted its own bins could not clear the tile counters, raster_px.hip k_praster_fwd SORT: the first
   // launch of the backward does, one lane per tile)
+  // (this kernel's own copy of clear_tile_counter, composite_dev.h, which says why)
   if (!LONG && (CG == 1 || D == 3) && clear_counts && (b & 3) == 0 && threadIdx.x == 0) {
     clear_counts[ty0 * tile_w + (b >> 2)] = 0;  // (any one-to-one map of items to tiles does for clearing)
     if (b == 0 && clear_state) *clear_state = 0;
@@ -549,32 +539,22 @@ __device__ __forceinline__ void qraster_bwd_item(
   } else {
     tile = ty0 * tile_w + item;
   }
-  int tyi = tile / tile_w, txi = tile - tyi * tile_w;
-  int lane = threadIdx.x, grp = lane >> 4, p = lane & 15;
-  int j = txi * 16 + (quad & 1) * 8 + (grp & 1) * 4 + (p & 3);
-  int i = tyi * 16 + (quad >> 1) * 8 + (grp >> 1) * 4 + (p >> 2);
-  float px = (float)j + 0.5f, py = (float)i + 0.5f;
-  bool inside = (i < H) && (j < W) && (i >= row0) && (i < row1);
+  const int lane = threadIdx.x;
+  const TilePixel tp = quadrant_pixel<true>(tile, tile_w, quad, lane);  // (the forward's map, the quadrant from the item)
+  bool inside = pixel_inside(tp, W, H, row0, row1);
 
-  long long rs = tile_offsets[tile], re = tile_offsets[tile + 1];
-  if (re > capacity) re = capacity;
-  if (rs >= re) return;
-  if (!LONG && long_min > 0 && re - rs > long_min) return;
-  if (LONG) {
-    rs += (long long)sgm * GSL_SEG;
-    re = min(rs + (long long)GSL_SEG, re);
-  }
-  size_t pid = inside ? ((size_t)i * W + j) : 0;
-  int bin_final = inside ? last_ids[pid] : -1;
+  ListSpan sp = tile_span(tile_offsets, tile, capacity);
+  if (sp.rs >= sp.re) return;
+  if (!LONG && long_min > 0 && sp.re - sp.rs > long_min) return;
+  if (LONG) sp = segment_span(sp, sgm);
+  size_t pid = pixel_index(tp, W, inside);
+  int bin_final = last_composited(last_ids, pid, inside);
   // nothing behind the last entry a pixel of this quadrant composited: start there (and leave if that is before rs)
-  int quad_final = bin_final;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) quad_final = max(quad_final, __shfl_xor(quad_final, o, 64));
-  if ((long long)quad_final + 1 < re) re = (long long)quad_final + 1;
-  if (rs >= re) return;
+  trim_span(sp, wave_max(bin_final));
+  if (sp.rs >= sp.re) return;
+  // the upstream colour gradient decides whose quadrant this is, before anything else of the pixel is loaded
   float vc[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) vc[k] = inside ? v_render[pid * D + k] : 0.f;
+  load_upstream<D>(v_render, pid, inside, vc);
   if (D == 4) {
     bool rgb_grad = (vc[0] != 0.f) || (vc[1] != 0.f) || (vc[2] != 0.f);
     bool any_rgb = __ballot(rgb_grad) != 0ull;
@@ -583,15 +563,8 @@ __device__ __forceinline__ void qraster_bwd_item(
       return;
     }
   }
-  float Aimg = inside ? alphas[pid] : 0.f;
-  float T_final = 1.f - Aimg;
-  float va = inside ? v_alphas[pid] : 0.f;
-  if (ED && inside) {
-    const EdGrad g = ed_backward(Aimg, render[pid * D + (D - 1)], va, vc[D - 1]);
-    va = g.va;
-    vc[D - 1] = g.vd;
-  }
-  float T_init = T_final, Bp_init = -T_final * va;
+  const BwdStart st = bwd_start<D, ED>(alphas, render, v_alphas, pid, inside, vc);
+  float T_init = st.T_final, Bp_init = st.Bp();
   if (LONG) {
     int nseg = lw.seg_cnt[gseg];
     long long seg_end = min(tile_offsets[tile] + (long long)(sgm + 1) * GSL_SEG, (long long)tile_offsets[tile + 1]);
@@ -631,20 +604,14 @@ __device__ __forceinline__ void qraster_bwd_item(
   const uint32_t* qh = nullptr;
   int nqh = 0;
   if (isect_hits) {
-    long long ls = tile_offsets[tile], le = tile_offsets[tile + 1];
-    if (le > capacity) le = capacity;
-    if (LONG) {
-      ls += (long long)sgm * GSL_SEG;
-      le = min(ls + (long long)GSL_SEG, le);
-      nqh = lw.seg_qcnt[gseg * 4 + quad];
-    } else {
-      nqh = isect_hit_counts[tile * 4 + quad];
-    }
-    qh = isect_hits + 4 * ls + (long long)quad * (le - ls);
+    // (the untrimmed span again)
+    const ListSpan whole = tile_span(tile_offsets, tile, capacity), list = LONG ? segment_span(whole, sgm) : whole;
+    nqh = LONG ? lw.seg_qcnt[gseg * 4 + quad] : isect_hit_counts[tile * 4 + quad];
+    qh = isect_hits + 4 * list.rs + (long long)quad * (list.re - list.rs);
     if (nqh == 0) return;
   }
-  qraster_bwd_body<D, CG>(sb, Q0, Q1, Q2, Qh, flatten_ids, vacc, rs, re, lane, quad, px, py, (float)(txi * 16),
-                          (float)(tyi * 16), bin_final, T_init, Bp_init, vc, qh, nqh);
+  qraster_bwd_body<D, CG>(sb, Q0, Q1, Q2, Qh, flatten_ids, vacc, sp.rs, sp.re, lane, quad, tp.px, tp.py, (float)(tp.txi * 16),
+                          (float)(tp.tyi * 16), bin_final, T_init, Bp_init, vc, qh, nqh);
 }
 
 // One wave per workgroup.  The grid is one workgroup per item for every launch but the full-colour second one of
@@ -738,11 +705,11 @@ extern "C" int gsl_fused_raster_bwd(const float* Q0, const float* Q1, const floa
                                    const int32_t* isect_hit_counts, int long_min, void* clear_ws, void* stream) {
   if (!gsl::frame_ok(width, height, tile_w, tile_h, ty0, ty1, capacity, row0, row1)) return GSL_ERR_BAD_ARG;
   if (!tile_offsets || !render || !alphas || !last_ids || !v_render || !v_alphas) return GSL_ERR_BAD_ARG;
-  if (ed && channels == 3) return GSL_ERR_BAD_ARG;
+  if (!gsl::ed_ok(channels, ed)) return GSL_ERR_BAD_ARG;
   if (capacity == 0 || ty0 == ty1 || row0 == row1) return GSL_OK;
   if (!flatten_ids || (!vacc && !vrow)) return GSL_ERR_BAD_ARG;
   if (isect_hits && !isect_hit_counts) return GSL_ERR_BAD_ARG;
-  if (!Qh && (!Q0 || !Q1 || (channels >= 3 && !Q2))) return GSL_ERR_BAD_ARG;
+  if (!gsl::records_ok(Qh, Q0, Q1, Q2, channels)) return GSL_ERR_BAD_ARG;
   if (vrow && clear_ws) return GSL_ERR_BAD_ARG;  // (the deterministic mode keeps the separate sort launch)
   if (vrow)  // deterministic mode: one row per intersection, plain stores, no atomics anywhere
     return gsl::launch_mraster_bwd(Q0, Q1, Q2, channels, ed, width, height, tile_w, ty0, ty1, tile_offsets, flatten_ids,
@@ -767,9 +734,9 @@ extern "C" int gsl_long_raster_bwd(const float* Q0, const float* Q1, const float
       max_seg <= 0 || !long_ws)
     return GSL_ERR_BAD_ARG;
   if (!tile_offsets || !render || !alphas || !last_ids || !v_render || !v_alphas || !vacc) return GSL_ERR_BAD_ARG;
-  if (ed && channels == 3) return GSL_ERR_BAD_ARG;
+  if (!gsl::ed_ok(channels, ed)) return GSL_ERR_BAD_ARG;
   if (capacity == 0 || ty0 == ty1 || row0 == row1) return GSL_OK;
-  if (!flatten_ids || (!Qh && (!Q0 || !Q1 || (channels >= 3 && !Q2)))) return GSL_ERR_BAD_ARG;
+  if (!flatten_ids || !gsl::records_ok(Qh, Q0, Q1, Q2, channels)) return GSL_ERR_BAD_ARG;
   return g16_raster_bwd_launch(Q0, Q1, Q2, channels, ed, width, height, tile_w, ty0, ty1, tile_offsets, flatten_ids,
                                capacity, render, alphas, last_ids, v_render, v_alphas, vacc, row0, row1, Qh,
                                isect_hits, nullptr, long_min, long_ws, max_seg, 0, nullptr, stream);

@@ -21,7 +21,11 @@
 //
 // Skipped candidates are exactly those the reference loop would `continue` over (alpha < 1/255), so the
 // per-pixel sequence of composited splats -- and therefore every output -- is unchanged.
+// What the kernels here open and close with -- list span, lane -> pixel, the backward's starting state and list trim, the
+// counter clearing, the pixel write-out -- and the alpha expression that forward and backward share (stage_conic,
+// sigma_log2e) are in composite_dev.h.
 #include "gsloc_internal.h"
+#include "composite_dev.h"
 #include "long_dev.h"
 #include "loss_dev.h"
 #include "sort_dev.h"
@@ -209,20 +213,19 @@ __device__ __forceinline__ void praster_walk(
       int g = flatten_ids[bstart + tid];
       float4 r2 = make_float4(0.f, 0.f, 0.f, 0.f);
       load_record(Q0, Q1, Q2, Qh, g, RGB && MODE == 0, r0, r1, r2);
-      // staged for the walk: the conic times log2(e) (and its diagonal halved), so that a trip gets
-      // log2(e) sigma = a' dx^2 + c' dy^2 + b' dx dy in six operations and alpha = opacity exp2(-that) without the scaling
-      // multiply of expf.  Laid out for the trip's LDS reads (round 4; the LDS array was 47 % busy, profiles/r04_*):
+      // staged for the walk: the conic as stage_conic (composite_dev.h) scales it, laid out for the trip's LDS reads
+      // (round 4; the LDS array was 47 % busy, profiles/r04_*):
       //   s0 = (x, y, a', b')   s1 = (c', opacity, r, g)   s2 = (b, depth, r_cull, -)      [colour modes]
       //   s0 = (x, y, a', b')   s1 = (c', opacity, depth, r_cull)                          [depth only]
       // two 16-byte reads and one 8-byte read per candidate (10 LDS cycles) instead of 8 + 4 + 12 + 16 bytes (16 cycles: a
       // 12-byte read costs 8)
-      const float ca = r1.x * (0.5f * GSL_LOG2E), cb = r1.y * GSL_LOG2E, cc = r1.z * (0.5f * GSL_LOG2E);
-      sb.s0[tid] = make_float4(r0.x, r0.y, ca, cb);
+      const float3 cn = stage_conic(r1);
+      sb.s0[tid] = make_float4(r0.x, r0.y, cn.x, cn.y);
       if (RGB) {
-        sb.s1[tid] = make_float4(cc, r0.w, r2.x, r2.y);
+        sb.s1[tid] = make_float4(cn.z, r0.w, r2.x, r2.y);
         sb.s2[tid] = make_float4(r2.z, r0.z, r1.w, 0.f);
       } else {
-        sb.s1[tid] = make_float4(cc, r0.w, r0.z, r1.w);
+        sb.s1[tid] = make_float4(cn.z, r0.w, r0.z, r1.w);
       }
     } else {
       // every slot holds finite numbers: a lane without a candidate reads SOME slot in the straight-line trip and
@@ -284,8 +287,7 @@ __device__ __forceinline__ void praster_walk(
           float4 p0 = rec_at(sb.s0, t0), p1 = rec_at(sb.s1, t0);  // (x, y, a', b'), (c', opacity, r | depth, g | r_cull)
           float4 u0 = rec_at(sb.s0, t1), u1 = rec_at(sb.s1, t1);
           float dx0 = p0.x - px, dy0 = p0.y - py, dx1 = u0.x - px, dy1 = u0.y - py;
-          float sg0 = fmaf(p0.w * dx0, dy0, fmaf(p0.z * dx0, dx0, p1.x * dy0 * dy0));  // log2(e) sigma (see the staging)
-          float sg1 = fmaf(u0.w * dx1, dy1, fmaf(u0.z * dx1, dx1, u1.x * dy1 * dy1));
+          float sg0 = sigma_log2e(p0.z, p0.w, p1.x, dx0, dy0), sg1 = sigma_log2e(u0.z, u0.w, u1.x, dx1, dy1);
           float al0 = fminf(GSL_ALPHA_MAX, p1.y * __builtin_amdgcn_exp2f(-sg0));
           float al1 = fminf(GSL_ALPHA_MAX, u1.y * __builtin_amdgcn_exp2f(-sg1));
           const unsigned long long OK0 = ACT & __ballot(sg0 >= 0.f) & __ballot(al0 >= GSL_ALPHA_MIN);
@@ -362,23 +364,6 @@ __device__ __forceinline__ void praster_walk(
   done = ((DONE >> lane) & 1ull) != 0ull;
 }
 
-// lane -> pixel of the compositing kernels: wave = 8x8 quadrant, DPP row g = 4x4 block g of the quadrant, lane p of
-// the row = pixel (p & 3, p >> 2) of the block
-struct TilePixel {
-  int tyi, txi, qx, qy, i, j;
-};
-__device__ __forceinline__ TilePixel tile_pixel(int tile, int tile_w, int tid) {
-  TilePixel t;
-  int lane = tid & 63, wv = tid >> 6, grp = lane >> 4, pp = lane & 15;
-  t.tyi = tile / tile_w;
-  t.txi = tile - t.tyi * tile_w;
-  t.qx = t.txi * 16 + (wv & 1) * 8;
-  t.qy = t.tyi * 16 + (wv >> 1) * 8;
-  t.j = t.qx + 4 * (grp & 1) + (pp & 3);
-  t.i = t.qy + 4 * (grp >> 1) + (pp >> 2);
-  return t;
-}
-
 // SORT = 2 / 3 (binned projection, whole frame, every list <= 1024 / 2048 keys, no long lists): the kernel turns its
 // tile's bin into the sorted list ITSELF before compositing it -- what k_tile_sort_wg does in a launch of its own: adds up
 // the sizes of the tiles before its own (offsets, total, overflow flags), sorts (four waves sort quarters in registers,
@@ -442,17 +427,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SORT == 3 ?
   }
   // binned projection: the tile-size counter of this tile has been consumed by the sort kernel; clear it for the next
   // projection (no clearing launch; sizes of tiles outside the strip are never raised)
-  if (clear_counts && threadIdx.x == 0) {
-    clear_counts[tile] = 0;
-    if (blockIdx.x == 0 && clear_state) *clear_state = 0;  // counters consumed and cleared: the next projection may bin
-  }
+  clear_tile_counter(clear_counts, clear_state, tile, blockIdx.x == 0);
   // "some quadrant needs the full-colour backward" flag behind the hit-list lengths (raster_g16.hip): cleared here
   if (isect_hit_counts && blockIdx.x == 0 && threadIdx.x == 0) isect_hit_counts[4 * n_tiles_total] = 0;
   int tid = threadIdx.x;
   TilePixel tp = tile_pixel(tile, tile_w, tid);
-  int i = tp.i, j = tp.j;
-  float px = (float)j + 0.5f, py = (float)i + 0.5f;
-  bool inside = (i < H) && (j < W) && (i >= row0) && (i < row1);
+  bool inside = pixel_inside(tp, W, H, row0, row1);
   bool done = !inside;
 
   long long rs, re;
@@ -460,10 +440,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SORT == 3 ?
     rs = sorted_rs;
     re = sorted_re;
   } else {
-    rs = tile_offsets[tile];
-    re = tile_offsets[tile + 1];
-    if (re > capacity) re = capacity;
-    if (rs > re) rs = re;
+    const ListSpan sp = tile_span(tile_offsets, tile, capacity);
+    rs = min(sp.rs, sp.re);
+    re = sp.re;
     if (long_min > 0 && re - rs > long_min) return;
   }
 
@@ -473,18 +452,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SORT == 3 ?
 #pragma unroll
   for (int k = 0; k < D; ++k) pix[k] = 0.f;
   int n_hits = 0;
-  praster_walk<D, 0>(sb, Q0, Q1, Q2, Qh, flatten_ids, rs, re, tid, px, py, tp.qx, tp.qy, tp.txi, tp.tyi, done, T, pix,
+  praster_walk<D, 0>(sb, Q0, Q1, Q2, Qh, flatten_ids, rs, re, tid, tp.px, tp.py, tp.qx, tp.qy, tp.txi, tp.tyi, done, T, pix,
                      cur_idx, isect_hits, n_hits);
   if (isect_hits && (tid & 63) == 0) isect_hit_counts[tile * 4 + (tid >> 6)] = n_hits;
-  if (inside) {
-    size_t pid = (size_t)i * W + j;
-    float A = 1.f - T;
-    alphas[pid] = A;
-    if (ED) pix[D - 1] = pix[D - 1] / fmaxf(A, GSL_ED_ALPHA_MIN);
-#pragma unroll
-    for (int k = 0; k < D; ++k) render[pid * D + k] = pix[k];
-    last_ids[pid] = cur_idx;
-  }
+  if (inside) write_pixel<D, ED>(render, alphas, last_ids, pixel_index(tp, W, true), T, pix, cur_idx);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -607,12 +578,8 @@ __global__ __launch_bounds__(256) void k_long_fwd(
   if (tile < 0) return;  // a tile whose segments did not fit the workspace (flagged by k_long_map)
   int tid = threadIdx.x;
   TilePixel tp = tile_pixel(tile, tile_w, tid);
-  int i = tp.i, j = tp.j;
-  float px = (float)j + 0.5f, py = (float)i + 0.5f;
-  bool inside = (i < H) && (j < W) && (i >= row0) && (i < row1);
-  long long rs = tile_offsets[tile], re = tile_offsets[tile + 1];
-  if (re > capacity) re = capacity;
-  long long ss = rs + (long long)sgm * GSL_SEG, se = min(ss + (long long)GSL_SEG, re);
+  bool inside = pixel_inside(tp, W, H, row0, row1);
+  const ListSpan seg = segment_span(tile_span(tile_offsets, tile, capacity), sgm);
   float pix[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) pix[k] = 0.f;
@@ -622,7 +589,7 @@ __global__ __launch_bounds__(256) void k_long_fwd(
     int cur = 0;
     bool done = !inside;
     int nh = 0;
-    praster_walk<D, 1>(sb, Q0, Q1, Q2, Qh, flatten_ids, ss, se, tid, px, py, tp.qx, tp.qy, tp.txi, tp.tyi, done, T, pix,
+    praster_walk<D, 1>(sb, Q0, Q1, Q2, Qh, flatten_ids, seg.rs, seg.re, tid, tp.px, tp.py, tp.qx, tp.qy, tp.txi, tp.tyi, done, T, pix,
                        cur, nullptr, nh);
     w.P[slot] = T;
   } else {
@@ -645,7 +612,7 @@ __global__ __launch_bounds__(256) void k_long_fwd(
     bool done = dead;
     int cur = -1;
     int nh = 0;  // the segment's hit lists sit at 4 ss + quadrant (se - ss), their lengths in the workspace
-    praster_walk<D, 0>(sb, Q0, Q1, Q2, Qh, flatten_ids, ss, se, tid, px, py, tp.qx, tp.qy, tp.txi, tp.tyi, done, T, pix,
+    praster_walk<D, 0>(sb, Q0, Q1, Q2, Qh, flatten_ids, seg.rs, seg.re, tid, tp.px, tp.py, tp.qx, tp.qy, tp.txi, tp.tyi, done, T, pix,
                        cur, isect_hits, nh);
     if ((tid & 63) == 0) w.seg_qcnt[g * 4 + (tid >> 6)] = isect_hits ? nh : 0;
     // negative: the pixel stopped inside this segment (T is the value before the stop); 2: dead on arrival (a
@@ -674,8 +641,7 @@ __global__ __launch_bounds__(1024) void k_long_combine(int W, int H, int tile_w,
   if (tile < 0) return;
   int tid = threadIdx.x & 255, quarter = threadIdx.x >> 8;
   TilePixel tp = tile_pixel(tile, tile_w, tid);
-  int i = tp.i, j = tp.j;
-  bool inside = (i < H) && (j < W) && (i >= row0) && (i < row1);
+  bool inside = pixel_inside(tp, W, H, row0, row1);
   float pix[4] = {0.f, 0.f, 0.f, 0.f};
   float T = 1.f;
   int last = -1;
@@ -722,13 +688,7 @@ __global__ __launch_bounds__(1024) void k_long_combine(int W, int H, int tile_w,
     stop = (st & 2) != 0;
   }
   if (last < 0) last = 0;
-  size_t pid = (size_t)i * W + j;
-  float A = 1.f - T;
-  alphas[pid] = A;
-  if (ED) pix[D - 1] = pix[D - 1] / fmaxf(A, GSL_ED_ALPHA_MIN);
-#pragma unroll
-  for (int k = 0; k < D; ++k) render[pid * D + k] = pix[k];
-  last_ids[pid] = last;
+  write_pixel<D, ED>(render, alphas, last_ids, pixel_index(tp, W, true), T, pix, last);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -780,23 +740,17 @@ __global__ __launch_bounds__(256) void k_tiny_bwd(
     float2* __restrict__ trec, float* __restrict__ vcT, int row0, int row1, int32_t* __restrict__ flags, int long_min,
     TinyLoss tl, int32_t* __restrict__ clear_counts, int32_t* __restrict__ clear_state) {
   constexpr bool RGB = D >= 3;
-  constexpr bool DEPTH = (D == 1) || (D == 4);
   __shared__ TStage<D> sb;
   __shared__ int s_final[4];
   __shared__ TinyLossLds<LOSS> sl;
   int tile = ty0 * tile_w + GSL_TILE_OF_BLOCK();
-  // (the forward sorted its own bins and could not clear the tile counters: see k_praster_fwd, SORT)
-  if (clear_counts && threadIdx.x == 0) {
-    clear_counts[tile] = 0;
-    if (blockIdx.x == 0 && clear_state) *clear_state = 0;
-  }
-  int tyi = tile / tile_w, txi = tile - tyi * tile_w;
+  clear_tile_counter(clear_counts, clear_state, tile, blockIdx.x == 0);  // (see k_praster_fwd, SORT)
   int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int qx = txi * 16 + (wv & 1) * 8, qy = tyi * 16 + (wv >> 1) * 8;
-  int j = qx + (lane & 7), i = qy + (lane >> 3);
-  float px = (float)j + 0.5f, py = (float)i + 0.5f;
-  bool inside = (i < H) && (j < W) && (i >= row0) && (i < row1);
-  size_t pid = inside ? ((size_t)i * W + j) : 0;
+  const TilePixel tp = quadrant_pixel<false>(tile, tile_w, wv, lane);
+  const int tyi = tp.tyi, txi = tp.txi, qx = tp.qx, qy = tp.qy, i = tp.i, j = tp.j;
+  const float px = tp.px, py = tp.py;
+  bool inside = pixel_inside(tp, W, H, row0, row1);
+  size_t pid = pixel_index(tp, W, inside);
   if constexpr (LOSS) {
     float g, l1, le;
     bool has_pixel;
@@ -810,9 +764,10 @@ __global__ __launch_bounds__(256) void k_tiny_bwd(
     if (tid < 2)
       tl.partial[2 * (size_t)tile + tid] = sl.L.red[0][tid] + sl.L.red[1][tid] + sl.L.red[2][tid] + sl.L.red[3][tid];
   }
+  // (this kernel's own copy of bwd_start, composite_dev.h, which says why)
   float Aimg = inside ? alphas[pid] : 0.f;
   float T_final = 1.f - Aimg;
-  int bin_final = inside ? last_ids[pid] : -1;
+  int bin_final = last_composited(last_ids, pid, inside);
   float vc[D];
   float va = inside ? v_alphas[pid] : 0.f;
   if constexpr (LOSS) {
@@ -820,8 +775,7 @@ __global__ __launch_bounds__(256) void k_tiny_bwd(
     for (int k = 0; k < D; ++k) vc[k] = 0.f;  // (the tracker's loss has no colour term)
     if (inside) vc[D - 1] = sl.grad[(wv >> 1) * 8 + (lane >> 3)][(wv & 1) * 8 + (lane & 7)];
   } else {
-#pragma unroll
-    for (int k = 0; k < D; ++k) vc[k] = inside ? v_render[pid * D + k] : 0.f;
+    load_upstream<D>(v_render, pid, inside, vc);
   }
   if (ED && inside) {
     const EdGrad g = ed_backward(Aimg, render[pid * D + (D - 1)], va, vc[D - 1]);
@@ -832,17 +786,14 @@ __global__ __launch_bounds__(256) void k_tiny_bwd(
 #pragma unroll
     for (int k = 0; k < D; ++k) vcT[pid * D + k] = vc[k];
   }
-  long long rs = tile_offsets[tile], re = tile_offsets[tile + 1];
-  if (re > capacity) re = capacity;
-  if (rs >= re) return;
-  if (long_min > 0 && re - rs > long_min) return;  // long list: gsl_long_raster_bwd adds this tile's rows to vacc
-  int wave_final = bin_final;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) wave_final = max(wave_final, __shfl_xor(wave_final, o, 64));
+  ListSpan sp = tile_span(tile_offsets, tile, capacity);
+  if (sp.rs >= sp.re) return;
+  if (long_min > 0 && sp.re - sp.rs > long_min) return;  // long list: gsl_long_raster_bwd adds this tile's rows to vacc
+  const int wave_final = wave_max(bin_final);
   if (lane == 0) s_final[wv] = wave_final;
   __syncthreads();
-  int block_final = max(max(s_final[0], s_final[1]), max(s_final[2], s_final[3]));
-  if ((long long)block_final + 1 < re) re = max((long long)block_final + 1, rs);
+  block_last_trim(s_final, sp);
+  const long long rs = sp.rs, re = sp.re;
   if (rs >= re) return;
   int nb = (int)((re - rs + 255) / 256);
   float T = T_final;
@@ -859,9 +810,8 @@ __global__ __launch_bounds__(256) void k_tiny_bwd(
       r0 = GSL_Q(Q0, g);
       r1 = GSL_Q(Q1, g);
       sb.s0[tid] = r0;
-      // the conic as the FORWARD stages it (times log2 e, diagonal halved: praster_walk), so that a trip evaluates alpha
-      // with the forward's very operations and both sides take the same alpha >= 1/255 decision for every pair
-      sb.s1[tid] = make_float4(r1.x * (0.5f * GSL_LOG2E), r1.y * GSL_LOG2E, r1.z * (0.5f * GSL_LOG2E), r1.w);
+      const float3 cn = stage_conic(r1);
+      sb.s1[tid] = make_float4(cn.x, cn.y, cn.z, r1.w);
       if (RGB) sb.s2[tid] = GSL_Q(Q2, g);
     } else {  // (finite numbers in every slot: see praster_walk)
       sb.id[tid] = 0;
@@ -907,8 +857,7 @@ __global__ __launch_bounds__(256) void k_tiny_bwd(
           float4 p0 = sb.s0[t0], p1 = sb.s1[t0];
           float4 u0 = sb.s0[t1], u1 = sb.s1[t1];
           float dx0 = p0.x - px, dy0 = p0.y - py, dx1 = u0.x - px, dy1 = u0.y - py;
-          float sg0 = fmaf(p1.y * dx0, dy0, fmaf(p1.x * dx0, dx0, p1.z * dy0 * dy0));  // log2(e) sigma, the forward's
-          float sg1 = fmaf(u1.y * dx1, dy1, fmaf(u1.x * dx1, dx1, u1.z * dy1 * dy1));  // expression
+          float sg0 = sigma_log2e(p1.x, p1.y, p1.z, dx0, dy0), sg1 = sigma_log2e(u1.x, u1.y, u1.z, dx1, dy1);
           float vis0 = __builtin_amdgcn_exp2f(-sg0), vis1 = __builtin_amdgcn_exp2f(-sg1);
           float opv0 = p0.w * vis0, opv1 = u0.w * vis1;
           float al0 = fminf(GSL_ALPHA_MAX, opv0), al1 = fminf(GSL_ALPHA_MAX, opv1);
@@ -916,13 +865,7 @@ __global__ __launch_bounds__(256) void k_tiny_bwd(
               ACT & __ballot(t0 >= t_lane) & __ballot(sg0 >= 0.f) & __ballot(al0 >= GSL_ALPHA_MIN);
           const unsigned long long OK1 =
               TWO & __ballot(t1 >= t_lane) & __ballot(sg1 >= 0.f) & __ballot(al1 >= GSL_ALPHA_MIN);
-          float cd0 = 0.f, cd1 = 0.f;
-          if constexpr (RGB) {
-            float4 q20 = sb.s2[t0], q21 = sb.s2[t1];
-            cd0 = q20.x * vc[0] + q20.y * vc[1] + q20.z * vc[2];
-            cd1 = q21.x * vc[0] + q21.y * vc[1] + q21.z * vc[2];
-          }
-          if (DEPTH) { cd0 += p0.z * vc[D - 1]; cd1 += u0.z * vc[D - 1]; }
+          const float cd0 = colour_dot<D>(sb.s2, t0, p0.z, vc), cd1 = colour_dot<D>(sb.s2, t1, u0.z, vc);
           const float a0 = sel(OK0, al0, 0.f), a1 = sel(OK1, al1, 0.f);
           const float ra0 = __builtin_amdgcn_rcpf(1.f - a0), ra1 = __builtin_amdgcn_rcpf(1.f - a1);  // (alpha 0: exactly 1)
           const float T0 = T * ra0;
@@ -969,7 +912,7 @@ extern "C" int gsl_tiny_raster_bwd(const float* Q0, const float* Q1, const float
   if (!gsl::frame_ok(width, height, tile_w, tile_h, ty0, ty1, capacity, row0, row1)) return GSL_ERR_BAD_ARG;
   if (!tile_offsets || !render || !alphas || !last_ids || !v_render || !v_alphas || !trec || !vcT)
     return GSL_ERR_BAD_ARG;
-  if (ed && channels == 3) return GSL_ERR_BAD_ARG;
+  if (!gsl::ed_ok(channels, ed)) return GSL_ERR_BAD_ARG;
   // loss_depth_gt != NULL: the kernel computes the tracking loss of gsl_tracking_loss itself and WRITES v_render's
   // depth channel and loss_partials[tiles][2]; whole frame only (the loss block of a tile is the tile)
   const bool loss = loss_depth_gt != nullptr;
@@ -977,7 +920,7 @@ extern "C" int gsl_tiny_raster_bwd(const float* Q0, const float* Q1, const float
                tile_w != (width + 15) / 16 || tile_h != (height + 15) / 16 || (channels != 1 && channels != 4)))
     return GSL_ERR_BAD_ARG;
   if (ty0 == ty1) return GSL_OK;
-  if (capacity > 0 && (!Q0 || !Q1 || !flatten_ids || (channels >= 3 && !Q2))) return GSL_ERR_BAD_ARG;
+  if (capacity > 0 && (!flatten_ids || !gsl::records_ok(nullptr, Q0, Q1, Q2, channels))) return GSL_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   int nblk = (ty1 - ty0) * tile_w;
   gsl::TinyLoss tl{loss_depth_gt, loss_partials, const_cast<float*>(v_render), depth_lambda, edge_lambda,
@@ -1011,8 +954,8 @@ extern "C" int gsl_fused_raster_fwd(const float* Q0, const float* Q1, const floa
   if (!gsl::frame_ok(width, height, tile_w, tile_h, ty0, ty1, capacity, row0, row1)) return GSL_ERR_BAD_ARG;
   if (!tile_offsets || !render || !alphas || !last_ids) return GSL_ERR_BAD_ARG;
   if (capacity > 0 && !flatten_ids) return GSL_ERR_BAD_ARG;
-  if (capacity > 0 && !Qh && (!Q0 || !Q1 || (channels >= 3 && !Q2))) return GSL_ERR_BAD_ARG;
-  if (ed && channels == 3) return GSL_ERR_BAD_ARG;
+  if (capacity > 0 && !gsl::records_ok(Qh, Q0, Q1, Q2, channels)) return GSL_ERR_BAD_ARG;
+  if (!gsl::ed_ok(channels, ed)) return GSL_ERR_BAD_ARG;
   if (isect_hits && !isect_hit_counts) return GSL_ERR_BAD_ARG;
   if (isect_hits && capacity >= ((int64_t)1 << GSL_HIT_SHIFT)) return GSL_ERR_BAD_ARG;  // a hit entry keeps the list index below its group bits
   const bool sort = sort_bins != nullptr;
@@ -1062,8 +1005,8 @@ extern "C" int gsl_long_raster_fwd(const float* Q0, const float* Q1, const float
     return GSL_ERR_BAD_ARG;
   if (!tile_offsets || !render || !alphas || !last_ids || !long_ws) return GSL_ERR_BAD_ARG;
   if (long_ws_bytes < gsl_long_ws_bytes(max_seg)) return GSL_ERR_WORKSPACE;
-  if (capacity > 0 && (!flatten_ids || (!Qh && (!Q0 || !Q1 || (channels >= 3 && !Q2))))) return GSL_ERR_BAD_ARG;
-  if (ed && channels == 3) return GSL_ERR_BAD_ARG;
+  if (capacity > 0 && (!flatten_ids || !gsl::records_ok(Qh, Q0, Q1, Q2, channels))) return GSL_ERR_BAD_ARG;
+  if (!gsl::ed_ok(channels, ed)) return GSL_ERR_BAD_ARG;
   if (ty0 == ty1 || capacity == 0) return GSL_OK;
   hipStream_t st = (hipStream_t)stream;
   gsl::LongWs w = gsl::long_ws_views(long_ws, max_seg);

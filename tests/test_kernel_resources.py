@@ -1,6 +1,7 @@
 """Register / LDS budget of the hot kernels, from hipcc's resource remarks (no GPU needed): the compositing kernels
 are occupancy-sensitive (round 2: k_mraster_bwd from 120 to 130 registers cost 17 % on hardware; round 3: the
 per-quadrant backward at 9.8 KB of LDS -- 4 waves/SIMD -- ran 264 us, at 8.4 KB 257 us), so the budget is pinned here."""
+import functools
 import os
 import re
 import subprocess
@@ -12,6 +13,7 @@ CSRC = os.path.join(ROOT, "gsplatloc_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
+@functools.lru_cache(maxsize=None)  # (one compile per source and flag set: the tests share the tables and do not change them)
 def _resources(src, *extra):
     cmd = [HIPCC, "-O3", "-std=c++17", "-fno-slp-vectorize", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
            "-Rpass-analysis=kernel-resource-usage", *extra]
@@ -89,6 +91,29 @@ def test_compaction_kernels_cost_what_their_hand_written_copies_did():
         r = hit[0]
         assert r["VGPRs"] <= vgprs and r["AGPRs"] == 0 and r["TotalSGPRs"] <= sgprs, (name, r)
         assert r["LDS"] <= lds and r["ScratchSize"] == 0 and r["Occupancy"] == 8, (name, r)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_compositing_kernels_cost_what_their_hand_written_openings_did():
+    """The compositing kernels no other test pins, written on the shared steps of csrc/composite_dev.h (list span, lane ->
+    pixel, the backward's starting state, the trim to the last composited entry, alpha, colour dot, write-out): no more
+    registers (VGPR, SGPR), LDS or scratch, and no fewer waves per SIMD, than the last commit in which each kernel wrote
+    those steps out itself (the numbers are that commit's)."""
+    budget = {  # kernel: (VGPRs, SGPRs, LDS bytes, waves/SIMD)
+        ("raster_px.hip", "k_tiny_bwdILi4ELb1ELb1E"): (67, 79, 22592, 7),
+        ("raster_px.hip", "k_tiny_bwdILi1ELb1ELb1E"): (62, 77, 18512, 8),
+        ("raster_px.hip", "k_long_fwdILi4ELi0E"): (52, 83, 14672, 8),
+        ("raster_px.hip", "k_long_fwdILi4ELi1E"): (64, 97, 14672, 8),
+        ("absgrad.hip", "k_absgradILi4ELb1ELb1E"): (56, 46, 3936, 8),
+        ("raster.hip", "k_raster_bwdILi3E"): (99, 62, 49680, 3),
+    }
+    files = {f: _resources(f) for f in sorted({f for f, _ in budget})}
+    for (f, name), (vgprs, sgprs, lds, waves) in budget.items():
+        hit = [v for k, v in files[f].items() if name in k]
+        assert len(hit) == 1, (f, name, list(files[f]))
+        r = hit[0]
+        assert r["VGPRs"] <= vgprs and r["AGPRs"] == 0 and r["TotalSGPRs"] <= sgprs, (name, r)
+        assert r["LDS"] <= lds and r["ScratchSize"] == 0 and r["Occupancy"] >= waves, (name, r)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
