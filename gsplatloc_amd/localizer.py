@@ -24,6 +24,9 @@ it did not hold the render the new pixels are judged against is made from a sele
 With ``MapConfig.free_rho`` the map also shrinks: after the insertion of a frame that is not lost, the live rows that
 frame sees through -- in front of everything it observes around their pixel -- are removed
 (``GaussianMap.remove_seen_through``).  The hole a removed ghost leaves is filled by the NEXT frame's insertion.
+With ``MapConfig.evict`` the map lives in its capacity: before the insertion of a frame that is not lost the rows it
+observes are stamped with its index (``GaussianMap.observe``, at the estimate), and an insertion that is short of room
+first evicts the least recently observed rows (``GaussianMap.evict``).
 """
 from __future__ import annotations
 
@@ -74,6 +77,7 @@ class LocalizeResult:
     tracked: Optional[int] = None  # mode="map": rows the tracker saw (all live rows, or those in the guarded view)
     view_violations: Optional[int] = None  # view_guard_px: rows in reach of the view from c2w that were not tracked
     removed: Optional[int] = None  # free_rho: live rows this frame saw through, removed after its insertion
+    evicted: Optional[int] = None  # evict: least recently observed rows that made room for this frame's insertion
 
 
 def _default_factory(N, W, H, config, device, render_mode):
@@ -102,8 +106,11 @@ class Localizer:
     appended sit at their own pixel's observed depth and cannot go) the rows the frame sees through are removed,
     ``LocalizeResult.removed`` counts them and ``map_size`` is the count after the removal; the pixels behind a removed
     ghost are uncovered only now, so it is the next frame's insertion that fills the hole.  A lost frame removes
-    nothing.  Everything else -- normalisation, the re-rendered query depth, the scales, the hand-over, ``best_c2w`` --
-    is the frame mode's."""
+    nothing.  ``map_config.evict``: between the insertion render and the insertion the rows the frame observes from the
+    estimate are stamped (``GaussianMap.observe``), and an insertion that does not fit evicts the least recently
+    observed rows first (``LocalizeResult.evicted``; ``map_size`` never exceeds the capacity and the map is not
+    ``full`` while enough rows are old enough to go); a lost frame stamps, evicts and inserts nothing.  Everything else
+    -- normalisation, the re-rendered query depth, the scales, the hand-over, ``best_c2w`` -- is the frame mode's."""
 
     def __init__(self, K: Tensor, width: int, height: int, config: TrackerConfig = TrackerConfig(),
                  normalize: bool = True, motion: str = "constant_velocity", device="cuda", render_mode: str = "ED",
@@ -131,12 +138,14 @@ class Localizer:
         self.map = None
         self._view_guard = None  # MapConfig.view_guard_px
         self._free = False  # MapConfig.free_rho is set
+        self._evict = False  # MapConfig.evict
         if self.map_mode:
             make = map_factory if map_factory is not None else GaussianMap
             map_config = map_config if map_config is not None else MapConfig()
             self.map = make(self.W, self.H, map_config, self.device)
             self._view_guard = map_config.view_guard_px
             self._free = map_config.free_rho is not None
+            self._evict = bool(map_config.evict)
         self._render_map = map_renderer if map_renderer is not None else render_depth_alpha
 
     def _frame(self, depth, rgb):
@@ -222,6 +231,7 @@ class Localizer:
         if self.map_mode:
             out.added, out.tracked = 0, N
             out.removed = 0 if self._free else None
+            out.evicted = 0 if self._evict else None
             if not out.lost:  # a lost frame's pose is a guess: it adds nothing
                 at = best
                 if self._view_guard is not None:
@@ -235,7 +245,12 @@ class Localizer:
                         scales = init_gs_scales(d.tar_points)
                         at = transform_cameras(d.norm_T, est.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else est
                 render, alphas = self._map_render(d, scales, at)
+                if self._evict:
+                    # stamp before the insertion: what this frame observes must not make room for its own rows
+                    self.map.observe(depth, self.K, est, self.cfg.gs.near_plane, self.cfg.gs.far_plane)
                 _, out.added = self.map.insert_frame(depth, rgb, self.K, est, render, alphas)
+                if self._evict:
+                    out.evicted = self.map.last_evicted
                 if self._free:
                     # insert first, then remove: the insertion render was made from the cloud that was tracked, and
                     # the rows just appended sit at their own pixel's observed depth

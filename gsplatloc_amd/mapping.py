@@ -17,7 +17,13 @@ this selection left out.  Two more entry points; each of the two calls reads its
 Free space (``MapConfig.free_rho``, csrc/map_free.hip): ``remove_seen_through`` removes the live rows a depth frame sees
 through -- rows that project into the image and lie more than ``free_rho`` in front of everything the frame observes in
 a window of ``free_window_px`` pixels around their pixel -- and compacts the survivors, in map order, into a spare pair
-of buffers that then becomes the map.  One more entry point and the local map's gather; one read-back."""
+of buffers that then becomes the map.  One more entry point and the local map's gather; one read-back.
+
+A bounded map (``MapConfig.evict``, csrc/map_evict.hip): every row carries the index of the last frame that observed it
+(``stamps``; ``observe`` stamps the rows a frame sees where it expects them, the rows a frame appends get its index), and
+when a frame's new rows do not fit ``insert_frame`` first evicts exactly as many rows as are short -- the least recently
+observed first, in map order among equals (``evict``) -- into the same spare buffers.  Only such a frame reads the
+selection's count back before the append; a frame with room to spare keeps its single synchronisation."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -46,8 +52,30 @@ class MapConfig:
     # grows).  The window is what keeps the edge of a surface that is still there when the pose is a little off
     free_rho: Optional[float] = None
     free_window_px: int = 1
+    # a bounded map: when a frame's new rows do not fit, the least recently observed rows go first (in map order among
+    # rows last observed by the same frame), exactly as many as are short plus evict_headroom; only rows last observed
+    # at least evict_min_age frames ago can go (False: the rows that do not fit are dropped and the map is ``full``)
+    evict: bool = False
+    evict_min_age: int = 1
+    evict_headroom: int = 0
+    # a row counts as observed by a frame when a pixel within this many pixels of its own shows its depth, within
+    # depth_rho either way (or when it lies in the view_reach_px band around the image)
+    observe_window_px: int = 1
 
     def __post_init__(self):
+        whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+        if not isinstance(self.evict, bool):
+            raise ValueError(f"evict {self.evict!r}: True or False")
+        if not whole(self.evict_min_age) or not 1 <= self.evict_min_age <= 1023:
+            raise ValueError(f"evict_min_age {self.evict_min_age}: a whole number of frames, 1 .. 1023 (the rows of the "
+                             "current frame never go; ages are clamped at 1023)")
+        if not whole(self.evict_headroom) or self.evict_headroom < 0:
+            raise ValueError(f"evict_headroom {self.evict_headroom}: a whole number of rows, not negative")
+        if not whole(self.observe_window_px) or not 0 <= self.observe_window_px <= 3:
+            raise ValueError(f"observe_window_px {self.observe_window_px}: a whole number of pixels, 0 .. 3")
+        if self.evict and not 0.0 <= self.depth_rho < 1.0:
+            raise ValueError(f"depth_rho {self.depth_rho}: evict holds a row against the observed depth within this "
+                             "fraction, inside [0, 1)")
         if self.free_rho is not None and not 0.0 < self.free_rho < 1.0:
             raise ValueError(f"free_rho {self.free_rho}: a fraction of the observed depth, inside (0, 1)")
         if isinstance(self.free_window_px, bool) or not isinstance(self.free_window_px, int) \
@@ -84,6 +112,10 @@ class GaussianMap:
         self.colors = torch.zeros(self.capacity, 3, device=self.device)
         self.n_live = 0
         self.full = False  # some frame's rows were dropped at the capacity
+        # the index of the last frame that observed each row (observe / insert_frame), and of the current frame
+        self.stamps = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
+        self.frame_index = 0
+        self.last_evicted = 0  # rows the last insert_frame evicted to make room
         # float32 values of the rule, computed here once: the kernel multiplies and compares, nothing else
         self.alpha_min = float(np.float32(config.alpha_min))
         self.keep = float(np.float32(1.0) - np.float32(config.depth_rho))
@@ -96,6 +128,8 @@ class GaussianMap:
         self._free = None
         self._free_keep = None if config.free_rho is None else float(np.float32(1.0) - np.float32(config.free_rho))
         self._n_survivors = 0
+        # evict: its workspace (not the selection's: the append still needs that one), allocated on first use
+        self._evict_ws = None
 
     def _alloc_ws(self):
         if self.device.type != "cuda":
@@ -113,14 +147,15 @@ class GaussianMap:
 
     @property
     def survivors(self) -> Tensor:
-        """int32: the old row of every row that was live after the last ``remove_seen_through`` (empty before the first
-        one); a view that the next call overwrites."""
+        """int32: the old row of every row that was live after the last ``remove_seen_through`` or ``evict`` (empty before
+        the first one); a view that the next call overwrites."""
         if self._free is None:
             return torch.zeros(0, dtype=torch.int32, device=self.device)
         return self._free["ids"][: self._n_survivors]
 
     def clear(self) -> None:
         self.n_live, self.full = 0, False
+        self.frame_index, self.last_evicted = 0, 0
         self._view_rows = -1
         self._n_survivors = 0
 
@@ -138,12 +173,32 @@ class GaussianMap:
         selected, appended = self._counters.tolist()  # the frame's one synchronisation
         return selected, appended
 
+    def _select_launch(self, depth: Tensor, render: Optional[Tensor], alphas: Optional[Tensor]) -> int:
+        """The first entry point alone and the read-back of the pixels selected: a frame that may not fit."""
+        assert depth.is_cuda, "GaussianMap.insert_frame: the map is grown by HIP kernels, no CPU path"
+        lib, st, ptr, ws = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._ws
+        _lib.check(lib.gsl_map_select(ptr(render), ptr(alphas), ptr(depth), self.W, self.H, self.alpha_min, self.keep,
+                                      ptr(self._counters), ptr(ws), ws.numel(), st), "gsl_map_select")
+        return self._counters.tolist()[0]  # the extra synchronisation of a frame that is short of room
+
+    def _append_launch(self, depth: Tensor, rgb: Tensor, intr: Tuple[float, float, float, float], c2w: Tensor) -> int:
+        """The second entry point after ``_select_launch`` (the selection's workspace is untouched: the eviction in
+        between has its own) and the read-back of the rows appended."""
+        lib, st, ptr, ws = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._ws
+        _lib.check(lib.gsl_map_append(ptr(depth), ptr(rgb), self.W, self.H, *intr, ptr(c2w), ptr(self.means),
+                                      ptr(self.colors), self.n_live, self.capacity, ptr(self._counters), ptr(ws),
+                                      ws.numel(), st), "gsl_map_append")
+        return self._counters.tolist()[1]
+
     @torch.no_grad()
     def insert_frame(self, depth, rgb, K, c2w, render: Optional[Tensor] = None,
                      alphas: Optional[Tensor] = None) -> Tuple[int, int]:
         """depth [H,W] metres, rgb [H,W,3] in 0..255, K [3,3], c2w [4,4] the frame's pose in the world; render / alphas
         [H,W]: the map's expected depth (metres) and alpha at that pose -- both None: every pixel with a valid depth is
-        new (the first frame).  Returns (pixels selected, rows appended); they differ when the map is full."""
+        new (the first frame).  Returns (pixels selected, rows appended); they differ when the map is full.  The rows
+        appended are stamped with ``frame_index``.  ``MapConfig.evict``: a frame that may not fit (n_live + W * H above
+        the capacity) reads its selection's count back before the append and, when it is short of room, first evicts
+        that many rows plus ``evict_headroom`` (``evict``; ``last_evicted`` counts them)."""
         if (render is None) != (alphas is None):
             raise ValueError("insert_frame: render and alphas come together (or neither, for the first frame)")
 
@@ -159,7 +214,17 @@ class GaussianMap:
             render, alphas = image(render, hw, "render"), image(alphas, hw, "alphas")
         intr, c2w = _intr_and_pose(K, c2w)
         c2w = c2w.to(device=self.device, dtype=torch.float32).contiguous()
-        selected, appended = self._launch(depth, rgb, intr, c2w, render, alphas)
+        self.last_evicted = 0
+        if self.cfg.evict and self.n_live + self.W * self.H > self.capacity:
+            selected = self._select_launch(depth, render, alphas)
+            short = selected - (self.capacity - self.n_live) + int(self.cfg.evict_headroom)
+            if selected > 0 and short > 0:
+                self.last_evicted = self.evict(short)[0]
+            appended = self._append_launch(depth, rgb, intr, c2w)
+        else:
+            selected, appended = self._launch(depth, rgb, intr, c2w, render, alphas)
+        if appended > 0:
+            self.stamps[self.n_live:self.n_live + appended] = self.frame_index
         self.n_live += appended
         self.full = self.full or appended < selected
         return selected, appended
@@ -232,6 +297,7 @@ class GaussianMap:
             if dev.type == "cuda":
                 ws = torch.empty(_lib.load_library().gsl_map_view_ws_bytes(cap), dtype=torch.uint8, device=dev)
             self._free = dict(means=torch.zeros(cap, 3, device=dev), colors=torch.zeros(cap, 3, device=dev),
+                              stamps=torch.zeros(cap, dtype=torch.int32, device=dev),
                               ids=torch.zeros(cap, dtype=torch.int32, device=dev),
                               counters=torch.zeros(3, dtype=torch.int32, device=dev), ws=ws)
         return self._free
@@ -250,7 +316,25 @@ class GaussianMap:
                                            ptr(f["colors"]), ptr(f["ids"]), self.capacity, ptr(f["counters"]),
                                            ptr(ws), ws.numel(), st), "gsl_map_view_gather")
         stay, _, stored = f["counters"].tolist()  # the call's one synchronisation
+        if stored < self.n_live:  # something goes: the buffers will be swapped, the stamps follow their rows
+            self._gather_stamps(stored)
         return stay, stored
+
+    def _gather_stamps(self, n: int) -> None:
+        """The stamps of the n rows the gather just moved, through the ids it wrote, into the spare stamps."""
+        f = self._free
+        _lib.check(_lib.load_library().gsl_map_gather_i32(_lib.ptr(self.stamps), self.n_live, _lib.ptr(f["ids"]), n,
+                                                          _lib.ptr(f["stamps"]), _lib.current_stream()),
+                   "gsl_map_gather_i32")
+
+    def _swap_spare(self, n_live: int) -> None:
+        """The spare buffers, which hold the survivors, become the map (a swap, not a copy)."""
+        f = self._free
+        self.means, f["means"] = f["means"], self.means
+        self.colors, f["colors"] = f["colors"], self.colors
+        self.stamps, f["stamps"] = f["stamps"], self.stamps
+        self.n_live = n_live
+        self._view_rows = -1  # the view ballots describe other rows
 
     @torch.no_grad()
     def remove_seen_through(self, depth, K, c2w, near: float) -> Tuple[int, int]:
@@ -274,9 +358,66 @@ class GaussianMap:
         assert stored == stay <= self.n_live, (stay, stored, self.n_live)  # the spare buffers hold the capacity
         removed, self._n_survivors = self.n_live - stay, stay
         if removed > 0:
-            f = self._free
-            self.means, f["means"] = f["means"], self.means
-            self.colors, f["colors"] = f["colors"], self.colors
-            self.n_live = stay
-            self._view_rows = -1  # the view ballots describe other rows
+            self._swap_spare(stay)
         return removed, stay
+
+    # ---- a bounded map: last-observed stamps, the least recently observed rows evicted (csrc/map_evict.hip) ---------
+    def _observe_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, near: float,
+                        far: float) -> None:
+        assert depth.is_cuda, "GaussianMap.observe: the rows are stamped by a HIP kernel, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        _lib.check(lib.gsl_map_observe(ptr(self.means), self.n_live, ptr(w2c), *intr, ptr(depth), self.W, self.H,
+                                       self.keep, int(self.cfg.observe_window_px), float(self.cfg.view_reach_px), near,
+                                       far, self.frame_index, ptr(self.stamps), st), "gsl_map_observe")
+
+    @torch.no_grad()
+    def observe(self, depth, K, c2w, near: float, far: float) -> None:
+        """A new frame: ``frame_index`` goes up by one, and the live rows that the depth frame [H,W] (metres) at the pose
+        c2w [4,4] observes (the rule: include/gsloc_hip.h, with ``depth_rho``, ``observe_window_px`` and
+        ``view_reach_px``) are stamped with it.  No read-back."""
+        self.frame_index += 1
+        if self.n_live == 0:
+            return
+        depth = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
+        if depth.numel() != self.H * self.W:
+            raise ValueError(f"depth is {tuple(depth.shape)}, the map was built for {(self.H, self.W)}")
+        depth = depth.reshape(self.H, self.W).contiguous()
+        intr, w2c = self._view_args(K, c2w)
+        self._observe_launch(depth, intr, w2c, float(near), float(far))
+
+    def _evict_launch(self, need: int) -> Tuple[int, int, int]:
+        """The selection over the stamps of the live rows, the gather of the rows that stay into the spare buffers
+        (means, colours, old rows) and of their stamps; the read-back of (rows that stay, rows evicted, rows stored)."""
+        assert self.means.is_cuda, "GaussianMap.evict: the rows are chosen and moved by HIP kernels, no CPU path"
+        lib, st, ptr, f = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._free_buffers()
+        if self._evict_ws is None:
+            self._evict_ws = torch.empty(lib.gsl_map_evict_ws_bytes(self.capacity), dtype=torch.uint8, device=self.device)
+        ws = self._evict_ws
+        _lib.check(lib.gsl_map_evict_select(ptr(self.stamps), self.n_live, self.frame_index,
+                                            int(self.cfg.evict_min_age), need, ptr(f["counters"]), ptr(ws), ws.numel(),
+                                            st), "gsl_map_evict_select")
+        _lib.check(lib.gsl_map_view_gather(ptr(self.means), ptr(self.colors), self.n_live, ptr(f["means"]),
+                                           ptr(f["colors"]), ptr(f["ids"]), self.capacity, ptr(f["counters"]),
+                                           ptr(ws), ws.numel(), st), "gsl_map_view_gather")
+        # every live row at most: the count is not known on the host yet, and the rows past it are never read
+        _lib.check(lib.gsl_map_gather_i32(ptr(self.stamps), self.n_live, ptr(f["ids"]), self.n_live, ptr(f["stamps"]),
+                                          st), "gsl_map_gather_i32")
+        stay, evicted, stored = f["counters"].tolist()  # the call's one synchronisation
+        return stay, evicted, stored
+
+    @torch.no_grad()
+    def evict(self, need: int) -> Tuple[int, int]:
+        """Removes min(need, evictable) live rows -- evictable: last observed at least ``evict_min_age`` frames before
+        ``frame_index`` -- the least recently observed first, in map order among rows of the same age (the rule:
+        include/gsloc_hip.h); the rows that stay keep their order.  Returns (evicted, kept).  A swap as in
+        ``remove_seen_through``: when something went, views taken before the call are stale, ``survivors`` holds the
+        old row of every live row, and the next ``view_violations`` needs a fresh ``select_view``."""
+        need = int(need)
+        if need <= 0 or self.n_live == 0:
+            return 0, self.n_live
+        stay, evicted, stored = self._evict_launch(need)
+        assert stored == stay == self.n_live - evicted, (stay, evicted, stored, self.n_live)
+        self._n_survivors = stay
+        if evicted > 0:
+            self._swap_spare(stay)
+        return evicted, stay

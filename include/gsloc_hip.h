@@ -207,6 +207,50 @@ int gsl_map_free_select(const float* means, int64_t n_rows, const float* w2c, fl
                         const float* depth, int width, int height, float keep, int window_px, float near_plane,
                         int32_t* counters, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- bounded map: a last-observed stamp per row, the least recently observed rows evicted (csrc/map_evict.hip) ----
+ * stamps[n_rows] int32 on the device: the index of the last frame that observed the row.
+ *
+ * gsl_map_observe: row i of means[n_rows,3], with w2c[16] (world to camera, row-major, on the device) and
+ *   depth[height,width] float32 (the observed depth, metres):
+ *   x = ((w0 px + w1 py) + w2 pz) + w3, and y, z likewise from rows 1 and 2 of w2c;
+ *   u = fx x / z + cx, v = fy y / z + cy;  uf = rintf(u), vf = rintf(v) (round half to even);
+ *   IN REACH when z > near_plane and z < far_plane and -reach_px <= u <= (width - 1) + reach_px and
+ *            -reach_px <= v <= (height - 1) + reach_px (the rule of gsl_map_view_select with guard_px = reach_px);
+ *   INSIDE   when 0 <= uf <= width - 1 and 0 <= vf <= height - 1 (float comparisons; uf = -0 is column 0);
+ *   AGREES   when some pixel (uf + du, vf + dv), |du|, |dv| <= window_px, that lies inside the image has a depth d
+ *            that is finite and > 0 with z >= d * keep and z * keep <= d (two rounded products, no division);
+ *   OBSERVED when in reach and (not inside, or agrees): a row in the band around the image paints into the frame and
+ *            there is no depth to hold it against.
+ *   Observed rows get stamps[i] = now, every other row keeps its stamp.  float32, evaluated exactly as written (no
+ *   fused operation, correctly rounded division, the two upper limits one rounded sum each), comparisons false for a
+ *   NaN: NaN / inf rows are never observed.  keep is 1 - rho, the float32 difference taken by the caller.
+ *
+ * gsl_map_evict_select: integers only.  age = clamp(now - stamp, 0, 1023) (the difference taken in 64 bits); a row is
+ *   EVICTABLE when age >= min_age; E = min(need, evictable rows); a* = the largest age with count(age >= a*) >= E.
+ *   EVICTED are the rows with age > a* and, of the rows with age == a*, the first E - count(age > a*) (the tie quota)
+ *   in ascending row index.  need == 0 or nothing evictable: E = 0, a* = 1023, every row stays.
+ *   Leaves in the head of ws -- gsl_map_view_ws_bytes(n_rows) bytes, the layout of gsl_map_view_select -- one ballot
+ *   per wave of the rows that STAY and the row offset of every workgroup; counters[0] = rows that stay,
+ *   counters[1] = E, counters[2] = 0.  gsl_map_view_gather on the same rows and the same, untouched ws then moves the
+ *   survivors into another buffer (out_ids: the old row of every survivor).  Behind the head, with
+ *   nb = ceil(n_rows / 256): the ballots of age == a*, nb x 4 uint64; the 1024 age bins, uint32; and uint32
+ *   a*, the tie quota, E, count(age == a*).  counters is int32[3].
+ * gsl_map_gather_i32: dst[r] = src[ids[r]] for r < n_ids (0 for an id outside [0, n_src)): the stamps follow the rows
+ *   that gsl_map_view_gather moved, with the ids it wrote.  n_ids == 0 does nothing.
+ *
+ * All return GSL_ERR_BAD_ARG before any launch for a NULL array, n_rows (n_src) <= 0 or >= 2^31, n_ids < 0 or >= 2^31,
+ * width or height <= 0 or width * height > 2^31 - 1, fx or fy not non-zero, keep outside (0, 1], window_px outside
+ * 0..3, reach_px negative or NaN, near_plane >= far_plane, need < 0, min_age < 1; and GSL_ERR_WORKSPACE for a
+ * workspace smaller than gsl_map_evict_ws_bytes. */
+int gsl_map_observe(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx, float cy,
+                    const float* depth, int width, int height, float keep, int window_px, float reach_px,
+                    float near_plane, float far_plane, int now, int32_t* stamps, void* stream);
+size_t gsl_map_evict_ws_bytes(int64_t n_rows);
+int gsl_map_evict_select(const int32_t* stamps, int64_t n_rows, int now, int min_age, int64_t need,
+                         int32_t* counters, void* ws, size_t ws_bytes, void* stream);
+int gsl_map_gather_i32(const int32_t* src, int64_t n_src, const int32_t* ids, int64_t n_ids, int32_t* dst,
+                       void* stream);
+
 /* ---- spherical harmonics: gsplat.spherical_harmonics fwd/bwd (IDX:14306, IDX:14297) ----
  * dirs[M,3], coeffs[M,K,3] with K >= (degree+1)^2, masks[M] (uint8, may be NULL).
  * degree 0..3.  v_dirs may be NULL. */

@@ -6,9 +6,12 @@ read-back) and of building a tracker, per frame, beside the frame's total -- its
 tracker is kept there.  The sweep row ("Local map" in NOTES.md): a camera that keeps turning, map mode against the
 whole map beside map mode against the part in view, and the host cost of the selection and the check.  The vanish row
 ("Free space" in NOTES.md): a panel that is taken away while the camera looks on, map mode without and with the removal
-of the rows a frame sees through (MapConfig.free_rho), and the host cost of the removal.
+of the rows a frame sees through (MapConfig.free_rho), and the host cost of the removal.  The evict row ("Bounded map"
+in NOTES.md, printed only with --only evict): the sweep in a map whose capacity is the uncut run's map after half of the
+frames, map mode without a bound beside map mode with MapConfig.evict, and the host cost of observe, of the eviction and
+of the whole insertion per frame.
 
-    python scripts/map_figures.py [--frames 20] [--size 640 480] [--only there_and_back | sweep | vanish] [--no-cost]
+    python scripts/map_figures.py [--frames 20] [--size 640 480] [--only there_and_back | sweep | vanish | evict] [--no-cost]
                                   [--sweep DEG FRAMES GUARD_PX] [--vanish FRAMES WITH RHO WINDOW_PX]"""
 import argparse
 import json
@@ -146,6 +149,52 @@ def vanish(W, H, n, n_with, rho, window, cost=True):
               flush=True)
 
 
+def evict(W, H, n, deg, cost=True, free_rho=None):
+    """The sweep (``deg`` degrees and 1 cm per frame, ``n`` frames) in a bounded map: the capacity is the uncut run's
+    map after frame n // 2, which every later frame outgrows.  Map mode without a bound beside map mode with
+    MapConfig.evict, alternating in one process, the second pass of each reported; then the per-frame host cost of
+    observe (no read-back: synchronised here on both sides), of evict (one read-back) and of insert_frame as a whole
+    (the eviction and the extra read-back of a frame that is short included) in a pass of its own.  ``free_rho``: both
+    rows with the free-space removal as well, so that a kernel trace of this run holds k_map_free_select at the same
+    row counts beside the eviction's kernels."""
+    root = pathlib.Path(tempfile.mkdtemp())
+    write_replica_constant_twist(root, W, H, n, rot_deg=deg, trans=0.01)
+
+    def room(capacity, on):
+        return evaluate_room(Parser("Replica", "room0", normalize=True, input_folder=str(root)), 2000, None,
+                             sequential=True, map_mode=True, map_capacity=capacity, map_evict=on, map_free_rho=free_rho)
+
+    uncut = room(None, False)
+    capacity = W * H + sum(uncut["added_per_frame"][:n // 2])
+    for _ in range(2):
+        rows = [room(None, False), room(capacity, True)]
+    for on, r in zip((False, True), rows):
+        print("MAP_FIG " + json.dumps({"sequence": f"sweep {deg} deg x {n}", "map": True, "evict": on, "free_rho": free_rho,
+                                       "capacity": capacity if on else None, **r}), flush=True)
+    if not cost:
+        return
+    parser = Parser("Replica", "room0", normalize=True, input_folder=str(root))
+    depth, rgb, pose = parser.frame(0)
+    loc = Localizer(parser.K, W, H, TrackerConfig(max_steps=2000), mode="map",
+                    map_config=MapConfig(capacity=capacity, evict=True))
+    observe, evicting, insert, frames, evicted = [], [], [], [], []
+    loc.map.observe, loc.map.evict = timed(loc.map.observe, observe), timed(loc.map.evict, evicting)
+    loc.reset(depth, rgb, pose)
+    loc.map.insert_frame = timed(loc.map.insert_frame, insert)
+    for i in range(1, len(parser) + 1):
+        depth, rgb, pose = parser.frame(i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = loc.track(depth, rgb, gt_c2w=pose)
+        torch.cuda.synchronize()
+        frames.append(time.perf_counter() - t0)
+        evicted.append(r.evicted)
+    ms = lambda xs: [round(1e3 * x, 3) for x in xs]  # noqa: E731
+    print("EVICT_COST " + json.dumps({"frame_ms": ms(frames), "observe_ms": ms(observe), "evict_ms": ms(evicting),
+                                      "insert_frame_ms": ms(insert), "evicted": evicted, "capacity": capacity,
+                                      "map_gaussians": loc.map.n_live}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20)
@@ -158,8 +207,13 @@ def main():
                     metavar=("FRAMES", "WITH", "RHO", "WINDOW_PX"),
                     help="the vanish row (--only vanish): frames, how many of them show the panel, free_rho, "
                          "free_window_px")
+    ap.add_argument("--evict-free-rho", type=float, default=None, metavar="RHO",
+                    help="the evict row (--only evict) with free_rho = RHO in both runs (for a kernel trace that holds "
+                         "k_map_free_select beside the eviction's kernels)")
     a = ap.parse_args()
     (W, H), n = a.size, a.frames
+    if a.only == "evict":
+        evict(W, H, int(a.sweep[1]), a.sweep[0], cost=not a.no_cost, free_rho=a.evict_free_rho)
     if a.only in (None, "vanish"):
         vanish(W, H, int(a.vanish[0]), int(a.vanish[1]), a.vanish[2], int(a.vanish[3]), cost=not a.no_cost)
     if a.only in (None, "sweep"):
