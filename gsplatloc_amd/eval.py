@@ -36,7 +36,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   profile: bool = False, rgb_lambda: float = 0.0, ssim_lambda: float = 0.5, sequential: bool = False,
                   motion: str = "constant_velocity", map_mode: bool = False,
                   map_capacity: Optional[int] = None, map_view_guard: Optional[float] = None,
-                  map_free_rho: Optional[float] = None, map_free_window: int = 1, map_evict: bool = False) -> Dict:
+                  map_free_rho: Optional[float] = None, map_free_window: int = 1, map_evict: bool = False,
+                  map_merge_voxel: Optional[float] = None, map_merge_every: int = 1) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -46,8 +47,12 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     ``map_mode``: frames are tracked against a map grown on the device, of ``map_capacity`` rows at most;
     ``map_view_guard``: against the part of it in view, the image widened by that many pixels; ``map_free_rho`` /
     ``map_free_window``: MapConfig.free_rho / free_window_px, the rows a frame sees through are removed;
-    ``map_evict``: MapConfig.evict, a frame that does not fit evicts the least recently observed rows)."""
+    ``map_evict``: MapConfig.evict, a frame that does not fit evicts the least recently observed rows;
+    ``map_merge_voxel`` / ``map_merge_every``: MapConfig.merge_voxel / merge_every, the rows that share a voxel of that
+    side are fused after every that-many-th frame)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
+    if map_merge_voxel is not None and not map_mode:
+        raise ValueError("map_merge_voxel belongs to the map mode (map_mode=True)")
     if map_view_guard is not None and not map_mode:
         raise ValueError("map_view_guard belongs to the map mode (map_mode=True)")
     if map_free_rho is not None and not map_mode:
@@ -56,7 +61,7 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         raise ValueError("map_evict belongs to the map mode (map_mode=True)")
     if sequential:
         return evaluate_sequential(parser, cfg, max_frames, verbose, motion, map_mode, map_capacity, map_view_guard,
-                                   map_free_rho, map_free_window, map_evict)
+                                   map_free_rho, map_free_window, map_evict, map_merge_voxel, map_merge_every)
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -119,14 +124,16 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                         motion: str = "constant_velocity", map_mode: bool = False,
                         map_capacity: Optional[int] = None, map_view_guard: Optional[float] = None,
                         map_free_rho: Optional[float] = None, map_free_window: int = 1,
-                        map_evict: bool = False) -> Dict:
+                        map_evict: bool = False, map_merge_voxel: Optional[float] = None,
+                        map_merge_every: int = 1) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
     map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
     tracked_per_frame (rows the tracker saw) and map_full (some frame's points were dropped at map_capacity).
     map_view_guard: MapConfig.view_guard_px; the report gains view_violations_per_frame.  map_free_rho /
     map_free_window: MapConfig.free_rho / free_window_px; the report gains removed_per_frame.  map_evict:
-    MapConfig.evict; the report gains evicted_per_frame."""
+    MapConfig.evict; the report gains evicted_per_frame.  map_merge_voxel / map_merge_every: MapConfig.merge_voxel /
+    merge_every; the report gains merged_per_frame and merged_at_reset (rows the first frame's own merge removed)."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
@@ -134,12 +141,14 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     if map_mode:
         extra = dict(mode="map", map_config=MapConfig(capacity=map_capacity, view_guard_px=map_view_guard,
                                                        free_rho=map_free_rho, free_window_px=map_free_window,
-                                                       evict=bool(map_evict)))
+                                                       evict=bool(map_evict), merge_voxel=map_merge_voxel,
+                                                       merge_every=map_merge_every))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
+    merged_at_reset = loc.merged_at_reset
     eTs, eRs, steps, lost, path, last_t = [], [], [], 0, 0.0, pose[:3, 3]
-    added, tracked, violations, removed, evicted = [], [], [], [], []
+    added, tracked, violations, removed, evicted, merged = [], [], [], [], [], []
     for i in range(1, n + 1):
         depth, rgb, pose = parser.frame(i)
         r = loc.track(depth, rgb, gt_c2w=pose)
@@ -152,6 +161,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
         violations.append(r.view_violations)
         removed.append(r.removed)
         evicted.append(r.evicted)
+        merged.append(r.merged)
         path += float(torch.norm(pose[:3, 3] - last_t))
         last_t = pose[:3, 3]
         if verbose:
@@ -168,7 +178,9 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                if map_view_guard is not None else {}),
             **({"free_rho": map_free_rho, "free_window_px": map_free_window, "removed_per_frame": removed}
                if map_free_rho is not None else {}),
-            **({"evict": True, "evicted_per_frame": evicted} if map_evict else {})}
+            **({"evict": True, "evicted_per_frame": evicted} if map_evict else {}),
+            **({"merge_voxel": map_merge_voxel, "merge_every": map_merge_every, "merged_per_frame": merged,
+                "merged_at_reset": merged_at_reset} if map_merge_voxel is not None else {})}
 
 
 def main(argv=None):
@@ -205,7 +217,16 @@ def main(argv=None):
     ap.add_argument("--map-evict", action="store_true",
                     help="--map: a bounded map -- a frame whose new points do not fit in --map-capacity first evicts "
                          "the least recently observed points (default: they are dropped and the map is full)")
+    ap.add_argument("--map-merge-voxel", type=float, default=None, metavar="M",
+                    help="--map: a map with a resolution -- the points that share a cube of side M metres are fused into "
+                         "one after a frame's insertion (default: every inserted point stays one point)")
+    ap.add_argument("--map-merge-every", type=int, default=1, metavar="K",
+                    help="--map-merge-voxel: fuse after every K-th frame")
     a = ap.parse_args(argv)
+    if a.map_merge_voxel is not None and not a.map:
+        ap.error("--map-merge-voxel needs --map")
+    if a.map_merge_every != 1 and a.map_merge_voxel is None:
+        ap.error("--map-merge-every needs --map-merge-voxel")
     if a.map and not a.sequential:
         ap.error("--map needs --sequential")
     if a.map_view_guard is not None and not a.map:
@@ -222,7 +243,8 @@ def main(argv=None):
         r = evaluate_room(parser, a.num_iters, a.max_frames, a.verbose, rgb_lambda=a.rgb_lambda,
                           ssim_lambda=a.ssim_lambda, sequential=a.sequential, motion=a.motion, map_mode=a.map,
                           map_capacity=a.map_capacity, map_view_guard=a.map_view_guard,
-                          map_free_rho=a.map_free_rho, map_free_window=a.map_free_window, map_evict=a.map_evict)
+                          map_free_rho=a.map_free_rho, map_free_window=a.map_free_window, map_evict=a.map_evict,
+                          map_merge_voxel=a.map_merge_voxel, map_merge_every=a.map_merge_every)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

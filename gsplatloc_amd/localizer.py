@@ -27,6 +27,9 @@ frame sees through -- in front of everything it observes around their pixel -- a
 With ``MapConfig.evict`` the map lives in its capacity: before the insertion of a frame that is not lost the rows it
 observes are stamped with its index (``GaussianMap.observe``, at the estimate), and an insertion that is short of room
 first evicts the least recently observed rows (``GaussianMap.evict``).
+With ``MapConfig.merge_voxel`` the map has a resolution: after the first frame's insertion and after the insertion (and
+the free-space removal) of every ``merge_every``-th tracked frame that is not lost, the live rows that share a voxel are
+fused into one (``GaussianMap.merge``).
 """
 from __future__ import annotations
 
@@ -78,6 +81,7 @@ class LocalizeResult:
     view_violations: Optional[int] = None  # view_guard_px: rows in reach of the view from c2w that were not tracked
     removed: Optional[int] = None  # free_rho: live rows this frame saw through, removed after its insertion
     evicted: Optional[int] = None  # evict: least recently observed rows that made room for this frame's insertion
+    merged: Optional[int] = None  # merge_voxel: rows removed by fusing the rows that share a voxel, after the insertion
 
 
 def _default_factory(N, W, H, config, device, render_mode):
@@ -109,7 +113,11 @@ class Localizer:
     nothing.  ``map_config.evict``: between the insertion render and the insertion the rows the frame observes from the
     estimate are stamped (``GaussianMap.observe``), and an insertion that does not fit evicts the least recently
     observed rows first (``LocalizeResult.evicted``; ``map_size`` never exceeds the capacity and the map is not
-    ``full`` while enough rows are old enough to go); a lost frame stamps, evicts and inserts nothing.  Everything else
+    ``full`` while enough rows are old enough to go); a lost frame stamps, evicts and inserts nothing.
+    ``map_config.merge_voxel``: last of all -- after ``reset``'s insertion, and after the insertion and the free-space
+    removal of every ``merge_every``-th call of ``track`` whose frame is not lost -- the rows that share a voxel are
+    fused (``GaussianMap.merge``), ``LocalizeResult.merged`` counts the rows it removed (0 on the frames in between)
+    and ``map_size`` is the count after it.  Everything else
     -- normalisation, the re-rendered query depth, the scales, the hand-over, ``best_c2w`` -- is the frame mode's."""
 
     def __init__(self, K: Tensor, width: int, height: int, config: TrackerConfig = TrackerConfig(),
@@ -139,6 +147,9 @@ class Localizer:
         self._view_guard = None  # MapConfig.view_guard_px
         self._free = False  # MapConfig.free_rho is set
         self._evict = False  # MapConfig.evict
+        self._merge_every = 0  # MapConfig.merge_every when merge_voxel is set, else 0
+        self._tracked = 0  # calls of track since reset
+        self.merged_at_reset = None  # merge_voxel: rows the merge after reset's insertion removed
         if self.map_mode:
             make = map_factory if map_factory is not None else GaussianMap
             map_config = map_config if map_config is not None else MapConfig()
@@ -146,6 +157,7 @@ class Localizer:
             self._view_guard = map_config.view_guard_px
             self._free = map_config.free_rho is not None
             self._evict = bool(map_config.evict)
+            self._merge_every = int(map_config.merge_every) if map_config.merge_voxel is not None else 0
         self._render_map = map_renderer if map_renderer is not None else render_depth_alpha
 
     def _frame(self, depth, rgb):
@@ -193,6 +205,9 @@ class Localizer:
         if self.map_mode:
             self.map.clear()
             self.map.insert_frame(depth, rgb, self.K, self._poses[0])  # no render yet: every valid pixel
+            self._tracked = 0
+            if self._merge_every:
+                self.merged_at_reset = self.map.merge()[0]
 
     @torch.no_grad()
     def track(self, depth, rgb=None, gt_c2w: Optional[Tensor] = None) -> LocalizeResult:
@@ -232,6 +247,8 @@ class Localizer:
             out.added, out.tracked = 0, N
             out.removed = 0 if self._free else None
             out.evicted = 0 if self._evict else None
+            out.merged = 0 if self._merge_every else None
+            self._tracked += 1
             if not out.lost:  # a lost frame's pose is a guess: it adds nothing
                 at = best
                 if self._view_guard is not None:
@@ -255,6 +272,8 @@ class Localizer:
                     # insert first, then remove: the insertion render was made from the cloud that was tracked, and
                     # the rows just appended sit at their own pixel's observed depth
                     out.removed, _ = self.map.remove_seen_through(depth, self.K, est, self.cfg.gs.near_plane)
+                if self._merge_every and self._tracked % self._merge_every == 0:
+                    out.merged, _ = self.map.merge()
             out.map_size = self.map.n_live
         if gt is not None:
             out.eT, out.eR = calculate_translation_error(est, gt), calculate_rotation_error(est, gt)

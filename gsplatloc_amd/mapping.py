@@ -23,7 +23,12 @@ A bounded map (``MapConfig.evict``, csrc/map_evict.hip): every row carries the i
 (``stamps``; ``observe`` stamps the rows a frame sees where it expects them, the rows a frame appends get its index), and
 when a frame's new rows do not fit ``insert_frame`` first evicts exactly as many rows as are short -- the least recently
 observed first, in map order among equals (``evict``) -- into the same spare buffers.  Only such a frame reads the
-selection's count back before the append; a frame with room to spare keeps its single synchronisation."""
+selection's count back before the append; a frame with room to spare keeps its single synchronisation.
+
+A map with a resolution (``MapConfig.merge_voxel``, csrc/map_merge.hip): ``merge`` fuses the live rows that share a
+voxel of that side into one row at the first of them, in integer arithmetic that does not depend on the order of the
+rows, and compacts the rows that stay, in map order, into the same spare buffers.  Two more entry points, the local
+map's gather and the stamps' gather; one read-back."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -34,6 +39,9 @@ import torch
 from torch import Tensor
 
 from . import _lib
+
+MERGE_CELL_MAX = 2 ** 20 - 1  # |cell| along an axis that the 3 x 21-bit voxel key of csrc/map_merge.hip holds
+MERGE_SCENE_M = 100.0  # a merge_voxel that leaves that range within this distance of the origin is refused
 
 
 @dataclass
@@ -61,9 +69,30 @@ class MapConfig:
     # a row counts as observed by a frame when a pixel within this many pixels of its own shows its depth, within
     # depth_rho either way (or when it lies in the view_reach_px band around the image)
     observe_window_px: int = 1
+    # a map with a resolution: the live rows that fall into the same cube of this side, metres in the world, are fused
+    # into one row at the first of them -- the mean of their positions and colours, the latest of their stamps -- by
+    # GaussianMap.merge, which Localizer(mode="map") calls after the insertion of every merge_every-th frame
+    # (None: every inserted row stays one row)
+    merge_voxel: Optional[float] = None
+    merge_every: int = 1
 
     def __post_init__(self):
         whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+        if self.merge_voxel is not None:
+            v = self.merge_voxel
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+                raise ValueError(f"merge_voxel {v!r}: a length in metres (or None)")
+            h = np.float32(v)  # the kernel's h and 1 / h are float32
+            if not (np.isfinite(h) and h > 0):
+                raise ValueError(f"merge_voxel {v!r}: finite and above 0 as a float32")
+            with np.errstate(all="ignore"):
+                inv_h = np.float32(1.0) / h
+            if not np.isfinite(inv_h) or float(np.float32(MERGE_SCENE_M) * inv_h) > MERGE_CELL_MAX:
+                raise ValueError(f"merge_voxel {v!r}: a scene of {MERGE_SCENE_M:g} m has more than {MERGE_CELL_MAX} "
+                                 f"voxels of that side along an axis, the voxel key holds 21 bits per axis (at least "
+                                 f"{MERGE_SCENE_M / MERGE_CELL_MAX:.2e} m)")
+        if not whole(self.merge_every) or self.merge_every < 1:
+            raise ValueError(f"merge_every {self.merge_every!r}: a whole number of frames, at least 1")
         if not isinstance(self.evict, bool):
             raise ValueError(f"evict {self.evict!r}: True or False")
         if not whole(self.evict_min_age) or not 1 <= self.evict_min_age <= 1023:
@@ -130,6 +159,12 @@ class GaussianMap:
         self._n_survivors = 0
         # evict: its workspace (not the selection's: the append still needs that one), allocated on first use
         self._evict_ws = None
+        # merge: h and 1 / h as the float32 values the kernel is given, its workspace and four counters on first use
+        self._merge_h = self._merge_inv_h = None
+        if config.merge_voxel is not None:
+            h = np.float32(config.merge_voxel)
+            self._merge_h, self._merge_inv_h = float(h), float(np.float32(1.0) / h)
+        self._merge = None
 
     def _alloc_ws(self):
         if self.device.type != "cuda":
@@ -421,3 +456,51 @@ class GaussianMap:
         if evicted > 0:
             self._swap_spare(stay)
         return evicted, stay
+
+    # ---- a map with a resolution: the rows that share a voxel are fused into one (csrc/map_merge.hip) ----------------
+    def _merge_launch(self) -> Tuple[int, int, int, int]:
+        """The rule over the live rows, the gather of the rows that stay into the spare buffers (means, colours, old
+        rows) and of their stamps, and the fused rows written over the first row of their voxel there; the read-back of
+        (rows that stay, rows removed, rows stored, the table's overflow flag)."""
+        assert self.means.is_cuda, "GaussianMap.merge: the rows are fused and moved by HIP kernels, no CPU path"
+        lib, st, ptr, f = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._free_buffers()
+        if self._merge is None:
+            self._merge = dict(ws=torch.empty(lib.gsl_map_merge_ws_bytes(self.capacity), dtype=torch.uint8,
+                                              device=self.device),
+                               counters=torch.zeros(4, dtype=torch.int32, device=self.device))
+        ws, counters = self._merge["ws"], self._merge["counters"]
+        _lib.check(lib.gsl_map_merge_select(ptr(self.means), ptr(self.colors), ptr(self.stamps), self.n_live,
+                                            self._merge_inv_h, self._merge_h, ptr(counters), ptr(ws), ws.numel(), st),
+                   "gsl_map_merge_select")
+        _lib.check(lib.gsl_map_view_gather(ptr(self.means), ptr(self.colors), self.n_live, ptr(f["means"]),
+                                           ptr(f["colors"]), ptr(f["ids"]), self.capacity, ptr(counters), ptr(ws),
+                                           ws.numel(), st), "gsl_map_view_gather")
+        # every live row at most: the count is not known on the host yet, and the rows past it are never read
+        _lib.check(lib.gsl_map_gather_i32(ptr(self.stamps), self.n_live, ptr(f["ids"]), self.n_live, ptr(f["stamps"]),
+                                          st), "gsl_map_gather_i32")
+        _lib.check(lib.gsl_map_merge_apply(ptr(f["ids"]), ptr(counters), self.n_live, ptr(f["means"]), ptr(f["colors"]),
+                                           ptr(f["stamps"]), ptr(ws), ws.numel(), st), "gsl_map_merge_apply")
+        stay, removed, stored, overflow = counters.tolist()  # the call's one synchronisation
+        return stay, removed, stored, overflow
+
+    @torch.no_grad()
+    def merge(self) -> Tuple[int, int]:
+        """Fuses the live rows that share a voxel of side ``merge_voxel`` (the rule: include/gsloc_hip.h): of the rows
+        of a voxel the first in map order stays and becomes their mean position, mean colour and latest stamp, the
+        others are removed; a row alone in its voxel, and a row with a NaN / inf or too distant mean, keeps every bit.
+        The rows that stay keep their order.  Returns (removed, kept).  A swap as in ``remove_seen_through``: when
+        something was removed, views taken before the call are stale, ``survivors`` holds the old row of every live
+        row, and the next ``view_violations`` needs a fresh ``select_view``.  When nothing was removed nothing
+        changes."""
+        if self._merge_h is None:
+            raise RuntimeError("merge: MapConfig.merge_voxel is None, the map has no resolution")
+        if self.n_live == 0:
+            return 0, 0
+        stay, removed, stored, overflow = self._merge_launch()
+        if overflow != 0:
+            raise RuntimeError("GaussianMap.merge: a row found no slot in the voxel table (gsl_map_merge_select)")
+        assert stored == stay == self.n_live - removed, (stay, removed, stored, self.n_live)
+        self._n_survivors = stay
+        if removed > 0:
+            self._swap_spare(stay)
+        return removed, stay

@@ -251,6 +251,48 @@ int gsl_map_evict_select(const int32_t* stamps, int64_t n_rows, int now, int min
 int gsl_map_gather_i32(const int32_t* src, int64_t n_src, const int32_t* ids, int64_t n_ids, int32_t* dst,
                        void* stream);
 
+/* ---- map resolution: the rows that share a voxel of side h are fused into one (csrc/map_merge.hip) ----
+ * means[n_rows,3], colors[n_rows,3] float32 and stamps[n_rows] int32 on the device, as in the map.  h and inv_h are
+ * float32 values taken by the caller: h = (float)merge_voxel, inv_h = 1.0f / h (one correctly rounded division).
+ * The rule is evaluated exactly as written: float32 with no fused operation where float32 is named, IEEE double
+ * elsewhere.
+ *   CELL      for each axis a: f_a = p_a * inv_h (one rounded product), c_a = floorf(f_a);
+ *   MERGEABLE when the three f_a are finite and |c_a| <= 2^20 - 1.  Every other row -- NaN, inf, too far for a key of
+ *             3 x 21 bits -- stays as it is, and no other row is ever merged with it.  The voxel key is the three
+ *             cells, each biased by 2^20 - 1, packed into 63 bits (axis a at bit 21 a); the all-ones word is the empty
+ *             slot of the table;
+ *   VOXEL STATISTICS over the k mergeable rows of a voxel: first = the smallest row index;
+ *             S_a = the integer sum of q_a = (uint32)rintf((f_a - c_a) * 65536.f);
+ *             C_j = the integer sum of rintf(fminf(fmaxf(colour_j, 0.f), 1.f) * 65280.f) -- 65280 = 255 * 256, so that
+ *             8-bit colours are exact; a NaN colour counts as 0;  T = the largest stamp;
+ *   k == 1    the row keeps every bit of its mean, colour and stamp;
+ *   k > 1     the rows other than first are REMOVED, and row first becomes
+ *             mean_a   = (float)(((double)c_a + (double)S_a / (65536.0 * (double)k)) * (double)h),
+ *             colour_j = (float)((double)C_j / (65280.0 * (double)k)),  stamp = T;
+ *   ORDER     the rows that stay keep their map order.
+ * All sums are integers: the result does not depend on the order in which the rows arrive, nor on the table's hash.
+ *
+ * gsl_map_merge_select: evaluates the rule over the rows and leaves, in the head of ws -- gsl_map_view_ws_bytes(n_rows)
+ *   bytes, the layout of gsl_map_view_select -- one ballot per wave of the rows that STAY and the row offset of every
+ *   workgroup; behind the head the voxel table (the smallest power of two >= 2 n_rows slots, open addressing), the
+ *   voxel sums, the slot of every row, and h.  counters is int32[4]: counters[0] = rows that stay, counters[1] = rows
+ *   removed, counters[2] = 0, counters[3] = 0 -- or 1 when some row found no slot within as many probes as the table
+ *   has slots (it was then treated as not mergeable; with a table half empty this cannot happen, and a caller that
+ *   reads 1 must not trust the result).
+ * gsl_map_view_gather on the same rows and the same, untouched ws then moves the survivors into another buffer
+ *   (out_ids: the old row of every survivor, counters[2]: rows stored), and gsl_map_gather_i32 their stamps.
+ * gsl_map_merge_apply: after those, with the same n_rows and the same, untouched ws; ids = the out_ids of the gather,
+ *   out_means / out_colors / out_stamps = what the gathers filled.  For r < counters[2] (read on the device): where the
+ *   voxel of old row ids[r] has k > 1, rows r of the three outputs are overwritten by the rule.
+ *
+ * Both return GSL_ERR_BAD_ARG before any launch for a NULL array, n_rows <= 0 or >= 2^31, h or inv_h not finite and
+ * positive; and GSL_ERR_WORKSPACE for a workspace smaller than gsl_map_merge_ws_bytes. */
+size_t gsl_map_merge_ws_bytes(int64_t n_rows);
+int gsl_map_merge_select(const float* means, const float* colors, const int32_t* stamps, int64_t n_rows, float inv_h,
+                         float h, int32_t* counters, void* ws, size_t ws_bytes, void* stream);
+int gsl_map_merge_apply(const int32_t* ids, const int32_t* counters, int64_t n_rows, float* out_means,
+                        float* out_colors, int32_t* out_stamps, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- spherical harmonics: gsplat.spherical_harmonics fwd/bwd (IDX:14306, IDX:14297) ----
  * dirs[M,3], coeffs[M,K,3] with K >= (degree+1)^2, masks[M] (uint8, may be NULL).
  * degree 0..3.  v_dirs may be NULL. */

@@ -9,10 +9,14 @@ whole map beside map mode against the part in view, and the host cost of the sel
 of the rows a frame sees through (MapConfig.free_rho), and the host cost of the removal.  The evict row ("Bounded map"
 in NOTES.md, printed only with --only evict): the sweep in a map whose capacity is the uncut run's map after half of the
 frames, map mode without a bound beside map mode with MapConfig.evict, and the host cost of observe, of the eviction and
-of the whole insertion per frame.
+of the whole insertion per frame.  The merge rows ("Map resolution" in NOTES.md, printed only with --only merge): the
+there-and-back sequence and the sweep, map mode unmerged beside map mode with MapConfig.merge_voxel, and the host cost
+of the merge per frame.
 
-    python scripts/map_figures.py [--frames 20] [--size 640 480] [--only there_and_back | sweep | vanish | evict] [--no-cost]
-                                  [--sweep DEG FRAMES GUARD_PX] [--vanish FRAMES WITH RHO WINDOW_PX]"""
+    python scripts/map_figures.py [--frames 20] [--size 640 480] [--no-cost]
+                                  [--only there_and_back | sweep | vanish | evict | merge]
+                                  [--sweep DEG FRAMES GUARD_PX] [--vanish FRAMES WITH RHO WINDOW_PX]
+                                  [--merge-voxel M] [--merge-every K]"""
 import argparse
 import json
 import os
@@ -195,6 +199,62 @@ def evict(W, H, n, deg, cost=True, free_rho=None):
                                       "map_gaussians": loc.map.n_live}), flush=True)
 
 
+def merge(W, H, n, deg, n_sweep, voxel=None, every=1, cost=True):
+    """A map with a resolution (MapConfig.merge_voxel) on the there-and-back sequence (``n // 2`` steps out and back) and
+    on the sweep (``deg`` degrees and 1 cm per frame, ``n_sweep`` frames): map mode unmerged beside map mode merged,
+    alternating in one process, the second pass of each reported.  ``voxel`` None: the median over frame 0's pixels of
+    the distance between the back-projections of a pixel and its nearer right / lower neighbour -- the spacing of the
+    closest view.  Then the per-frame host cost of merge (wall time, synchronised on both sides, the read-back
+    included) in a pass of its own on each sequence."""
+    from gsplatloc_amd.my_gsplat.geometry import depth_to_points
+
+    sequences = (("there_and_back", lambda root: write_replica_there_and_back(root, W, H, n // 2)),
+                 (f"sweep {deg} deg x {n_sweep}",
+                  lambda root: write_replica_constant_twist(root, W, H, n_sweep, rot_deg=deg, trans=0.01)))
+    for name, writer in sequences:
+        root = pathlib.Path(tempfile.mkdtemp())
+        writer(root)
+        parser = Parser("Replica", "room0", normalize=True, input_folder=str(root))
+        h = voxel
+        if h is None:
+            p = depth_to_points(parser.frame(0)[0], parser.K).reshape(H, W, 3)
+            right, down = (p[:-1, 1:] - p[:-1, :-1]).norm(dim=-1), (p[1:, :-1] - p[:-1, :-1]).norm(dim=-1)
+            h = float(torch.minimum(right, down).median())
+        for _ in range(2):
+            rows = [evaluate_room(Parser("Replica", "room0", normalize=True, input_folder=str(root)), 2000, None,
+                                  sequential=True, map_mode=True, map_merge_voxel=v, map_merge_every=every)
+                    for v in (None, h)]
+        for v, r in zip((None, h), rows):
+            print("MAP_FIG " + json.dumps({"sequence": name, "map": True, "merge_voxel": v, **r}), flush=True)
+        if not cost:
+            continue
+        depth, rgb, pose = parser.frame(0)
+        loc = Localizer(parser.K, W, H, TrackerConfig(max_steps=2000), mode="map",
+                        map_config=MapConfig(merge_voxel=h, merge_every=every))
+        merging, frames, merged, before = [], [], [], []
+        real = timed(loc.map.merge, merging)
+
+        def logged():
+            before.append(loc.map.n_live)
+            return real()
+
+        loc.map.merge = logged
+        loc.reset(depth, rgb, pose)
+        for i in range(1, len(parser) + 1):
+            depth, rgb, pose = parser.frame(i)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = loc.track(depth, rgb, gt_c2w=pose)
+            torch.cuda.synchronize()
+            frames.append(time.perf_counter() - t0)
+            merged.append(r.merged)
+        ms = lambda xs: [round(1e3 * x, 3) for x in xs]  # noqa: E731
+        print("MERGE_COST " + json.dumps({"sequence": name, "merge_voxel": h, "frame_ms": ms(frames),
+                                          "merge_ms": ms(merging), "rows_before_merge": before,
+                                          "merged_at_reset": loc.merged_at_reset, "merged": merged,
+                                          "map_gaussians": loc.map.n_live}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20)
@@ -210,8 +270,15 @@ def main():
     ap.add_argument("--evict-free-rho", type=float, default=None, metavar="RHO",
                     help="the evict row (--only evict) with free_rho = RHO in both runs (for a kernel trace that holds "
                          "k_map_free_select beside the eviction's kernels)")
+    ap.add_argument("--merge-voxel", type=float, default=None, metavar="M",
+                    help="the merge row (--only merge): MapConfig.merge_voxel in metres (default: the spacing of frame "
+                         "0's back-projected pixels)")
+    ap.add_argument("--merge-every", type=int, default=1, metavar="K", help="the merge row: MapConfig.merge_every")
     a = ap.parse_args()
     (W, H), n = a.size, a.frames
+    if a.only == "merge":
+        merge(W, H, n, a.sweep[0], int(a.sweep[1]), voxel=a.merge_voxel, every=a.merge_every, cost=not a.no_cost)
+        return
     if a.only == "evict":
         evict(W, H, int(a.sweep[1]), a.sweep[0], cost=not a.no_cost, free_rho=a.evict_free_rho)
     if a.only in (None, "vanish"):
