@@ -57,6 +57,9 @@ _SIGNATURES = {
     "gsl_map_merge_ws_bytes": (c_size_t, [c_int64]),
     "gsl_map_merge_select": (c_int, [P, P, P, c_int64, c_float, c_float, P, P, c_size_t, P]),
     "gsl_map_merge_apply": (c_int, [P, P, c_int64, P, P, P, P, c_size_t, P]),
+    "gsl_map_score_max_poses": (c_int, []),
+    "gsl_map_score": (c_int, [P, c_int64, P, c_int, c_float, c_float, c_float, c_float, P, c_int, c_int, c_float, c_float,
+                              c_float, P, P]),
     "gsl_sh_fwd": (c_int, [c_int, P, P, P, c_int, c_int, P, P]),
     "gsl_sh_bwd": (c_int, [c_int, P, P, P, c_int, c_int, P, P, P, P]),
     "gsl_isect_ws_bytes": (c_size_t, [c_int]),

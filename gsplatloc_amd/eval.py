@@ -37,7 +37,9 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   motion: str = "constant_velocity", map_mode: bool = False,
                   map_capacity: Optional[int] = None, map_view_guard: Optional[float] = None,
                   map_free_rho: Optional[float] = None, map_free_window: int = 1, map_evict: bool = False,
-                  map_merge_voxel: Optional[float] = None, map_merge_every: int = 1) -> Dict:
+                  map_merge_voxel: Optional[float] = None, map_merge_every: int = 1, map_reloc: bool = False,
+                  map_reloc_min_agree: Optional[float] = None, map_reloc_rot_deg: Optional[float] = None,
+                  map_reloc_trans: Optional[float] = None) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -49,7 +51,10 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     ``map_free_window``: MapConfig.free_rho / free_window_px, the rows a frame sees through are removed;
     ``map_evict``: MapConfig.evict, a frame that does not fit evicts the least recently observed rows;
     ``map_merge_voxel`` / ``map_merge_every``: MapConfig.merge_voxel / merge_every, the rows that share a voxel of that
-    side are fused after every that-many-th frame)."""
+    side are fused after every that-many-th frame; ``map_reloc``: MapConfig.reloc, an estimate the map does not confirm
+    is tracked once more from the best-scoring pose of a grid around the start poses, with ``map_reloc_min_agree`` /
+    ``map_reloc_rot_deg`` / ``map_reloc_trans`` for MapConfig.reloc_min_agree / reloc_rot_deg / reloc_trans where not
+    None)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
     if map_merge_voxel is not None and not map_mode:
         raise ValueError("map_merge_voxel belongs to the map mode (map_mode=True)")
@@ -59,9 +64,16 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         raise ValueError("map_free_rho belongs to the map mode (map_mode=True)")
     if map_evict and not map_mode:
         raise ValueError("map_evict belongs to the map mode (map_mode=True)")
+    reloc = {k: v for k, v in (("reloc_min_agree", map_reloc_min_agree), ("reloc_rot_deg", map_reloc_rot_deg),
+                               ("reloc_trans", map_reloc_trans)) if v is not None}
+    if (map_reloc or reloc) and not map_mode:
+        raise ValueError("map_reloc belongs to the map mode (map_mode=True)")
+    if reloc and not map_reloc:
+        raise ValueError(f"{', '.join('map_' + k for k in reloc)}: options of map_reloc=True")
     if sequential:
         return evaluate_sequential(parser, cfg, max_frames, verbose, motion, map_mode, map_capacity, map_view_guard,
-                                   map_free_rho, map_free_window, map_evict, map_merge_voxel, map_merge_every)
+                                   map_free_rho, map_free_window, map_evict, map_merge_voxel, map_merge_every,
+                                   dict(reloc, reloc=True) if map_reloc else None)
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -125,7 +137,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                         map_capacity: Optional[int] = None, map_view_guard: Optional[float] = None,
                         map_free_rho: Optional[float] = None, map_free_window: int = 1,
                         map_evict: bool = False, map_merge_voxel: Optional[float] = None,
-                        map_merge_every: int = 1) -> Dict:
+                        map_merge_every: int = 1, map_reloc: Optional[Dict] = None) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
     map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
@@ -133,7 +145,10 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     map_view_guard: MapConfig.view_guard_px; the report gains view_violations_per_frame.  map_free_rho /
     map_free_window: MapConfig.free_rho / free_window_px; the report gains removed_per_frame.  map_evict:
     MapConfig.evict; the report gains evicted_per_frame.  map_merge_voxel / map_merge_every: MapConfig.merge_voxel /
-    merge_every; the report gains merged_per_frame and merged_at_reset (rows the first frame's own merge removed)."""
+    merge_every; the report gains merged_per_frame and merged_at_reset (rows the first frame's own merge removed).
+    map_reloc: the MapConfig fields of relocalisation (reloc=True and any of reloc_min_agree, reloc_rot_deg,
+    reloc_trans); the report gains relocalised_frames and agree_share_per_frame (agree / (agree + front) of the
+    estimate that was kept, None where no row was judged)."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
@@ -142,13 +157,14 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
         extra = dict(mode="map", map_config=MapConfig(capacity=map_capacity, view_guard_px=map_view_guard,
                                                        free_rho=map_free_rho, free_window_px=map_free_window,
                                                        evict=bool(map_evict), merge_voxel=map_merge_voxel,
-                                                       merge_every=map_merge_every))
+                                                       merge_every=map_merge_every, **(map_reloc or {})))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
     merged_at_reset = loc.merged_at_reset
     eTs, eRs, steps, lost, path, last_t = [], [], [], 0, 0.0, pose[:3, 3]
     added, tracked, violations, removed, evicted, merged = [], [], [], [], [], []
+    relocalised, shares = 0, []
     for i in range(1, n + 1):
         depth, rgb, pose = parser.frame(i)
         r = loc.track(depth, rgb, gt_c2w=pose)
@@ -162,6 +178,9 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
         removed.append(r.removed)
         evicted.append(r.evicted)
         merged.append(r.merged)
+        if map_reloc:
+            relocalised += int(r.relocalised)
+            shares.append(r.agree / (r.agree + r.front) if r.agree + r.front > 0 else None)
         path += float(torch.norm(pose[:3, 3] - last_t))
         last_t = pose[:3, 3]
         if verbose:
@@ -180,7 +199,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                if map_free_rho is not None else {}),
             **({"evict": True, "evicted_per_frame": evicted} if map_evict else {}),
             **({"merge_voxel": map_merge_voxel, "merge_every": map_merge_every, "merged_per_frame": merged,
-                "merged_at_reset": merged_at_reset} if map_merge_voxel is not None else {})}
+                "merged_at_reset": merged_at_reset} if map_merge_voxel is not None else {}),
+            **({"reloc": True, "relocalised_frames": relocalised, "agree_share_per_frame": shares} if map_reloc else {})}
 
 
 def main(argv=None):
@@ -222,6 +242,16 @@ def main(argv=None):
                          "one after a frame's insertion (default: every inserted point stays one point)")
     ap.add_argument("--map-merge-every", type=int, default=1, metavar="K",
                     help="--map-merge-voxel: fuse after every K-th frame")
+    ap.add_argument("--map-reloc", action="store_true",
+                    help="--map: relocalisation -- an estimate the map does not confirm is tracked once more, from the "
+                         "best-scoring pose of a grid around the frame's start poses; rejected again, the frame is lost "
+                         "and leaves the map alone (default: every estimate with a recorded minimum is inserted)")
+    ap.add_argument("--map-reloc-min-agree", type=float, default=None, metavar="S",
+                    help="--map-reloc: least share of the judged map points that must lie on the observed surface")
+    ap.add_argument("--map-reloc-rot-deg", type=float, default=None, metavar="D",
+                    help="--map-reloc: rotation step of the candidate grid, degrees")
+    ap.add_argument("--map-reloc-trans", type=float, default=None, metavar="M",
+                    help="--map-reloc: translation step of the candidate grid, metres")
     a = ap.parse_args(argv)
     if a.map_merge_voxel is not None and not a.map:
         ap.error("--map-merge-voxel needs --map")
@@ -237,6 +267,14 @@ def main(argv=None):
         ap.error("--map-evict needs --map")
     if a.map_free_window != 1 and not a.map:
         ap.error("--map-free-window needs --map")
+    if a.map_reloc and not a.map:
+        ap.error("--map-reloc needs --map")
+    for flag, value in (("--map-reloc-min-agree", a.map_reloc_min_agree), ("--map-reloc-rot-deg", a.map_reloc_rot_deg),
+                        ("--map-reloc-trans", a.map_reloc_trans)):
+        if value is not None and not a.map:
+            ap.error(f"{flag} needs --map")
+        if value is not None and not a.map_reloc:
+            ap.error(f"{flag} needs --map-reloc")
     out = {}
     for room in a.rooms:
         parser = Parser(a.dataset, room, normalize=not a.no_normalize, input_folder=a.root)
@@ -244,7 +282,9 @@ def main(argv=None):
                           ssim_lambda=a.ssim_lambda, sequential=a.sequential, motion=a.motion, map_mode=a.map,
                           map_capacity=a.map_capacity, map_view_guard=a.map_view_guard,
                           map_free_rho=a.map_free_rho, map_free_window=a.map_free_window, map_evict=a.map_evict,
-                          map_merge_voxel=a.map_merge_voxel, map_merge_every=a.map_merge_every)
+                          map_merge_voxel=a.map_merge_voxel, map_merge_every=a.map_merge_every, map_reloc=a.map_reloc,
+                          map_reloc_min_agree=a.map_reloc_min_agree, map_reloc_rot_deg=a.map_reloc_rot_deg,
+                          map_reloc_trans=a.map_reloc_trans)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

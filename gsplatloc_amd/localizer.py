@@ -30,9 +30,16 @@ first evicts the least recently observed rows (``GaussianMap.evict``).
 With ``MapConfig.merge_voxel`` the map has a resolution: after the first frame's insertion and after the insertion (and
 the free-space removal) of every ``merge_every``-th tracked frame that is not lost, the live rows that share a voxel are
 fused into one (``GaussianMap.merge``).
+With ``MapConfig.reloc`` an estimate has to be confirmed by the map before any of that: the live rows the new frame
+tests, confirms and sees through from the estimate are counted (``GaussianMap.score_poses``), and an estimate with too
+few rows tested, or too small a share of confirmed rows among those confirmed or seen through, is rejected.  The frame
+is then tracked once more, from the best-scoring pose of a small grid of turns and shifts around its start poses
+(``reloc_candidates``); an estimate rejected again makes the frame a lost one, which leaves the map alone.  This is no
+place recognition -- nothing beyond that grid is tried -- and it repairs nothing a wrongly accepted frame has inserted.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Callable, List, Optional
 
@@ -41,7 +48,7 @@ from torch import Tensor
 
 from .data.dataset import build_pair
 from .data.normalize import denormalize_camera, transform_cameras
-from .mapping import GaussianMap, MapConfig
+from .mapping import SCORE_MAX_POSES, GaussianMap, MapConfig
 from .my_gsplat.geometry import construct_full_pose, depth_to_points, init_gs_scales, render_depth_alpha
 from .my_gsplat.trainer import TrackerConfig, calculate_rotation_error, calculate_translation_error
 from .my_gsplat.transform import normalize_quaternion, quat_to_rotation_matrix, rotation_matrix_to_quaternion
@@ -82,6 +89,53 @@ class LocalizeResult:
     removed: Optional[int] = None  # free_rho: live rows this frame saw through, removed after its insertion
     evicted: Optional[int] = None  # evict: least recently observed rows that made room for this frame's insertion
     merged: Optional[int] = None  # merge_voxel: rows removed by fusing the rows that share a voxel, after the insertion
+    # reloc: ``lost`` is "the map does not confirm the estimate" (not accepted, also after a second tracking);
+    # relocalised: the estimate is that of a second tracking, started from the best-scoring candidate pose; tested /
+    # agree / front: the map's verdict on c2w (GaussianMap.score_poses)
+    relocalised: Optional[bool] = None
+    tested: Optional[int] = None
+    agree: Optional[int] = None
+    front: Optional[int] = None
+
+
+def _step(axis: int, rot_deg: float = 0.0, trans: float = 0.0) -> Tensor:
+    """float64 [4,4]: a turn by rot_deg degrees about, or a shift by trans along, coordinate axis 0 / 1 / 2."""
+    M = torch.eye(4, dtype=torch.float64)
+    if rot_deg != 0.0:
+        a, b = (axis + 1) % 3, (axis + 2) % 3
+        c, s = math.cos(math.radians(rot_deg)), math.sin(math.radians(rot_deg))
+        M[a, a], M[a, b], M[b, a], M[b, b] = c, -s, s, c
+    M[axis, 3] = trans
+    return M
+
+
+def reloc_candidates(bases, rot_deg: float, trans: float, levels: int) -> Tensor:
+    """The candidate start poses of a relocalisation, [k,4,4] float32 on the device of the first base: for every base
+    c2w [4,4], in the order given, the base itself; then for level l = 1 .. levels and axis x, y, z the turns
+    c2w @ R(axis, +l rot_deg), c2w @ R(axis, -l rot_deg); then for l = 1 .. levels and axis x, y, z the shifts
+    c2w @ T(axis, +l trans), c2w @ T(axis, -l trans) -- the camera's own axes, 1 + 12 levels poses per base.  Composed
+    in float64 and rounded to float32 once (a base comes back bit for bit).  More poses than one call of
+    ``GaussianMap.score_poses`` takes (64) are refused."""
+    bases = [torch.as_tensor(b) for b in bases]
+    levels = int(levels)
+    if not bases or levels < 1:
+        raise ValueError("reloc_candidates: at least one base pose and one level")
+    if len(bases) * (1 + 12 * levels) > SCORE_MAX_POSES:
+        raise ValueError(f"reloc_candidates: {len(bases)} bases x {1 + 12 * levels} poses are more than the "
+                         f"{SCORE_MAX_POSES} one scoring call takes")
+    out = []
+    for b in bases:
+        if b.shape != (4, 4):
+            raise ValueError(f"a base pose is {tuple(b.shape)}, not (4, 4)")
+        c2w = b.detach().cpu().double()
+        out.append(c2w)
+        for kind in ("rot_deg", "trans"):
+            size = float(rot_deg) if kind == "rot_deg" else float(trans)
+            for level in range(1, levels + 1):
+                for axis in range(3):
+                    for sign in (1.0, -1.0):
+                        out.append(c2w @ _step(axis, **{kind: sign * level * size}))
+    return torch.stack(out).to(dtype=torch.float32, device=bases[0].device)
 
 
 def _default_factory(N, W, H, config, device, render_mode):
@@ -117,7 +171,17 @@ class Localizer:
     ``map_config.merge_voxel``: last of all -- after ``reset``'s insertion, and after the insertion and the free-space
     removal of every ``merge_every``-th call of ``track`` whose frame is not lost -- the rows that share a voxel are
     fused (``GaussianMap.merge``), ``LocalizeResult.merged`` counts the rows it removed (0 on the frames in between)
-    and ``map_size`` is the count after it.  Everything else
+    and ``map_size`` is the count after it.  ``map_config.reloc``: first of all -- after ``run()``, before the band is
+    checked or anything is rendered, stamped or inserted -- the estimate is scored against the map
+    (``GaussianMap.score_poses``; ``LocalizeResult.tested`` / ``agree`` / ``front``) and accepted when the tracker
+    recorded a minimum, at least ``reloc_min_tested`` rows were tested and ``agree >= reloc_min_agree * (agree +
+    front)``.  If not, ``reloc_candidates`` around the start pose (and around the previous estimate, where the motion
+    model made the two differ) are scored in one call and the one with the largest ``agree - front`` (the lowest index
+    among equals) is tracked from, on a pair built at that pose; its estimate, if accepted, is the frame's
+    (``relocalised``).  If it is not, or if the start that failed scored highest itself, the frame is ``lost`` -- which
+    with this option means "not accepted" -- the better-scoring of the two estimates is handed on, and the map is left
+    as it was.  ``steps`` counts both runs; ``best_step``, ``best_loss`` and ``init_c2w`` are those of the run that
+    was kept.  Everything else
     -- normalisation, the re-rendered query depth, the scales, the hand-over, ``best_c2w`` -- is the frame mode's."""
 
     def __init__(self, K: Tensor, width: int, height: int, config: TrackerConfig = TrackerConfig(),
@@ -148,6 +212,8 @@ class Localizer:
         self._free = False  # MapConfig.free_rho is set
         self._evict = False  # MapConfig.evict
         self._merge_every = 0  # MapConfig.merge_every when merge_voxel is set, else 0
+        self._reloc = None  # the MapConfig when MapConfig.reloc is on
+        self._min_tested = 0  # MapConfig.reloc_min_tested, or its default for this image size
         self._tracked = 0  # calls of track since reset
         self.merged_at_reset = None  # merge_voxel: rows the merge after reset's insertion removed
         if self.map_mode:
@@ -158,6 +224,10 @@ class Localizer:
             self._free = map_config.free_rho is not None
             self._evict = bool(map_config.evict)
             self._merge_every = int(map_config.merge_every) if map_config.merge_voxel is not None else 0
+            if map_config.reloc:
+                self._reloc = map_config
+                self._min_tested = (map_config.reloc_min_tested if map_config.reloc_min_tested is not None
+                                    else (self.W * self.H) // 16)
         self._render_map = map_renderer if map_renderer is not None else render_depth_alpha
 
     def _frame(self, depth, rgb):
@@ -190,6 +260,32 @@ class Localizer:
         metres up to the pair's scale factor, which build_pair divides the query depth by as well)."""
         render, alphas = self._render_map(d.tar_points, scales, self.K.unsqueeze(0), c2w_n.unsqueeze(0), self.H, self.W)
         return render / d.pca_factor.reshape(()), alphas
+
+    def _run_tracker(self, d, init: Tensor):
+        """Steps 4 - 6 on the pair ``d`` from the world pose ``init``: (Gaussians tracked, their scales, the tracker's
+        result, its minimum-loss pose in the pair's frame, that pose in the world)."""
+        init_n = transform_cameras(d.norm_T, init.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else init
+        N = d.tar_points.shape[0]
+        if self.tracker is None or self._tracker_N != N:
+            self.tracker, self._tracker_N = self._factory(N, self.W, self.H, self.cfg, self.device, self.render_mode), N
+        scales = init_gs_scales(d.tar_points)
+        self.tracker.load_frame(d.tar_points, d.colors, scales, d.src_depth, init_n, d.src_c2w,
+                                self.K, pixels=d.pixels if self.photo else None)
+        res = self.tracker.run()
+        best = res.best_c2w.to(self.device)
+        est = denormalize_camera(d.norm_T, best) if d.norm_T is not None else best.clone()
+        return N, scales, res, best, est
+
+    def _verdict(self, depth: Tensor, c2w: Tensor):
+        """(tested, agree, front), Python ints: the map's rows that the depth frame judges from the world pose c2w."""
+        return tuple(int(c) for c in self.map.score_poses(depth, self.K, [c2w], self.cfg.gs.near_plane)[0])
+
+    def _accepted(self, res, verdict) -> bool:
+        """reloc: the tracker recorded a minimum, enough rows were tested, and of those the frame judges against its
+        own surface -- in front of it or on it -- at least ``reloc_min_agree`` are on it."""
+        tested, agree, front = verdict
+        return (res.best_step != -1 and tested >= self._min_tested
+                and agree >= self._reloc.reloc_min_agree * (agree + front))
 
     @property
     def trajectory(self) -> Tensor:
@@ -229,20 +325,35 @@ class Localizer:
         else:
             d = build_pair(self._prev[0], self._prev[1], pts, col, depth, rgb, placed, gt if gt is not None else init,
                            self.K, self.normalize)
-        init_n = transform_cameras(d.norm_T, init.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else init
-        N = d.tar_points.shape[0]
-        if self.tracker is None or self._tracker_N != N:
-            self.tracker, self._tracker_N = self._factory(N, self.W, self.H, self.cfg, self.device, self.render_mode), N
-        scales = init_gs_scales(d.tar_points)
-        self.tracker.load_frame(d.tar_points, d.colors, scales, d.src_depth, init_n, d.src_c2w,
-                                self.K, pixels=d.pixels if self.photo else None)
-        res = self.tracker.run()
-        best = res.best_c2w.to(self.device)
-        est = denormalize_camera(d.norm_T, best) if d.norm_T is not None else best.clone()
+        N, scales, res, best, est = self._run_tracker(d, init)
+        steps, lost, verdict, relocalised = res.steps, res.best_step == -1, None, None
+        if self._reloc is not None:
+            # before anything touches the map: does it confirm the estimate?  If not, the best-scoring pose of a grid
+            # around the start poses is tracked from once more; an estimate the map still rejects is a lost frame's
+            verdict, relocalised = self._verdict(depth, est), False
+            lost = not self._accepted(res, verdict)
+            if lost:
+                bases = [init] if torch.equal(placed, init) else [init, placed]
+                cands = reloc_candidates(bases, self._reloc.reloc_rot_deg, self._reloc.reloc_trans,
+                                         self._reloc.reloc_levels).to(self.device)
+                scores = self.map.score_poses(depth, self.K, cands, self.cfg.gs.near_plane)
+                margins = [int(s[1]) - int(s[2]) for s in scores]
+                winner = margins.index(max(margins))  # the lowest index among equals
+                if winner != 0:  # 0 is the start that has just failed
+                    again = self._map_pair(cands[winner], frame)
+                    second = self._run_tracker(again, cands[winner])
+                    steps += second[2].steps
+                    verdict2 = self._verdict(depth, second[4])
+                    relocalised = self._accepted(second[2], verdict2)
+                    lost = not relocalised
+                    if relocalised or verdict2[1] - verdict2[2] > verdict[1] - verdict[2]:
+                        (N, scales, res, best, est), d, init, verdict = second, again, cands[winner], verdict2
         self._prev = (pts, col)
         self._poses.append(est)
-        out = LocalizeResult(c2w=est, init_c2w=init, steps=res.steps, best_step=res.best_step, best_loss=res.best_loss,
-                             lost=res.best_step == -1)
+        out = LocalizeResult(c2w=est, init_c2w=init, steps=steps, best_step=res.best_step, best_loss=res.best_loss,
+                             lost=lost)
+        if verdict is not None:
+            out.relocalised, (out.tested, out.agree, out.front) = relocalised, verdict
         if self.map_mode:
             out.added, out.tracked = 0, N
             out.removed = 0 if self._free else None

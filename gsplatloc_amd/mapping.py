@@ -28,7 +28,13 @@ selection's count back before the append; a frame with room to spare keeps its s
 A map with a resolution (``MapConfig.merge_voxel``, csrc/map_merge.hip): ``merge`` fuses the live rows that share a
 voxel of that side into one row at the first of them, in integer arithmetic that does not depend on the order of the
 rows, and compacts the rows that stay, in map order, into the same spare buffers.  Two more entry points, the local
-map's gather and the stamps' gather; one read-back."""
+map's gather and the stamps' gather; one read-back.
+
+Pose scores (``MapConfig.reloc``, csrc/map_score.hip): ``score_poses`` counts, for each of up to 64 poses at once, the
+live rows a depth frame tests, those it confirms (within ``depth_rho`` of the depth their own pixel observes) and those
+it sees through (in front of that depth) -- integer counts, the same on every run -- which is what
+``Localizer(mode="map")`` accepts an estimate by and chooses a new start by when it does not (localizer.py).  It changes
+nothing in the map.  One more entry point; one read-back."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -42,6 +48,7 @@ from . import _lib
 
 MERGE_CELL_MAX = 2 ** 20 - 1  # |cell| along an axis that the 3 x 21-bit voxel key of csrc/map_merge.hip holds
 MERGE_SCENE_M = 100.0  # a merge_voxel that leaves that range within this distance of the origin is refused
+SCORE_MAX_POSES = 64  # poses one call of csrc/map_score.hip scores (gsl_map_score_max_poses())
 
 
 @dataclass
@@ -75,9 +82,39 @@ class MapConfig:
     # (None: every inserted row stays one row)
     merge_voxel: Optional[float] = None
     merge_every: int = 1
+    # Localizer(mode="map"): relocalisation.  A frame's estimate is held against the map (GaussianMap.score_poses: of
+    # the live rows whose own pixel has a depth, those within depth_rho of it AGREE, those nearer are in FRONT) and is
+    # accepted when at least reloc_min_tested rows were tested (None: W * H // 16) and agree >= reloc_min_agree *
+    # (agree + front).  A rejected estimate is tracked once more, from the best-scoring pose of a grid around the
+    # start poses: reloc_levels steps of reloc_rot_deg degrees about, and of reloc_trans metres along, each of the
+    # camera's axes, both ways.  A frame rejected again is lost and leaves the map alone
+    reloc: bool = False
+    # the midpoint of what was measured at 160x120 (NOTES.md, "Relocalisation"): good poses give a share of 0.973 at the
+    # least (508 ghost rows of a panel that has gone, in front of what the frame sees), a start 0.3 m off 0.23
+    reloc_min_agree: float = 0.6
+    reloc_min_tested: Optional[int] = None
+    reloc_rot_deg: float = 2.0
+    reloc_trans: float = 0.05
+    reloc_levels: int = 2
 
     def __post_init__(self):
         whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+        number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer))  # noqa: E731
+        if not isinstance(self.reloc, bool):
+            raise ValueError(f"reloc {self.reloc!r}: True or False")
+        if not number(self.reloc_min_agree) or not 0.0 < self.reloc_min_agree <= 1.0:
+            raise ValueError(f"reloc_min_agree {self.reloc_min_agree!r}: a share of the rows judged, inside (0, 1]")
+        if self.reloc_min_tested is not None and (not whole(self.reloc_min_tested) or self.reloc_min_tested < 1):
+            raise ValueError(f"reloc_min_tested {self.reloc_min_tested!r}: a whole number of rows, at least 1 (or None)")
+        if not number(self.reloc_rot_deg) or not (np.isfinite(self.reloc_rot_deg) and self.reloc_rot_deg > 0):
+            raise ValueError(f"reloc_rot_deg {self.reloc_rot_deg!r}: degrees, finite and above 0")
+        if not number(self.reloc_trans) or not (np.isfinite(self.reloc_trans) and self.reloc_trans > 0):
+            raise ValueError(f"reloc_trans {self.reloc_trans!r}: metres, finite and above 0")
+        if not whole(self.reloc_levels) or not 1 <= self.reloc_levels <= 2:
+            raise ValueError(f"reloc_levels {self.reloc_levels!r}: a whole number of steps per direction, 1 .. 2")
+        if self.reloc and not 0.0 <= self.depth_rho < 1.0:
+            raise ValueError(f"depth_rho {self.depth_rho}: reloc holds a row against the observed depth within this "
+                             "fraction, inside [0, 1)")
         if self.merge_voxel is not None:
             v = self.merge_voxel
             if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
@@ -165,6 +202,9 @@ class GaussianMap:
             h = np.float32(config.merge_voxel)
             self._merge_h, self._merge_inv_h = float(h), float(np.float32(1.0) / h)
         self._merge = None
+        # score_poses: 1 + depth_rho as the float32 value the kernel is given; its two buffers on first use
+        self.beyond = float(np.float32(1.0) + np.float32(config.depth_rho))
+        self._score = None
 
     def _alloc_ws(self):
         if self.device.type != "cuda":
@@ -504,3 +544,43 @@ class GaussianMap:
         if removed > 0:
             self._swap_spare(stay)
         return removed, stay
+
+    # ---- pose scores: how many live rows a depth frame confirms from each of a set of poses (csrc/map_score.hip) ----
+    def _score_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, near: float) -> np.ndarray:
+        """w2c [k,4,4] float32 on the host.  The poses' copy to the device, the entry point (which zeroes the counts) and
+        the read-back of int64 [k,3]: (tested, agree, front) per pose."""
+        assert depth.is_cuda, "GaussianMap.score_poses: the rows are judged and counted by a HIP kernel, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        if self._score is None:
+            self._score = dict(counts=torch.empty(SCORE_MAX_POSES, 3, dtype=torch.int32, device=self.device),
+                               poses=torch.empty(SCORE_MAX_POSES, 16, device=self.device))
+        k, s = w2c.shape[0], self._score
+        s["poses"][:k].copy_(w2c.reshape(k, 16))
+        _lib.check(lib.gsl_map_score(ptr(self.means), self.n_live, ptr(s["poses"]), k, *intr, ptr(depth), self.W, self.H,
+                                     self.keep, self.beyond, near, ptr(s["counts"]), st), "gsl_map_score")
+        return s["counts"][:k].cpu().numpy().astype(np.int64)  # the call's one synchronisation
+
+    @torch.no_grad()
+    def score_poses(self, depth, K, c2ws, near: float) -> np.ndarray:
+        """How the depth frame [H,W] (metres) agrees with the live rows from each of the poses c2ws [k,4,4] (a tensor,
+        or a sequence of [4,4] poses; k <= 64).  Returns int64 [k,3]: per pose the rows TESTED (in the image, beyond the
+        near plane, their own pixel has a depth), those that AGREE (within ``depth_rho`` of that depth either way) and
+        those in FRONT of it (the rule: include/gsloc_hip.h); tested - agree - front lie behind, where a frame that
+        sees a nearer surface says nothing against them.  One launch for all poses, one read-back; an empty map gives
+        zeros without a launch."""
+        poses = [torch.as_tensor(c) for c in c2ws]
+        for c in poses:
+            if c.shape != (4, 4):
+                raise ValueError(f"a pose is {tuple(c.shape)}, not (4, 4)")
+        if len(poses) > SCORE_MAX_POSES:
+            raise ValueError(f"{len(poses)} poses: one call scores at most {SCORE_MAX_POSES}")
+        if self.n_live == 0 or not poses:
+            return np.zeros((len(poses), 3), dtype=np.int64)
+        depth = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
+        if depth.numel() != self.H * self.W:
+            raise ValueError(f"depth is {tuple(depth.shape)}, the map was built for {(self.H, self.W)}")
+        depth = depth.reshape(self.H, self.W).contiguous()
+        intr, _ = _intr_and_pose(K, poses[0])
+        # the float64 inverses, rounded to float32 here: the kernel multiplies and adds, nothing else
+        w2c = np.linalg.inv(torch.stack([c.detach().cpu().double() for c in poses]).numpy()).astype(np.float32)
+        return self._score_launch(depth, intr, torch.from_numpy(w2c), float(near))

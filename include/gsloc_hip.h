@@ -293,6 +293,32 @@ int gsl_map_merge_select(const float* means, const float* colors, const int32_t*
 int gsl_map_merge_apply(const int32_t* ids, const int32_t* counters, int64_t n_rows, float* out_means,
                         float* out_colors, int32_t* out_stamps, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- pose scores: how many rows of the map a depth frame confirms from each of n_poses poses (csrc/map_score.hip) ----
+ * depth[height,width] float32 on the device, row-major: the observed depth, metres.  w2c[n_poses,16]: world to camera,
+ * row-major, on the device.  counts[n_poses,3] int32 on the device; it need not be initialised, the entry point zeroes
+ * it on the stream.  Row i of means[n_rows,3], pose k, with w the rows of w2c[k]:
+ *   x = ((w0 px + w1 py) + w2 pz) + w3, and y, z likewise from rows 1 and 2 of w2c[k];
+ *   u = fx x / z + cx, v = fy y / z + cy;  uf = rintf(u), vf = rintf(v) (round half to even);
+ *   TESTED when z > near_plane and 0 <= uf <= width - 1 and 0 <= vf <= height - 1 (float comparisons, then the
+ *          conversion to int; uf = -0 passes and is column 0) and the row's own pixel d = depth[vf, uf] is finite
+ *          and > 0 -- no window;
+ *   FRONT  when tested and z < d * keep;  BEHIND when tested and z > d * beyond (one rounded product each);
+ *   AGREE  when tested and neither: z == d * keep and z == d * beyond agree;
+ *   counts[k] = (rows tested, rows that agree, rows in front).
+ * float32, evaluated exactly as written (no fused operation, correctly rounded division), comparisons false for a
+ * NaN: NaN / inf rows, rows behind near_plane, rows outside the image and pixels without depth add nothing.  keep is
+ * 1 - rho and beyond 1 + rho, the float32 difference and sum taken by the caller.  The sums are integers: they do not
+ * depend on the order of rows, waves or workgroups.  One zeroing launch and one kernel; the number of global atomics
+ * is bounded by the kernel's grid cap times 3 n_poses, not by n_rows.
+ * Returns GSL_ERR_BAD_ARG before any launch for a NULL means, w2c, depth or counts, n_rows <= 0 or >= 2^31, n_poses
+ * outside 1 .. GSL_MAP_SCORE_MAX_POSES (gsl_map_score_max_poses()), width or height <= 0 or width * height > 2^31 - 1,
+ * fx or fy not non-zero, keep outside (0, 1], beyond not >= 1. */
+#define GSL_MAP_SCORE_MAX_POSES 64
+int gsl_map_score_max_poses(void);
+int gsl_map_score(const float* means, int64_t n_rows, const float* w2c, int n_poses, float fx, float fy, float cx,
+                  float cy, const float* depth, int width, int height, float keep, float beyond, float near_plane,
+                  int32_t* counts, void* stream);
+
 /* ---- spherical harmonics: gsplat.spherical_harmonics fwd/bwd (IDX:14306, IDX:14297) ----
  * dirs[M,3], coeffs[M,K,3] with K >= (degree+1)^2, masks[M] (uint8, may be NULL).
  * degree 0..3.  v_dirs may be NULL. */
