@@ -60,6 +60,9 @@ _SIGNATURES = {
     "gsl_map_score_max_poses": (c_int, []),
     "gsl_map_score": (c_int, [P, c_int64, P, c_int, c_float, c_float, c_float, c_float, P, c_int, c_int, c_float, c_float,
                               c_float, P, P]),
+    "gsl_map_place_cells": (c_int, []),
+    "gsl_map_place_describe": (c_int, [P, c_int, c_int, P, P]),
+    "gsl_map_place_match": (c_int, [P, P, c_int, P, P]),
     "gsl_sh_fwd": (c_int, [c_int, P, P, P, c_int, c_int, P, P]),
     "gsl_sh_bwd": (c_int, [c_int, P, P, P, c_int, c_int, P, P, P, P]),
     "gsl_isect_ws_bytes": (c_size_t, [c_int]),

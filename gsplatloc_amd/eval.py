@@ -39,7 +39,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   map_free_rho: Optional[float] = None, map_free_window: int = 1, map_evict: bool = False,
                   map_merge_voxel: Optional[float] = None, map_merge_every: int = 1, map_reloc: bool = False,
                   map_reloc_min_agree: Optional[float] = None, map_reloc_rot_deg: Optional[float] = None,
-                  map_reloc_trans: Optional[float] = None) -> Dict:
+                  map_reloc_trans: Optional[float] = None, map_keyframes: bool = False,
+                  map_keyframe_rot_deg: Optional[float] = None, map_keyframe_trans: Optional[float] = None) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -54,7 +55,9 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     side are fused after every that-many-th frame; ``map_reloc``: MapConfig.reloc, an estimate the map does not confirm
     is tracked once more from the best-scoring pose of a grid around the start poses, with ``map_reloc_min_agree`` /
     ``map_reloc_rot_deg`` / ``map_reloc_trans`` for MapConfig.reloc_min_agree / reloc_rot_deg / reloc_trans where not
-    None)."""
+    None; ``map_keyframes``: MapConfig.keyframes, a frame that stays lost is compared with the keyframes of the map and
+    tracked once more from the best-scoring pose around the most similar ones, with ``map_keyframe_rot_deg`` /
+    ``map_keyframe_trans`` for MapConfig.keyframe_rot_deg / keyframe_trans where not None)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
     if map_merge_voxel is not None and not map_mode:
         raise ValueError("map_merge_voxel belongs to the map mode (map_mode=True)")
@@ -70,10 +73,17 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         raise ValueError("map_reloc belongs to the map mode (map_mode=True)")
     if reloc and not map_reloc:
         raise ValueError(f"{', '.join('map_' + k for k in reloc)}: options of map_reloc=True")
+    keyframes = {k: v for k, v in (("keyframe_rot_deg", map_keyframe_rot_deg), ("keyframe_trans", map_keyframe_trans))
+                 if v is not None}
+    if (map_keyframes or keyframes) and not map_reloc:
+        raise ValueError("map_keyframes belongs to the relocalisation (map_reloc=True)")
+    if keyframes and not map_keyframes:
+        raise ValueError(f"{', '.join('map_' + k for k in keyframes)}: options of map_keyframes=True")
     if sequential:
         return evaluate_sequential(parser, cfg, max_frames, verbose, motion, map_mode, map_capacity, map_view_guard,
                                    map_free_rho, map_free_window, map_evict, map_merge_voxel, map_merge_every,
-                                   dict(reloc, reloc=True) if map_reloc else None)
+                                   dict(reloc, reloc=True) if map_reloc else None,
+                                   dict(keyframes, keyframes=True) if map_keyframes else None)
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -137,7 +147,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                         map_capacity: Optional[int] = None, map_view_guard: Optional[float] = None,
                         map_free_rho: Optional[float] = None, map_free_window: int = 1,
                         map_evict: bool = False, map_merge_voxel: Optional[float] = None,
-                        map_merge_every: int = 1, map_reloc: Optional[Dict] = None) -> Dict:
+                        map_merge_every: int = 1, map_reloc: Optional[Dict] = None,
+                        map_keyframes: Optional[Dict] = None) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
     map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
@@ -148,7 +159,9 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     merge_every; the report gains merged_per_frame and merged_at_reset (rows the first frame's own merge removed).
     map_reloc: the MapConfig fields of relocalisation (reloc=True and any of reloc_min_agree, reloc_rot_deg,
     reloc_trans); the report gains relocalised_frames and agree_share_per_frame (agree / (agree + front) of the
-    estimate that was kept, None where no row was judged)."""
+    estimate that was kept, None where no row was judged).  map_keyframes: the MapConfig fields of place recognition
+    (keyframes=True and any of keyframe_rot_deg, keyframe_trans); the report gains keyframes (those the map holds at the
+    end) and recognised_frames (frames that a keyframe's neighbourhood was accepted from)."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
@@ -157,14 +170,15 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
         extra = dict(mode="map", map_config=MapConfig(capacity=map_capacity, view_guard_px=map_view_guard,
                                                        free_rho=map_free_rho, free_window_px=map_free_window,
                                                        evict=bool(map_evict), merge_voxel=map_merge_voxel,
-                                                       merge_every=map_merge_every, **(map_reloc or {})))
+                                                       merge_every=map_merge_every, **(map_reloc or {}),
+                                                       **(map_keyframes or {})))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
     merged_at_reset = loc.merged_at_reset
     eTs, eRs, steps, lost, path, last_t = [], [], [], 0, 0.0, pose[:3, 3]
     added, tracked, violations, removed, evicted, merged = [], [], [], [], [], []
-    relocalised, shares = 0, []
+    relocalised, shares, recognised = 0, [], 0
     for i in range(1, n + 1):
         depth, rgb, pose = parser.frame(i)
         r = loc.track(depth, rgb, gt_c2w=pose)
@@ -181,6 +195,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
         if map_reloc:
             relocalised += int(r.relocalised)
             shares.append(r.agree / (r.agree + r.front) if r.agree + r.front > 0 else None)
+        if map_keyframes:
+            recognised += int(r.recognised >= 0)
         path += float(torch.norm(pose[:3, 3] - last_t))
         last_t = pose[:3, 3]
         if verbose:
@@ -200,7 +216,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             **({"evict": True, "evicted_per_frame": evicted} if map_evict else {}),
             **({"merge_voxel": map_merge_voxel, "merge_every": map_merge_every, "merged_per_frame": merged,
                 "merged_at_reset": merged_at_reset} if map_merge_voxel is not None else {}),
-            **({"reloc": True, "relocalised_frames": relocalised, "agree_share_per_frame": shares} if map_reloc else {})}
+            **({"reloc": True, "relocalised_frames": relocalised, "agree_share_per_frame": shares} if map_reloc else {}),
+            **({"keyframes": loc.map.n_keyframes, "recognised_frames": recognised} if map_keyframes else {})}
 
 
 def main(argv=None):
@@ -252,6 +269,13 @@ def main(argv=None):
                     help="--map-reloc: rotation step of the candidate grid, degrees")
     ap.add_argument("--map-reloc-trans", type=float, default=None, metavar="M",
                     help="--map-reloc: translation step of the candidate grid, metres")
+    ap.add_argument("--map-keyframes", action="store_true",
+                    help="--map-reloc: place recognition -- a frame that stays lost is compared with the keyframes of "
+                         "the map, and tracked once more from the best-scoring pose around the most similar ones")
+    ap.add_argument("--map-keyframe-rot-deg", type=float, default=None, metavar="D",
+                    help="--map-keyframes: a frame further than D degrees from every keyframe becomes one")
+    ap.add_argument("--map-keyframe-trans", type=float, default=None, metavar="M",
+                    help="--map-keyframes: a frame further than M metres from every keyframe becomes one")
     a = ap.parse_args(argv)
     if a.map_merge_voxel is not None and not a.map:
         ap.error("--map-merge-voxel needs --map")
@@ -275,6 +299,11 @@ def main(argv=None):
             ap.error(f"{flag} needs --map")
         if value is not None and not a.map_reloc:
             ap.error(f"{flag} needs --map-reloc")
+    if a.map_keyframes and not a.map_reloc:
+        ap.error("--map-keyframes needs --map-reloc")
+    for flag, value in (("--map-keyframe-rot-deg", a.map_keyframe_rot_deg), ("--map-keyframe-trans", a.map_keyframe_trans)):
+        if value is not None and not a.map_keyframes:
+            ap.error(f"{flag} needs --map-keyframes")
     out = {}
     for room in a.rooms:
         parser = Parser(a.dataset, room, normalize=not a.no_normalize, input_folder=a.root)
@@ -284,7 +313,8 @@ def main(argv=None):
                           map_free_rho=a.map_free_rho, map_free_window=a.map_free_window, map_evict=a.map_evict,
                           map_merge_voxel=a.map_merge_voxel, map_merge_every=a.map_merge_every, map_reloc=a.map_reloc,
                           map_reloc_min_agree=a.map_reloc_min_agree, map_reloc_rot_deg=a.map_reloc_rot_deg,
-                          map_reloc_trans=a.map_reloc_trans)
+                          map_reloc_trans=a.map_reloc_trans, map_keyframes=a.map_keyframes,
+                          map_keyframe_rot_deg=a.map_keyframe_rot_deg, map_keyframe_trans=a.map_keyframe_trans)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

@@ -36,6 +36,10 @@ few rows tested, or too small a share of confirmed rows among those confirmed or
 is then tracked once more, from the best-scoring pose of a small grid of turns and shifts around its start poses
 (``reloc_candidates``); an estimate rejected again makes the frame a lost one, which leaves the map alone.  This is no
 place recognition -- nothing beyond that grid is tried -- and it repairs nothing a wrongly accepted frame has inserted.
+With ``MapConfig.keyframes`` place recognition follows: the map keeps the pose and a small descriptor of the depth image
+of the frames that built it (``GaussianMap.add_keyframe``), and a frame that the grid leaves lost is compared with all
+of them (``GaussianMap.match_place``).  The poses of the most similar keyframes, each turned by the image shift under
+which it matched (``place_base``), are the bases of one more grid, which is scored and tracked from as before.
 """
 from __future__ import annotations
 
@@ -90,12 +94,17 @@ class LocalizeResult:
     evicted: Optional[int] = None  # evict: least recently observed rows that made room for this frame's insertion
     merged: Optional[int] = None  # merge_voxel: rows removed by fusing the rows that share a voxel, after the insertion
     # reloc: ``lost`` is "the map does not confirm the estimate" (not accepted, also after a second tracking);
-    # relocalised: the estimate is that of a second tracking, started from the best-scoring candidate pose; tested /
-    # agree / front: the map's verdict on c2w (GaussianMap.score_poses)
+    # relocalised: the estimate is that of a second (keyframes: or third) tracking, started from the best-scoring
+    # candidate pose; tested / agree / front: the map's verdict on c2w (GaussianMap.score_poses)
     relocalised: Optional[bool] = None
     tested: Optional[int] = None
     agree: Optional[int] = None
     front: Optional[int] = None
+    # keyframes: the slot this frame was kept in as a keyframe after its insertion (None: it was not, or the option is
+    # off); recognised: the slot of the keyframe whose turned pose was the base of the candidate that a third tracking
+    # was accepted from, -1 on a frame that did not need place recognition or that it did not save (None: option off)
+    keyframe: Optional[int] = None
+    recognised: Optional[int] = None
 
 
 def _step(axis: int, rot_deg: float = 0.0, trans: float = 0.0) -> Tensor:
@@ -136,6 +145,19 @@ def reloc_candidates(bases, rot_deg: float, trans: float, levels: int) -> Tensor
                     for sign in (1.0, -1.0):
                         out.append(c2w @ _step(axis, **{kind: sign * level * size}))
     return torch.stack(out).to(dtype=torch.float32, device=bases[0].device)
+
+
+def place_base(c2w_kf, sx: int, sy: int, width: int, height: int, fx: float, fy: float) -> Tensor:
+    """The pose a frame is looked for at when its descriptor matched that of the keyframe at c2w_kf [4,4] under the
+    shift (sx, sy) of the 16 x 12 grid: c2w_kf @ R_y(-a) @ R_x(+b), a = atan(sx (width / 16) / fx), b = atan(sy
+    (height / 12) / fy) -- x right, y down, z forward, ``_step``'s rotations.  What the keyframe saw in cell (i, j) the
+    frame sees in cell (i + sx, j + sy): sx cells to the right is a camera turned to the left about its y, sy cells
+    down one tilted up about its x.  Composed in float64 and rounded to float32 once (no shift: the keyframe's pose
+    bit for bit); on the host."""
+    c2w = torch.as_tensor(c2w_kf).detach().cpu().double()
+    a = math.degrees(math.atan(sx * (width / 16.0) / fx))
+    b = math.degrees(math.atan(sy * (height / 12.0) / fy))
+    return (c2w @ _step(1, rot_deg=-a) @ _step(0, rot_deg=b)).to(torch.float32)
 
 
 def _default_factory(N, W, H, config, device, render_mode):
@@ -181,7 +203,16 @@ class Localizer:
     (``relocalised``).  If it is not, or if the start that failed scored highest itself, the frame is ``lost`` -- which
     with this option means "not accepted" -- the better-scoring of the two estimates is handed on, and the map is left
     as it was.  ``steps`` counts both runs; ``best_step``, ``best_loss`` and ``init_c2w`` are those of the run that
-    was kept.  Everything else
+    was kept.  ``map_config.keyframes``: ``reset`` keeps the first frame as keyframe 0 after its insertion, and every
+    frame that is not lost is offered to ``GaussianMap.add_keyframe`` with its estimate after its insertion (and
+    removal and merge: the descriptor reads the depth image only; ``LocalizeResult.keyframe``).  When the flow above
+    ends with the frame lost -- an estimate rejected twice, or a grid whose winner is the failed start -- and the map
+    has keyframes, the first ``place_top`` entries of ``GaussianMap.match_place`` give the bases ``place_base`` of one
+    more ``reloc_candidates`` grid; one ``score_poses`` call scores it, the candidate with the largest ``agree -
+    front`` (the lowest index among equals) is tracked from, and its estimate, if accepted, is the frame's
+    (``relocalised``, and ``recognised`` is the slot of the winning base's keyframe).  If not, the frame stays lost, the
+    map is left alone and the best-scoring estimate of all runs is handed on; ``steps`` counts every run.  With the
+    option on and no frame rejected, poses, step counts and added rows are those of the run without it.  Everything else
     -- normalisation, the re-rendered query depth, the scales, the hand-over, ``best_c2w`` -- is the frame mode's."""
 
     def __init__(self, K: Tensor, width: int, height: int, config: TrackerConfig = TrackerConfig(),
@@ -214,6 +245,7 @@ class Localizer:
         self._merge_every = 0  # MapConfig.merge_every when merge_voxel is set, else 0
         self._reloc = None  # the MapConfig when MapConfig.reloc is on
         self._min_tested = 0  # MapConfig.reloc_min_tested, or its default for this image size
+        self._keyframes = False  # MapConfig.keyframes
         self._tracked = 0  # calls of track since reset
         self.merged_at_reset = None  # merge_voxel: rows the merge after reset's insertion removed
         if self.map_mode:
@@ -228,6 +260,7 @@ class Localizer:
                 self._reloc = map_config
                 self._min_tested = (map_config.reloc_min_tested if map_config.reloc_min_tested is not None
                                     else (self.W * self.H) // 16)
+                self._keyframes = bool(map_config.keyframes)
         self._render_map = map_renderer if map_renderer is not None else render_depth_alpha
 
     def _frame(self, depth, rgb):
@@ -304,6 +337,29 @@ class Localizer:
             self._tracked = 0
             if self._merge_every:
                 self.merged_at_reset = self.map.merge()[0]
+            if self._keyframes:
+                self.map.add_keyframe(depth, self._poses[0])  # keyframe 0: clear() has forgotten the others
+
+    def _recognise(self, depth: Tensor, frame):
+        """Place recognition for a frame that the grid around its start poses has left lost: (the third run as
+        ``_run_tracker`` returns it, its pair, its start pose, its verdict, accepted, the keyframe slot of the winning
+        base), or None when no keyframe has an admissible match."""
+        cfg = self._reloc
+        ranked = self.map.match_place(depth)[: cfg.place_top]
+        if not ranked:
+            return None
+        poses = self.map.keyframe_poses
+        fx, fy = float(self.K[0, 0]), float(self.K[1, 1])
+        bases = [place_base(poses[slot], sx, sy, self.W, self.H, fx, fy) for slot, sx, sy, _, _ in ranked]
+        cands = reloc_candidates(bases, cfg.reloc_rot_deg, cfg.reloc_trans, cfg.reloc_levels).to(self.device)
+        scores = self.map.score_poses(depth, self.K, cands, self.cfg.gs.near_plane)
+        margins = [int(s[1]) - int(s[2]) for s in scores]
+        winner = margins.index(max(margins))  # the lowest index among equals
+        pair = self._map_pair(cands[winner], frame)
+        third = self._run_tracker(pair, cands[winner])
+        verdict = self._verdict(depth, third[4])
+        slot = ranked[winner // (1 + 12 * cfg.reloc_levels)][0]
+        return third, pair, cands[winner], verdict, self._accepted(third[2], verdict), slot
 
     @torch.no_grad()
     def track(self, depth, rgb=None, gt_c2w: Optional[Tensor] = None) -> LocalizeResult:
@@ -326,7 +382,7 @@ class Localizer:
             d = build_pair(self._prev[0], self._prev[1], pts, col, depth, rgb, placed, gt if gt is not None else init,
                            self.K, self.normalize)
         N, scales, res, best, est = self._run_tracker(d, init)
-        steps, lost, verdict, relocalised = res.steps, res.best_step == -1, None, None
+        steps, lost, verdict, relocalised, recognised = res.steps, res.best_step == -1, None, None, None
         if self._reloc is not None:
             # before anything touches the map: does it confirm the estimate?  If not, the best-scoring pose of a grid
             # around the start poses is tracked from once more; an estimate the map still rejects is a lost frame's
@@ -348,12 +404,23 @@ class Localizer:
                     lost = not relocalised
                     if relocalised or verdict2[1] - verdict2[2] > verdict[1] - verdict[2]:
                         (N, scales, res, best, est), d, init, verdict = second, again, cands[winner], verdict2
+            if self._keyframes:
+                recognised = -1
+                found = self._recognise(depth, frame) if lost and self.map.n_keyframes > 0 else None
+                if found is not None:
+                    third, pair, start, verdict3, accepted, slot = found
+                    steps += third[2].steps
+                    if accepted:
+                        lost, relocalised, recognised = False, True, slot
+                    if accepted or verdict3[1] - verdict3[2] > verdict[1] - verdict[2]:
+                        (N, scales, res, best, est), d, init, verdict = third, pair, start, verdict3
         self._prev = (pts, col)
         self._poses.append(est)
         out = LocalizeResult(c2w=est, init_c2w=init, steps=steps, best_step=res.best_step, best_loss=res.best_loss,
                              lost=lost)
         if verdict is not None:
             out.relocalised, (out.tested, out.agree, out.front) = relocalised, verdict
+            out.recognised = recognised
         if self.map_mode:
             out.added, out.tracked = 0, N
             out.removed = 0 if self._free else None
@@ -385,6 +452,9 @@ class Localizer:
                     out.removed, _ = self.map.remove_seen_through(depth, self.K, est, self.cfg.gs.near_plane)
                 if self._merge_every and self._tracked % self._merge_every == 0:
                     out.merged, _ = self.map.merge()
+                if self._keyframes:
+                    # after the frame is done: the descriptor reads the depth image only, nothing above depends on it
+                    out.keyframe = self.map.add_keyframe(depth, est)
             out.map_size = self.map.n_live
         if gt is not None:
             out.eT, out.eR = calculate_translation_error(est, gt), calculate_rotation_error(est, gt)

@@ -34,9 +34,17 @@ Pose scores (``MapConfig.reloc``, csrc/map_score.hip): ``score_poses`` counts, f
 live rows a depth frame tests, those it confirms (within ``depth_rho`` of the depth their own pixel observes) and those
 it sees through (in front of that depth) -- integer counts, the same on every run -- which is what
 ``Localizer(mode="map")`` accepts an estimate by and chooses a new start by when it does not (localizer.py).  It changes
-nothing in the map.  One more entry point; one read-back."""
+nothing in the map.  One more entry point; one read-back.
+
+Place recognition (``MapConfig.keyframes``, csrc/map_place.hip): the map remembers what the frames that built it looked
+like -- ``add_keyframe`` keeps the pose of a frame that lies far enough from every stored one and a 16 x 12 integer
+descriptor of its depth image (``describe``), in a ring of ``keyframe_max`` -- and ``match_place`` holds a frame's
+descriptor against all of them under 15 small shifts of the grid and ranks the keyframes it resembles, which is where
+``Localizer(mode="map")`` looks for a frame that the relocalisation above has given up on.  Two more entry points;
+``match_place`` reads back once, ``add_keyframe`` never."""
 from __future__ import annotations
 
+import functools
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -49,6 +57,10 @@ from . import _lib
 MERGE_CELL_MAX = 2 ** 20 - 1  # |cell| along an axis that the 3 x 21-bit voxel key of csrc/map_merge.hip holds
 MERGE_SCENE_M = 100.0  # a merge_voxel that leaves that range within this distance of the origin is refused
 SCORE_MAX_POSES = 64  # poses one call of csrc/map_score.hip scores (gsl_map_score_max_poses())
+PLACE_CELLS = 192  # the 16 x 12 cells of a descriptor of csrc/map_place.hip (gsl_map_place_cells())
+PLACE_GW, PLACE_GH = 16, 12
+PLACE_MAX_KEYFRAMES = 256  # keyframes one call of gsl_map_place_match compares (GSL_MAP_PLACE_MAX_KEYFRAMES)
+PLACE_SHIFTS = tuple((sx, sy) for sy in (-1, 0, 1) for sx in (-2, -1, 0, 1, 2))  # the kernel's order
 
 
 @dataclass
@@ -96,12 +108,42 @@ class MapConfig:
     reloc_rot_deg: float = 2.0
     reloc_trans: float = 0.05
     reloc_levels: int = 2
+    # Localizer(mode="map"), with reloc: place recognition.  The map keeps up to keyframe_max keyframes (a ring: the
+    # oldest goes first) -- the pose of an inserted frame and a 16 x 12 integer descriptor of its depth image
+    # (GaussianMap.add_keyframe) -- and a frame that the relocalisation above leaves lost is compared with all of them
+    # (GaussianMap.match_place); the poses of the place_top most similar ones, each turned by the image shift under
+    # which it matched best, are the bases of one more candidate grid, scored and tracked from as above
+    keyframes: bool = False
+    keyframe_max: int = 256
+    # a frame becomes a keyframe when its pose is further than keyframe_rot_deg degrees OR further than keyframe_trans
+    # metres from every stored keyframe's.  The defaults are half the jump between two frames that the tracker was
+    # measured to absorb (12.8 degrees and 32 cm; NOTES.md, "Relocalisation"): a camera within half a spacing of some
+    # keyframe is then inside that basin.  The figure comes from one synthetic room
+    keyframe_rot_deg: float = 6.0
+    keyframe_trans: float = 0.15
+    place_top: int = 2  # this many best-matching keyframes become bases: place_top * (1 + 12 reloc_levels) <= 64
+    place_min_common: int = 48  # a shift under which fewer cells are valid in both descriptors, a quarter of the 192, does not count
 
     def __post_init__(self):
         whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
         number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer))  # noqa: E731
         if not isinstance(self.reloc, bool):
             raise ValueError(f"reloc {self.reloc!r}: True or False")
+        if not isinstance(self.keyframes, bool):
+            raise ValueError(f"keyframes {self.keyframes!r}: True or False")
+        if not whole(self.keyframe_max) or not 1 <= self.keyframe_max <= PLACE_MAX_KEYFRAMES:
+            raise ValueError(f"keyframe_max {self.keyframe_max!r}: a whole number of keyframes, 1 .. {PLACE_MAX_KEYFRAMES}")
+        if not number(self.keyframe_rot_deg) or not (np.isfinite(self.keyframe_rot_deg) and self.keyframe_rot_deg > 0):
+            raise ValueError(f"keyframe_rot_deg {self.keyframe_rot_deg!r}: degrees, finite and above 0")
+        if not number(self.keyframe_trans) or not (np.isfinite(self.keyframe_trans) and self.keyframe_trans > 0):
+            raise ValueError(f"keyframe_trans {self.keyframe_trans!r}: metres, finite and above 0")
+        if not whole(self.place_top) or self.place_top < 1:
+            raise ValueError(f"place_top {self.place_top!r}: a whole number of keyframes, at least 1")
+        if not whole(self.place_min_common) or not 1 <= self.place_min_common <= PLACE_CELLS:
+            raise ValueError(f"place_min_common {self.place_min_common!r}: a whole number of cells, 1 .. {PLACE_CELLS}")
+        if self.keyframes and not self.reloc:
+            raise ValueError("keyframes=True needs reloc=True: place recognition is what a frame that the "
+                             "relocalisation leaves lost is tried with")
         if not number(self.reloc_min_agree) or not 0.0 < self.reloc_min_agree <= 1.0:
             raise ValueError(f"reloc_min_agree {self.reloc_min_agree!r}: a share of the rows judged, inside (0, 1]")
         if self.reloc_min_tested is not None and (not whole(self.reloc_min_tested) or self.reloc_min_tested < 1):
@@ -112,6 +154,10 @@ class MapConfig:
             raise ValueError(f"reloc_trans {self.reloc_trans!r}: metres, finite and above 0")
         if not whole(self.reloc_levels) or not 1 <= self.reloc_levels <= 2:
             raise ValueError(f"reloc_levels {self.reloc_levels!r}: a whole number of steps per direction, 1 .. 2")
+        if self.place_top * (1 + 12 * self.reloc_levels) > SCORE_MAX_POSES:
+            raise ValueError(f"place_top {self.place_top!r}: with reloc_levels {self.reloc_levels} that many bases make "
+                             f"{self.place_top * (1 + 12 * self.reloc_levels)} candidate poses, one scoring call takes "
+                             f"{SCORE_MAX_POSES}")
         if self.reloc and not 0.0 <= self.depth_rho < 1.0:
             raise ValueError(f"depth_rho {self.depth_rho}: reloc holds a row against the observed depth within this "
                              "fraction, inside [0, 1)")
@@ -205,6 +251,11 @@ class GaussianMap:
         # score_poses: 1 + depth_rho as the float32 value the kernel is given; its two buffers on first use
         self.beyond = float(np.float32(1.0) + np.float32(config.depth_rho))
         self._score = None
+        # keyframes: the host poses of the ring and how many frames were ever kept; the device table, the query's
+        # descriptor and the match's output on first use
+        self._kf_poses = np.zeros((int(config.keyframe_max), 4, 4), dtype=np.float32)
+        self._kf_made = 0
+        self._place = None
 
     def _alloc_ws(self):
         if self.device.type != "cuda":
@@ -233,6 +284,7 @@ class GaussianMap:
         self.frame_index, self.last_evicted = 0, 0
         self._view_rows = -1
         self._n_survivors = 0
+        self._kf_made = 0
 
     def _launch(self, depth: Tensor, rgb: Tensor, intr: Tuple[float, float, float, float], c2w: Tensor,
                 render: Optional[Tensor], alphas: Optional[Tensor]) -> Tuple[int, int]:
@@ -584,3 +636,130 @@ class GaussianMap:
         # the float64 inverses, rounded to float32 here: the kernel multiplies and adds, nothing else
         w2c = np.linalg.inv(torch.stack([c.detach().cpu().double() for c in poses]).numpy()).astype(np.float32)
         return self._score_launch(depth, intr, torch.from_numpy(w2c), float(near))
+
+    # ---- place recognition: keyframes, their depth descriptors and the match of a frame against them (csrc/map_place.hip)
+    def _place_buffers(self):
+        if self._place is None:
+            dev, i32 = self.device, torch.int32
+            self._place = dict(table=torch.full((int(self.cfg.keyframe_max), PLACE_CELLS), -1, dtype=i32, device=dev),
+                               query=torch.full((PLACE_CELLS,), -1, dtype=i32, device=dev),
+                               out=torch.zeros(PLACE_MAX_KEYFRAMES, len(PLACE_SHIFTS), 2, dtype=i32, device=dev))
+        return self._place
+
+    def _depth_image(self, depth) -> Tensor:
+        depth = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
+        if depth.numel() != self.H * self.W:
+            raise ValueError(f"depth is {tuple(depth.shape)}, the map was built for {(self.H, self.W)}")
+        return depth.reshape(self.H, self.W).contiguous()
+
+    def _describe_launch(self, depth: Tensor, desc: Tensor) -> None:
+        """The descriptor of depth [H,W] into desc, 192 contiguous int32 on the device.  No read-back."""
+        assert depth.is_cuda, "GaussianMap.describe: the descriptor is made by a HIP kernel, no CPU path"
+        _lib.check(_lib.load_library().gsl_map_place_describe(_lib.ptr(depth), self.W, self.H, _lib.ptr(desc),
+                                                              _lib.current_stream()), "gsl_map_place_describe")
+
+    def _match_launch(self, query: Tensor, table: Tensor, n: int) -> np.ndarray:
+        """query [192] against the first n rows of table [keyframe_max,192]; the read-back of int64 [n,15,2]: per
+        keyframe and shift (common, sum)."""
+        assert query.is_cuda, "GaussianMap.match_place: the descriptors are compared by a HIP kernel, no CPU path"
+        out = self._place_buffers()["out"]
+        _lib.check(_lib.load_library().gsl_map_place_match(_lib.ptr(query), _lib.ptr(table), n, _lib.ptr(out),
+                                                           _lib.current_stream()), "gsl_map_place_match")
+        return out[:n].cpu().numpy().astype(np.int64)  # the call's one synchronisation
+
+    @property
+    def n_keyframes(self) -> int:
+        return min(self._kf_made, int(self.cfg.keyframe_max))
+
+    @property
+    def keyframe_poses(self) -> Tensor:
+        """float32 [n_keyframes,4,4] on the host: the pose of the keyframe in every slot."""
+        return torch.from_numpy(self._kf_poses[: self.n_keyframes].copy())
+
+    @torch.no_grad()
+    def describe(self, depth) -> Tensor:
+        """int32 [192] on the device: the 16 x 12 descriptor of the depth frame [H,W] (metres) -- per cell of the image
+        the mean of the valid depths in units of 1 / 1024 m, or -1 where fewer than half of the cell's pixels have one
+        (the rule: include/gsloc_hip.h).  One launch, no read-back."""
+        depth = self._depth_image(depth)
+        desc = torch.empty(PLACE_CELLS, dtype=torch.int32, device=self.device)
+        self._describe_launch(depth, desc)
+        return desc
+
+    @torch.no_grad()
+    def add_keyframe(self, depth, c2w) -> Optional[int]:
+        """Keeps the frame -- its pose c2w [4,4] on the host, its descriptor on the device -- as a keyframe when the
+        pose is further than ``keyframe_rot_deg`` degrees or further than ``keyframe_trans`` metres from the pose of
+        every stored keyframe (the first frame always is one); decided on the host from the stored poses alone, and
+        only then is the descriptor launched, straight into the keyframe's row of the device table.  Returns the slot,
+        or None.  With ``keyframe_max`` keyframes stored the oldest one is overwritten (a ring).  No read-back.
+
+        Keyframes describe frames, not rows: eviction, free space and merging leave them alone.  A keyframe whose rows
+        have all gone is harmless -- the candidate poses around it test too few rows and are rejected by the rule that
+        every estimate is held against (``reloc_min_tested``)."""
+        if not self.cfg.keyframes:
+            raise RuntimeError("add_keyframe: MapConfig.keyframes is False, the map keeps no keyframes")
+        depth = self._depth_image(depth)
+        pose = torch.as_tensor(c2w)
+        if pose.shape != (4, 4):
+            raise ValueError(f"c2w is {tuple(pose.shape)}, not (4, 4)")
+        pose = pose.detach().cpu().to(torch.float32).numpy()
+        n = self.n_keyframes
+        if n > 0:
+            stored, new = self._kf_poses[:n].astype(np.float64), pose.astype(np.float64)
+            dist = np.linalg.norm(stored[:, :3, 3] - new[None, :3, 3], axis=1)
+            # the angle of R_stored^T R_new, from its trace
+            cos = (np.einsum("kij,ij->k", stored[:, :3, :3], new[:3, :3]) - 1.0) / 2.0
+            angle = np.degrees(np.arccos(np.clip(cos, -1.0, 1.0)))
+            far = (angle > float(self.cfg.keyframe_rot_deg)) | (dist > float(self.cfg.keyframe_trans))
+            if not bool(far.all()):
+                return None
+        slot = self._kf_made % int(self.cfg.keyframe_max)
+        self._describe_launch(depth, self._place_buffers()["table"][slot])
+        self._kf_poses[slot] = pose
+        self._kf_made += 1
+        return slot
+
+    @torch.no_grad()
+    def match_place(self, depth) -> list:
+        """The stored keyframes that the depth frame [H,W] resembles, the most similar first: a list of
+        (slot, sx, sy, sum, common).  One descriptor launch, one match launch of the frame's descriptor against all
+        keyframes under the 15 shifts sx in -2 .. 2, sy in -1 .. 1 of the grid (the rule: include/gsloc_hip.h) and one
+        read-back; then, in Python integers, every keyframe's shift with the smallest sum / common among those with
+        ``common >= place_min_common``, and the keyframes in ascending order of that value.  Fractions are compared
+        exactly (cross-multiplied); ties go to the smaller |sx| + |sy|, then the earlier shift, then the lower slot.
+        Keyframes with no admissible shift are left out; no keyframes: an empty list without a launch."""
+        if not self.cfg.keyframes:
+            raise RuntimeError("match_place: MapConfig.keyframes is False, the map keeps no keyframes")
+        n = self.n_keyframes
+        if n == 0:
+            return []
+        depth, p = self._depth_image(depth), self._place_buffers()
+        self._describe_launch(depth, p["query"])
+        result = self._match_launch(p["query"], p["table"], n)
+        return rank_places(result, int(self.cfg.place_min_common))
+
+
+def rank_places(result, min_common: int) -> list:
+    """``GaussianMap.match_place``'s ranking of [n,15,2] (common, sum) pairs: [(slot, sx, sy, sum, common), ...]."""
+
+    def better(a, b) -> bool:
+        """a, b: (sum, common, |sx| + |sy|, shift, slot).  sum_a / common_a < sum_b / common_b, exactly; then the
+        rest in order."""
+        left, right = a[0] * b[1], b[0] * a[1]
+        return left < right or (left == right and a[2:] < b[2:])
+
+    best = []
+    for slot, per_shift in enumerate(np.asarray(result).tolist()):
+        top = None
+        for s, (common, total) in enumerate(per_shift):
+            if common < max(int(min_common), 1):
+                continue
+            sx, sy = PLACE_SHIFTS[s]
+            entry = (int(total), int(common), abs(sx) + abs(sy), s, slot)
+            if top is None or better(entry, top):
+                top = entry
+        if top is not None:
+            best.append(top)
+    ranked = sorted(best, key=functools.cmp_to_key(lambda a, b: -1 if better(a, b) else int(better(b, a))))
+    return [(slot, PLACE_SHIFTS[s][0], PLACE_SHIFTS[s][1], total, common) for total, common, _, s, slot in ranked]

@@ -204,15 +204,17 @@ def write_replica_sequence(root, W, H, n):
 
 
 def write_replica_constant_twist(root, W, H, n, rot_deg: float = 0.4, trans: float = 0.01, axis=(0.3, 1.0, -0.2),
-                                 direction=(0.6, 0.1, 0.8)):
+                                 direction=(0.6, 0.1, 0.8), start=None):
     """The Replica layout of write_replica_sequence for a camera that moves by the SAME twist every frame (rot_deg about
     ``axis``, ``trans`` metres along ``direction``, both fixed in the camera frame): the sequence a constant-velocity
     hand-over predicts up to its second-order term.  With more frames and a larger angle it is the sweep of a camera that
     keeps turning until the map has outgrown the view (1 degree x 16 frames at 160x120 in the tests of the local map, 2
-    degrees x 24 at 640x480 in scripts/map_figures.py).  Returns the n camera-to-world poses [n,4,4] (float64)."""
+    degrees x 24 at 640x480 in scripts/map_figures.py).  ``start``: the first pose [4,4] (default: the identity, the
+    room's centre -- from where the box is symmetric).  Returns the n camera-to-world poses [n,4,4] (float64)."""
     import numpy as np
 
-    poses, c2w, step = [], np.eye(4), _twist(rot_deg, trans, axis, direction)
+    first = np.eye(4) if start is None else np.asarray(start, dtype=np.float64).reshape(4, 4)
+    poses, c2w, step = [], first.copy(), _twist(rot_deg, trans, axis, direction)
     for i in range(n):
         if i:
             c2w = c2w @ step

@@ -319,6 +319,37 @@ int gsl_map_score(const float* means, int64_t n_rows, const float* w2c, int n_po
                   float cy, const float* depth, int width, int height, float keep, float beyond, float near_plane,
                   int32_t* counts, void* stream);
 
+/* ---- place recognition: a 16 x 12 descriptor of a depth frame, and its match against keyframes (csrc/map_place.hip) ----
+ * gsl_map_place_describe: depth[height,width] float32 on the device, row-major, metres; desc[192] int32 on the device,
+ * row-major over GSL_MAP_PLACE_GH lines of GSL_MAP_PLACE_GW cells (gsl_map_place_cells() = 192).  It need not be
+ * initialised: every entry is written by the one workgroup that owns its cell, nothing is accumulated in global memory.
+ *   Pixel (u, v) belongs to cell ((u * 16) / width, (v * 12) / height), integer division.
+ *   A pixel counts when d > 0 and d < inf (both false for a NaN): its value is
+ *     q = (uint32) rintf(fminf(d, 63.f) * 1024.f) -- one rounded float32 product, round half to even, at most 64 512.
+ *   desc[cell] = sum(q) / count (floored integer division) when count > 0 and 2 count >= the pixels of the cell;
+ *     otherwise -1 (invalid).
+ * Everything after q is integer arithmetic: the result does not depend on the order of pixels, waves or workgroups.
+ * One kernel; no atomics on global memory.
+ * Returns GSL_ERR_BAD_ARG before any launch for a NULL depth or desc, width < 16 or height < 12, or an image whose
+ * largest cell, ceil(width / 16) x ceil(height / 12) pixels, holds more than 65 536 (its sum would leave 32 bits).
+ *
+ * gsl_map_place_match: query[192] and table[n_keyframes,192] int32 on the device, descriptors as above (an entry is
+ * valid when it is >= 0); out[n_keyframes,15,2] int32 on the device, written whole.  The 15 shifts (sx, sy), sx in
+ * -2 .. 2 and sy in -1 .. 1, are numbered s = (sy + 1) * 5 + (sx + 2): sy-major, both ascending.  For keyframe k and
+ * shift s, over the cells (i, j) with 0 <= i + sx < 16 and 0 <= j + sy < 12 at which query[(j + sy) * 16 + i + sx] and
+ * table[k][j * 16 + i] are both valid:
+ *   out[k][s][0] = common, the number of those cells;
+ *   out[k][s][1] = sum, the sum of |query[(j + sy) * 16 + i + sx] - table[k][j * 16 + i]| over them (<= 192 x 64 512).
+ * Integers: the same on every run.  One kernel, one 64-lane wave per (keyframe, shift).
+ * Returns GSL_ERR_BAD_ARG before any launch for a NULL query, table or out, or n_keyframes outside
+ * 1 .. GSL_MAP_PLACE_MAX_KEYFRAMES. */
+#define GSL_MAP_PLACE_GW 16
+#define GSL_MAP_PLACE_GH 12
+#define GSL_MAP_PLACE_MAX_KEYFRAMES 256
+int gsl_map_place_cells(void);
+int gsl_map_place_describe(const float* depth, int width, int height, int32_t* desc, void* stream);
+int gsl_map_place_match(const int32_t* query, const int32_t* table, int n_keyframes, int32_t* out, void* stream);
+
 /* ---- spherical harmonics: gsplat.spherical_harmonics fwd/bwd (IDX:14306, IDX:14297) ----
  * dirs[M,3], coeffs[M,K,3] with K >= (degree+1)^2, masks[M] (uint8, may be NULL).
  * degree 0..3.  v_dirs may be NULL. */
