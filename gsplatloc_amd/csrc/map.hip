@@ -13,6 +13,7 @@
 // Memory-streaming: 12 B read per pixel in the first pass, 16 B read and 24 B written per selected pixel in the second.
 #include "compact_dev.h"
 #include "gsloc_internal.h"
+#include "map_dev.h"
 
 namespace gsl {
 
@@ -69,7 +70,7 @@ extern "C" size_t gsl_map_ws_bytes(int width, int height) {
 
 // Argument checks shared by the two passes.
 static int map_check(const float* depth, int width, int height, const int32_t* n_new, const void* ws, size_t ws_bytes) {
-  if (width <= 0 || height <= 0 || (long long)width * height > 0x7FFFFFFFll) return GSL_ERR_BAD_ARG;  // 32-bit counts
+  if (!gsl::map_image_ok(width, height)) return GSL_ERR_BAD_ARG;
   if (!depth || !n_new || !ws || ws_bytes < gsl_map_ws_bytes(width, height)) return GSL_ERR_BAD_ARG;
   return GSL_OK;
 }
@@ -97,8 +98,7 @@ extern "C" int gsl_map_append(const float* depth, const float* rgb, int width, i
   int rc = map_check(depth, width, height, n_new, ws, ws_bytes);
   if (rc != GSL_OK) return rc;
   if (!rgb || !c2w || !means || !colors) return GSL_ERR_BAD_ARG;
-  if (capacity <= 0 || n_live < 0 || n_live > capacity) return GSL_ERR_BAD_ARG;
-  if (!(fx != 0.f) || !(fy != 0.f)) return GSL_ERR_BAD_ARG;
+  if (capacity <= 0 || n_live < 0 || n_live > capacity || !gsl::map_focal_ok(fx, fy)) return GSL_ERR_BAD_ARG;
   const int nb = (int)gsl::compact_blocks((long long)width * height);
   const gsl::CompactWs w = gsl::compact_ws(ws, nb);
   hipLaunchKernelGGL(gsl::k_map_append, dim3(nb), dim3(gsl::COMPACT_THREADS), 0, (hipStream_t)stream, depth, rgb,

@@ -4,17 +4,13 @@
 // surface -- and when a frame's new rows do not fit, exactly as many rows as are needed go: the least recently observed
 // first, in map order among rows of the same age.
 //
-// gsl_map_observe, one row per thread.  Row i of means[n,3], with w the rows of w2c (world to camera, row-major):
-//   x = ((w0 px + w1 py) + w2 pz) + w3, y and z likewise;  u = fx x / z + cx, v = fy y / z + cy;
-//   uf = rintf(u), vf = rintf(v) (round half to even);
-//   in reach = z > near and z < far and -reach <= u <= (width - 1) + reach and -reach <= v <= (height - 1) + reach
-//              (the view rule of map_view.hip with guard = reach; the two upper limits are float32 sums of the host);
-//   inside   = 0 <= uf <= width - 1 and 0 <= vf <= height - 1 (float comparisons, then the conversion; -0 is column 0);
-//   agrees   = some pixel (uf + du, vf + dv), |du|, |dv| <= window, INSIDE the image has a depth d that is finite and
-//              > 0 with z >= d * keep and z * keep <= d -- two rounded products, no division;
+// gsl_map_observe, one row per thread.  Row i of means[n,3], projected to z, u, v, uf, vf (map_dev.h: the projection,
+// the band rule, the inside rule and the window):
+//   in reach = in the band with lo = -reach: the view rule of map_view.hip with guard = reach;
+//   agrees   = some pixel of the window has a depth d that is finite and > 0 with z >= d * keep and z * keep <= d --
+//              two rounded products, no division;
 //   observed = in reach and (not inside or agrees):  stamps[i] = now.  Every other row keeps its stamp.
-// float32, every operation rounded once in the order written (no contraction, correctly rounded division), comparisons
-// that are false for a NaN: NaN / inf rows are never observed.  The arithmetic up to uf, vf is k_map_free_select's.
+// Comparisons that are false for a NaN: NaN / inf rows are never observed.
 // 12 B read per row, up to (2 window + 1)^2 depth values, one conditional 4 B store; no LDS, no atomics.
 //
 // gsl_map_evict_select, all in integers.  age = clamp(now - stamp, 0, 1023); a row is evictable when age >= min_age;
@@ -35,15 +31,13 @@
 //
 // ws = [head: gsl_map_view_ws_bytes(n) -- ballots of the rows that stay nb x 4 uint64, counts nb, bases nb, tie counts
 //       nb, tie bases nb][tie ballots nb x 4 uint64][bins 1024 uint32][a*, tie quota, E, rows of age a*] (uint32).
-#include <math.h>
-
 #include "compact_dev.h"
 #include "gsloc_internal.h"
+#include "map_dev.h"
 
 namespace gsl {
 
-constexpr int OBSERVE_MAX_WINDOW = 3;  // window_px is 0 .. 3 (the entry point refuses anything else)
-constexpr int AGE_BINS = 1024;         // ages are clamped to 0 .. AGE_BINS - 1
+constexpr int AGE_BINS = 1024;  // ages are clamped to 0 .. AGE_BINS - 1
 constexpr int HIST_THREADS = 256;
 constexpr int HIST_ROWS = 2048;  // rows per workgroup of k_map_age_hist: eight per thread, one clear and one flush
 constexpr int EVICT_PARAMS = 4;  // a*, tie quota, E, rows of age a*
@@ -77,31 +71,20 @@ __global__ __launch_bounds__(COMPACT_THREADS) void k_map_observe(
     float cy, const float* __restrict__ depth, int width, int height, float u_last, float v_last, float keep, int window,
     float reach_lo, float u_hi, float v_hi, float near_plane, float far_plane, int32_t now,
     int32_t* __restrict__ stamps) {
-#pragma clang fp contract(off)
   const long long g = (long long)blockIdx.x * COMPACT_THREADS + threadIdx.x;
   if (g >= n_rows) return;
-  const float px = means[3 * (size_t)g], py = means[3 * (size_t)g + 1], pz = means[3 * (size_t)g + 2];
-  const float x = ((w2c[0] * px + w2c[1] * py) + w2c[2] * pz) + w2c[3];
-  const float y = ((w2c[4] * px + w2c[5] * py) + w2c[6] * pz) + w2c[7];
-  const float z = ((w2c[8] * px + w2c[9] * py) + w2c[10] * pz) + w2c[11];
-  const float u = fx * x / z + cx, v = fy * y / z + cy;
-  const float uf = rintf(u), vf = rintf(v);
-  const bool in_reach =
-      z > near_plane && z < far_plane && u >= reach_lo && u <= u_hi && v >= reach_lo && v <= v_hi;
-  if (!in_reach) return;
+  const MapPixel p = map_project(w2c, map_load_row(means, g), fx, fy, cx, cy);
+  if (!map_in_band(p, near_plane, far_plane, reach_lo, u_hi, v_hi)) return;
   bool observed = true;  // in the band around the image: it paints into the frame, there is no depth to hold it against
-  if (uf >= 0.f && uf <= u_last && vf >= 0.f && vf <= v_last) {
-    // uf, vf are integers in [0, width - 1] x [0, height - 1]: every index below is inside
-    const int uc = (int)uf, vc = (int)vf;
-    const int u0 = uc - window > 0 ? uc - window : 0, u1 = uc + window < width - 1 ? uc + window : width - 1;
-    const int v0 = vc - window > 0 ? vc - window : 0, v1 = vc + window < height - 1 ? vc + window : height - 1;
-    const float zk = z * keep;
+  if (map_inside(p, u_last, v_last)) {
+    const MapWindow win = map_window(p, window, width, height);
+    const float zk = p.z * keep;
     observed = false;
-    for (int vv = v0; vv <= v1; ++vv) {
+    for (int vv = win.v0; vv <= win.v1; ++vv) {
       const float* line = depth + (size_t)vv * (size_t)width;
-      for (int uu = u0; uu <= u1; ++uu) {
+      for (int uu = win.u0; uu <= win.u1; ++uu) {
         const float d = line[uu];
-        observed = observed || (d > 0.f && d < INFINITY && z >= d * keep && zk <= d);
+        observed = observed || (d > 0.f && d < INFINITY && p.z >= d * keep && zk <= d);
       }
     }
   }
@@ -214,10 +197,9 @@ extern "C" int gsl_map_observe(const float* means, int64_t n_rows, const float* 
                                float reach_px, float near_plane, float far_plane, int now, int32_t* stamps,
                                void* stream) {
   if (!means || !w2c || !depth || !stamps) return GSL_ERR_BAD_ARG;
-  if (n_rows <= 0 || n_rows >= 0x80000000ll) return GSL_ERR_BAD_ARG;  // 32-bit row indices
-  if (width <= 0 || height <= 0 || (long long)width * height > 0x7fffffffll) return GSL_ERR_BAD_ARG;
-  if (!(fx != 0.f) || !(fy != 0.f) || !(keep > 0.f && keep <= 1.f)) return GSL_ERR_BAD_ARG;
-  if (window_px < 0 || window_px > gsl::OBSERVE_MAX_WINDOW) return GSL_ERR_BAD_ARG;
+  if (!gsl::map_rows_ok(n_rows) || !gsl::map_image_ok(width, height)) return GSL_ERR_BAD_ARG;
+  if (!gsl::map_focal_ok(fx, fy) || !(keep > 0.f && keep <= 1.f)) return GSL_ERR_BAD_ARG;
+  if (window_px < 0 || window_px > gsl::MAP_MAX_WINDOW) return GSL_ERR_BAD_ARG;
   if (!(reach_px >= 0.f) || !(near_plane < far_plane)) return GSL_ERR_BAD_ARG;
   const int nb = (int)gsl::compact_blocks(n_rows);
   const float u_hi = (float)(width - 1) + reach_px, v_hi = (float)(height - 1) + reach_px;  // one float32 sum each
@@ -235,7 +217,7 @@ extern "C" size_t gsl_map_evict_ws_bytes(int64_t n_rows) {
 extern "C" int gsl_map_evict_select(const int32_t* stamps, int64_t n_rows, int now, int min_age, int64_t need,
                                     int32_t* counters, void* ws, size_t ws_bytes, void* stream) {
   if (!stamps || !counters || !ws) return GSL_ERR_BAD_ARG;
-  if (n_rows <= 0 || n_rows >= 0x80000000ll) return GSL_ERR_BAD_ARG;  // 32-bit counts and indices
+  if (!gsl::map_rows_ok(n_rows)) return GSL_ERR_BAD_ARG;
   if (need < 0 || min_age < 1) return GSL_ERR_BAD_ARG;
   if (ws_bytes < gsl_map_evict_ws_bytes(n_rows)) return GSL_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -267,7 +249,7 @@ extern "C" int gsl_map_evict_select(const int32_t* stamps, int64_t n_rows, int n
 extern "C" int gsl_map_gather_i32(const int32_t* src, int64_t n_src, const int32_t* ids, int64_t n_ids, int32_t* dst,
                                   void* stream) {
   if (!src || !ids || !dst) return GSL_ERR_BAD_ARG;
-  if (n_src <= 0 || n_src >= 0x80000000ll || n_ids < 0 || n_ids >= 0x80000000ll) return GSL_ERR_BAD_ARG;
+  if (!gsl::map_rows_ok(n_src) || n_ids < 0 || n_ids >= 0x80000000ll) return GSL_ERR_BAD_ARG;
   if (n_ids == 0) return GSL_OK;
   hipLaunchKernelGGL(gsl::k_map_gather_i32, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      src, (long long)n_src, ids, (long long)n_ids, dst);

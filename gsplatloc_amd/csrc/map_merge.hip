@@ -35,10 +35,9 @@
 //       counts nb, their bases nb][params: flag, h (float bits), 0, 0 (uint32)][table: slots x (key uint64, count
 //       uint32, first uint32)][sums n x 6 uint64: S_0 S_1 S_2 C_0 C_1 C_2, indexed by a voxel's first row][largest stamps
 //       n int32, likewise][slot of every row n uint32, all ones: none];  slots = the smallest power of two >= 2 n.
-#include <math.h>
-
 #include "compact_dev.h"
 #include "gsloc_internal.h"
+#include "map_dev.h"
 
 namespace gsl {
 
@@ -263,7 +262,7 @@ extern "C" size_t gsl_map_merge_ws_bytes(int64_t n_rows) {
 extern "C" int gsl_map_merge_select(const float* means, const float* colors, const int32_t* stamps, int64_t n_rows,
                                     float inv_h, float h, int32_t* counters, void* ws, size_t ws_bytes, void* stream) {
   if (!means || !colors || !stamps || !counters || !ws) return GSL_ERR_BAD_ARG;
-  if (n_rows <= 0 || n_rows >= 0x80000000ll) return GSL_ERR_BAD_ARG;  // 32-bit counts and indices
+  if (!gsl::map_rows_ok(n_rows)) return GSL_ERR_BAD_ARG;
   if (!(h > 0.f && h < INFINITY) || !(inv_h > 0.f && inv_h < INFINITY)) return GSL_ERR_BAD_ARG;
   if (ws_bytes < gsl_map_merge_ws_bytes(n_rows)) return GSL_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -292,7 +291,7 @@ extern "C" int gsl_map_merge_select(const float* means, const float* colors, con
 extern "C" int gsl_map_merge_apply(const int32_t* ids, const int32_t* counters, int64_t n_rows, float* out_means,
                                    float* out_colors, int32_t* out_stamps, void* ws, size_t ws_bytes, void* stream) {
   if (!ids || !counters || !out_means || !out_colors || !out_stamps || !ws) return GSL_ERR_BAD_ARG;
-  if (n_rows <= 0 || n_rows >= 0x80000000ll) return GSL_ERR_BAD_ARG;
+  if (!gsl::map_rows_ok(n_rows)) return GSL_ERR_BAD_ARG;
   if (ws_bytes < gsl_map_merge_ws_bytes(n_rows)) return GSL_ERR_WORKSPACE;
   const int nb = (int)gsl::compact_blocks(n_rows);
   const gsl::MergeWs w = gsl::merge_ws(ws, (long long)n_rows, nb);

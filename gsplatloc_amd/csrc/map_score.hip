@@ -4,19 +4,14 @@
 // those verdicts over all live rows say whether a pose can be the frame's -- the acceptance test of an estimate and the
 // choice among the candidate starts of a relocalisation (gsplatloc_amd/localizer.py).  No render.
 //
-// Row i of means[n,3], pose k, with w the rows of w2c[k] (world to camera, row-major):
-//   x = ((w0 px + w1 py) + w2 pz) + w3, y and z likewise;  u = fx x / z + cx, v = fy y / z + cy;
-//   uf = rintf(u), vf = rintf(v) (round half to even, as k_map_free_select);
-//   tested = z > near and 0 <= uf <= width - 1 and 0 <= vf <= height - 1 (float comparisons, then the conversion;
-//            rintf(-0.5) = -0 passes and is column 0) and d > 0 and d < inf, d = depth[vf, uf] -- the row's own pixel, no
-//            window;
+// Row i of means[n,3], pose k, projected through w2c[k] to z, uf, vf (map_dev.h: the projection and the inside rule):
+//   tested = z > near and inside and d > 0 and d < inf, d = depth[vf, uf] -- the row's own pixel, no window;
 //   front  = tested and z < d * keep;  behind = tested and z > d * beyond -- one rounded product each;
 //   agree  = tested and not front and not behind;
 //   counts[k] = (rows tested, rows that agree, rows in front).
-// float32, every operation rounded once in the order written (no contraction, correctly rounded division), comparisons
-// that are false for a NaN: NaN / inf rows, rows behind the camera or outside the image and pixels without depth add
-// nothing, a row with z == d * keep or z == d * beyond agrees.  The sums are integers: they do not depend on the order
-// of rows, waves or workgroups, and the numpy mirror of the tests gives the same three numbers.
+// Comparisons that are false for a NaN: NaN / inf rows, rows behind the camera or outside the image and pixels without
+// depth add nothing, a row with z == d * keep or z == d * beyond agrees.  The sums are integers: they do not depend on
+// the order of rows, waves or workgroups, and the numpy mirror of the tests gives the same three numbers.
 //
 // One thread per row over a grid-stride loop, at most SCORE_MAX_BLOCKS workgroups.  A thread loads its row once (12 B)
 // and loops over the poses; a pose's twelve entries are read with a wave-uniform index (scalar loads through the
@@ -25,9 +20,8 @@
 // adds to a table [n_poses][3] in LDS (ds_add_u32; 768 B); after the rows the workgroup adds its non-zero entries to
 // counts with one integer atomic each: at most SCORE_MAX_BLOCKS x 3 x n_poses global atomics whatever n_rows is.  No
 // float atomics.  counts is zeroed by a launch of zero_u32 in front (never a memset node: misc.hip).
-#include <math.h>
-
 #include "gsloc_internal.h"
+#include "map_dev.h"
 
 namespace gsl {
 
@@ -40,7 +34,6 @@ __global__ __launch_bounds__(SCORE_THREADS) void k_map_score(
     const float* __restrict__ means, long long n_rows, const float* __restrict__ w2c, int n_poses, float fx, float fy,
     float cx, float cy, const float* __restrict__ depth, int width, float u_last, float v_last, float keep, float beyond,
     float near_plane, int32_t* __restrict__ counts) {
-#pragma clang fp contract(off)
   __shared__ uint32_t table[SCORE_COUNTS];
   if ((int)threadIdx.x < SCORE_COUNTS) table[threadIdx.x] = 0u;
   __syncthreads();
@@ -50,26 +43,17 @@ __global__ __launch_bounds__(SCORE_THREADS) void k_map_score(
   for (long long base = (long long)blockIdx.x * SCORE_THREADS; base < n_rows; base += stride) {
     const long long g = base + threadIdx.x;
     const bool live = g < n_rows;
-    float px = 0.f, py = 0.f, pz = 0.f;
-    if (live) {
-      px = means[3 * (size_t)g];
-      py = means[3 * (size_t)g + 1];
-      pz = means[3 * (size_t)g + 2];
-    }
+    float3 row = {0.f, 0.f, 0.f};
+    if (live) row = map_load_row(means, g);
     for (int k = 0; k < n_poses; ++k) {
-      const float* __restrict__ w = w2c + 16 * k;  // wave-uniform
-      const float x = ((w[0] * px + w[1] * py) + w[2] * pz) + w[3];
-      const float y = ((w[4] * px + w[5] * py) + w[6] * pz) + w[7];
-      const float z = ((w[8] * px + w[9] * py) + w[10] * pz) + w[11];
-      const float u = fx * x / z + cx, v = fy * y / z + cy;
-      const float uf = rintf(u), vf = rintf(v);
-      bool tested = live && z > near_plane && uf >= 0.f && uf <= u_last && vf >= 0.f && vf <= v_last;
+      const MapPixel p = map_project(w2c + 16 * k, row, fx, fy, cx, cy);  // the pose: wave-uniform
+      bool tested = live && p.z > near_plane && map_inside(p, u_last, v_last);
       bool front = false, behind = false;
-      if (tested) {  // uf, vf are integers in [0, width - 1] x [0, height - 1]: the index is inside
-        const float d = depth[(size_t)(int)vf * (size_t)width + (size_t)(int)uf];
+      if (tested) {  // the index is inside
+        const float d = depth[(size_t)(int)p.vf * (size_t)width + (size_t)(int)p.uf];
         tested = d > 0.f && d < INFINITY;
-        front = tested && z < d * keep;
-        behind = tested && z > d * beyond;
+        front = tested && p.z < d * keep;
+        behind = tested && p.z > d * beyond;
       }
       const bool agree = tested && !front && !behind;
       const unsigned long long b_tested = __ballot(tested), b_agree = __ballot(agree), b_front = __ballot(front);
@@ -95,10 +79,9 @@ extern "C" int gsl_map_score(const float* means, int64_t n_rows, const float* w2
                              float cx, float cy, const float* depth, int width, int height, float keep, float beyond,
                              float near_plane, int32_t* counts, void* stream) {
   if (!means || !w2c || !depth || !counts) return GSL_ERR_BAD_ARG;
-  if (n_rows <= 0 || n_rows >= 0x80000000ll) return GSL_ERR_BAD_ARG;  // 32-bit counts
-  if (n_poses < 1 || n_poses > GSL_MAP_SCORE_MAX_POSES) return GSL_ERR_BAD_ARG;
-  if (width <= 0 || height <= 0 || (long long)width * height > 0x7fffffffll) return GSL_ERR_BAD_ARG;
-  if (!(fx != 0.f) || !(fy != 0.f) || !(keep > 0.f && keep <= 1.f) || !(beyond >= 1.f)) return GSL_ERR_BAD_ARG;
+  if (!gsl::map_rows_ok(n_rows) || n_poses < 1 || n_poses > GSL_MAP_SCORE_MAX_POSES) return GSL_ERR_BAD_ARG;
+  if (!gsl::map_image_ok(width, height) || !gsl::map_focal_ok(fx, fy)) return GSL_ERR_BAD_ARG;
+  if (!(keep > 0.f && keep <= 1.f) || !(beyond >= 1.f)) return GSL_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   const int rc = gsl::zero_u32(counts, (size_t)3 * (size_t)n_poses, st);
   if (rc != GSL_OK) return rc;

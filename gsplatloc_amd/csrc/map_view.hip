@@ -2,12 +2,8 @@
 // band of guard_px pixels, between the depth planes -- are compacted, in map order, into a working set that the tracker
 // sees instead of the whole map (gsplatloc_amd/mapping.py: select_view / view_violations).
 //
-// Row i of means[n,3] is in view when, with w the rows of w2c (world to camera, row-major),
-//   x = ((w0 px + w1 py) + w2 pz) + w3, y and z likewise; z > near and z < far;
-//   u = fx x / z + cx, v = fy y / z + cy;  -guard <= u <= (width - 1) + guard,  -guard <= v <= (height - 1) + guard.
-// float32, every operation rounded once in the order written (no contraction, correctly rounded division), comparisons
-// that are false for a NaN: on given inputs the rule has no rounding freedom and the numpy mirror of the tests selects
-// the same rows.  The two upper limits are float32 sums taken on the host.
+// Row i of means[n,3] is in view when it is in the band (map_dev.h: the projection and the band rule) with lo = -guard:
+//   z > near and z < far;  -guard <= u <= (width - 1) + guard,  -guard <= v <= (height - 1) + guard.
 //
 // Order-preserving compaction (compact_dev.h), one row per thread; the order is the map's in every run:
 //   k_map_view_select  evaluates the rule and records it -- and, given the ballots an earlier call left for the same
@@ -17,11 +13,9 @@
 //   k_map_view_gather  the lanes whose ballot bit is set copy their mean, colour and index to their position; rows at
 //                      or beyond out_capacity are dropped, the number stored -> counters[2].
 // Memory-streaming: 12 B read per row in the first pass, 24 B read and 24 - 28 B written per selected row in the second.
-// The 12-byte rows do not line up with lanes: a lane reads its row with one global_load_dwordx3, a wave's 768 contiguous
-// bytes are six 128-byte lines that this one instruction touches once each ("Map growth": what the ISA
-// shows and why the rows do not go through LDS).
 #include "compact_dev.h"
 #include "gsloc_internal.h"
+#include "map_dev.h"
 
 namespace gsl {
 
@@ -36,15 +30,9 @@ __global__ __launch_bounds__(COMPACT_THREADS) void k_map_view_select(
     counters[2] = 0;  // nothing gathered yet
   }
   bool in_view = false;
-  if (g < n_rows) {
-#pragma clang fp contract(off)
-    const float px = means[3 * (size_t)g], py = means[3 * (size_t)g + 1], pz = means[3 * (size_t)g + 2];
-    const float x = ((w2c[0] * px + w2c[1] * py) + w2c[2] * pz) + w2c[3];
-    const float y = ((w2c[4] * px + w2c[5] * py) + w2c[6] * pz) + w2c[7];
-    const float z = ((w2c[8] * px + w2c[9] * py) + w2c[10] * pz) + w2c[11];
-    const float u = fx * x / z + cx, v = fy * y / z + cy;
-    in_view = z > near_plane && z < far_plane && u >= guard_lo && u <= u_hi && v >= guard_lo && v <= v_hi;
-  }
+  if (g < n_rows)
+    in_view = map_in_band(map_project(w2c, map_load_row(means, g), fx, fy, cx, cy), near_plane, far_plane, guard_lo,
+                          u_hi, v_hi);
   const unsigned long long sel = compact_ballot(in_view, ballots);
   // second mask: in view now, bit clear in prev
   const unsigned long long mask[2] = {sel, prev_ballots ? sel & ~prev_ballots[compact_wave_slot()] : 0ull};
@@ -86,7 +74,7 @@ extern "C" size_t gsl_map_view_ws_bytes(int64_t n_rows) {
 
 // Argument checks shared by the two passes.
 static int view_check(const float* means, int64_t n_rows, const int32_t* counters, const void* ws, size_t ws_bytes) {
-  if (n_rows <= 0 || n_rows >= 0x80000000ll) return GSL_ERR_BAD_ARG;  // 32-bit counts and indices
+  if (!gsl::map_rows_ok(n_rows)) return GSL_ERR_BAD_ARG;
   if (!means || !counters || !ws) return GSL_ERR_BAD_ARG;
   if (ws_bytes < gsl_map_view_ws_bytes(n_rows)) return GSL_ERR_WORKSPACE;
   return GSL_OK;
@@ -95,7 +83,7 @@ static int view_check(const float* means, int64_t n_rows, const int32_t* counter
 extern "C" int gsl_map_view_select(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx,
                                    float cy, int width, int height, float guard_px, float near_plane, float far_plane,
                                    const void* prev_ws, int32_t* counters, void* ws, size_t ws_bytes, void* stream) {
-  if (!w2c || width <= 0 || height <= 0 || !(fx != 0.f) || !(fy != 0.f)) return GSL_ERR_BAD_ARG;
+  if (!w2c || width <= 0 || height <= 0 || !gsl::map_focal_ok(fx, fy)) return GSL_ERR_BAD_ARG;
   if (!(guard_px >= 0.f) || !(near_plane < far_plane) || (prev_ws != nullptr && prev_ws == ws)) return GSL_ERR_BAD_ARG;
   int rc = view_check(means, n_rows, counters, ws, ws_bytes);
   if (rc != GSL_OK) return rc;

@@ -340,26 +340,40 @@ class Localizer:
             if self._keyframes:
                 self.map.add_keyframe(depth, self._poses[0])  # keyframe 0: clear() has forgotten the others
 
-    def _recognise(self, depth: Tensor, frame):
-        """Place recognition for a frame that the grid around its start poses has left lost: (the third run as
-        ``_run_tracker`` returns it, its pair, its start pose, its verdict, accepted, the keyframe slot of the winning
-        base), or None when no keyframe has an admissible match."""
+    def _retry(self, depth: Tensor, frame, bases, kept, failed_start: bool = False):
+        """One more run for a frame whose estimate the map rejected.  The ``reloc_candidates`` around the bases are scored
+        in one call; the one with the largest ``agree - front`` (the lowest index among equals) is tracked from, on a
+        pair built at that pose, and the estimate is held against the map.  kept: (run as ``_run_tracker`` returns it,
+        pair, start pose, verdict) of the run kept so far.  Returns (that candidate's index, accepted, the run's steps,
+        the state to keep now) -- or None when failed_start says that candidate 0 is the start that has just failed,
+        and it scores highest."""
         cfg = self._reloc
-        ranked = self.map.match_place(depth)[: cfg.place_top]
+        cands = reloc_candidates(bases, cfg.reloc_rot_deg, cfg.reloc_trans, cfg.reloc_levels).to(self.device)
+        scores = self.map.score_poses(depth, self.K, cands, self.cfg.gs.near_plane)
+        margins = [int(s[1]) - int(s[2]) for s in scores]
+        winner = margins.index(max(margins))  # the lowest index among equals
+        if failed_start and winner == 0:
+            return None
+        pair = self._map_pair(cands[winner], frame)
+        run = self._run_tracker(pair, cands[winner])
+        verdict = self._verdict(depth, run[4])
+        accepted = self._accepted(run[2], verdict)
+        if accepted or verdict[1] - verdict[2] > kept[3][1] - kept[3][2]:  # better-scoring, rejected: still handed on
+            kept = (run, pair, cands[winner], verdict)
+        return winner, accepted, run[2].steps, kept
+
+    def _recognise(self, depth: Tensor, frame, kept):
+        """Place recognition for a frame that the grid around its start poses has left lost: ``_retry`` around the turned
+        poses of the best-matching keyframes, with the keyframe slot of the winning base in place of the winner; None
+        when no keyframe has an admissible match."""
+        ranked = self.map.match_place(depth)[: self._reloc.place_top]
         if not ranked:
             return None
         poses = self.map.keyframe_poses
         fx, fy = float(self.K[0, 0]), float(self.K[1, 1])
         bases = [place_base(poses[slot], sx, sy, self.W, self.H, fx, fy) for slot, sx, sy, _, _ in ranked]
-        cands = reloc_candidates(bases, cfg.reloc_rot_deg, cfg.reloc_trans, cfg.reloc_levels).to(self.device)
-        scores = self.map.score_poses(depth, self.K, cands, self.cfg.gs.near_plane)
-        margins = [int(s[1]) - int(s[2]) for s in scores]
-        winner = margins.index(max(margins))  # the lowest index among equals
-        pair = self._map_pair(cands[winner], frame)
-        third = self._run_tracker(pair, cands[winner])
-        verdict = self._verdict(depth, third[4])
-        slot = ranked[winner // (1 + 12 * cfg.reloc_levels)][0]
-        return third, pair, cands[winner], verdict, self._accepted(third[2], verdict), slot
+        winner, *rest = self._retry(depth, frame, bases, kept)
+        return (ranked[winner // (1 + 12 * self._reloc.reloc_levels)][0], *rest)
 
     @torch.no_grad()
     def track(self, depth, rgb=None, gt_c2w: Optional[Tensor] = None) -> LocalizeResult:
@@ -388,32 +402,21 @@ class Localizer:
             # around the start poses is tracked from once more; an estimate the map still rejects is a lost frame's
             verdict, relocalised = self._verdict(depth, est), False
             lost = not self._accepted(res, verdict)
+            kept = ((N, scales, res, best, est), d, init, verdict)
             if lost:
-                bases = [init] if torch.equal(placed, init) else [init, placed]
-                cands = reloc_candidates(bases, self._reloc.reloc_rot_deg, self._reloc.reloc_trans,
-                                         self._reloc.reloc_levels).to(self.device)
-                scores = self.map.score_poses(depth, self.K, cands, self.cfg.gs.near_plane)
-                margins = [int(s[1]) - int(s[2]) for s in scores]
-                winner = margins.index(max(margins))  # the lowest index among equals
-                if winner != 0:  # 0 is the start that has just failed
-                    again = self._map_pair(cands[winner], frame)
-                    second = self._run_tracker(again, cands[winner])
-                    steps += second[2].steps
-                    verdict2 = self._verdict(depth, second[4])
-                    relocalised = self._accepted(second[2], verdict2)
-                    lost = not relocalised
-                    if relocalised or verdict2[1] - verdict2[2] > verdict[1] - verdict[2]:
-                        (N, scales, res, best, est), d, init, verdict = second, again, cands[winner], verdict2
+                again = self._retry(depth, frame, [init] if torch.equal(placed, init) else [init, placed], kept, True)
+                if again is not None:
+                    _, relocalised, more, kept = again
+                    steps, lost = steps + more, not relocalised
             if self._keyframes:
                 recognised = -1
-                found = self._recognise(depth, frame) if lost and self.map.n_keyframes > 0 else None
+                found = self._recognise(depth, frame, kept) if lost and self.map.n_keyframes > 0 else None
                 if found is not None:
-                    third, pair, start, verdict3, accepted, slot = found
-                    steps += third[2].steps
+                    slot, accepted, more, kept = found
+                    steps += more
                     if accepted:
                         lost, relocalised, recognised = False, True, slot
-                    if accepted or verdict3[1] - verdict3[2] > verdict[1] - verdict[2]:
-                        (N, scales, res, best, est), d, init, verdict = third, pair, start, verdict3
+            (N, scales, res, best, est), d, init, verdict = kept
         self._prev = (pts, col)
         self._poses.append(est)
         out = LocalizeResult(c2w=est, init_c2w=init, steps=steps, best_step=res.best_step, best_loss=res.best_loss,

@@ -45,6 +45,7 @@ descriptor against all of them under 15 small shifts of the grid and ranks the k
 from __future__ import annotations
 
 import functools
+import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -163,7 +164,7 @@ class MapConfig:
                              "fraction, inside [0, 1)")
         if self.merge_voxel is not None:
             v = self.merge_voxel
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+            if not number(v):
                 raise ValueError(f"merge_voxel {v!r}: a length in metres (or None)")
             h = np.float32(v)  # the kernel's h and 1 / h are float32
             if not (np.isfinite(h) and h > 0):
@@ -190,8 +191,7 @@ class MapConfig:
                              "fraction, inside [0, 1)")
         if self.free_rho is not None and not 0.0 < self.free_rho < 1.0:
             raise ValueError(f"free_rho {self.free_rho}: a fraction of the observed depth, inside (0, 1)")
-        if isinstance(self.free_window_px, bool) or not isinstance(self.free_window_px, int) \
-                or not 0 <= self.free_window_px <= 3:
+        if not whole(self.free_window_px) or not 0 <= self.free_window_px <= 3:
             raise ValueError(f"free_window_px {self.free_window_px}: a whole number of pixels, 0 .. 3")
         if not self.view_reach_px >= 0.0:
             raise ValueError(f"view_reach_px {self.view_reach_px}: not negative")
@@ -207,6 +207,12 @@ def _intr_and_pose(K, c2w) -> Tuple[Tuple[float, float, float, float], Tensor]:
     if c2w.shape != (4, 4):
         raise ValueError(f"c2w is {tuple(c2w.shape)}, not (4, 4)")
     return (float(Kc[0, 0]), float(Kc[1, 1]), float(Kc[0, 2]), float(Kc[1, 2])), c2w
+
+
+def _world_to_camera(c2w: Tensor) -> Tensor:
+    """c2w [..., 4, 4] -> float32 on the host: the float64 inverse, rounded to float32 here, once -- the kernels multiply
+    and add, nothing else."""
+    return torch.from_numpy(np.linalg.inv(c2w.detach().cpu().double().numpy()).astype(np.float32))
 
 
 class GaussianMap:
@@ -286,36 +292,43 @@ class GaussianMap:
         self._n_survivors = 0
         self._kf_made = 0
 
+    def _image(self, a, shape, what: str) -> Tensor:
+        """a as a contiguous float32 tensor of that shape on the map's device, refused unless it has that many elements."""
+        a = torch.as_tensor(a, dtype=torch.float32, device=self.device)
+        if a.numel() != math.prod(shape):
+            raise ValueError(f"{what} is {tuple(a.shape)}, the map was built for {shape}")
+        return a.reshape(shape).contiguous()
+
+    def _depth_image(self, depth) -> Tensor:
+        return self._image(depth, (self.H, self.W), "depth")
+
+    def _select_launch(self, depth: Tensor, render: Optional[Tensor], alphas: Optional[Tensor],
+                       read_back: bool = True) -> Optional[int]:
+        """The first entry point on the current stream; a frame that may not fit reads the pixels selected back here,
+        its extra synchronisation."""
+        assert depth.is_cuda, "GaussianMap.insert_frame: the map is grown by HIP kernels, no CPU path"
+        lib, st, ptr, ws = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._ws
+        _lib.check(lib.gsl_map_select(ptr(render), ptr(alphas), ptr(depth), self.W, self.H, self.alpha_min, self.keep,
+                                      ptr(self._counters), ptr(ws), ws.numel(), st), "gsl_map_select")
+        return self._counters.tolist()[0] if read_back else None
+
+    def _append_launch(self, depth: Tensor, rgb: Tensor, intr: Tuple[float, float, float, float], c2w: Tensor,
+                       read_back: bool = True) -> Optional[int]:
+        """The second entry point after ``_select_launch`` (the selection's workspace is untouched: an eviction in
+        between has its own) and, for that frame, the read-back of the rows appended."""
+        lib, st, ptr, ws = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._ws
+        _lib.check(lib.gsl_map_append(ptr(depth), ptr(rgb), self.W, self.H, *intr, ptr(c2w), ptr(self.means),
+                                      ptr(self.colors), self.n_live, self.capacity, ptr(self._counters), ptr(ws),
+                                      ws.numel(), st), "gsl_map_append")
+        return self._counters.tolist()[1] if read_back else None
+
     def _launch(self, depth: Tensor, rgb: Tensor, intr: Tuple[float, float, float, float], c2w: Tensor,
                 render: Optional[Tensor], alphas: Optional[Tensor]) -> Tuple[int, int]:
-        """The two entry points on the current stream and the read-back of (selected, appended)."""
-        assert depth.is_cuda, "GaussianMap.insert_frame: the map is grown by HIP kernels, no CPU path"
-        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
-        ws = self._ws
-        _lib.check(lib.gsl_map_select(ptr(render), ptr(alphas), ptr(depth), self.W, self.H, self.alpha_min, self.keep,
-                                      ptr(self._counters), ptr(ws), ws.numel(), st), "gsl_map_select")
-        _lib.check(lib.gsl_map_append(ptr(depth), ptr(rgb), self.W, self.H, *intr, ptr(c2w), ptr(self.means),
-                                      ptr(self.colors), self.n_live, self.capacity, ptr(self._counters), ptr(ws),
-                                      ws.numel(), st), "gsl_map_append")
+        """A frame with room: the two entry points and one read-back of (selected, appended)."""
+        self._select_launch(depth, render, alphas, read_back=False)
+        self._append_launch(depth, rgb, intr, c2w, read_back=False)
         selected, appended = self._counters.tolist()  # the frame's one synchronisation
         return selected, appended
-
-    def _select_launch(self, depth: Tensor, render: Optional[Tensor], alphas: Optional[Tensor]) -> int:
-        """The first entry point alone and the read-back of the pixels selected: a frame that may not fit."""
-        assert depth.is_cuda, "GaussianMap.insert_frame: the map is grown by HIP kernels, no CPU path"
-        lib, st, ptr, ws = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._ws
-        _lib.check(lib.gsl_map_select(ptr(render), ptr(alphas), ptr(depth), self.W, self.H, self.alpha_min, self.keep,
-                                      ptr(self._counters), ptr(ws), ws.numel(), st), "gsl_map_select")
-        return self._counters.tolist()[0]  # the extra synchronisation of a frame that is short of room
-
-    def _append_launch(self, depth: Tensor, rgb: Tensor, intr: Tuple[float, float, float, float], c2w: Tensor) -> int:
-        """The second entry point after ``_select_launch`` (the selection's workspace is untouched: the eviction in
-        between has its own) and the read-back of the rows appended."""
-        lib, st, ptr, ws = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._ws
-        _lib.check(lib.gsl_map_append(ptr(depth), ptr(rgb), self.W, self.H, *intr, ptr(c2w), ptr(self.means),
-                                      ptr(self.colors), self.n_live, self.capacity, ptr(self._counters), ptr(ws),
-                                      ws.numel(), st), "gsl_map_append")
-        return self._counters.tolist()[1]
 
     @torch.no_grad()
     def insert_frame(self, depth, rgb, K, c2w, render: Optional[Tensor] = None,
@@ -328,17 +341,10 @@ class GaussianMap:
         that many rows plus ``evict_headroom`` (``evict``; ``last_evicted`` counts them)."""
         if (render is None) != (alphas is None):
             raise ValueError("insert_frame: render and alphas come together (or neither, for the first frame)")
-
-        def image(a, shape, what):
-            a = torch.as_tensor(a, dtype=torch.float32, device=self.device)
-            if a.numel() != shape[0] * shape[1] * (shape[2] if len(shape) > 2 else 1):
-                raise ValueError(f"{what} is {tuple(a.shape)}, the map was built for {shape}")
-            return a.reshape(shape).contiguous()
-
         hw = (self.H, self.W)
-        depth, rgb = image(depth, hw, "depth"), image(torch.as_tensor(rgb)[..., :3], hw + (3,), "rgb")
+        depth, rgb = self._depth_image(depth), self._image(torch.as_tensor(rgb)[..., :3], hw + (3,), "rgb")
         if render is not None:
-            render, alphas = image(render, hw, "render"), image(alphas, hw, "alphas")
+            render, alphas = self._image(render, hw, "render"), self._image(alphas, hw, "alphas")
         intr, c2w = _intr_and_pose(K, c2w)
         c2w = c2w.to(device=self.device, dtype=torch.float32).contiguous()
         self.last_evicted = 0
@@ -388,10 +394,7 @@ class GaussianMap:
 
     def _view_args(self, K, c2w):
         intr, c2w = _intr_and_pose(K, c2w)
-        # the float64 inverse, rounded to float32 here: the kernel multiplies and adds, nothing else
-        w2c = np.linalg.inv(c2w.detach().cpu().double().numpy()).astype(np.float32)
-        w2c = torch.from_numpy(w2c).to(self.device).contiguous()
-        return intr, w2c
+        return intr, _world_to_camera(c2w).to(self.device).contiguous()
 
     @torch.no_grad()
     def select_view(self, K, c2w, guard_px: float, near: float, far: float) -> Tuple[Tensor, Tensor, Tensor, int]:
@@ -429,39 +432,57 @@ class GaussianMap:
                               counters=torch.zeros(3, dtype=torch.int32, device=dev), ws=ws)
         return self._free
 
+    def _survivors_launch(self, counters: Tensor, ws: Tensor, stamps_early: bool, then=None) -> list:
+        """What follows an operation's own selection of the rows that stay (their ballots in the head of ws, in the
+        layout of gsl_map_view_select): their gather into the spare buffers (means, colours, old rows), the gather of
+        their stamps, ``then()`` -- launches that work on the gathered rows -- and the read-back of the counters, the
+        call's one synchronisation.  stamps_early: the stamps go before the read-back, every live row at most (the count
+        is not known on the host yet, and the rows past it are never read); otherwise after it, the rows stored, and
+        only when something goes -- the buffers will be swapped, the stamps follow their rows."""
+        lib, st, ptr, f = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._free_buffers()
+
+        def stamps(n):
+            _lib.check(lib.gsl_map_gather_i32(ptr(self.stamps), self.n_live, ptr(f["ids"]), n, ptr(f["stamps"]), st),
+                       "gsl_map_gather_i32")
+
+        _lib.check(lib.gsl_map_view_gather(ptr(self.means), ptr(self.colors), self.n_live, ptr(f["means"]),
+                                           ptr(f["colors"]), ptr(f["ids"]), self.capacity, ptr(counters), ptr(ws),
+                                           ws.numel(), st), "gsl_map_view_gather")
+        if stamps_early:
+            stamps(self.n_live)
+        if then is not None:
+            then()
+        out = counters.tolist()
+        if not stamps_early and out[2] < self.n_live:
+            stamps(out[2])
+        return out
+
+    def _keep_survivors(self, stay: int, gone: int, stored: int) -> Tuple[int, int]:
+        """The end of a removal, from the counts its launches read back: ``survivors`` describes the rows that stay, and
+        when something went the spare buffers, which hold them, become the map (a swap, not a copy).  (gone, kept)."""
+        # the spare buffers hold the capacity: every row that stays was stored
+        assert stored == stay == self.n_live - gone <= self.n_live, (stay, gone, stored, self.n_live)
+        self._n_survivors = stay
+        if gone > 0:
+            f = self._free
+            self.means, f["means"] = f["means"], self.means
+            self.colors, f["colors"] = f["colors"], self.colors
+            self.stamps, f["stamps"] = f["stamps"], self.stamps
+            self.n_live = stay
+            self._view_rows = -1  # the view ballots describe other rows
+        return gone, stay
+
     def _free_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, keep: float,
                      window: int, near: float) -> Tuple[int, int]:
-        """The rule over the live rows and the gather of those that stay into the spare buffers (means, colours, old
-        rows); the read-back of (rows that stay, rows stored)."""
+        """The rule over the live rows and ``_survivors_launch``; (rows that stay, rows stored)."""
         assert depth.is_cuda, "GaussianMap.remove_seen_through: the rows are judged and moved by HIP kernels, no CPU path"
-        lib, st, ptr, f = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._free_buffers()
-        ws = f["ws"]
-        _lib.check(lib.gsl_map_free_select(ptr(self.means), self.n_live, ptr(w2c), *intr, ptr(depth), self.W, self.H,
-                                           keep, window, near, ptr(f["counters"]), ptr(ws), ws.numel(), st),
-                   "gsl_map_free_select")
-        _lib.check(lib.gsl_map_view_gather(ptr(self.means), ptr(self.colors), self.n_live, ptr(f["means"]),
-                                           ptr(f["colors"]), ptr(f["ids"]), self.capacity, ptr(f["counters"]),
-                                           ptr(ws), ws.numel(), st), "gsl_map_view_gather")
-        stay, _, stored = f["counters"].tolist()  # the call's one synchronisation
-        if stored < self.n_live:  # something goes: the buffers will be swapped, the stamps follow their rows
-            self._gather_stamps(stored)
+        f = self._free_buffers()
+        ws, ptr = f["ws"], _lib.ptr
+        _lib.check(_lib.load_library().gsl_map_free_select(
+            ptr(self.means), self.n_live, ptr(w2c), *intr, ptr(depth), self.W, self.H, keep, window, near,
+            ptr(f["counters"]), ptr(ws), ws.numel(), _lib.current_stream()), "gsl_map_free_select")
+        stay, _, stored = self._survivors_launch(f["counters"], ws, stamps_early=False)
         return stay, stored
-
-    def _gather_stamps(self, n: int) -> None:
-        """The stamps of the n rows the gather just moved, through the ids it wrote, into the spare stamps."""
-        f = self._free
-        _lib.check(_lib.load_library().gsl_map_gather_i32(_lib.ptr(self.stamps), self.n_live, _lib.ptr(f["ids"]), n,
-                                                          _lib.ptr(f["stamps"]), _lib.current_stream()),
-                   "gsl_map_gather_i32")
-
-    def _swap_spare(self, n_live: int) -> None:
-        """The spare buffers, which hold the survivors, become the map (a swap, not a copy)."""
-        f = self._free
-        self.means, f["means"] = f["means"], self.means
-        self.colors, f["colors"] = f["colors"], self.colors
-        self.stamps, f["stamps"] = f["stamps"], self.stamps
-        self.n_live = n_live
-        self._view_rows = -1  # the view ballots describe other rows
 
     @torch.no_grad()
     def remove_seen_through(self, depth, K, c2w, near: float) -> Tuple[int, int]:
@@ -476,17 +497,10 @@ class GaussianMap:
             raise RuntimeError("remove_seen_through: MapConfig.free_rho is None, the map only grows")
         if self.n_live == 0:
             return 0, 0
-        depth = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
-        if depth.numel() != self.H * self.W:
-            raise ValueError(f"depth is {tuple(depth.shape)}, the map was built for {(self.H, self.W)}")
-        depth = depth.reshape(self.H, self.W).contiguous()
+        depth = self._depth_image(depth)
         intr, w2c = self._view_args(K, c2w)
         stay, stored = self._free_launch(depth, intr, w2c, self._free_keep, int(self.cfg.free_window_px), float(near))
-        assert stored == stay <= self.n_live, (stay, stored, self.n_live)  # the spare buffers hold the capacity
-        removed, self._n_survivors = self.n_live - stay, stay
-        if removed > 0:
-            self._swap_spare(stay)
-        return removed, stay
+        return self._keep_survivors(stay, self.n_live - stay, stored)
 
     # ---- a bounded map: last-observed stamps, the least recently observed rows evicted (csrc/map_evict.hip) ---------
     def _observe_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, near: float,
@@ -505,32 +519,22 @@ class GaussianMap:
         self.frame_index += 1
         if self.n_live == 0:
             return
-        depth = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
-        if depth.numel() != self.H * self.W:
-            raise ValueError(f"depth is {tuple(depth.shape)}, the map was built for {(self.H, self.W)}")
-        depth = depth.reshape(self.H, self.W).contiguous()
+        depth = self._depth_image(depth)
         intr, w2c = self._view_args(K, c2w)
         self._observe_launch(depth, intr, w2c, float(near), float(far))
 
     def _evict_launch(self, need: int) -> Tuple[int, int, int]:
-        """The selection over the stamps of the live rows, the gather of the rows that stay into the spare buffers
-        (means, colours, old rows) and of their stamps; the read-back of (rows that stay, rows evicted, rows stored)."""
+        """The selection over the stamps of the live rows and ``_survivors_launch``; (rows that stay, rows evicted, rows
+        stored)."""
         assert self.means.is_cuda, "GaussianMap.evict: the rows are chosen and moved by HIP kernels, no CPU path"
-        lib, st, ptr, f = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._free_buffers()
+        lib, f = _lib.load_library(), self._free_buffers()
         if self._evict_ws is None:
             self._evict_ws = torch.empty(lib.gsl_map_evict_ws_bytes(self.capacity), dtype=torch.uint8, device=self.device)
         ws = self._evict_ws
-        _lib.check(lib.gsl_map_evict_select(ptr(self.stamps), self.n_live, self.frame_index,
-                                            int(self.cfg.evict_min_age), need, ptr(f["counters"]), ptr(ws), ws.numel(),
-                                            st), "gsl_map_evict_select")
-        _lib.check(lib.gsl_map_view_gather(ptr(self.means), ptr(self.colors), self.n_live, ptr(f["means"]),
-                                           ptr(f["colors"]), ptr(f["ids"]), self.capacity, ptr(f["counters"]),
-                                           ptr(ws), ws.numel(), st), "gsl_map_view_gather")
-        # every live row at most: the count is not known on the host yet, and the rows past it are never read
-        _lib.check(lib.gsl_map_gather_i32(ptr(self.stamps), self.n_live, ptr(f["ids"]), self.n_live, ptr(f["stamps"]),
-                                          st), "gsl_map_gather_i32")
-        stay, evicted, stored = f["counters"].tolist()  # the call's one synchronisation
-        return stay, evicted, stored
+        _lib.check(lib.gsl_map_evict_select(_lib.ptr(self.stamps), self.n_live, self.frame_index,
+                                            int(self.cfg.evict_min_age), need, _lib.ptr(f["counters"]), _lib.ptr(ws),
+                                            ws.numel(), _lib.current_stream()), "gsl_map_evict_select")
+        return tuple(self._survivors_launch(f["counters"], ws, stamps_early=True))
 
     @torch.no_grad()
     def evict(self, need: int) -> Tuple[int, int]:
@@ -542,18 +546,13 @@ class GaussianMap:
         need = int(need)
         if need <= 0 or self.n_live == 0:
             return 0, self.n_live
-        stay, evicted, stored = self._evict_launch(need)
-        assert stored == stay == self.n_live - evicted, (stay, evicted, stored, self.n_live)
-        self._n_survivors = stay
-        if evicted > 0:
-            self._swap_spare(stay)
-        return evicted, stay
+        return self._keep_survivors(*self._evict_launch(need))
 
     # ---- a map with a resolution: the rows that share a voxel are fused into one (csrc/map_merge.hip) ----------------
     def _merge_launch(self) -> Tuple[int, int, int, int]:
-        """The rule over the live rows, the gather of the rows that stay into the spare buffers (means, colours, old
-        rows) and of their stamps, and the fused rows written over the first row of their voxel there; the read-back of
-        (rows that stay, rows removed, rows stored, the table's overflow flag)."""
+        """The rule over the live rows and ``_survivors_launch``, with the fused rows written over the first row of
+        their voxel in the spare buffers before the read-back; (rows that stay, rows removed, rows stored, the table's
+        overflow flag)."""
         assert self.means.is_cuda, "GaussianMap.merge: the rows are fused and moved by HIP kernels, no CPU path"
         lib, st, ptr, f = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._free_buffers()
         if self._merge is None:
@@ -564,16 +563,13 @@ class GaussianMap:
         _lib.check(lib.gsl_map_merge_select(ptr(self.means), ptr(self.colors), ptr(self.stamps), self.n_live,
                                             self._merge_inv_h, self._merge_h, ptr(counters), ptr(ws), ws.numel(), st),
                    "gsl_map_merge_select")
-        _lib.check(lib.gsl_map_view_gather(ptr(self.means), ptr(self.colors), self.n_live, ptr(f["means"]),
-                                           ptr(f["colors"]), ptr(f["ids"]), self.capacity, ptr(counters), ptr(ws),
-                                           ws.numel(), st), "gsl_map_view_gather")
-        # every live row at most: the count is not known on the host yet, and the rows past it are never read
-        _lib.check(lib.gsl_map_gather_i32(ptr(self.stamps), self.n_live, ptr(f["ids"]), self.n_live, ptr(f["stamps"]),
-                                          st), "gsl_map_gather_i32")
-        _lib.check(lib.gsl_map_merge_apply(ptr(f["ids"]), ptr(counters), self.n_live, ptr(f["means"]), ptr(f["colors"]),
-                                           ptr(f["stamps"]), ptr(ws), ws.numel(), st), "gsl_map_merge_apply")
-        stay, removed, stored, overflow = counters.tolist()  # the call's one synchronisation
-        return stay, removed, stored, overflow
+
+        def apply():
+            _lib.check(lib.gsl_map_merge_apply(ptr(f["ids"]), ptr(counters), self.n_live, ptr(f["means"]),
+                                               ptr(f["colors"]), ptr(f["stamps"]), ptr(ws), ws.numel(), st),
+                       "gsl_map_merge_apply")
+
+        return tuple(self._survivors_launch(counters, ws, stamps_early=True, then=apply))
 
     @torch.no_grad()
     def merge(self) -> Tuple[int, int]:
@@ -591,11 +587,7 @@ class GaussianMap:
         stay, removed, stored, overflow = self._merge_launch()
         if overflow != 0:
             raise RuntimeError("GaussianMap.merge: a row found no slot in the voxel table (gsl_map_merge_select)")
-        assert stored == stay == self.n_live - removed, (stay, removed, stored, self.n_live)
-        self._n_survivors = stay
-        if removed > 0:
-            self._swap_spare(stay)
-        return removed, stay
+        return self._keep_survivors(stay, removed, stored)
 
     # ---- pose scores: how many live rows a depth frame confirms from each of a set of poses (csrc/map_score.hip) ----
     def _score_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, near: float) -> np.ndarray:
@@ -628,14 +620,10 @@ class GaussianMap:
             raise ValueError(f"{len(poses)} poses: one call scores at most {SCORE_MAX_POSES}")
         if self.n_live == 0 or not poses:
             return np.zeros((len(poses), 3), dtype=np.int64)
-        depth = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
-        if depth.numel() != self.H * self.W:
-            raise ValueError(f"depth is {tuple(depth.shape)}, the map was built for {(self.H, self.W)}")
-        depth = depth.reshape(self.H, self.W).contiguous()
+        depth = self._depth_image(depth)
         intr, _ = _intr_and_pose(K, poses[0])
-        # the float64 inverses, rounded to float32 here: the kernel multiplies and adds, nothing else
-        w2c = np.linalg.inv(torch.stack([c.detach().cpu().double() for c in poses]).numpy()).astype(np.float32)
-        return self._score_launch(depth, intr, torch.from_numpy(w2c), float(near))
+        return self._score_launch(depth, intr, _world_to_camera(torch.stack([c.detach().cpu().double() for c in poses])),
+                                  float(near))
 
     # ---- place recognition: keyframes, their depth descriptors and the match of a frame against them (csrc/map_place.hip)
     def _place_buffers(self):
@@ -645,12 +633,6 @@ class GaussianMap:
                                query=torch.full((PLACE_CELLS,), -1, dtype=i32, device=dev),
                                out=torch.zeros(PLACE_MAX_KEYFRAMES, len(PLACE_SHIFTS), 2, dtype=i32, device=dev))
         return self._place
-
-    def _depth_image(self, depth) -> Tensor:
-        depth = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
-        if depth.numel() != self.H * self.W:
-            raise ValueError(f"depth is {tuple(depth.shape)}, the map was built for {(self.H, self.W)}")
-        return depth.reshape(self.H, self.W).contiguous()
 
     def _describe_launch(self, depth: Tensor, desc: Tensor) -> None:
         """The descriptor of depth [H,W] into desc, 192 contiguous int32 on the device.  No read-back."""

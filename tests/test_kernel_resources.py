@@ -76,13 +76,17 @@ def test_sort_and_projection_kernels_stay_in_registers():
 def test_compaction_kernels_cost_what_their_hand_written_copies_did():
     """The record and fill kernels of the three ordered compactions and the scan between them, written on the shared
     helpers of csrc/compact_dev.h: no more registers (VGPR, SGPR), LDS or scratch than the last commit in which each
-    kernel carried its own copy of the ballot, count and position steps (the numbers are that commit's)."""
+    kernel carried its own copy of the ballot, count and position steps (the numbers are that commit's).  Likewise the
+    map kernels that project a row, written on the row rule of csrc/map_dev.h."""
     budget = {  # kernel: (VGPRs, SGPRs, LDS bytes)
         ("project_packed.hip", "k_packed_projectILb0"): (33, 41, 16),
         ("project_packed.hip", "k_packed_projectILb1"): (41, 49, 0),
         ("map.hip", "k_map_select"): (6, 22, 16), ("map.hip", "k_map_append"): (20, 36, 0),
         ("map_view.hip", "k_map_view_select"): (14, 50, 32), ("map_view.hip", "k_map_view_gather"): (15, 30, 0),
         ("compact.hip", "k_count_scan"): (26, 20, 1024),
+        # the kernels on the row rule of csrc/map_dev.h: the last commit in which each wrote the projection out itself
+        ("map_free.hip", "k_map_free_select"): (14, 42, 16), ("map_evict.hip", "k_map_observe"): (16, 46, 0),
+        ("map_score.hip", "k_map_score"): (16, 62, 768),
     }
     files = {f: _resources(f) for f in sorted({f for f, _ in budget})}
     for (f, name), (vgprs, sgprs, lds) in budget.items():
