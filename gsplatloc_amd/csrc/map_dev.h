@@ -1,6 +1,7 @@
 // Frame-to-map localisation, the row rule, the one copy: where a row of the map lies in a frame.  Used by the view
-// selection (map_view.hip), free space (map_free.hip), the observation stamps (map_evict.hip) and the pose scores
-// (map_score.hip); what each of them does with the projected row -- its depth predicates, its counts -- is in its file.
+// selection (map_view.hip), free space (map_free.hip), the observation stamps (map_evict.hip), the pose scores
+// (map_score.hip) and the refinement (map_refine.hip, which takes z, u, v and leaves the rounded uf, vf alone); what each
+// of them does with the projected row -- its depth predicates, its counts -- is in its file.
 //
 // Row i of means[n,3], with w the rows of w2c (world to camera, row-major):
 //   x = ((w0 px + w1 py) + w2 pz) + w3, y and z likewise;  u = fx x / z + cx, v = fy y / z + cy;

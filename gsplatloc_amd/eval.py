@@ -40,7 +40,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   map_merge_voxel: Optional[float] = None, map_merge_every: int = 1, map_reloc: bool = False,
                   map_reloc_min_agree: Optional[float] = None, map_reloc_rot_deg: Optional[float] = None,
                   map_reloc_trans: Optional[float] = None, map_keyframes: bool = False,
-                  map_keyframe_rot_deg: Optional[float] = None, map_keyframe_trans: Optional[float] = None) -> Dict:
+                  map_keyframe_rot_deg: Optional[float] = None, map_keyframe_trans: Optional[float] = None,
+                  map_refine: bool = False, map_refine_max_weight: Optional[int] = None) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -57,7 +58,9 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     ``map_reloc_rot_deg`` / ``map_reloc_trans`` for MapConfig.reloc_min_agree / reloc_rot_deg / reloc_trans where not
     None; ``map_keyframes``: MapConfig.keyframes, a frame that stays lost is compared with the keyframes of the map and
     tracked once more from the best-scoring pose around the most similar ones, with ``map_keyframe_rot_deg`` /
-    ``map_keyframe_trans`` for MapConfig.keyframe_rot_deg / keyframe_trans where not None)."""
+    ``map_keyframe_trans`` for MapConfig.keyframe_rot_deg / keyframe_trans where not None; ``map_refine``:
+    MapConfig.refine, the rows a frame observes again move to the running mean of their depths, with
+    ``map_refine_max_weight`` for MapConfig.refine_max_weight where not None)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
     if map_merge_voxel is not None and not map_mode:
         raise ValueError("map_merge_voxel belongs to the map mode (map_mode=True)")
@@ -79,11 +82,19 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         raise ValueError("map_keyframes belongs to the relocalisation (map_reloc=True)")
     if keyframes and not map_keyframes:
         raise ValueError(f"{', '.join('map_' + k for k in keyframes)}: options of map_keyframes=True")
+    if (map_refine or map_refine_max_weight is not None) and not map_mode:
+        raise ValueError("map_refine belongs to the map mode (map_mode=True)")
+    if map_refine_max_weight is not None and not map_refine:
+        raise ValueError("map_refine_max_weight: an option of map_refine=True")
+    refine = None
+    if map_refine:
+        refine = dict(refine=True, **({} if map_refine_max_weight is None else
+                                      {"refine_max_weight": map_refine_max_weight}))
     if sequential:
         return evaluate_sequential(parser, cfg, max_frames, verbose, motion, map_mode, map_capacity, map_view_guard,
                                    map_free_rho, map_free_window, map_evict, map_merge_voxel, map_merge_every,
                                    dict(reloc, reloc=True) if map_reloc else None,
-                                   dict(keyframes, keyframes=True) if map_keyframes else None)
+                                   dict(keyframes, keyframes=True) if map_keyframes else None, map_refine=refine)
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -148,7 +159,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                         map_free_rho: Optional[float] = None, map_free_window: int = 1,
                         map_evict: bool = False, map_merge_voxel: Optional[float] = None,
                         map_merge_every: int = 1, map_reloc: Optional[Dict] = None,
-                        map_keyframes: Optional[Dict] = None) -> Dict:
+                        map_keyframes: Optional[Dict] = None, map_refine: Optional[Dict] = None) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
     map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
@@ -161,7 +172,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     reloc_trans); the report gains relocalised_frames and agree_share_per_frame (agree / (agree + front) of the
     estimate that was kept, None where no row was judged).  map_keyframes: the MapConfig fields of place recognition
     (keyframes=True and any of keyframe_rot_deg, keyframe_trans); the report gains keyframes (those the map holds at the
-    end) and recognised_frames (frames that a keyframe's neighbourhood was accepted from)."""
+    end) and recognised_frames (frames that a keyframe's neighbourhood was accepted from).  map_refine: the MapConfig
+    fields of refinement (refine=True and, where wanted, refine_max_weight); the report gains refined_per_frame."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
@@ -171,14 +183,14 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                                                        free_rho=map_free_rho, free_window_px=map_free_window,
                                                        evict=bool(map_evict), merge_voxel=map_merge_voxel,
                                                        merge_every=map_merge_every, **(map_reloc or {}),
-                                                       **(map_keyframes or {})))
+                                                       **(map_keyframes or {}), **(map_refine or {})))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
     merged_at_reset = loc.merged_at_reset
     eTs, eRs, steps, lost, path, last_t = [], [], [], 0, 0.0, pose[:3, 3]
     added, tracked, violations, removed, evicted, merged = [], [], [], [], [], []
-    relocalised, shares, recognised = 0, [], 0
+    relocalised, shares, recognised, refined = 0, [], 0, []
     for i in range(1, n + 1):
         depth, rgb, pose = parser.frame(i)
         r = loc.track(depth, rgb, gt_c2w=pose)
@@ -192,6 +204,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
         removed.append(r.removed)
         evicted.append(r.evicted)
         merged.append(r.merged)
+        refined.append(r.refined)
         if map_reloc:
             relocalised += int(r.relocalised)
             shares.append(r.agree / (r.agree + r.front) if r.agree + r.front > 0 else None)
@@ -217,7 +230,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             **({"merge_voxel": map_merge_voxel, "merge_every": map_merge_every, "merged_per_frame": merged,
                 "merged_at_reset": merged_at_reset} if map_merge_voxel is not None else {}),
             **({"reloc": True, "relocalised_frames": relocalised, "agree_share_per_frame": shares} if map_reloc else {}),
-            **({"keyframes": loc.map.n_keyframes, "recognised_frames": recognised} if map_keyframes else {})}
+            **({"keyframes": loc.map.n_keyframes, "recognised_frames": recognised} if map_keyframes else {}),
+            **({"refine": True, "refined_per_frame": refined} if map_refine else {})}
 
 
 def main(argv=None):
@@ -276,6 +290,11 @@ def main(argv=None):
                     help="--map-keyframes: a frame further than D degrees from every keyframe becomes one")
     ap.add_argument("--map-keyframe-trans", type=float, default=None, metavar="M",
                     help="--map-keyframes: a frame further than M metres from every keyframe becomes one")
+    ap.add_argument("--map-refine", action="store_true",
+                    help="--map: refinement -- the map's points that a frame observes again move along their ray to the "
+                         "running mean of the depths observed there (default: a point keeps its first depth)")
+    ap.add_argument("--map-refine-max-weight", type=int, default=None, metavar="N",
+                    help="--map-refine: the number of depths from which on the mean is an exponential one (default 64)")
     a = ap.parse_args(argv)
     if a.map_merge_voxel is not None and not a.map:
         ap.error("--map-merge-voxel needs --map")
@@ -304,6 +323,10 @@ def main(argv=None):
     for flag, value in (("--map-keyframe-rot-deg", a.map_keyframe_rot_deg), ("--map-keyframe-trans", a.map_keyframe_trans)):
         if value is not None and not a.map_keyframes:
             ap.error(f"{flag} needs --map-keyframes")
+    if a.map_refine and not a.map:
+        ap.error("--map-refine needs --map")
+    if a.map_refine_max_weight is not None and not a.map_refine:
+        ap.error("--map-refine-max-weight needs --map-refine")
     out = {}
     for room in a.rooms:
         parser = Parser(a.dataset, room, normalize=not a.no_normalize, input_folder=a.root)
@@ -314,7 +337,8 @@ def main(argv=None):
                           map_merge_voxel=a.map_merge_voxel, map_merge_every=a.map_merge_every, map_reloc=a.map_reloc,
                           map_reloc_min_agree=a.map_reloc_min_agree, map_reloc_rot_deg=a.map_reloc_rot_deg,
                           map_reloc_trans=a.map_reloc_trans, map_keyframes=a.map_keyframes,
-                          map_keyframe_rot_deg=a.map_keyframe_rot_deg, map_keyframe_trans=a.map_keyframe_trans)
+                          map_keyframe_rot_deg=a.map_keyframe_rot_deg, map_keyframe_trans=a.map_keyframe_trans,
+                          map_refine=a.map_refine, map_refine_max_weight=a.map_refine_max_weight)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

@@ -40,6 +40,9 @@ With ``MapConfig.keyframes`` place recognition follows: the map keeps the pose a
 of the frames that built it (``GaussianMap.add_keyframe``), and a frame that the grid leaves lost is compared with all
 of them (``GaussianMap.match_place``).  The poses of the most similar keyframes, each turned by the image shift under
 which it matched (``place_base``), are the bases of one more grid, which is scored and tracked from as before.
+With ``MapConfig.refine`` the map improves where it is seen again: after the insertion render of a frame that is not
+lost and before anything is stamped or inserted, the live rows the frame observes where it expects them move along
+their ray to the running mean of the depths observed there (``GaussianMap.refine``, at the estimate).
 """
 from __future__ import annotations
 
@@ -105,6 +108,7 @@ class LocalizeResult:
     # was accepted from, -1 on a frame that did not need place recognition or that it did not save (None: option off)
     keyframe: Optional[int] = None
     recognised: Optional[int] = None
+    refined: Optional[int] = None  # refine: live rows this frame observed again and moved, before its insertion
 
 
 def _step(axis: int, rot_deg: float = 0.0, trans: float = 0.0) -> Tensor:
@@ -212,7 +216,14 @@ class Localizer:
     front`` (the lowest index among equals) is tracked from, and its estimate, if accepted, is the frame's
     (``relocalised``, and ``recognised`` is the slot of the winning base's keyframe).  If not, the frame stays lost, the
     map is left alone and the best-scoring estimate of all runs is handed on; ``steps`` counts every run.  With the
-    option on and no frame rejected, poses, step counts and added rows are those of the run without it.  Everything else
+    option on and no frame rejected, poses, step counts and added rows are those of the run without it.
+    ``map_config.refine``: after the insertion render and before ``observe`` and the insertion -- every live row is then
+    an old one: the rows a frame appends sit at their own pixel's depth and must not count as observed again by that
+    frame, and the render is of the cloud that was tracked -- the rows the frame observes again from the estimate are
+    refined (``GaussianMap.refine``; ``LocalizeResult.refined`` counts them).  Their colours are refined with the
+    frame's image only when the localizer is photometric (``rgb_lambda != 0``): without an image the frame's colours
+    are a constant stand-in that must not bleach the stored ones.  A lost frame refines nothing.  Refinement at an
+    estimated pose feeds a share 1 / (weight + 1) of that pose's error into the rows it moves.  Everything else
     -- normalisation, the re-rendered query depth, the scales, the hand-over, ``best_c2w`` -- is the frame mode's."""
 
     def __init__(self, K: Tensor, width: int, height: int, config: TrackerConfig = TrackerConfig(),
@@ -246,6 +257,7 @@ class Localizer:
         self._reloc = None  # the MapConfig when MapConfig.reloc is on
         self._min_tested = 0  # MapConfig.reloc_min_tested, or its default for this image size
         self._keyframes = False  # MapConfig.keyframes
+        self._refine = False  # MapConfig.refine
         self._tracked = 0  # calls of track since reset
         self.merged_at_reset = None  # merge_voxel: rows the merge after reset's insertion removed
         if self.map_mode:
@@ -256,6 +268,7 @@ class Localizer:
             self._free = map_config.free_rho is not None
             self._evict = bool(map_config.evict)
             self._merge_every = int(map_config.merge_every) if map_config.merge_voxel is not None else 0
+            self._refine = bool(map_config.refine)
             if map_config.reloc:
                 self._reloc = map_config
                 self._min_tested = (map_config.reloc_min_tested if map_config.reloc_min_tested is not None
@@ -429,6 +442,7 @@ class Localizer:
             out.removed = 0 if self._free else None
             out.evicted = 0 if self._evict else None
             out.merged = 0 if self._merge_every else None
+            out.refined = 0 if self._refine else None
             self._tracked += 1
             if not out.lost:  # a lost frame's pose is a guess: it adds nothing
                 at = best
@@ -443,6 +457,11 @@ class Localizer:
                         scales = init_gs_scales(d.tar_points)
                         at = transform_cameras(d.norm_T, est.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else est
                 render, alphas = self._map_render(d, scales, at)
+                if self._refine:
+                    # after the render, before the insertion: every live row is an old one, and the render above is of
+                    # the cloud that was tracked
+                    out.refined = self.map.refine(depth, rgb if self.photo else None, self.K, est,
+                                                  self.cfg.gs.near_plane)
                 if self._evict:
                     # stamp before the insertion: what this frame observes must not make room for its own rows
                     self.map.observe(depth, self.K, est, self.cfg.gs.near_plane, self.cfg.gs.far_plane)

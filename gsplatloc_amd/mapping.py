@@ -41,7 +41,15 @@ like -- ``add_keyframe`` keeps the pose of a frame that lies far enough from eve
 descriptor of its depth image (``describe``), in a ring of ``keyframe_max`` -- and ``match_place`` holds a frame's
 descriptor against all of them under 15 small shifts of the grid and ranks the keyframes it resembles, which is where
 ``Localizer(mode="map")`` looks for a frame that the relocalisation above has given up on.  Two more entry points;
-``match_place`` reads back once, ``add_keyframe`` never."""
+``match_place`` reads back once, ``add_keyframe`` never.
+
+Refinement (``MapConfig.refine``, csrc/map_refine.hip): a row is written from one pixel of one depth frame and keeps that
+pixel's error; with the option every row carries a weight (``weights``, 1 for a row just appended), and ``refine`` moves
+the live rows a depth frame observes again -- every one of the four pixels around their projection shows their depth
+within ``refine_rho`` -- along their own ray to the running mean of the depths observed there (the four pixels' inverse
+depths blended at the row's position), blends their colours likewise and raises their weight up to
+``refine_max_weight``.  One more entry point; one read-back.  The weights follow their rows through every removal as
+the stamps do."""
 from __future__ import annotations
 
 import functools
@@ -124,10 +132,28 @@ class MapConfig:
     keyframe_trans: float = 0.15
     place_top: int = 2  # this many best-matching keyframes become bases: place_top * (1 + 12 reloc_levels) <= 64
     place_min_common: int = 48  # a shift under which fewer cells are valid in both descriptors, a quarter of the 192, does not count
+    # Localizer(mode="map"): refinement.  Every row carries the number of depths it is the mean of (GaussianMap.weights),
+    # and between a frame's insertion render and its insertion the live rows whose four surrounding pixels all show
+    # their depth within refine_rho (None: depth_rho) move along their ray to the running mean of those depths
+    # (GaussianMap.refine); a weight stops at refine_max_weight, from where on the mean is an exponential one with
+    # gain 1 / (refine_max_weight + 1)
+    refine: bool = False
+    refine_rho: Optional[float] = None
+    refine_max_weight: int = 64
 
     def __post_init__(self):
         whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
         number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer))  # noqa: E731
+        if not isinstance(self.refine, bool):
+            raise ValueError(f"refine {self.refine!r}: True or False")
+        if self.refine_rho is not None and (not number(self.refine_rho) or not 0.0 <= self.refine_rho < 1.0):
+            raise ValueError(f"refine_rho {self.refine_rho!r}: a fraction of the observed depth, inside [0, 1) (or None: "
+                             "depth_rho)")
+        if self.refine and self.refine_rho is None and not 0.0 <= self.depth_rho < 1.0:
+            raise ValueError(f"depth_rho {self.depth_rho}: refine holds a row against the observed depth within this "
+                             "fraction, inside [0, 1) (or set refine_rho)")
+        if not whole(self.refine_max_weight) or not 1 <= self.refine_max_weight <= 2 ** 30:
+            raise ValueError(f"refine_max_weight {self.refine_max_weight!r}: a whole number of depths, 1 .. 2^30")
         if not isinstance(self.reloc, bool):
             raise ValueError(f"reloc {self.reloc!r}: True or False")
         if not isinstance(self.keyframes, bool):
@@ -262,6 +288,14 @@ class GaussianMap:
         self._kf_poses = np.zeros((int(config.keyframe_max), 4, 4), dtype=np.float32)
         self._kf_made = 0
         self._place = None
+        # refine: the number of depths each row is the mean of, 1 - refine_rho as the float32 value the kernel is
+        # given and the one counter; nothing of it without the option
+        self.weights = self._refine_keep = self._refine_counter = None
+        if config.refine:
+            rho = config.depth_rho if config.refine_rho is None else config.refine_rho
+            self._refine_keep = float(np.float32(1.0) - np.float32(rho))
+            self.weights = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
+            self._refine_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def _alloc_ws(self):
         if self.device.type != "cuda":
@@ -338,7 +372,8 @@ class GaussianMap:
         new (the first frame).  Returns (pixels selected, rows appended); they differ when the map is full.  The rows
         appended are stamped with ``frame_index``.  ``MapConfig.evict``: a frame that may not fit (n_live + W * H above
         the capacity) reads its selection's count back before the append and, when it is short of room, first evicts
-        that many rows plus ``evict_headroom`` (``evict``; ``last_evicted`` counts them)."""
+        that many rows plus ``evict_headroom`` (``evict``; ``last_evicted`` counts them).  ``MapConfig.refine``: the rows
+        appended get the weight 1."""
         if (render is None) != (alphas is None):
             raise ValueError("insert_frame: render and alphas come together (or neither, for the first frame)")
         hw = (self.H, self.W)
@@ -358,6 +393,8 @@ class GaussianMap:
             selected, appended = self._launch(depth, rgb, intr, c2w, render, alphas)
         if appended > 0:
             self.stamps[self.n_live:self.n_live + appended] = self.frame_index
+            if self.weights is not None:
+                self.weights[self.n_live:self.n_live + appended] = 1
         self.n_live += appended
         self.full = self.full or appended < selected
         return selected, appended
@@ -428,6 +465,7 @@ class GaussianMap:
                 ws = torch.empty(_lib.load_library().gsl_map_view_ws_bytes(cap), dtype=torch.uint8, device=dev)
             self._free = dict(means=torch.zeros(cap, 3, device=dev), colors=torch.zeros(cap, 3, device=dev),
                               stamps=torch.zeros(cap, dtype=torch.int32, device=dev),
+                              weights=None if self.weights is None else torch.zeros(cap, dtype=torch.int32, device=dev),
                               ids=torch.zeros(cap, dtype=torch.int32, device=dev),
                               counters=torch.zeros(3, dtype=torch.int32, device=dev), ws=ws)
         return self._free
@@ -438,12 +476,16 @@ class GaussianMap:
         their stamps, ``then()`` -- launches that work on the gathered rows -- and the read-back of the counters, the
         call's one synchronisation.  stamps_early: the stamps go before the read-back, every live row at most (the count
         is not known on the host yet, and the rows past it are never read); otherwise after it, the rows stored, and
-        only when something goes -- the buffers will be swapped, the stamps follow their rows."""
+        only when something goes -- the buffers will be swapped, the stamps follow their rows.  ``MapConfig.refine``:
+        the weights follow them in the same way, by the same gather."""
         lib, st, ptr, f = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._free_buffers()
 
         def stamps(n):
             _lib.check(lib.gsl_map_gather_i32(ptr(self.stamps), self.n_live, ptr(f["ids"]), n, ptr(f["stamps"]), st),
                        "gsl_map_gather_i32")
+            if self.weights is not None:
+                _lib.check(lib.gsl_map_gather_i32(ptr(self.weights), self.n_live, ptr(f["ids"]), n, ptr(f["weights"]),
+                                                  st), "gsl_map_gather_i32")
 
         _lib.check(lib.gsl_map_view_gather(ptr(self.means), ptr(self.colors), self.n_live, ptr(f["means"]),
                                            ptr(f["colors"]), ptr(f["ids"]), self.capacity, ptr(counters), ptr(ws),
@@ -468,6 +510,8 @@ class GaussianMap:
             self.means, f["means"] = f["means"], self.means
             self.colors, f["colors"] = f["colors"], self.colors
             self.stamps, f["stamps"] = f["stamps"], self.stamps
+            if self.weights is not None:
+                self.weights, f["weights"] = f["weights"], self.weights
             self.n_live = stay
             self._view_rows = -1  # the view ballots describe other rows
         return gone, stay
@@ -579,7 +623,8 @@ class GaussianMap:
         The rows that stay keep their order.  Returns (removed, kept).  A swap as in ``remove_seen_through``: when
         something was removed, views taken before the call are stale, ``survivors`` holds the old row of every live
         row, and the next ``view_violations`` needs a fresh ``select_view``.  When nothing was removed nothing
-        changes."""
+        changes.  ``MapConfig.refine``: a fused row keeps the weight of the row it is kept at, the first of its voxel
+        (the weights of the others are not summed: csrc/map_merge.hip knows nothing of them)."""
         if self._merge_h is None:
             raise RuntimeError("merge: MapConfig.merge_voxel is None, the map has no resolution")
         if self.n_live == 0:
@@ -624,6 +669,41 @@ class GaussianMap:
         intr, _ = _intr_and_pose(K, poses[0])
         return self._score_launch(depth, intr, _world_to_camera(torch.stack([c.detach().cpu().double() for c in poses])),
                                   float(near))
+
+    # ---- refinement: the rows a depth frame observes again move to the running mean of their depths (csrc/map_refine.hip)
+    def _refine_launch(self, depth: Tensor, rgb: Optional[Tensor], intr: Tuple[float, float, float, float], w2c: Tensor,
+                       cam: Tuple[float, float, float], near: float) -> int:
+        """The entry point (which zeroes the counter) over the live rows, in place, and the read-back of the rows
+        refined, the call's one synchronisation."""
+        assert depth.is_cuda, "GaussianMap.refine: the rows are refined by a HIP kernel, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        _lib.check(lib.gsl_map_refine(ptr(self.means), None if rgb is None else ptr(self.colors), ptr(self.weights),
+                                      self.n_live, ptr(w2c), *cam, *intr, ptr(depth), ptr(rgb), self.W, self.H,
+                                      self._refine_keep, near, int(self.cfg.refine_max_weight),
+                                      ptr(self._refine_counter), st), "gsl_map_refine")
+        return self._refine_counter.tolist()[0]
+
+    @torch.no_grad()
+    def refine(self, depth, rgb, K, c2w, near: float) -> int:
+        """Moves the live rows that the depth frame [H,W] (metres) at the pose c2w [4,4] observes again -- they project
+        into the image beyond ``near`` and each of the four pixels around their projection shows their depth within
+        ``refine_rho`` either way -- along their own ray to the running mean of the depths observed there, and raises
+        their weight by one up to ``refine_max_weight`` (the rule: include/gsloc_hip.h); every other row keeps every
+        bit.  rgb [H,W,3] in 0..255: their colours go to the running mean of the image at their projection as well;
+        None: the colours are left alone.  In place: ``points`` / ``point_colors`` stay valid and show the refined
+        rows.  Returns the rows refined.  One zeroing launch, one kernel, one read-back; an empty map gives 0 without
+        a launch."""
+        if self.weights is None:
+            raise RuntimeError("refine: MapConfig.refine is False, the map keeps no weights")
+        if self.n_live == 0:
+            return 0
+        depth = self._depth_image(depth)
+        if rgb is not None:
+            rgb = self._image(torch.as_tensor(rgb)[..., :3], (self.H, self.W, 3), "rgb")
+        intr, c2w = _intr_and_pose(K, c2w)
+        w2c = _world_to_camera(c2w).to(self.device).contiguous()
+        cam = tuple(float(t) for t in c2w.detach().cpu()[:3, 3].to(torch.float32))
+        return self._refine_launch(depth, rgb, intr, w2c, cam, float(near))
 
     # ---- place recognition: keyframes, their depth descriptors and the match of a frame against them (csrc/map_place.hip)
     def _place_buffers(self):

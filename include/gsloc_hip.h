@@ -350,6 +350,43 @@ int gsl_map_place_cells(void);
 int gsl_map_place_describe(const float* depth, int width, int height, int32_t* desc, void* stream);
 int gsl_map_place_match(const int32_t* query, const int32_t* table, int n_keyframes, int32_t* out, void* stream);
 
+/* ---- refinement: the rows a depth frame observes again move to the running mean of their depths (csrc/map_refine.hip) ----
+ * means[n_rows,3] and colors[n_rows,3] float32 and weights[n_rows] int32 on the device, as in the map: weights[i] >= 1
+ * is the number of depths row i is the mean of.  depth[height,width] float32 (the observed depth, metres) and
+ * rgb[height,width,3] float32 in 0..255, row-major, on the device; w2c[16] (world to camera, row-major, on the device;
+ * twelve entries are read); cam_x, cam_y, cam_z: the camera centre in the world.  counters is int32[1]; it need not be
+ * initialised, the entry point zeroes it on the stream.  Row i with mean p, colour c and weight w:
+ *   x = ((w0 px + w1 py) + w2 pz) + w3, and y, z likewise from rows 1 and 2 of w2c;
+ *   u = fx x / z + cx, v = fy y / z + cy;
+ *   CANDIDATE when z > near_plane and 0 <= u <= width - 1 and 0 <= v <= height - 1 (on u and v, not on rounded values);
+ *   u0 = min((int)floorf(u), width - 2), v0 = min((int)floorf(v), height - 2), a = u - (float)u0, b = v - (float)v0:
+ *             a row on the last column or line has a == 1 or b == 1 and reads pixels inside the image only;
+ *   d00, d10, d01, d11 = depth at (u0, v0), (u0 + 1, v0), (u0, v0 + 1), (u0 + 1, v0 + 1);
+ *   REFINED   when candidate and each of the four is finite and > 0 with z >= d * keep and z * keep <= d (the
+ *             predicate of gsl_map_observe, both ways).  Every other row keeps every bit of its mean, colour and weight;
+ *   BLEND     a1 = 1 - a, b1 = 1 - b, w00 = a1 * b1, w10 = a * b1, w01 = a1 * b, w11 = a * b,
+ *             blend(x00, x10, x01, x11) = ((w00 * x00 + w10 * x10) + w01 * x01) + w11 * x11;
+ *   d  = 1 / blend(1 / d00, 1 / d10, 1 / d01, 1 / d11): the inverse depth of a plane is linear in the pixel, so on a
+ *             planar patch d is the depth on the row's own ray up to rounding, wherever in the pixel it projects;
+ *   wf = (float)(w + 1) (the sum taken in 64 bits),  t = (d - z) / (z * wf);
+ *   mean      p' = p + (p - cam) * t per component (one product and one sum each): along the row's ray, to the running
+ *             mean of its depths; d == z leaves p as it is;
+ *   colour    c' = c + (blend(rgb / 255.f at the four pixels, per channel) - c) / wf, when rgb is given;
+ *   weight    w' = min(w + 1, max_weight): at the cap the mean goes on as an exponential one, gain 1 / (max_weight + 1);
+ *   counters[0] = rows refined (an integer sum: it does not depend on the order of rows, waves or workgroups).
+ * float32, evaluated exactly as written (no fused operation, correctly rounded division), comparisons false for a NaN:
+ * NaN / inf rows, rows at or behind near_plane, rows outside the image and rows with a pixel without depth among their
+ * four are left alone.  keep is 1 - rho, the float32 difference taken by the caller.  In place: a thread reads and
+ * writes its own row only.  colors and rgb come together, or both are NULL and the colours are left alone.  One zeroing
+ * launch and one kernel; the number of global atomics is bounded by the kernel's grid cap, not by n_rows.
+ * Returns GSL_ERR_BAD_ARG before any launch for a NULL means, weights, w2c, depth or counters, colors without rgb or
+ * rgb without colors, n_rows <= 0 or >= 2^31, width or height < 2 or width * height > 2^31 - 1, fx or fy not non-zero,
+ * keep outside (0, 1], a camera centre that is not finite, max_weight outside 1 .. 2^30. */
+int gsl_map_refine(float* means, float* colors, int32_t* weights, int64_t n_rows, const float* w2c, float cam_x,
+                   float cam_y, float cam_z, float fx, float fy, float cx, float cy, const float* depth,
+                   const float* rgb, int width, int height, float keep, float near_plane, int max_weight,
+                   int32_t* counters, void* stream);
+
 /* ---- spherical harmonics: gsplat.spherical_harmonics fwd/bwd (IDX:14306, IDX:14297) ----
  * dirs[M,3], coeffs[M,K,3] with K >= (degree+1)^2, masks[M] (uint8, may be NULL).
  * degree 0..3.  v_dirs may be NULL. */

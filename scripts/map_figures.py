@@ -11,10 +11,13 @@ in NOTES.md, printed only with --only evict): the sweep in a map whose capacity 
 frames, map mode without a bound beside map mode with MapConfig.evict, and the host cost of observe, of the eviction and
 of the whole insertion per frame.  The merge rows ("Map resolution" in NOTES.md, printed only with --only merge): the
 there-and-back sequence and the sweep, map mode unmerged beside map mode with MapConfig.merge_voxel, and the host cost
-of the merge per frame.
+of the merge per frame.  The refine rows ("Refinement" in NOTES.md, printed only with --only refine): the constant twist
+and the there-and-back sequence with Gaussian depth noise, map mode without beside map mode with MapConfig.refine --
+ATE / AAE and the RMS distance of the live rows to the box's planes -- and the host cost of refine per frame.
 
     python scripts/map_figures.py [--frames 20] [--size 640 480] [--no-cost]
-                                  [--only there_and_back | sweep | vanish | evict | merge]
+                                  [--only there_and_back | sweep | vanish | evict | merge | refine]
+                                  [--refine-sigma M]
                                   [--sweep DEG FRAMES GUARD_PX] [--vanish FRAMES WITH RHO WINDOW_PX]
                                   [--merge-voxel M] [--merge-every K]"""
 import argparse
@@ -33,7 +36,8 @@ from gsplatloc_amd.eval import evaluate_room, rmse  # noqa: E402
 from gsplatloc_amd.localizer import Localizer  # noqa: E402
 from gsplatloc_amd.mapping import MapConfig  # noqa: E402
 from gsplatloc_amd.my_gsplat import TrackerConfig  # noqa: E402
-from gsplatloc_amd.synthetic import (write_replica_constant_twist, write_replica_sequence,  # noqa: E402
+from gsplatloc_amd.synthetic import (_twist, _write_replica_poses, room_depth,  # noqa: E402
+                                     write_replica_constant_twist, write_replica_sequence,
                                      write_replica_there_and_back, write_replica_vanishing_panel)
 
 
@@ -255,6 +259,74 @@ def merge(W, H, n, deg, n_sweep, voxel=None, every=1, cost=True):
                                           "map_gaussians": loc.map.n_live}), flush=True)
 
 
+def refine(W, H, n, sigma, cost=True):
+    """Refinement (MapConfig.refine) on the constant twist (``n`` frames) and the there-and-back sequence (``n // 2`` steps
+    out and back), 0.4 degrees and 1 cm a frame, every depth image with its own Gaussian noise of ``sigma`` metres
+    (through the ``depth_of`` hook of the sequence writer; the files keep it in steps of 1 / 6553.5 m): map mode
+    without the option beside map mode with it, alternating in one process, the second pass of each reported -- ATE /
+    AAE, the rows refined per frame and the RMS distance of the live rows to the nearest of the box's six planes at the
+    end (of all rows, and of frame 0's); then the per-frame host cost of refine (wall time, synchronised on both sides,
+    the read-back included) in a pass of its own."""
+    import numpy as np
+
+    half = torch.tensor([2.5, 1.5, 3.0], dtype=torch.float64)  # room_depth's box
+
+    def rms_to_planes(p):
+        d = (half.to(p.device) - p.double().abs()).abs().min(dim=1).values
+        return float(d.square().mean().sqrt())
+
+    step = _twist(0.4, 0.01, (0.3, 1.0, -0.2), (0.6, 0.1, 0.8))
+    out_poses, c2w = [], np.eye(4)
+    for i in range(n):
+        if i:
+            c2w = c2w @ step
+        out_poses.append(c2w.copy())
+    back = out_poses[:n // 2 + 1]
+    sequences = (("constant_twist", out_poses), ("there_and_back", back + [p.copy() for p in back[-2::-1]]))
+    for name, poses in sequences:
+        root = pathlib.Path(tempfile.mkdtemp())
+        rng = np.random.default_rng(0)
+
+        def depth_of(i, K, pose):
+            noise = torch.from_numpy((sigma * rng.standard_normal((H, W))).astype(np.float32))
+            return room_depth(W, H, K, pose) + noise
+
+        _write_replica_poses(root, W, H, poses, depth_of)
+        parser = Parser("Replica", "room0", normalize=True, input_folder=str(root))
+
+        def run(on, sink=None):
+            depth, rgb, pose = parser.frame(0)
+            loc = Localizer(parser.K, W, H, TrackerConfig(max_steps=2000), mode="map", map_config=MapConfig(refine=on))
+            if sink is not None:
+                loc.map.refine = timed(loc.map.refine, sink)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            loc.reset(depth, rgb, pose)
+            res = []
+            for i in range(1, len(parser) + 1):
+                depth, rgb, pose = parser.frame(i)
+                res.append(loc.track(depth, rgb, gt_c2w=pose))
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            return {"refine": on, "sigma": sigma, "ATE": rmse([r.eT for r in res]), "AAE": rmse([r.eR for r in res]),
+                    "eT_per_frame": [float("%.3e" % r.eT) for r in res], "refined_per_frame": [r.refined for r in res],
+                    "added_per_frame": [r.added for r in res], "steps": [r.steps for r in res],
+                    "lost_frames": sum(r.lost for r in res), "rms_to_planes": rms_to_planes(loc.map.points),
+                    "rms_to_planes_frame0": rms_to_planes(loc.map.points[:W * H]), "map_gaussians": loc.map.n_live,
+                    "frames": len(res), "seconds": dt, "frames_per_s": len(res) / dt}
+
+        for _ in range(2):
+            rows = [run(on) for on in (False, True)]
+        for r in rows:
+            print("MAP_FIG " + json.dumps({"sequence": f"{name} sigma {sigma}", "map": True, **r}), flush=True)
+        if cost:
+            sink = []
+            r = run(True, sink)
+            print("REFINE_COST " + json.dumps({"sequence": name, "refine_ms": [round(1e3 * x, 3) for x in sink],
+                                               "refined": r["refined_per_frame"],
+                                               "map_gaussians": r["map_gaussians"]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20)
@@ -274,8 +346,13 @@ def main():
                     help="the merge row (--only merge): MapConfig.merge_voxel in metres (default: the spacing of frame "
                          "0's back-projected pixels)")
     ap.add_argument("--merge-every", type=int, default=1, metavar="K", help="the merge row: MapConfig.merge_every")
+    ap.add_argument("--refine-sigma", type=float, default=0.005, metavar="M",
+                    help="the refine rows (--only refine): sigma of the Gaussian depth noise, metres")
     a = ap.parse_args()
     (W, H), n = a.size, a.frames
+    if a.only == "refine":
+        refine(W, H, n, a.refine_sigma, cost=not a.no_cost)
+        return
     if a.only == "merge":
         merge(W, H, n, a.sweep[0], int(a.sweep[1]), voxel=a.merge_voxel, every=a.merge_every, cost=not a.no_cost)
         return
