@@ -129,15 +129,15 @@ _SIGNATURES = {
     "gsl_isect_emit": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "gsl_isect_offsets": (c_int, [P, c_int64, c_int, c_int, c_int, P, P]),
     "gsl_rasterize_fwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P,
-                                  c_int64, P, P, P, P]),
+                                  c_int64, P, P, P, P, P]),
     "gsl_vacc_bytes": (c_size_t, [c_int, c_int]),
     "gsl_rasterize_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P,
-                                  c_int64, P, P, P, P, P, P]),
+                                  c_int64, P, P, P, P, P, P, P]),
     "gsl_vacc_unpack": (c_int, [P, c_int, c_int, P, P, P, P, P]),
     "gsl_fused_absgrad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int64, P, P, P, P, P, P,
                                   P, P, P]),
     "gsl_rasterize_absgrad": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int64, P, P,
-                                      P, P, P, P]),
+                                      P, P, P, P, P]),
 }
 
 

@@ -68,14 +68,17 @@ __global__ __launch_bounds__(256) void k_absgrad(
   float vc[D];
   load_upstream<D>(v_render, pid, inside, vc);
   const BwdStart st = bwd_start<D, FUSED && ED>(alphas, render, v_alphas, pid, inside, vc);
-  float Bp = st.Bp();
+  // staged: `render` carries gsl_rasterize_fwd's t_final when the caller has it -- the pixel's last T itself, which
+  // 1 - alpha no longer holds once T is small (include/gsloc_hip.h)
+  float T = st.T_final;
+  if (!FUSED && render && inside) T = render[pid];
+  float Bp = FUSED ? st.Bp() : -T * st.va;
   if (!FUSED && backgrounds) {  // (the staged forward's background term)
     float bg_dot = 0.f;
 #pragma unroll
     for (int k = 0; k < D; ++k) bg_dot += backgrounds[k] * vc[k];
-    Bp += st.T_final * bg_dot;
+    Bp += T * bg_dot;
   }
-  float T = st.T_final;
 
   const int qfin = wave_max(bin_final);
   if (lane == 0) sb.fin[wv] = qfin;
@@ -229,7 +232,7 @@ extern "C" int gsl_rasterize_absgrad(const float* means2d, const float* conics, 
                                      const float* opacities, const float* backgrounds, int channels, int width,
                                      int height, int tile_size, int tile_w, int tile_h, const int32_t* tile_offsets,
                                      const int32_t* flatten_ids, int64_t capacity, const float* render_alphas,
-                                     const int32_t* last_ids, const float* v_render_colors,
+                                     const int32_t* last_ids, const float* t_final, const float* v_render_colors,
                                      const float* v_render_alphas, float* absgrad, void* stream) {
   if (!gsl::frame_ok(width, height, tile_w, tile_h, 0, tile_h, capacity, 0, height)) return GSL_ERR_BAD_ARG;  // (whole frame)
   if (tile_size != 16) return GSL_ERR_BAD_ARG;
@@ -245,7 +248,7 @@ extern "C" int gsl_rasterize_absgrad(const float* means2d, const float* conics, 
 #define CALL_AB(DD)                                                                                                   \
   hipLaunchKernelGGL((gsl::k_absgrad<DD, false, false>), dim3(tile_w * tile_h), dim3(256), 0, st, nullptr, nullptr,  \
                      nullptr, means2d, conics, colors, opacities, backgrounds, width, height, tile_w, tile_offsets,    \
-                     flatten_ids, (long long)capacity, nullptr, render_alphas, last_ids, v_render_colors,             \
+                     flatten_ids, (long long)capacity, t_final, render_alphas, last_ids, v_render_colors,             \
                      v_render_alphas, nullptr, nullptr, absgrad)
   switch (channels) {
     case 1: CALL_AB(1); break;

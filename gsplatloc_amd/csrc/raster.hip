@@ -45,7 +45,8 @@ __global__ __launch_bounds__(256) void k_raster_fwd(
     const float* __restrict__ means2d, const float* __restrict__ conics, const float* __restrict__ colors,
     const float* __restrict__ opacities, const float* __restrict__ backgrounds, int W, int H, int tile_w, int ty0,
     const int32_t* __restrict__ tile_offsets, const int32_t* __restrict__ flatten_ids, long long capacity,
-    float* __restrict__ render_colors, float* __restrict__ render_alphas, int32_t* __restrict__ last_ids) {
+    float* __restrict__ render_colors, float* __restrict__ render_alphas, int32_t* __restrict__ last_ids,
+    float* __restrict__ t_final) {
   __shared__ Batch<D> sb;
   int tile = ty0 * tile_w + blockIdx.x;
   int tid = threadIdx.x, lane = tid & 63;
@@ -121,6 +122,7 @@ __global__ __launch_bounds__(256) void k_raster_fwd(
   if (inside) {
     size_t pid = pixel_index(tp, W, true);
     render_alphas[pid] = 1.f - T;
+    if (t_final) t_final[pid] = T;  // what 1 - alpha no longer holds once T is small (include/gsloc_hip.h)
 #pragma unroll
     for (int k = 0; k < D; ++k)
       render_colors[pid * D + k] = backgrounds ? (pix[k] + T * backgrounds[k]) : pix[k];
@@ -145,8 +147,9 @@ struct BatchB {
   uint16_t list[4][64];
 };
 
-template <int D>
-__global__ __launch_bounds__(256) void k_raster_bwd(
+// TF: `render_alphas` is the forward's t_final (the pixel's last T itself), not its alpha image.
+template <int D, bool TF>
+__device__ __forceinline__ void raster_bwd_body(
     const float* __restrict__ means2d, const float* __restrict__ conics, const float* __restrict__ colors,
     const float* __restrict__ opacities, const float* __restrict__ backgrounds, int W, int H, int tile_w, int ty0,
     const int32_t* __restrict__ tile_offsets, const int32_t* __restrict__ flatten_ids, long long capacity,
@@ -174,7 +177,7 @@ __global__ __launch_bounds__(256) void k_raster_bwd(
   float vc[D], buf[D];
   load_upstream<D>(v_render_colors, pid, inside, vc);
   const BwdStart st = bwd_start<D, false>(render_alphas, nullptr, v_render_alphas, pid, inside, vc);
-  const float T_final = st.T_final, va = st.va;
+  const float T_final = TF ? st.Aimg : st.T_final, va = st.va;  // (TF: the value loaded is T)
   float T = T_final;
   float bg_dot = 0.f;  // the background term is this kernel's own
 #pragma unroll
@@ -323,6 +326,28 @@ __global__ __launch_bounds__(256) void k_raster_bwd(
   }
 }
 
+#define GSL_RASTER_BWD_PARAMS                                                                                       \
+  const float *__restrict__ means2d, const float *__restrict__ conics, const float *__restrict__ colors,             \
+      const float *__restrict__ opacities, const float *__restrict__ backgrounds, int W, int H, int tile_w, int ty0, \
+      const int32_t *__restrict__ tile_offsets, const int32_t *__restrict__ flatten_ids, long long capacity,         \
+      const float *__restrict__ render_alphas, const int32_t *__restrict__ last_ids,                                 \
+      const float *__restrict__ v_render_colors, const float *__restrict__ v_render_alphas, float *__restrict__ vacc
+#define GSL_RASTER_BWD_ARGS                                                                                       \
+  means2d, conics, colors, opacities, backgrounds, W, H, tile_w, ty0, tile_offsets, flatten_ids, capacity,       \
+      render_alphas, last_ids, v_render_colors, v_render_alphas, vacc
+// from the alpha image (T_final = 1 - alpha) ...
+template <int D>
+__global__ __launch_bounds__(256) void k_raster_bwd(GSL_RASTER_BWD_PARAMS) {
+  raster_bwd_body<D, false>(GSL_RASTER_BWD_ARGS);
+}
+// ... and from the forward's t_final
+template <int D>
+__global__ __launch_bounds__(256) void k_raster_bwd_tf(GSL_RASTER_BWD_PARAMS) {
+  raster_bwd_body<D, true>(GSL_RASTER_BWD_ARGS);
+}
+#undef GSL_RASTER_BWD_PARAMS
+#undef GSL_RASTER_BWD_ARGS
+
 // vacc rows -> the four gsplat-style gradient tensors.
 __global__ __launch_bounds__(256) void k_vacc_unpack(const float* __restrict__ vacc, int n, int D, int AS,
                                                      float* __restrict__ v_means2d, float* __restrict__ v_conics,
@@ -343,10 +368,11 @@ template <int D>
 static int launch_fwd(const float* means2d, const float* conics, const float* colors, const float* opacities,
                       const float* backgrounds, int W, int H, int tile_w, int ty0, int ty1,
                       const int32_t* tile_offsets, const int32_t* flatten_ids, long long capacity,
-                      float* render_colors, float* render_alphas, int32_t* last_ids, hipStream_t st) {
+                      float* render_colors, float* render_alphas, int32_t* last_ids, float* t_final, hipStream_t st) {
   int nblk = (ty1 - ty0) * tile_w;
   hipLaunchKernelGGL(k_raster_fwd<D>, dim3(nblk), dim3(256), 0, st, means2d, conics, colors, opacities, backgrounds,
-                     W, H, tile_w, ty0, tile_offsets, flatten_ids, capacity, render_colors, render_alphas, last_ids);
+                     W, H, tile_w, ty0, tile_offsets, flatten_ids, capacity, render_colors, render_alphas, last_ids,
+                     t_final);
   GSL_CHECK_LAUNCH();
   return GSL_OK;
 }
@@ -355,12 +381,17 @@ template <int D>
 static int launch_bwd(const float* means2d, const float* conics, const float* colors, const float* opacities,
                       const float* backgrounds, int W, int H, int tile_w, int ty0, int ty1,
                       const int32_t* tile_offsets, const int32_t* flatten_ids, long long capacity,
-                      const float* render_alphas, const int32_t* last_ids, const float* v_render_colors,
-                      const float* v_render_alphas, float* vacc, hipStream_t st) {
+                      const float* render_alphas, const int32_t* last_ids, const float* t_final,
+                      const float* v_render_colors, const float* v_render_alphas, float* vacc, hipStream_t st) {
   int nblk = (ty1 - ty0) * tile_w;
-  hipLaunchKernelGGL(k_raster_bwd<D>, dim3(nblk), dim3(256), 0, st, means2d, conics, colors, opacities, backgrounds,
-                     W, H, tile_w, ty0, tile_offsets, flatten_ids, capacity, render_alphas, last_ids,
-                     v_render_colors, v_render_alphas, vacc);
+  if (t_final)
+    hipLaunchKernelGGL(k_raster_bwd_tf<D>, dim3(nblk), dim3(256), 0, st, means2d, conics, colors, opacities,
+                       backgrounds, W, H, tile_w, ty0, tile_offsets, flatten_ids, capacity, t_final, last_ids,
+                       v_render_colors, v_render_alphas, vacc);
+  else
+    hipLaunchKernelGGL(k_raster_bwd<D>, dim3(nblk), dim3(256), 0, st, means2d, conics, colors, opacities,
+                       backgrounds, W, H, tile_w, ty0, tile_offsets, flatten_ids, capacity, render_alphas, last_ids,
+                       v_render_colors, v_render_alphas, vacc);
   GSL_CHECK_LAUNCH();
   return GSL_OK;
 }
@@ -384,7 +415,8 @@ extern "C" int gsl_rasterize_fwd(const float* means2d, const float* conics, cons
                                  const float* opacities, const float* backgrounds, int channels, int width,
                                  int height, int tile_size, int tile_w, int tile_h, int ty0, int ty1,
                                  const int32_t* tile_offsets, const int32_t* flatten_ids, int64_t capacity,
-                                 float* render_colors, float* render_alphas, int32_t* last_ids, void* stream) {
+                                 float* render_colors, float* render_alphas, int32_t* last_ids, float* t_final,
+                                 void* stream) {
   if (tile_size != 16) return GSL_ERR_BAD_ARG;  // the wave64 quadrant mapping is built for 16x16 tiles
   if (width <= 0 || height <= 0 || tile_w <= 0 || tile_h <= 0 || ty0 < 0 || ty1 > tile_h || ty0 > ty1 ||
       capacity < 0)
@@ -396,7 +428,8 @@ extern "C" int gsl_rasterize_fwd(const float* means2d, const float* conics, cons
   hipStream_t st = (hipStream_t)stream;
 #define CALL_FWD(DD)                                                                                             \
   gsl::launch_fwd<DD>(means2d, conics, colors, opacities, backgrounds, width, height, tile_w, ty0, ty1,         \
-                      tile_offsets, flatten_ids, (long long)capacity, render_colors, render_alphas, last_ids, st)
+                      tile_offsets, flatten_ids, (long long)capacity, render_colors, render_alphas, last_ids,   \
+                      t_final, st)
   GSL_DISPATCH_D(channels, CALL_FWD)
 #undef CALL_FWD
 }
@@ -409,7 +442,7 @@ extern "C" int gsl_rasterize_bwd(const float* means2d, const float* conics, cons
                                  const float* opacities, const float* backgrounds, int channels, int width,
                                  int height, int tile_size, int tile_w, int tile_h, int ty0, int ty1,
                                  const int32_t* tile_offsets, const int32_t* flatten_ids, int64_t capacity,
-                                 const float* render_alphas, const int32_t* last_ids,
+                                 const float* render_alphas, const int32_t* last_ids, const float* t_final,
                                  const float* v_render_colors, const float* v_render_alphas, float* vacc,
                                  void* stream) {
   if (tile_size != 16) return GSL_ERR_BAD_ARG;
@@ -423,8 +456,8 @@ extern "C" int gsl_rasterize_bwd(const float* means2d, const float* conics, cons
   hipStream_t st = (hipStream_t)stream;
 #define CALL_BWD(DD)                                                                                             \
   gsl::launch_bwd<DD>(means2d, conics, colors, opacities, backgrounds, width, height, tile_w, ty0, ty1,         \
-                      tile_offsets, flatten_ids, (long long)capacity, render_alphas, last_ids, v_render_colors,  \
-                      v_render_alphas, vacc, st)
+                      tile_offsets, flatten_ids, (long long)capacity, render_alphas, last_ids, t_final,         \
+                      v_render_colors, v_render_alphas, vacc, st)
   GSL_DISPATCH_D(channels, CALL_BWD)
 #undef CALL_BWD
 }

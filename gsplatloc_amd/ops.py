@@ -465,16 +465,19 @@ class _RasterizeToPixels(torch.autograd.Function):
         render_colors = torch.empty(C, height, width, D, dtype=torch.float32, device=dev)
         render_alphas = torch.empty(C, height, width, 1, dtype=torch.float32, device=dev)
         last_ids = torch.empty(C, height, width, dtype=torch.int32, device=dev)
+        # the transmittance every pixel ends with, for the backward: 1 - render_alphas keeps 2^-24 absolute of it, which
+        # behind many thin layers (T near the 1e-4 stop) is 3e-4 relative -- of every gradient term of the pixel
+        t_final = torch.empty(C, height, width, dtype=torch.float32, device=dev)
         st = current_stream()
         for c in range(C):
             check(lib.gsl_rasterize_fwd(
                 ptr(means2d), ptr(conics), ptr(colors), ptr(opacities),
                 ptr(backgrounds[c]) if backgrounds is not None else None, D, width, height, tile_size, tw, th, 0, th,
                 ptr(offs_ext[c * n_tiles:]), ptr(flatten_ids) if n_isects else None, n_isects, ptr(render_colors[c]),
-                ptr(render_alphas[c]), ptr(last_ids[c]), st), "gsl_rasterize_fwd")
+                ptr(render_alphas[c]), ptr(last_ids[c]), ptr(t_final[c]), st), "gsl_rasterize_fwd")
         ctx.save_for_backward(means2d, conics, colors, opacities,
                               backgrounds if backgrounds is not None else torch.empty(0, device=dev), offs_ext,
-                              flatten_ids, render_alphas, last_ids)
+                              flatten_ids, render_alphas, last_ids, t_final)
         ctx.dims = (width, height, tile_size, tw, th, C, backgrounds is not None)
         ctx.absgrad = absgrad
         return render_colors, render_alphas
@@ -483,7 +486,7 @@ class _RasterizeToPixels(torch.autograd.Function):
     def backward(ctx, v_render_colors, v_render_alphas):
         lib = load_library()
         (means2d, conics, colors, opacities, backgrounds, offs_ext, flatten_ids, render_alphas,
-         last_ids) = ctx.saved_tensors
+         last_ids, t_final) = ctx.saved_tensors
         width, height, tile_size, tw, th, C, has_bg = ctx.dims
         D = colors.shape[-1]
         n_rows = opacities.numel()
@@ -502,7 +505,7 @@ class _RasterizeToPixels(torch.autograd.Function):
                 check(lib.gsl_rasterize_bwd(
                     ptr(means2d), ptr(conics), ptr(colors), ptr(opacities), ptr(backgrounds[c]) if has_bg else None,
                     D, width, height, tile_size, tw, th, 0, th, ptr(offs_ext[c * n_tiles:]), ptr(flatten_ids),
-                    n_isects, ptr(render_alphas[c]), ptr(last_ids[c]), ptr(v_render_colors[c]),
+                    n_isects, ptr(render_alphas[c]), ptr(last_ids[c]), ptr(t_final[c]), ptr(v_render_colors[c]),
                     ptr(v_render_alphas[c]), ptr(vacc), st), "gsl_rasterize_bwd")
         check(lib.gsl_vacc_unpack(ptr(vacc), n_rows, D, ptr(v_means2d), ptr(v_conics), ptr(v_colors),
                                   ptr(v_opacities), st), "gsl_vacc_unpack")
@@ -515,11 +518,12 @@ class _RasterizeToPixels(torch.autograd.Function):
                     ptr(means2d), ptr(conics), ptr(colors), ptr(opacities), ptr(backgrounds[c]) if has_bg else None,
                     D, width, height, tile_size, tw, th, ptr(offs_ext[c * n_tiles:]),
                     ptr(flatten_ids) if n_isects else None, n_isects, ptr(render_alphas[c]), ptr(last_ids[c]),
-                    ptr(v_render_colors[c]), ptr(v_render_alphas[c]), ptr(absgrad), st), "gsl_rasterize_absgrad")
+                    ptr(t_final[c]), ptr(v_render_colors[c]), ptr(v_render_alphas[c]), ptr(absgrad), st),
+                    "gsl_rasterize_absgrad")
             means2d.absgrad = absgrad  # assigned by every backward, as gsplat does
         v_backgrounds = None
         if has_bg and ctx.needs_input_grad[4]:
-            v_backgrounds = (v_render_colors * (1.0 - render_alphas)).sum(dim=(1, 2))
+            v_backgrounds = (v_render_colors * t_final[..., None]).sum(dim=(1, 2))
         return v_means2d, v_conics, v_colors, v_opacities, v_backgrounds, None, None, None, None, None, None
 
 

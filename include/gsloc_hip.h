@@ -447,24 +447,30 @@ int gsl_isect_offsets(const int64_t* isect_ids, int64_t n_isects, int n_cameras,
  * One camera.  channels in {1,2,3,4,5,8,16,32}.  tile_offsets[n_tiles+1] (global tile ids),
  * flatten_ids index the per-Gaussian arrays directly.  Rows of tile rows [ty0,ty1) are
  * rendered into full-size images (pixels outside the strip are left untouched).
- * backgrounds[channels] may be NULL. */
+ * backgrounds[channels] may be NULL.
+ * t_final[height*width] (may be NULL): the transmittance T every pixel ends with, as the forward holds it.
+ * render_alphas is 1 - T rounded to float32, and 1 - render_alphas keeps no more than 2^-24 absolute of T: behind
+ * many thin layers (T near the 1e-4 stop) that is 3e-4 relative, and every gradient term of the pixel scales with it.
+ * A backward given t_final starts from T itself; given NULL it starts from 1 - render_alphas. */
 int gsl_rasterize_fwd(const float* means2d, const float* conics, const float* colors,
                       const float* opacities, const float* backgrounds, int channels, int width,
                       int height, int tile_size, int tile_w, int tile_h, int ty0, int ty1,
                       const int32_t* tile_offsets, const int32_t* flatten_ids, int64_t capacity,
-                      float* render_colors, float* render_alphas, int32_t* last_ids, void* stream);
+                      float* render_colors, float* render_alphas, int32_t* last_ids, float* t_final,
+                      void* stream);
 
 /* vjp.  Per-Gaussian gradients are ACCUMULATED INTO `vacc`, one padded row per Gaussian:
  * [v_means2d 2][v_conics 3][v_opacity 1][v_colors channels], row pitch 16 floats for
  * channels <= 10 and 48 floats otherwise (gsl_vacc_bytes gives the size).  The caller zeroes
  * vacc before the first camera; rows are indexed by the same ids as flatten_ids.
- * gsl_vacc_unpack splits the rows into the four gsplat gradient tensors. */
+ * gsl_vacc_unpack splits the rows into the four gsplat gradient tensors.
+ * t_final (may be NULL): what gsl_rasterize_fwd wrote for this camera, see there. */
 size_t gsl_vacc_bytes(int n_gaussians, int channels);
 int gsl_rasterize_bwd(const float* means2d, const float* conics, const float* colors,
                       const float* opacities, const float* backgrounds, int channels, int width,
                       int height, int tile_size, int tile_w, int tile_h, int ty0, int ty1,
                       const int32_t* tile_offsets, const int32_t* flatten_ids, int64_t capacity,
-                      const float* render_alphas, const int32_t* last_ids,
+                      const float* render_alphas, const int32_t* last_ids, const float* t_final,
                       const float* v_render_colors, const float* v_render_alphas, float* vacc,
                       void* stream);
 int gsl_vacc_unpack(const float* vacc, int n_gaussians, int channels, float* v_means2d,
@@ -808,7 +814,7 @@ int gsl_knn_query(const float* points, int N, const float* bbox, const int32_t* 
  *   float32 records), channels 1 / 3 / 4, ed as there; render is read for ed only.  isect_hits / isect_hit_counts
  *   (may be NULL together): the forward's hit lists -- each quadrant then walks only the entries it composited.
  * gsl_rasterize_absgrad: the arrays of gsl_rasterize_fwd / _bwd for one camera (same channel counts, backgrounds may
- *   be NULL); call once per camera with its tile_offsets, as gsl_rasterize_bwd. */
+ *   be NULL); call once per camera with its tile_offsets, as gsl_rasterize_bwd; t_final (may be NULL) as there. */
 int gsl_fused_absgrad(const float* Q0, const float* Q1, const float* Q2, int channels, int ed, int width, int height,
                       int tile_w, int tile_h, const int32_t* tile_offsets, const int32_t* flatten_ids, int64_t capacity,
                       const float* render, const float* alphas, const int32_t* last_ids, const float* v_render,
@@ -817,8 +823,8 @@ int gsl_fused_absgrad(const float* Q0, const float* Q1, const float* Q2, int cha
 int gsl_rasterize_absgrad(const float* means2d, const float* conics, const float* colors, const float* opacities,
                           const float* backgrounds, int channels, int width, int height, int tile_size, int tile_w,
                           int tile_h, const int32_t* tile_offsets, const int32_t* flatten_ids, int64_t capacity,
-                          const float* render_alphas, const int32_t* last_ids, const float* v_render_colors,
-                          const float* v_render_alphas, float* absgrad, void* stream);
+                          const float* render_alphas, const int32_t* last_ids, const float* t_final,
+                          const float* v_render_colors, const float* v_render_alphas, float* absgrad, void* stream);
 
 #ifdef __cplusplus
 }

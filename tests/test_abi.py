@@ -96,7 +96,7 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert lib.gsl_project_fwd(None, None, None, None, None, 5, 0, 48, 0.3, 0.01, 1e10, 0.0, None, None, None, None,
                                None, None) == -1
     assert lib.gsl_rasterize_fwd(None, None, None, None, None, 7, 64, 48, 16, 4, 3, 0, 3, None, None, 0, None, None,
-                                 None, None) == -1
+                                 None, None, None) == -1
     assert lib.gsl_isect_count(None, None, 0, 16, 4, 3, 0, 4, None, None, None, None, 0, None) == -1  # ty1 > tile_h
     assert lib.gsl_sh_fwd(4, None, None, None, 1, 25, None, None) == -1
     # more Gaussians than the packed gradient rows can address with 32-bit byte offsets (include/gsloc_hip.h, "Limits"):

@@ -46,8 +46,9 @@ def test_bad_arguments_are_rejected_without_a_gpu():
 
     def staged(channels=3, tile_size=16, means=p, absgrad=p, cap=10, bg=None):
         # means2d, conics, colors, opacities, backgrounds, channels, width, height, tile_size, tile_w, tile_h,
-        # tile_offsets, flatten_ids, capacity, render_alphas, last_ids, v_render_colors, v_render_alphas, absgrad, stream
-        return lib.gsl_rasterize_absgrad(means, p, p, p, bg, channels, W, H, tile_size, tw, th, p, p, cap, p, p, p, p,
+        # tile_offsets, flatten_ids, capacity, render_alphas, last_ids, t_final, v_render_colors, v_render_alphas, absgrad,
+        # stream
+        return lib.gsl_rasterize_absgrad(means, p, p, p, bg, channels, W, H, tile_size, tw, th, p, p, cap, p, p, None, p, p,
                                          absgrad, None)
 
     assert staged(tile_size=8) == -1

@@ -16,11 +16,15 @@ N = 300
 _X = {"RGB": 3, "D": 1, "ED": 1, "RGB+D": 4, "RGB+ED": 4}
 
 
-def _scene(C=1, deg=None, seed=42):
+def _scene(C=1, deg=None, seed=42, features=None):
+    """``features``: that many feature channels per Gaussian in place of RGB (with deg=None)."""
     sc = random_scene(N, W, H, seed=seed, sigma_px=1.5, dtype=torch.float64, aniso=True, opacity=(0.3, 1.0))
     sc["means"][:4, 2] = -1.0  # behind the camera: radii 0
     g = torch.Generator().manual_seed(seed + 1)
-    if deg is None:
+    if features is not None:
+        assert deg is None
+        sc["colors"] = torch.rand(N, features, generator=g, dtype=torch.float64)
+    elif deg is None:
         sc["colors"] = sc["rgbs"]
     else:
         sc["colors"] = 0.5 * torch.randn(N, (deg + 1) ** 2, 3, generator=g, dtype=torch.float64)
@@ -29,9 +33,10 @@ def _scene(C=1, deg=None, seed=42):
     return sc
 
 
-def _upstream(C, mode, seed=3):
+def _upstream(C, mode, seed=3, channels=None):
+    """``channels``: of the render, where the colours are feature vectors (default: the mode's with RGB)."""
     g = torch.Generator().manual_seed(seed)
-    return (torch.randn(C, H, W, _X[mode], generator=g, dtype=torch.float64),
+    return (torch.randn(C, H, W, _X[mode] if channels is None else channels, generator=g, dtype=torch.float64),
             torch.randn(C, H, W, 1, generator=g, dtype=torch.float64))
 
 
@@ -130,6 +135,28 @@ def test_absgrad_and_grad_match_the_float64_oracle(path, mode, deg, aa, C, with_
     assert m2.shape == (C, N, 2) and m2.absgrad.shape == (C, N, 2) and m2.absgrad.dtype == torch.float32
     _agree(m2.absgrad, ref_abs, f"{path} {mode} absgrad")
     _agree(m2.grad, ref_grad, f"{path} {mode} grad")
+    assert float(m2.absgrad[(radii == 0).cuda()].abs().max()) == 0.0
+
+
+# the staged walk at the widths only feature vectors reach: k_absgrad<8>, <16>, <32> (features + the depth channel)
+WIDE_CASES = [(7, 1, True), (15, 2, False), (31, 1, False)]  # (features, cameras, background)
+
+
+@pytest.mark.parametrize("features,C,with_bg", WIDE_CASES)
+def test_staged_absgrad_at_the_wide_widths(features, C, with_bg, monkeypatch):
+    monkeypatch.setenv("GSLOC_DROPIN_CACHE", "0")
+    monkeypatch.setenv("GSLOC_DISABLE_FUSED", "1")
+    mode = "RGB+D"
+    sc = _scene(C, None, features=features)
+    v, va = _upstream(C, mode, channels=features + 1)
+    bg = torch.rand(C, features, generator=torch.Generator().manual_seed(9), dtype=torch.float64) if with_bg else None
+    ref_grad, ref_abs, radii = _oracle(sc, mode, None, False, bg, v, va)
+    r, a, info, _ = _ours(sc, mode, None, False, bg, v, va)
+    assert r.shape == (C, H, W, features + 1) and "Q0" not in info
+    m2 = info["means2d"]
+    assert m2.shape == (C, N, 2) and m2.absgrad.shape == (C, N, 2) and m2.absgrad.dtype == torch.float32
+    _agree(m2.absgrad, ref_abs, f"staged {features + 1} channels absgrad")
+    _agree(m2.grad, ref_grad, f"staged {features + 1} channels grad")
     assert float(m2.absgrad[(radii == 0).cuda()].abs().max()) == 0.0
 
 
