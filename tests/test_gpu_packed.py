@@ -61,7 +61,9 @@ def _case(name, C):
         Vs = _poses(C, rot=0.5, trans=0.01) if name == "one_gaussian" else _poses(C)
         aa = name == "antialiased"
     out = {k: sc[k].to(DEV) for k in ("means", "quats", "scales", "opacities", "rgbs")}
-    out.update(Vs=Vs.to(DEV), Ks=sc["K"][None].expand(C, 3, 3).contiguous().to(DEV), W=W, H=H, kw=kw, aa=aa)
+    # Ks is a stride-0 view on the device (expanded after the copy: copying an expanded tensor makes it dense): the staged
+    # wrappers accept it, see test_stride_0_Ks_gives_the_contiguous_result
+    out.update(Vs=Vs.to(DEV), Ks=sc["K"].to(DEV)[None].expand(C, 3, 3), W=W, H=H, kw=kw, aa=aa)
     return out
 
 
@@ -101,6 +103,22 @@ def test_packed_projection_is_the_dense_projection_packed(name, C):
         assert got[k].shape == want[k].shape, k
         same = got[k] == want[k]
         assert bool(same.all()), (k, int((~same).sum()), float((got[k] - want[k]).abs().max()))
+
+
+@pytest.mark.parametrize("packed", [False, True])
+def test_stride_0_Ks_gives_the_contiguous_result(packed, monkeypatch):
+    """_case() hands every test of this file one K expanded to [C,3,3] with stride 0; the projection wrappers make it
+    contiguous themselves.  Same bits as with a contiguous copy, from the operator and from rasterization()."""
+    A = _gpu()
+    sc = _case("antialiased", 3)
+    assert sc["Ks"].stride(0) == 0 and not sc["Ks"].is_contiguous()
+    dense = dict(sc, Ks=sc["Ks"].contiguous())
+    for a, b in zip(_project(A, sc, packed=packed), _project(A, dense, packed=packed)):
+        assert torch.equal(a, b)
+    via = "sparse" if packed else "dense"
+    r0, a0, _, _ = _render(A, sc, "RGB+ED", monkeypatch, via, sh=1)
+    r1, a1, _, _ = _render(A, dense, "RGB+ED", monkeypatch, via, sh=1)
+    assert torch.equal(r0, r1) and torch.equal(a0, a1)
 
 
 def test_packed_projection_across_many_workgroups():

@@ -711,18 +711,22 @@ def test_tiny_backward_reports_a_splat_that_outgrew_its_slab(monkeypatch):
     assert rel_inf(got, want) < 1e-5
 
 
-def test_legacy_pair_on_the_gpu():
+@pytest.mark.parametrize("camera", ["control", "wide_y"])
+def test_legacy_pair_on_the_gpu(camera):
     """project_gaussians / rasterize_gaussians (north_star's legacy operator pair, IDX:14774 / 14765) over the HIP
     stage operators against the ORACLE (oracle.gsplat_oracle.rasterization, float64 autograd) on the same inputs --
     not against another HIP path: images to the image tolerance, gradients to the view matrix
     and to the means flip-aware (tests/parity.py).  The glue itself is also covered on the CPU by
-    tests/test_legacy_cpu.py."""
+    tests/test_legacy_cpu.py.  project_gaussians takes fx, fy, cx, cy by position: at wide_y (tests/cameras.py) all four
+    differ, so their order is checked."""
     import gsplat
     from oracle import gsplat_oracle as G
-    from tests.scenes import random_scene, small_pose
+    from tests.cameras import camera_scene, skewed_K
+    from tests.scenes import small_pose
 
     N, W, H = 4000, 200, 150
-    sc = random_scene(N, W, H, seed=5, sigma_px=2.0, aniso=True, opacity=(0.3, 1.0), dtype=torch.float32)
+    sc = camera_scene(N, W, H, skewed_K(W, H, camera), seed=5, sigma_px=2.0, aniso=True, opacity=(0.3, 1.0),
+                      dtype=torch.float32)  # ("control": random_scene's camera and draws)
     Vc = torch.linalg.inv(small_pose(1.0, 0.03, dtype=torch.float32))
     V = Vc.cuda()
     cu = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in sc.items()}
@@ -747,7 +751,7 @@ def test_legacy_pair_on_the_gpu():
     (img * w.float().cuda()).sum().backward()
     (ro[0] * w).sum().backward()
     ev, em = rel_inf(V1.grad[:3], V2.grad[:3]), rel_inf(m1.grad, m2.grad)
-    report("legacy pair vs float64 oracle", flipped, v_viewmat=ev, v_means=em)
+    report("legacy pair vs float64 oracle" + ("" if camera == "control" else " at " + camera), flipped, v_viewmat=ev, v_means=em)
     assert flipped < 1e-3
     assert ev < POSE_GRAD_TOL, ev
     assert em < 1e-3, em  # per-Gaussian gradients: largest entry of a single splat, float32 against float64

@@ -120,18 +120,21 @@ def test_fused_loss_kernel_matches_autograd_loss():
         assert float(v[..., :3].abs().max()) == 0.0
 
 
-def test_fused_normal_loss_kernel_matches_autograd_loss():
+@pytest.mark.parametrize("camera", ["replica", "wide_x"])
+def test_fused_normal_loss_kernel_matches_autograd_loss(camera):
     """gsl_normal_loss (the normal-consistency term the reference keeps switched off: row-wise cosine of the normal
     maps of the masked depth images) on top of gsl_tracking_loss vs autograd of the float64 oracle loss, whole image
     and a strip with its one-row halo.  Tolerance: 2e-4 of the largest gradient entry (float32 cross products of
-    central differences against float64)."""
+    central differences against float64).  Replica's intrinsics have a half-integer cx; wide_x (tests/cameras.py) puts
+    (j - cx) / fx and (i - cy) / fy at a fractional, off-centre principal point."""
     import oracle.tracker_oracle as TO
     from gsplatloc_amd._lib import check, load_library, ptr
     from gsplatloc_amd.parallel import strip_tracking_loss
     from gsplatloc_amd.synthetic import replica_intrinsics
+    from tests.cameras import skewed_K
     lib = load_library()
     W, H, D = 75, 52, 4
-    K = replica_intrinsics(W, H, dtype=torch.float64)
+    K = replica_intrinsics(W, H, dtype=torch.float64) if camera == "replica" else skewed_K(W, H, "wide_x")
     g = torch.Generator().manual_seed(5)
     gt = torch.rand(H, W, generator=g, dtype=torch.float64) * 3 + 0.5
     render = torch.rand(H, W, D, generator=g, dtype=torch.float64)
@@ -169,7 +172,7 @@ def test_fused_normal_loss_kernel_matches_autograd_loss():
         assert abs(float(value) - float(total)) < 2e-5 * abs(float(total)), (float(value), float(total))
         ref = r.grad[..., 3]
         err = float((v[..., 3].double().cpu() - ref).abs().max()) / float(ref.abs().max())
-        print(f"[parity] normal-consistency term rows={rows}: value rel {abs(float(value) - float(total)) / abs(float(total)):.1e}, "
+        print(f"[parity] normal-consistency term {camera} rows={rows}: value rel {abs(float(value) - float(total)) / abs(float(total)):.1e}, "
               f"v_depth rel-inf {err:.1e}")
         assert err < 2e-4, err
         assert float(v[..., :3].abs().max()) == 0.0
