@@ -60,6 +60,10 @@ _SIGNATURES = {
     "gsl_map_score_max_poses": (c_int, []),
     "gsl_map_score": (c_int, [P, c_int64, P, c_int, c_float, c_float, c_float, c_float, P, c_int, c_int, c_float, c_float,
                               c_float, P, P]),
+    "gsl_map_info_values": (c_int, []),
+    "gsl_map_info_max_rows": (c_int64, [c_float, c_float, c_float, c_float, c_int, c_int, c_float]),
+    "gsl_map_pose_info": (c_int, [P, c_int64, P, c_float, c_float, c_float, c_float, P, c_int, c_int, c_float, c_float,
+                                  c_float, c_float, P, P]),
     "gsl_map_place_cells": (c_int, []),
     "gsl_map_place_describe": (c_int, [P, c_int, c_int, P, P]),
     "gsl_map_place_match": (c_int, [P, P, c_int, P, P]),

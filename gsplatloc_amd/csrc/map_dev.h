@@ -1,7 +1,8 @@
 // Frame-to-map localisation, the row rule, the one copy: where a row of the map lies in a frame.  Used by the view
 // selection (map_view.hip), free space (map_free.hip), the observation stamps (map_evict.hip), the pose scores
-// (map_score.hip) and the refinement (map_refine.hip, which takes z, u, v and leaves the rounded uf, vf alone); what each
-// of them does with the projected row -- its depth predicates, its counts -- is in its file.
+// (map_score.hip), the refinement (map_refine.hip, which takes z, u, v and leaves the rounded uf, vf alone) and the pose
+// information (map_info.hip, which takes the camera x and y as well); what each of them does with the projected row --
+// its depth predicates, its counts -- is in its file.
 //
 // Row i of means[n,3], with w the rows of w2c (world to camera, row-major):
 //   x = ((w0 px + w1 py) + w2 pz) + w3, y and z likewise;  u = fx x / z + cx, v = fy y / z + cy;
@@ -47,15 +48,24 @@ __device__ static inline float3 map_load_row(const float* __restrict__ means, lo
   return {means[3 * (size_t)g], means[3 * (size_t)g + 1], means[3 * (size_t)g + 2]};
 }
 
-// w: the twelve leading entries of a row-major world-to-camera matrix.
-__device__ static inline MapPixel map_project(const float* __restrict__ w, float3 r, float fx, float fy, float cx,
-                                              float cy) {
+// w: the twelve leading entries of a row-major world-to-camera matrix.  cam_x, cam_y: the row's camera x and y, which
+// the pixel is made from (its camera z is MapPixel::z) -- for the caller that needs the point itself (map_info.hip).
+__device__ static inline MapPixel map_project_point(const float* __restrict__ w, float3 r, float fx, float fy, float cx,
+                                                    float cy, float& cam_x, float& cam_y) {
 #pragma clang fp contract(off)
   const float x = ((w[0] * r.x + w[1] * r.y) + w[2] * r.z) + w[3];
   const float y = ((w[4] * r.x + w[5] * r.y) + w[6] * r.z) + w[7];
   const float z = ((w[8] * r.x + w[9] * r.y) + w[10] * r.z) + w[11];
   const float u = fx * x / z + cx, v = fy * y / z + cy;
+  cam_x = x;
+  cam_y = y;
   return {z, u, v, rintf(u), rintf(v)};
+}
+
+__device__ static inline MapPixel map_project(const float* __restrict__ w, float3 r, float fx, float fy, float cx,
+                                              float cy) {
+  float x, y;
+  return map_project_point(w, r, fx, fy, cx, cy, x, y);
 }
 
 // (p by value: behind a reference the chain's short circuits guard loads, and k_map_view_select keeps a branch for them)

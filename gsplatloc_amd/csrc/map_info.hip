@@ -1,0 +1,203 @@
+// Frame-to-map localisation: how well a depth frame constrains a pose (gsplatloc_amd/mapping.py: pose_information).
+// The rows of the map are world points and the frame is a depth image: a row that agrees with the surface its own pixel
+// observes gives one point-to-plane equation in the six parameters of a small move of the camera, and the sum of those
+// equations over all live rows -- the 6 x 6 information matrix H, the gradient g and the residual sum -- says which
+// moves the frame pins down and which it leaves open.  No render, and nothing is written but the 30 sums.
+//
+// A left perturbation w2c' = exp(xi^) w2c, xi = (omega [rad], upsilon [m]) in the camera's frame, moves a row's camera
+// point p to p + omega x p + upsilon.  Against the plane through q0 with unit normal n the residual is r = n . (p - q0)
+// and its derivative J = (p x n, n): H = sum J J^T, g = sum J r, delta = -H^-1 g is the Gauss-Newton step.
+//
+// Row i of means[n,3], projected through w2c to its camera point p = (x, y, z) and to uf, vf (map_dev.h: the one copy
+// of the projection), in float32 with one rounding per operation in the order written here:
+//   tested = z > near and 1 <= uf <= width - 2 and 1 <= vf <= height - 2 (an inner pixel: the four neighbours exist)
+//            and d0 > 0 and d0 < inf, d0 = depth[vf, uf];
+//   lo = d0 * keep, hi = d0 * beyond;
+//   used   = tested and z >= lo and z <= hi (map_score's "agree") and z < 64 (INFO_MAX_DEPTH: the bound below)
+//            and each of dl, dr, du, dd = depth[vf, uf - 1], [vf, uf + 1], [vf - 1, uf], [vf + 1, uf] has
+//              d > 0 and d < inf and d >= lo and d <= hi
+//            and planar: i0 = 1 / d0, s0 = i0 + i0, tol = kappa * i0,
+//              |(1 / dl + 1 / dr) - s0| <= tol and |(1 / du + 1 / dd) - s0| <= tol
+//              (the inverse depth of a plane is linear in the pixel: exact on a plane, violated at a crease)
+//            and len > 0 (below);
+//   q(u, v, d) = (((float)u - cx) / fx * d, ((float)v - cy) / fy * d, d) -- k_map_append's back-projection;
+//   a = q(uf + 1, vf, dr) - q(uf - 1, vf, dl),  b = q(uf, vf + 1, dd) - q(uf, vf - 1, du),
+//   c = a x b = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x),
+//   len = sqrtf((c.x c.x + c.y c.y) + c.z c.z),  n = c / len (three divisions; its sign cancels in every sum);
+//   e = p - q(uf, vf, d0),  r = (n.x e.x + n.y e.y) + n.z e.z,
+//   m = p x n = (y n.z - z n.y, z n.x - x n.z, x n.y - y n.x),  J = (m.x, m.y, m.z, n.x, n.y, n.z).
+// Comparisons that are false for a NaN; correctly rounded division and sqrtf; no contraction.
+//
+// The sums are fixed point: fix(s, t) = llrintf((s * t) * 2^20) -- one float32 product, an exact scaling, round half to
+// even -- added as int64.  out[30] int64: the 21 fix(J_a, J_b), a <= b, the upper triangle row-major; the 6
+// fix(J_a, r); fix(r, r); rows used; rows tested.  Integer sums do not depend on the order of rows, waves or
+// workgroups, and the numpy mirror of the tests (tests/map_info_ref.py) gives the same 30 integers.
+//
+// No sum can overflow.  With tx = max(|0.5 - cx|, |width - 1.5 - cx|) / |fx| and ty likewise -- the tangents of the
+// half-angles of the inner pixels, which hold u and v within half a pixel of uf and vf -- and S = sqrt(1 + tx^2 + ty^2):
+// a used row has z < 64, so |p| <= 64 S; its pixel's point has d0 <= z / keep, so |q0| <= 64 S / keep; |n| = 1.  Hence
+// |n_a| <= 1, |m_a| <= |p| <= 64 S and |r| <= |p - q0| <= 64 S (1 + 1 / keep) =: B, every product is at most B^2 and
+// every term at most B^2 2^20 + 1 in size.  n rows stay inside int64 while n (1.01^2 B^2 2^20 + 1) < 2^63 (the 1 % on B
+// pays for the float32 roundings of u, n and e): that n, and 2^31 - 1 at the most, is gsl_map_info_max_rows, and the
+// entry point refuses more rows.  (Replica intrinsics at 160 x 120, keep = 0.95: about 1.9e8 rows.)
+//
+// One thread per row over a grid-stride loop, at most INFO_MAX_BLOCKS workgroups.  A thread loads its row once (12 B),
+// the lanes that pass the float tests gather five depths.  A lane keeps the 28 sums in 56 registers over all its trips;
+// the two counts are ballots and population counts in scalar registers.  After the rows each wave adds its lanes' sums
+// (six xor-shuffle steps per value), lane 0 adds them to a table of 30 in LDS (ds_add_u64; 240 B), and the workgroup
+// adds its non-zero entries to out with one 64-bit integer atomic each: at most INFO_MAX_BLOCKS x 30 global atomics
+// whatever n_rows is.  No float atomics.  out is zeroed by a launch of zero_u32 in front (never a memset node).
+#include "gsloc_internal.h"
+#include "map_dev.h"
+
+namespace gsl {
+
+constexpr int INFO_THREADS = 256;
+constexpr int INFO_MAX_BLOCKS = 1024;  // four workgroups of 256 threads for each of the 256 CUs
+constexpr int INFO_SUMS = 28;          // 21 + 6 + 1 fixed-point sums; then the two counts
+constexpr float INFO_MAX_DEPTH = 64.f;
+constexpr float INFO_ONE = 1048576.f;  // 2^20
+static_assert(INFO_SUMS + 2 == GSL_MAP_INFO_VALUES, "out is the sums and the two counts");
+static_assert(GSL_MAP_INFO_VALUES <= INFO_THREADS, "one thread per entry of the table flushes it");
+
+// Where fix(J_a, J_b), a <= b <= 6 with J_6 = r, goes in out.
+__host__ __device__ constexpr int info_slot(int a, int b) {
+  return b < 6 ? a * 6 - a * (a - 1) / 2 + (b - a) : a < 6 ? 21 + a : 27;
+}
+static_assert(info_slot(0, 0) == 0 && info_slot(0, 5) == 5 && info_slot(1, 1) == 6 && info_slot(5, 5) == 20 &&
+                  info_slot(0, 6) == 21 && info_slot(5, 6) == 26 && info_slot(6, 6) == 27,
+              "the upper triangle row-major, then g, then the residual sum");
+
+__device__ static inline long long info_fix(float s, float t) {
+#pragma clang fp contract(off)
+  return llrintf((s * t) * INFO_ONE);
+}
+
+__device__ static inline bool info_neighbour_ok(float d, float lo, float hi) {
+  return d > 0.f && d < INFINITY && d >= lo && d <= hi;
+}
+
+__global__ __launch_bounds__(INFO_THREADS) void k_map_pose_info(
+    const float* __restrict__ means, long long n_rows, const float* __restrict__ w2c, float fx, float fy, float cx,
+    float cy, const float* __restrict__ depth, int width, float u_inner, float v_inner, float keep, float beyond,
+    float kappa, float near_plane, unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long table[GSL_MAP_INFO_VALUES];
+  if ((int)threadIdx.x < GSL_MAP_INFO_VALUES) table[threadIdx.x] = 0ull;
+  __syncthreads();
+  long long acc[INFO_SUMS];
+#pragma unroll
+  for (int i = 0; i < INFO_SUMS; ++i) acc[i] = 0;
+  uint32_t n_used = 0u, n_tested = 0u;  // the wave's: wave-uniform
+  const long long stride = (long long)gridDim.x * INFO_THREADS;
+  // the trip count is the workgroup's: every lane of a wave reaches every ballot
+  for (long long base = (long long)blockIdx.x * INFO_THREADS; base < n_rows; base += stride) {
+#pragma clang fp contract(off)
+    const long long g = base + threadIdx.x;
+    const bool live = g < n_rows;
+    float3 row = {0.f, 0.f, 0.f};
+    if (live) row = map_load_row(means, g);
+    float x, y;
+    const MapPixel p = map_project_point(w2c, row, fx, fy, cx, cy, x, y);
+    bool tested = live && p.z > near_plane && p.uf >= 1.f && p.uf <= u_inner && p.vf >= 1.f && p.vf <= v_inner;
+    bool used = false;
+    float J[7];
+    if (tested) {  // the five indices are inside
+      const size_t at = (size_t)(int)p.vf * (size_t)width + (size_t)(int)p.uf;
+      const float d0 = depth[at];
+      tested = d0 > 0.f && d0 < INFINITY;
+      const float lo = d0 * keep, hi = d0 * beyond;
+      if (tested && p.z >= lo && p.z <= hi && p.z < INFO_MAX_DEPTH) {
+        const float dl = depth[at - 1], dr = depth[at + 1], du = depth[at - (size_t)width], dd = depth[at + (size_t)width];
+        if (info_neighbour_ok(dl, lo, hi) && info_neighbour_ok(dr, lo, hi) && info_neighbour_ok(du, lo, hi) &&
+            info_neighbour_ok(dd, lo, hi)) {
+          const float i0 = 1.f / d0, s0 = i0 + i0, tol = kappa * i0;
+          const float su = 1.f / dl + 1.f / dr, sv = 1.f / du + 1.f / dd;
+          if (fabsf(su - s0) <= tol && fabsf(sv - s0) <= tol) {
+            // q(u, v, d): the back-projection of k_map_append
+            const float kx0 = (p.uf - cx) / fx, ky0 = (p.vf - cy) / fy;
+            const float kxl = ((p.uf - 1.f) - cx) / fx, kxr = ((p.uf + 1.f) - cx) / fx;
+            const float kyu = ((p.vf - 1.f) - cy) / fy, kyd = ((p.vf + 1.f) - cy) / fy;
+            const float ax = kxr * dr - kxl * dl, ay = ky0 * dr - ky0 * dl, az = dr - dl;
+            const float bx = kx0 * dd - kx0 * du, by = kyd * dd - kyu * du, bz = dd - du;
+            const float c0 = ay * bz - az * by, c1 = az * bx - ax * bz, c2 = ax * by - ay * bx;
+            const float len = sqrtf((c0 * c0 + c1 * c1) + c2 * c2);
+            if (len > 0.f) {
+              const float n0 = c0 / len, n1 = c1 / len, n2 = c2 / len;
+              const float e0 = x - kx0 * d0, e1 = y - ky0 * d0, e2 = p.z - d0;
+              J[0] = y * n2 - p.z * n1;
+              J[1] = p.z * n0 - x * n2;
+              J[2] = x * n1 - y * n0;
+              J[3] = n0;
+              J[4] = n1;
+              J[5] = n2;
+              J[6] = (n0 * e0 + n1 * e1) + n2 * e2;
+              used = true;
+            }
+          }
+        }
+      }
+    }
+    if (used) {
+#pragma unroll
+      for (int a = 0; a < 7; ++a)
+#pragma unroll
+        for (int b = a; b < 7; ++b) acc[info_slot(a, b)] += info_fix(J[a], J[b]);
+    }
+    n_tested += (uint32_t)__popcll(__ballot(tested));
+    n_used += (uint32_t)__popcll(__ballot(used));
+  }
+  // per wave, then LDS
+  const bool first_lane = (threadIdx.x & 63) == 0;
+#pragma unroll
+  for (int i = 0; i < INFO_SUMS; ++i) {
+    long long v = acc[i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    if (first_lane && v != 0) atomicAdd(&table[i], (unsigned long long)v);
+  }
+  if (first_lane && n_tested != 0u) {
+    atomicAdd(&table[INFO_SUMS + 1], (unsigned long long)n_tested);
+    if (n_used != 0u) atomicAdd(&table[INFO_SUMS], (unsigned long long)n_used);
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < GSL_MAP_INFO_VALUES) {
+    const unsigned long long c = table[threadIdx.x];
+    if (c != 0ull) atomicAdd(&out[threadIdx.x], c);
+  }
+}
+
+}  // namespace gsl
+
+extern "C" int gsl_map_info_values(void) { return GSL_MAP_INFO_VALUES; }
+
+extern "C" int64_t gsl_map_info_max_rows(float fx, float fy, float cx, float cy, int width, int height, float keep) {
+  if (!gsl::map_image_ok(width, height) || !gsl::map_focal_ok(fx, fy) || !(keep > 0.f && keep <= 1.f)) return 0;
+  const double ax = fabs(0.5 - (double)cx), bx = fabs((double)width - 1.5 - (double)cx);
+  const double ay = fabs(0.5 - (double)cy), by = fabs((double)height - 1.5 - (double)cy);
+  const double tx = (ax > bx ? ax : bx) / fabs((double)fx), ty = (ay > by ? ay : by) / fabs((double)fy);
+  const double B = 1.01 * (double)gsl::INFO_MAX_DEPTH * sqrt(1.0 + tx * tx + ty * ty) * (1.0 + 1.0 / (double)keep);
+  const double rows = 9223372036854775807.0 / (B * B * (double)gsl::INFO_ONE + 1.0);
+  if (!(rows >= 1.0)) return 0;  // also a NaN: cx, cy not finite
+  return rows < 2147483647.0 ? (int64_t)rows : (int64_t)0x7fffffffll;
+}
+
+extern "C" int gsl_map_pose_info(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx,
+                                 float cy, const float* depth, int width, int height, float keep, float beyond,
+                                 float kappa, float near_plane, int64_t* out, void* stream) {
+  if (!means || !w2c || !depth || !out) return GSL_ERR_BAD_ARG;
+  if (!gsl::map_rows_ok(n_rows)) return GSL_ERR_BAD_ARG;
+  if (!gsl::map_image_ok(width, height) || !gsl::map_focal_ok(fx, fy)) return GSL_ERR_BAD_ARG;
+  if (!(keep > 0.f && keep <= 1.f) || !(beyond >= 1.f && beyond < INFINITY)) return GSL_ERR_BAD_ARG;
+  if (!(kappa >= 0.f && kappa < INFINITY)) return GSL_ERR_BAD_ARG;
+  if (n_rows > gsl_map_info_max_rows(fx, fy, cx, cy, width, height, keep)) return GSL_ERR_BAD_ARG;  // a sum could overflow
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = gsl::zero_u32(out, (size_t)2 * GSL_MAP_INFO_VALUES, st);
+  if (rc != GSL_OK) return rc;
+  const long long blocks = (n_rows + gsl::INFO_THREADS - 1) / gsl::INFO_THREADS;
+  const int nb = (int)(blocks < gsl::INFO_MAX_BLOCKS ? blocks : gsl::INFO_MAX_BLOCKS);
+  hipLaunchKernelGGL(gsl::k_map_pose_info, dim3(nb), dim3(gsl::INFO_THREADS), 0, st, means, (long long)n_rows, w2c, fx,
+                     fy, cx, cy, depth, width, (float)(width - 2), (float)(height - 2), keep, beyond, kappa, near_plane,
+                     (unsigned long long*)out);
+  GSL_CHECK_LAUNCH();
+  return GSL_OK;
+}

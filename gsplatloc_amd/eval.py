@@ -41,7 +41,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   map_reloc_min_agree: Optional[float] = None, map_reloc_rot_deg: Optional[float] = None,
                   map_reloc_trans: Optional[float] = None, map_keyframes: bool = False,
                   map_keyframe_rot_deg: Optional[float] = None, map_keyframe_trans: Optional[float] = None,
-                  map_refine: bool = False, map_refine_max_weight: Optional[int] = None) -> Dict:
+                  map_refine: bool = False, map_refine_max_weight: Optional[int] = None,
+                  map_info: bool = False) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -60,7 +61,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     tracked once more from the best-scoring pose around the most similar ones, with ``map_keyframe_rot_deg`` /
     ``map_keyframe_trans`` for MapConfig.keyframe_rot_deg / keyframe_trans where not None; ``map_refine``:
     MapConfig.refine, the rows a frame observes again move to the running mean of their depths, with
-    ``map_refine_max_weight`` for MapConfig.refine_max_weight where not None)."""
+    ``map_refine_max_weight`` for MapConfig.refine_max_weight where not None; ``map_info``: MapConfig.info, every frame
+    that is not lost reports the covariance of its pose from the map's rows against its depth image)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
     if map_merge_voxel is not None and not map_mode:
         raise ValueError("map_merge_voxel belongs to the map mode (map_mode=True)")
@@ -86,6 +88,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         raise ValueError("map_refine belongs to the map mode (map_mode=True)")
     if map_refine_max_weight is not None and not map_refine:
         raise ValueError("map_refine_max_weight: an option of map_refine=True")
+    if map_info and not map_mode:
+        raise ValueError("map_info belongs to the map mode (map_mode=True)")
     refine = None
     if map_refine:
         refine = dict(refine=True, **({} if map_refine_max_weight is None else
@@ -94,7 +98,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         return evaluate_sequential(parser, cfg, max_frames, verbose, motion, map_mode, map_capacity, map_view_guard,
                                    map_free_rho, map_free_window, map_evict, map_merge_voxel, map_merge_every,
                                    dict(reloc, reloc=True) if map_reloc else None,
-                                   dict(keyframes, keyframes=True) if map_keyframes else None, map_refine=refine)
+                                   dict(keyframes, keyframes=True) if map_keyframes else None, map_refine=refine,
+                                   map_info=bool(map_info))
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -159,7 +164,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                         map_free_rho: Optional[float] = None, map_free_window: int = 1,
                         map_evict: bool = False, map_merge_voxel: Optional[float] = None,
                         map_merge_every: int = 1, map_reloc: Optional[Dict] = None,
-                        map_keyframes: Optional[Dict] = None, map_refine: Optional[Dict] = None) -> Dict:
+                        map_keyframes: Optional[Dict] = None, map_refine: Optional[Dict] = None,
+                        map_info: bool = False) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
     map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
@@ -173,7 +179,10 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     estimate that was kept, None where no row was judged).  map_keyframes: the MapConfig fields of place recognition
     (keyframes=True and any of keyframe_rot_deg, keyframe_trans); the report gains keyframes (those the map holds at the
     end) and recognised_frames (frames that a keyframe's neighbourhood was accepted from).  map_refine: the MapConfig
-    fields of refinement (refine=True and, where wanted, refine_max_weight); the report gains refined_per_frame."""
+    fields of refinement (refine=True and, where wanted, refine_max_weight); the report gains refined_per_frame.  map_info: MapConfig.info; every frame prints
+    the standard deviations of its pose, the rows used, the smallest eigenvalue of H / used and the verdict, and the report
+    gains sigma_t_per_frame (metres), sigma_r_per_frame (degrees), info_used_per_frame, info_min_eig_per_frame and
+    weak_frames (None in the lists for a lost frame, which is not asked)."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
@@ -183,7 +192,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                                                        free_rho=map_free_rho, free_window_px=map_free_window,
                                                        evict=bool(map_evict), merge_voxel=map_merge_voxel,
                                                        merge_every=map_merge_every, **(map_reloc or {}),
-                                                       **(map_keyframes or {}), **(map_refine or {})))
+                                                       **(map_keyframes or {}), **(map_refine or {}),
+                                                       info=bool(map_info)))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
@@ -191,6 +201,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     eTs, eRs, steps, lost, path, last_t = [], [], [], 0, 0.0, pose[:3, 3]
     added, tracked, violations, removed, evicted, merged = [], [], [], [], [], []
     relocalised, shares, recognised, refined = 0, [], 0, []
+    sigma_t, sigma_r, info_used, info_eig, weak = [], [], [], [], 0
     for i in range(1, n + 1):
         depth, rgb, pose = parser.frame(i)
         r = loc.track(depth, rgb, gt_c2w=pose)
@@ -210,6 +221,18 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             shares.append(r.agree / (r.agree + r.front) if r.agree + r.front > 0 else None)
         if map_keyframes:
             recognised += int(r.recognised >= 0)
+        if map_info:
+            sigma_t.append(r.sigma_t)
+            sigma_r.append(r.sigma_r)
+            info_used.append(r.info_used)
+            info_eig.append(r.info_min_eig)
+            weak += int(bool(r.weak))
+            if r.weak is None:
+                print(f"frame {i}: pose information: lost, not asked")
+            else:
+                sig = "none" if r.cov is None else f"sigma_t {r.sigma_t:.3e} m sigma_r {r.sigma_r:.3e} deg"
+                print(f"frame {i}: pose information: {sig} rows used {r.info_used} min eig {r.info_min_eig:.3e} "
+                      f"weak {r.weak}")
         path += float(torch.norm(pose[:3, 3] - last_t))
         last_t = pose[:3, 3]
         if verbose:
@@ -231,7 +254,10 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                 "merged_at_reset": merged_at_reset} if map_merge_voxel is not None else {}),
             **({"reloc": True, "relocalised_frames": relocalised, "agree_share_per_frame": shares} if map_reloc else {}),
             **({"keyframes": loc.map.n_keyframes, "recognised_frames": recognised} if map_keyframes else {}),
-            **({"refine": True, "refined_per_frame": refined} if map_refine else {})}
+            **({"refine": True, "refined_per_frame": refined} if map_refine else {}),
+            **({"info": True, "sigma_t_per_frame": sigma_t, "sigma_r_per_frame": sigma_r,
+                "info_used_per_frame": info_used, "info_min_eig_per_frame": info_eig, "weak_frames": weak}
+               if map_info else {})}
 
 
 def main(argv=None):
@@ -295,6 +321,11 @@ def main(argv=None):
                          "running mean of the depths observed there (default: a point keeps its first depth)")
     ap.add_argument("--map-refine-max-weight", type=int, default=None, metavar="N",
                     help="--map-refine: the number of depths from which on the mean is an exponential one (default 64)")
+    ap.add_argument("--map-info", action="store_true",
+                    help="--map: pose information -- every frame that is not lost prints the standard deviations of its "
+                         "pose (metres, degrees) from the map's points against its depth image, the points used, the "
+                         "smallest eigenvalue of the information matrix per point and whether the frame is weak; "
+                         "nothing is gated on them")
     a = ap.parse_args(argv)
     if a.map_merge_voxel is not None and not a.map:
         ap.error("--map-merge-voxel needs --map")
@@ -327,6 +358,8 @@ def main(argv=None):
         ap.error("--map-refine needs --map")
     if a.map_refine_max_weight is not None and not a.map_refine:
         ap.error("--map-refine-max-weight needs --map-refine")
+    if a.map_info and not a.map:
+        ap.error("--map-info needs --map")
     out = {}
     for room in a.rooms:
         parser = Parser(a.dataset, room, normalize=not a.no_normalize, input_folder=a.root)
@@ -338,7 +371,8 @@ def main(argv=None):
                           map_reloc_min_agree=a.map_reloc_min_agree, map_reloc_rot_deg=a.map_reloc_rot_deg,
                           map_reloc_trans=a.map_reloc_trans, map_keyframes=a.map_keyframes,
                           map_keyframe_rot_deg=a.map_keyframe_rot_deg, map_keyframe_trans=a.map_keyframe_trans,
-                          map_refine=a.map_refine, map_refine_max_weight=a.map_refine_max_weight)
+                          map_refine=a.map_refine, map_refine_max_weight=a.map_refine_max_weight,
+                          map_info=a.map_info)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

@@ -43,6 +43,10 @@ which it matched (``place_base``), are the bases of one more grid, which is scor
 With ``MapConfig.refine`` the map improves where it is seen again: after the insertion render of a frame that is not
 lost and before anything is stamped or inserted, the live rows the frame observes where it expects them move along
 their ray to the running mean of the depths observed there (``GaussianMap.refine``, at the estimate).
+With ``MapConfig.info`` a frame that is not lost also says how well it constrains its pose: after the relocalisation flow
+and before anything touches the map, the normal equations of the final estimate are summed over the map's rows against
+the frame's depth image (``GaussianMap.pose_information``), and the frame reports the covariance of its pose and whether
+it is weak.  Nothing is gated on it.
 """
 from __future__ import annotations
 
@@ -109,6 +113,17 @@ class LocalizeResult:
     keyframe: Optional[int] = None
     recognised: Optional[int] = None
     refined: Optional[int] = None  # refine: live rows this frame observed again and moved, before its insertion
+    # info (None on a lost frame, which is not asked): cov [6,6] float64 numpy, the covariance sigma^2 H^-1 of the left
+    # perturbation (omega [rad], upsilon [m]) of the world-to-camera pose in the camera's frame -- None when weak;
+    # sigma_t [m] / sigma_r [deg]: the square roots of the traces of its translation / rotation blocks (None when
+    # weak); info_used: the rows the sums were taken over; info_min_eig: the smallest eigenvalue of H / used; weak: fewer
+    # than 7 rows used, or that eigenvalue below MapConfig.info_min_eig
+    cov: Optional[object] = None
+    sigma_t: Optional[float] = None
+    sigma_r: Optional[float] = None
+    info_used: Optional[int] = None
+    info_min_eig: Optional[float] = None
+    weak: Optional[bool] = None
 
 
 def _step(axis: int, rot_deg: float = 0.0, trans: float = 0.0) -> Tensor:
@@ -223,7 +238,12 @@ class Localizer:
     refined (``GaussianMap.refine``; ``LocalizeResult.refined`` counts them).  Their colours are refined with the
     frame's image only when the localizer is photometric (``rgb_lambda != 0``): without an image the frame's colours
     are a constant stand-in that must not bleach the stored ones.  A lost frame refines nothing.  Refinement at an
-    estimated pose feeds a share 1 / (weight + 1) of that pose's error into the rows it moves.  Everything else
+    estimated pose feeds a share 1 / (weight + 1) of that pose's error into the rows it moves.
+    ``map_config.info``: for a frame that is not lost, one call of ``GaussianMap.pose_information`` at the frame's final
+    estimate -- after the relocalisation flow, before the band is checked and before anything is rendered, refined,
+    stamped or inserted -- fills ``LocalizeResult.cov`` / ``sigma_t`` / ``sigma_r`` / ``info_used`` / ``info_min_eig`` /
+    ``weak``.  It reads the map and the depth image and writes neither: poses, steps, added rows and the map are bit
+    for bit those of the run without the option.  Everything else
     -- normalisation, the re-rendered query depth, the scales, the hand-over, ``best_c2w`` -- is the frame mode's."""
 
     def __init__(self, K: Tensor, width: int, height: int, config: TrackerConfig = TrackerConfig(),
@@ -258,6 +278,7 @@ class Localizer:
         self._min_tested = 0  # MapConfig.reloc_min_tested, or its default for this image size
         self._keyframes = False  # MapConfig.keyframes
         self._refine = False  # MapConfig.refine
+        self._info = False  # MapConfig.info
         self._tracked = 0  # calls of track since reset
         self.merged_at_reset = None  # merge_voxel: rows the merge after reset's insertion removed
         if self.map_mode:
@@ -269,6 +290,7 @@ class Localizer:
             self._evict = bool(map_config.evict)
             self._merge_every = int(map_config.merge_every) if map_config.merge_voxel is not None else 0
             self._refine = bool(map_config.refine)
+            self._info = bool(map_config.info)
             if map_config.reloc:
                 self._reloc = map_config
                 self._min_tested = (map_config.reloc_min_tested if map_config.reloc_min_tested is not None
@@ -332,6 +354,15 @@ class Localizer:
         tested, agree, front = verdict
         return (res.best_step != -1 and tested >= self._min_tested
                 and agree >= self._reloc.reloc_min_agree * (agree + front))
+
+    @staticmethod
+    def _report_information(out: LocalizeResult, info) -> None:
+        """The fields of a frame's result that ``MapConfig.info`` fills, from its ``PoseInformation``."""
+        out.info_used, out.info_min_eig, out.weak = info.used, float(info.eigenvalues[0]), info.weak()
+        out.cov = info.covariance()
+        if out.cov is not None:
+            out.sigma_t = math.sqrt(float(out.cov[3:, 3:].trace()))
+            out.sigma_r = math.degrees(math.sqrt(float(out.cov[:3, :3].trace())))
 
     @property
     def trajectory(self) -> Tensor:
@@ -445,6 +476,9 @@ class Localizer:
             out.refined = 0 if self._refine else None
             self._tracked += 1
             if not out.lost:  # a lost frame's pose is a guess: it adds nothing
+                if self._info:
+                    # the frame's final estimate against the map as it was tracked: before anything below touches it
+                    self._report_information(out, self.map.pose_information(depth, self.K, est, self.cfg.gs.near_plane))
                 at = best
                 if self._view_guard is not None:
                     # the band is checked against the estimate, not assumed: rows that reach into the view from there

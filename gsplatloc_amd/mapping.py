@@ -49,7 +49,13 @@ the live rows a depth frame observes again -- every one of the four pixels aroun
 within ``refine_rho`` -- along their own ray to the running mean of the depths observed there (the four pixels' inverse
 depths blended at the row's position), blends their colours likewise and raises their weight up to
 ``refine_max_weight``.  One more entry point; one read-back.  The weights follow their rows through every removal as
-the stamps do."""
+the stamps do.
+
+Pose information (``MapConfig.info``, csrc/map_info.hip): ``pose_information`` sums the point-to-plane normal equations
+of a pose over the live rows that agree with a depth frame on a planar patch -- the 6 x 6 information matrix, the
+gradient and the residual sum, in fixed point, the same integers on every run -- and ``PoseInformation`` makes the
+covariance of the pose, the verdict ``weak`` and, for the tests, the Gauss-Newton step of them (``apply_twist``).  It
+changes nothing in the map.  One more entry point; one read-back."""
 from __future__ import annotations
 
 import functools
@@ -70,6 +76,74 @@ PLACE_CELLS = 192  # the 16 x 12 cells of a descriptor of csrc/map_place.hip (gs
 PLACE_GW, PLACE_GH = 16, 12
 PLACE_MAX_KEYFRAMES = 256  # keyframes one call of gsl_map_place_match compares (GSL_MAP_PLACE_MAX_KEYFRAMES)
 PLACE_SHIFTS = tuple((sx, sy) for sy in (-1, 0, 1) for sx in (-2, -1, 0, 1, 2))  # the kernel's order
+INFO_VALUES = 30  # int64 sums one call of csrc/map_info.hip leaves (gsl_map_info_values())
+INFO_ONE = float(2 ** 20)  # their fixed point
+# The default of MapConfig.info_min_eig.  An eigenvalue of H / used is the mean over the rows used of the squared
+# component of J along a direction: for a translation that of the unit normals (1 / 3 each in a corner seen evenly, 0
+# along a wall), for a rotation that of p x n in m^2.  1e-3 is normals within 1.8 degrees (rms) of perpendicular to a
+# direction -- a wall, to the eye -- and 2000 times the 2^-21 that the rounding of a fixed-point term can add to a mean
+INFO_MIN_EIG = 1e-3
+
+
+@dataclass
+class PoseInformation:
+    """The normal equations of a pose from the map's rows against a depth frame (``GaussianMap.pose_information``), for
+    a left perturbation w2c' = exp(xi^) w2c with xi = (omega [rad], upsilon [m]) in the camera's frame: H = sum J J^T
+    [6,6] and g = sum J r [6] over the rows used, float64 (the kernel's integers / 2^20); rss = sum r^2 in m^2; the rows
+    used and tested; min_eig: the bound ``weak`` takes by default."""
+    H: np.ndarray
+    g: np.ndarray
+    rss: float
+    used: int
+    tested: int
+    min_eig: float = INFO_MIN_EIG
+
+    @property
+    def eigenvalues(self) -> np.ndarray:
+        """Of H / used, ascending (zeros when no row was used)."""
+        if self.used == 0:
+            return np.zeros(6)
+        return np.linalg.eigvalsh(self.H / float(self.used))
+
+    def weak(self, min_eig: Optional[float] = None) -> bool:
+        """Fewer than 7 rows used (six unknowns and one degree of freedom for sigma), or the smallest eigenvalue of
+        H / used below min_eig: some move of the camera that the frame does not pin down."""
+        bound = self.min_eig if min_eig is None else float(min_eig)
+        return self.used < 7 or not float(self.eigenvalues[0]) >= bound
+
+    def covariance(self) -> Optional[np.ndarray]:
+        """sigma^2 H^-1 [6,6] with sigma^2 = rss / (used - 6), in (rad, m); None when weak."""
+        if self.weak():
+            return None
+        return (self.rss / float(self.used - 6)) * np.linalg.inv(self.H)
+
+    def step(self) -> Optional[np.ndarray]:
+        """The Gauss-Newton step -H^-1 g [6] = (omega, upsilon) (``apply_twist``); None when weak."""
+        if self.weak():
+            return None
+        return -np.linalg.solve(self.H, self.g)
+
+
+def apply_twist(c2w, xi) -> Tensor:
+    """The camera-to-world pose after the left perturbation w2c' = exp(xi^) w2c, xi = (omega [rad], upsilon [m]) in the
+    camera's frame: c2w' = c2w exp(-xi^).  The exponential of se(3) in float64 (Rodrigues; the series where |omega| is
+    tiny); returned in c2w's dtype, on its device."""
+    c2w = torch.as_tensor(c2w)
+    if c2w.shape != (4, 4):
+        raise ValueError(f"c2w is {tuple(c2w.shape)}, not (4, 4)")
+    xi = -np.asarray(xi, dtype=np.float64).reshape(6)
+    w, v = xi[:3], xi[3:]
+    th = float(np.linalg.norm(w))
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-6:
+        a, b, c = 1.0 - th * th / 6.0, 0.5 - th * th / 24.0, 1.0 / 6.0 - th * th / 120.0
+    else:
+        a, b, c = math.sin(th) / th, (1.0 - math.cos(th)) / (th * th), (th - math.sin(th)) / (th ** 3)
+    E = np.eye(4)
+    E[:3, :3] = np.eye(3) + a * K + b * (K @ K)
+    E[:3, 3] = (np.eye(3) + b * K + c * (K @ K)) @ v
+    out = c2w.detach().cpu().double().numpy() @ E
+    return torch.from_numpy(out).to(dtype=c2w.dtype if c2w.is_floating_point() else torch.float64, device=c2w.device)
 
 
 @dataclass
@@ -140,10 +214,40 @@ class MapConfig:
     refine: bool = False
     refine_rho: Optional[float] = None
     refine_max_weight: int = 64
+    # Localizer(mode="map"): pose information.  After the relocalisation flow and before anything touches the map, the
+    # normal equations of the frame's final estimate are summed over the live rows that agree with their own pixel
+    # within info_rho (None: depth_rho) and whose pixel and its four neighbours lie on one plane
+    # (GaussianMap.pose_information); the frame reports the covariance of its pose.  Read-only: nothing is gated on it
+    info: bool = False
+    info_rho: Optional[float] = None
+    # the planarity test: the inverse depths of a pixel's two neighbours along a line or a column may miss twice its
+    # own by this fraction of it.  A property of the sensor's depth quantisation, not of the scene: on a plane the sum
+    # is exact, so the bound has to pass what the sensor's rounding of the three depths adds and nothing more: depths
+    # quantised in steps of q metres at the depth d move the sum by up to 2 q / d^2, so info_kappa >= 2 q / d.  1e-3
+    # passes float32 depths and a sensor that resolves 1 mm at 2 m, and refuses the creases of a room (NOTES.md, "Pose
+    # information"); a sensor with 1 cm steps at 2 m needs 1e-2
+    info_kappa: float = 1e-3
+    # a frame is weak when fewer than 7 rows were used or the smallest eigenvalue of H / used is below this (None:
+    # INFO_MIN_EIG)
+    info_min_eig: Optional[float] = None
 
     def __post_init__(self):
         whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
         number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer))  # noqa: E731
+        if not isinstance(self.info, bool):
+            raise ValueError(f"info {self.info!r}: True or False")
+        if self.info_rho is not None and (not number(self.info_rho) or not 0.0 <= self.info_rho < 1.0):
+            raise ValueError(f"info_rho {self.info_rho!r}: a fraction of the observed depth, inside [0, 1) (or None: "
+                             "depth_rho)")
+        if self.info and self.info_rho is None and not 0.0 <= self.depth_rho < 1.0:
+            raise ValueError(f"depth_rho {self.depth_rho}: info holds a row against the observed depth within this "
+                             "fraction, inside [0, 1) (or set info_rho)")
+        if not number(self.info_kappa) or not (np.isfinite(self.info_kappa) and self.info_kappa >= 0):
+            raise ValueError(f"info_kappa {self.info_kappa!r}: a fraction of the inverse depth, finite and not negative")
+        if self.info_min_eig is not None and (not number(self.info_min_eig) or
+                                              not (np.isfinite(self.info_min_eig) and self.info_min_eig > 0)):
+            raise ValueError(f"info_min_eig {self.info_min_eig!r}: an eigenvalue of H / used, finite and above 0 (or "
+                             "None)")
         if not isinstance(self.refine, bool):
             raise ValueError(f"refine {self.refine!r}: True or False")
         if self.refine_rho is not None and (not number(self.refine_rho) or not 0.0 <= self.refine_rho < 1.0):
@@ -296,6 +400,8 @@ class GaussianMap:
             self._refine_keep = float(np.float32(1.0) - np.float32(rho))
             self.weights = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
             self._refine_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # pose_information: its 30 sums, on first use
+        self._info = None
 
     def _alloc_ws(self):
         if self.device.type != "cuda":
@@ -669,6 +775,52 @@ class GaussianMap:
         intr, _ = _intr_and_pose(K, poses[0])
         return self._score_launch(depth, intr, _world_to_camera(torch.stack([c.detach().cpu().double() for c in poses])),
                                   float(near))
+
+    # ---- pose information: the normal equations of a pose from the rows against a depth frame (csrc/map_info.hip) ------
+    def _info_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, keep: float,
+                     beyond: float, kappa: float, near: float) -> np.ndarray:
+        """w2c [4,4] float32 on the device.  The entry point (which zeroes the sums) and the read-back of int64 [30], the
+        call's one synchronisation."""
+        assert depth.is_cuda, "GaussianMap.pose_information: the rows are judged and summed by a HIP kernel, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        if self._info is None:
+            self._info = torch.empty(INFO_VALUES, dtype=torch.int64, device=self.device)
+        _lib.check(lib.gsl_map_pose_info(ptr(self.means), self.n_live, ptr(w2c), *intr, ptr(depth), self.W, self.H, keep,
+                                         beyond, kappa, near, ptr(self._info), st), "gsl_map_pose_info")
+        return self._info.cpu().numpy()
+
+    @torch.no_grad()
+    def pose_information(self, depth, K, c2w, near_plane: float, rho: Optional[float] = None,
+                         kappa: Optional[float] = None) -> PoseInformation:
+        """How well the depth frame [H,W] (metres) constrains the pose c2w [4,4]: the point-to-plane normal equations of
+        a small move of the camera, summed over the live rows that project onto an inner pixel beyond ``near_plane``,
+        agree with its depth within ``rho`` (None: ``info_rho``, and ``depth_rho`` when that is None) as do its four
+        neighbours, and whose patch is planar within ``kappa`` (None: ``info_kappa``) -- the rule: include/gsloc_hip.h.
+        Changes nothing in the map.  One zeroing launch, one kernel, one read-back; an empty map gives zeros (weak)
+        without a launch."""
+        min_eig = INFO_MIN_EIG if self.cfg.info_min_eig is None else float(self.cfg.info_min_eig)
+        if rho is None:
+            rho = self.cfg.depth_rho if self.cfg.info_rho is None else self.cfg.info_rho
+        if not 0.0 <= rho < 1.0:
+            raise ValueError(f"rho {rho!r}: a fraction of the observed depth, inside [0, 1)")
+        kappa = float(self.cfg.info_kappa if kappa is None else kappa)
+        if not (math.isfinite(kappa) and kappa >= 0.0):
+            raise ValueError(f"kappa {kappa!r}: a fraction of the inverse depth, finite and not negative")
+        depth = self._depth_image(depth)
+        intr, c2w = _intr_and_pose(K, c2w)
+        if self.n_live == 0:
+            return PoseInformation(np.zeros((6, 6)), np.zeros(6), 0.0, 0, 0, min_eig)
+        keep, beyond = float(np.float32(1.0) - np.float32(rho)), float(np.float32(1.0) + np.float32(rho))
+        sums = self._info_launch(depth, intr, _world_to_camera(c2w).to(self.device).contiguous(), keep, beyond,
+                                 float(np.float32(kappa)), float(near_plane))
+        sums = np.asarray(sums, dtype=np.int64)
+        H, k = np.zeros((6, 6)), 0
+        for a in range(6):
+            for b in range(a, 6):
+                H[a, b] = H[b, a] = float(sums[k]) / INFO_ONE
+                k += 1
+        return PoseInformation(H, sums[21:27].astype(np.float64) / INFO_ONE, float(sums[27]) / INFO_ONE, int(sums[28]),
+                               int(sums[29]), min_eig)
 
     # ---- refinement: the rows a depth frame observes again move to the running mean of their depths (csrc/map_refine.hip)
     def _refine_launch(self, depth: Tensor, rgb: Optional[Tensor], intr: Tuple[float, float, float, float], w2c: Tensor,

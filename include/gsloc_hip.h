@@ -319,6 +319,50 @@ int gsl_map_score(const float* means, int64_t n_rows, const float* w2c, int n_po
                   float cy, const float* depth, int width, int height, float keep, float beyond, float near_plane,
                   int32_t* counts, void* stream);
 
+/* ---- pose information: the normal equations of a pose from the map's rows against a depth frame (csrc/map_info.hip) ----
+ * means[n_rows,3], depth[height,width] float32 (the observed depth, metres) and w2c[16] (world to camera, row-major;
+ * twelve entries are read) on the device.  out[GSL_MAP_INFO_VALUES] int64 on the device; it need not be initialised,
+ * the entry point zeroes it on the stream.  A left perturbation w2c' = exp(xi^) w2c, xi = (omega [rad], upsilon [m]) in
+ * the camera's frame, moves a row's camera point p to p + omega x p + upsilon; against the plane through q0 with unit
+ * normal n the residual is r = n . (p - q0) and its derivative J = (p x n, n).  Row i with mean (px, py, pz), w the
+ * rows of w2c:
+ *   x = ((w0 px + w1 py) + w2 pz) + w3, and y, z likewise;  u = fx x / z + cx, v = fy y / z + cy;
+ *   uf = rintf(u), vf = rintf(v) (round half to even);
+ *   TESTED when z > near_plane and 1 <= uf <= width - 2 and 1 <= vf <= height - 2 (an inner pixel) and
+ *          d0 = depth[vf, uf] is finite and > 0;
+ *   lo = d0 * keep, hi = d0 * beyond (one rounded product each);
+ *   USED   when tested and z >= lo and z <= hi and z < 64 (what bounds the sums, below) and each of the neighbours
+ *          dl, dr, du, dd = depth[vf, uf - 1], depth[vf, uf + 1], depth[vf - 1, uf], depth[vf + 1, uf] is finite and
+ *          > 0 with lo <= d <= hi, and the inverse depth is linear across the patch -- with i0 = 1 / d0, s0 = i0 + i0,
+ *          tol = kappa * i0: |(1 / dl + 1 / dr) - s0| <= tol and |(1 / du + 1 / dd) - s0| <= tol -- and len > 0;
+ *   q(u, v, d) = ((u - cx) / fx * d, (v - cy) / fy * d, d), the back-projection of gsl_map_append;
+ *   a = q(uf + 1, vf, dr) - q(uf - 1, vf, dl),  b = q(uf, vf + 1, dd) - q(uf, vf - 1, du),
+ *   c = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x),  len = sqrtf((c.x c.x + c.y c.y) + c.z c.z),
+ *   n = c / len;  e = (x, y, z) - q(uf, vf, d0),  r = (n.x e.x + n.y e.y) + n.z e.z,
+ *   m = (y n.z - z n.y, z n.x - x n.z, x n.y - y n.x),  J = (m.x, m.y, m.z, n.x, n.y, n.z);
+ *   fix(s, t) = llrintf((s * t) * 1048576.f): one float32 product, scaled by 2^20, rounded half to even to an int64.
+ *   out[0 .. 20]  = sum of fix(J_a, J_b), a <= b: the upper triangle of H = sum J J^T, row-major;
+ *   out[21 .. 26] = sum of fix(J_a, r): g = sum J r;   out[27] = sum of fix(r, r);
+ *   out[28] = rows used;  out[29] = rows tested.
+ * float32, evaluated exactly as written (no fused operation, correctly rounded division and square root), comparisons
+ * false for a NaN: NaN / inf rows, rows at or behind near_plane, rows on the border or outside the image and pixels
+ * without depth add nothing.  keep is 1 - rho and beyond 1 + rho, the float32 difference and sum taken by the caller.
+ * The sums are integers: they do not depend on the order of rows, waves or workgroups.  The sign of n cancels in every
+ * product.  One zeroing launch and one kernel; the number of global atomics is bounded by the kernel's grid cap times
+ * GSL_MAP_INFO_VALUES, not by n_rows.  Nothing but out is written.
+ * gsl_map_info_max_rows: the rows one call takes, 2^31 - 1 at the most -- under it no sum can leave 64 bits (every
+ * |J_a| and |r| is at most B = 64 S (1 + 1 / keep), S^2 = 1 + tx^2 + ty^2 with tx, ty the tangents of the half-angles
+ * the inner pixels span; rows < 2^63 / (1.01^2 B^2 2^20 + 1)); 0 for arguments the entry point refuses.
+ * Returns GSL_ERR_BAD_ARG before any launch for a NULL means, w2c, depth or out, n_rows <= 0 or >= 2^31 or above
+ * gsl_map_info_max_rows, width or height <= 0 or width * height > 2^31 - 1 (an image without an inner pixel is taken:
+ * every sum is 0), fx or fy not non-zero, keep outside (0, 1], beyond not in [1, inf), kappa not in [0, inf). */
+#define GSL_MAP_INFO_VALUES 30
+int gsl_map_info_values(void);
+int64_t gsl_map_info_max_rows(float fx, float fy, float cx, float cy, int width, int height, float keep);
+int gsl_map_pose_info(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx, float cy,
+                      const float* depth, int width, int height, float keep, float beyond, float kappa,
+                      float near_plane, int64_t* out, void* stream);
+
 /* ---- place recognition: a 16 x 12 descriptor of a depth frame, and its match against keyframes (csrc/map_place.hip) ----
  * gsl_map_place_describe: depth[height,width] float32 on the device, row-major, metres; desc[192] int32 on the device,
  * row-major over GSL_MAP_PLACE_GH lines of GSL_MAP_PLACE_GW cells (gsl_map_place_cells() = 192).  It need not be
