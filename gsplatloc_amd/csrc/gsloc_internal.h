@@ -46,6 +46,12 @@ int launch_mraster_bwd(const float* Q0, const float* Q1, const float* Q2, int ch
                        const float* v_render, const float* v_alphas, float* vrow, int row0, int row1, const void* Qh,
                        hipStream_t st);
 
+// map_info.hip: the zeroing of out[GSL_MAP_INFO_VALUES] and the launch of k_map_pose_info, for arguments checked as
+// gsl_map_pose_info checks them; w2c on the device.  Returns GSL_OK or the status of the failed launch
+int map_pose_info_launch(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx, float cy,
+                         const float* depth, int width, int height, float keep, float beyond, float kappa,
+                         float near_plane, int64_t* out, hipStream_t st);
+
 // ---- workspace of the fused pipeline (sized by gsl_fused_ws_bytes, fused_project.hip) -------------------------------
 // ws = [tile_counts n_tiles][cursors n_tiles][pad to 16 bytes][pose-gradient rows ceil(N/256) x 16 floats][stage rows]
 #define GSL_VM_STAGE_ROWS 64  // scratch rows behind the ceil(N / 256) pose-gradient rows: stage 1 of the row reduction

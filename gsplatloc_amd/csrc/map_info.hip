@@ -166,6 +166,22 @@ __global__ __launch_bounds__(INFO_THREADS) void k_map_pose_info(
   }
 }
 
+// The zeroing of out and the launch of k_map_pose_info, for arguments that gsl_map_pose_info has checked: its own two
+// launches, and one iteration's of gsl_map_pose_align (map_align.hip), which gives the working pose on the device as w2c.
+int map_pose_info_launch(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx, float cy,
+                         const float* depth, int width, int height, float keep, float beyond, float kappa,
+                         float near_plane, int64_t* out, hipStream_t st) {
+  const int rc = zero_u32(out, (size_t)2 * GSL_MAP_INFO_VALUES, st);
+  if (rc != GSL_OK) return rc;
+  const long long blocks = (n_rows + INFO_THREADS - 1) / INFO_THREADS;
+  const int nb = (int)(blocks < INFO_MAX_BLOCKS ? blocks : INFO_MAX_BLOCKS);
+  hipLaunchKernelGGL(k_map_pose_info, dim3(nb), dim3(INFO_THREADS), 0, st, means, (long long)n_rows, w2c, fx, fy, cx, cy,
+                     depth, width, (float)(width - 2), (float)(height - 2), keep, beyond, kappa, near_plane,
+                     (unsigned long long*)out);
+  GSL_CHECK_LAUNCH();
+  return GSL_OK;
+}
+
 }  // namespace gsl
 
 extern "C" int gsl_map_info_values(void) { return GSL_MAP_INFO_VALUES; }
@@ -190,14 +206,6 @@ extern "C" int gsl_map_pose_info(const float* means, int64_t n_rows, const float
   if (!(keep > 0.f && keep <= 1.f) || !(beyond >= 1.f && beyond < INFINITY)) return GSL_ERR_BAD_ARG;
   if (!(kappa >= 0.f && kappa < INFINITY)) return GSL_ERR_BAD_ARG;
   if (n_rows > gsl_map_info_max_rows(fx, fy, cx, cy, width, height, keep)) return GSL_ERR_BAD_ARG;  // a sum could overflow
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = gsl::zero_u32(out, (size_t)2 * GSL_MAP_INFO_VALUES, st);
-  if (rc != GSL_OK) return rc;
-  const long long blocks = (n_rows + gsl::INFO_THREADS - 1) / gsl::INFO_THREADS;
-  const int nb = (int)(blocks < gsl::INFO_MAX_BLOCKS ? blocks : gsl::INFO_MAX_BLOCKS);
-  hipLaunchKernelGGL(gsl::k_map_pose_info, dim3(nb), dim3(gsl::INFO_THREADS), 0, st, means, (long long)n_rows, w2c, fx,
-                     fy, cx, cy, depth, width, (float)(width - 2), (float)(height - 2), keep, beyond, kappa, near_plane,
-                     (unsigned long long*)out);
-  GSL_CHECK_LAUNCH();
-  return GSL_OK;
+  return gsl::map_pose_info_launch(means, n_rows, w2c, fx, fy, cx, cy, depth, width, height, keep, beyond, kappa,
+                                   near_plane, out, (hipStream_t)stream);
 }

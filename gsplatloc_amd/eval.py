@@ -42,7 +42,7 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   map_reloc_trans: Optional[float] = None, map_keyframes: bool = False,
                   map_keyframe_rot_deg: Optional[float] = None, map_keyframe_trans: Optional[float] = None,
                   map_refine: bool = False, map_refine_max_weight: Optional[int] = None,
-                  map_info: bool = False) -> Dict:
+                  map_info: bool = False, map_align: bool = False, map_align_steps: Optional[int] = None) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -62,7 +62,9 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     ``map_keyframe_trans`` for MapConfig.keyframe_rot_deg / keyframe_trans where not None; ``map_refine``:
     MapConfig.refine, the rows a frame observes again move to the running mean of their depths, with
     ``map_refine_max_weight`` for MapConfig.refine_max_weight where not None; ``map_info``: MapConfig.info, every frame
-    that is not lost reports the covariance of its pose from the map's rows against its depth image)."""
+    that is not lost reports the covariance of its pose from the map's rows against its depth image; ``map_align``:
+    MapConfig.align, every frame's start pose is aligned to the map by Gauss-Newton steps before the tracker runs, with
+    ``map_align_steps`` for MapConfig.align_steps where not None)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
     if map_merge_voxel is not None and not map_mode:
         raise ValueError("map_merge_voxel belongs to the map mode (map_mode=True)")
@@ -90,6 +92,13 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         raise ValueError("map_refine_max_weight: an option of map_refine=True")
     if map_info and not map_mode:
         raise ValueError("map_info belongs to the map mode (map_mode=True)")
+    if (map_align or map_align_steps is not None) and not map_mode:
+        raise ValueError("map_align belongs to the map mode (map_mode=True)")
+    if map_align_steps is not None and not map_align:
+        raise ValueError("map_align_steps: an option of map_align=True")
+    align = None
+    if map_align:
+        align = dict(align=True, **({} if map_align_steps is None else {"align_steps": map_align_steps}))
     refine = None
     if map_refine:
         refine = dict(refine=True, **({} if map_refine_max_weight is None else
@@ -99,7 +108,7 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                                    map_free_rho, map_free_window, map_evict, map_merge_voxel, map_merge_every,
                                    dict(reloc, reloc=True) if map_reloc else None,
                                    dict(keyframes, keyframes=True) if map_keyframes else None, map_refine=refine,
-                                   map_info=bool(map_info))
+                                   map_info=bool(map_info), map_align=align)
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -165,7 +174,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                         map_evict: bool = False, map_merge_voxel: Optional[float] = None,
                         map_merge_every: int = 1, map_reloc: Optional[Dict] = None,
                         map_keyframes: Optional[Dict] = None, map_refine: Optional[Dict] = None,
-                        map_info: bool = False) -> Dict:
+                        map_info: bool = False, map_align: Optional[Dict] = None) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
     map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
@@ -182,7 +191,11 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     fields of refinement (refine=True and, where wanted, refine_max_weight); the report gains refined_per_frame.  map_info: MapConfig.info; every frame prints
     the standard deviations of its pose, the rows used, the smallest eigenvalue of H / used and the verdict, and the report
     gains sigma_t_per_frame (metres), sigma_r_per_frame (degrees), info_used_per_frame, info_min_eig_per_frame and
-    weak_frames (None in the lists for a lost frame, which is not asked)."""
+    weak_frames (None in the lists for a lost frame, which is not asked).  map_align: the MapConfig fields of pose
+    alignment (align=True and, where wanted, align_steps); every frame prints what the alignment did, and the report gains
+    aligned_per_frame (the aligned start was taken), align_steps_per_frame, align_status_per_frame, aligned_frames, and
+    the translation errors motion_eT_per_frame / start_eT_per_frame of the motion model's pose and of the pose the
+    tracker started from."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
@@ -193,7 +206,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                                                        evict=bool(map_evict), merge_voxel=map_merge_voxel,
                                                        merge_every=map_merge_every, **(map_reloc or {}),
                                                        **(map_keyframes or {}), **(map_refine or {}),
-                                                       info=bool(map_info)))
+                                                       info=bool(map_info), **(map_align or {})))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
@@ -202,6 +215,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     added, tracked, violations, removed, evicted, merged = [], [], [], [], [], []
     relocalised, shares, recognised, refined = 0, [], 0, []
     sigma_t, sigma_r, info_used, info_eig, weak = [], [], [], [], 0
+    aligned, align_steps, align_status, motion_eT, start_eT = [], [], [], [], []
     for i in range(1, n + 1):
         depth, rgb, pose = parser.frame(i)
         r = loc.track(depth, rgb, gt_c2w=pose)
@@ -233,6 +247,15 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                 sig = "none" if r.cov is None else f"sigma_t {r.sigma_t:.3e} m sigma_r {r.sigma_r:.3e} deg"
                 print(f"frame {i}: pose information: {sig} rows used {r.info_used} min eig {r.info_min_eig:.3e} "
                       f"weak {r.weak}")
+        if map_align:
+            aligned.append(bool(r.aligned))
+            align_steps.append(r.align_steps)
+            align_status.append(r.align_status)
+            gt_t = pose[:3, 3].to(r.init_c2w.device)
+            motion_eT.append(float(torch.norm(r.align_from[:3, 3] - gt_t)))
+            start_eT.append(float(torch.norm(r.init_c2w[:3, 3] - gt_t)))
+            print(f"frame {i}: pose alignment: {r.align_status} after {r.align_steps} steps, moved {r.align_moved_t:.3e} m "
+                  f"{r.align_moved_r_deg:.3e} deg, taken {r.aligned}: start eT {motion_eT[-1]:.3e} -> {start_eT[-1]:.3e}")
         path += float(torch.norm(pose[:3, 3] - last_t))
         last_t = pose[:3, 3]
         if verbose:
@@ -257,7 +280,10 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             **({"refine": True, "refined_per_frame": refined} if map_refine else {}),
             **({"info": True, "sigma_t_per_frame": sigma_t, "sigma_r_per_frame": sigma_r,
                 "info_used_per_frame": info_used, "info_min_eig_per_frame": info_eig, "weak_frames": weak}
-               if map_info else {})}
+               if map_info else {}),
+            **({"align": True, "aligned_per_frame": aligned, "align_steps_per_frame": align_steps,
+                "align_status_per_frame": align_status, "aligned_frames": sum(aligned),
+                "motion_eT_per_frame": motion_eT, "start_eT_per_frame": start_eT} if map_align else {})}
 
 
 def main(argv=None):
@@ -326,6 +352,11 @@ def main(argv=None):
                          "pose (metres, degrees) from the map's points against its depth image, the points used, the "
                          "smallest eigenvalue of the information matrix per point and whether the frame is weak; "
                          "nothing is gated on them")
+    ap.add_argument("--map-align", action="store_true",
+                    help="--map: pose alignment -- every frame's start pose is aligned to the map by Gauss-Newton steps "
+                         "on the device before the tracker runs, and taken when the map scores it no worse")
+    ap.add_argument("--map-align-steps", type=int, default=None, metavar="K",
+                    help="--map-align: iterations per frame, 1 .. 32 (default 8)")
     a = ap.parse_args(argv)
     if a.map_merge_voxel is not None and not a.map:
         ap.error("--map-merge-voxel needs --map")
@@ -360,6 +391,10 @@ def main(argv=None):
         ap.error("--map-refine-max-weight needs --map-refine")
     if a.map_info and not a.map:
         ap.error("--map-info needs --map")
+    if a.map_align and not a.map:
+        ap.error("--map-align needs --map")
+    if a.map_align_steps is not None and not a.map_align:
+        ap.error("--map-align-steps needs --map-align")
     out = {}
     for room in a.rooms:
         parser = Parser(a.dataset, room, normalize=not a.no_normalize, input_folder=a.root)
@@ -372,7 +407,7 @@ def main(argv=None):
                           map_reloc_trans=a.map_reloc_trans, map_keyframes=a.map_keyframes,
                           map_keyframe_rot_deg=a.map_keyframe_rot_deg, map_keyframe_trans=a.map_keyframe_trans,
                           map_refine=a.map_refine, map_refine_max_weight=a.map_refine_max_weight,
-                          map_info=a.map_info)
+                          map_info=a.map_info, map_align=a.map_align, map_align_steps=a.map_align_steps)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

@@ -47,6 +47,9 @@ With ``MapConfig.info`` a frame that is not lost also says how well it constrain
 and before anything touches the map, the normal equations of the final estimate are summed over the map's rows against
 the frame's depth image (``GaussianMap.pose_information``), and the frame reports the covariance of its pose and whether
 it is weak.  Nothing is gated on it.
+With ``MapConfig.align`` step 3 looks at the frame: the motion model's start pose is aligned to the map by a few
+Gauss-Newton steps on those normal equations, iterated on the device (``GaussianMap.align_pose``), and the aligned pose
+is what the frame starts from when the map scores it no worse than the motion model's (``GaussianMap.score_poses``).
 """
 from __future__ import annotations
 
@@ -124,6 +127,18 @@ class LocalizeResult:
     info_used: Optional[int] = None
     info_min_eig: Optional[float] = None
     weak: Optional[bool] = None
+    # align: aligned -- the start pose the map's Gauss-Newton steps gave was taken (init_c2w is then that pose; False:
+    # the alignment refused, or the map scored its pose worse than the motion model's, and the frame ran from that);
+    # align_status / align_steps: ``PoseAlignment.status`` / ``steps``; align_from: the motion model's pose [4,4];
+    # align_moved_t [m] / align_moved_r_deg: from there to the alignment's pose (0 when it did not move); align_scores:
+    # ((tested, agree, front) of the motion model's pose, of the alignment's) that decided, None when it refused
+    aligned: Optional[bool] = None
+    align_status: Optional[str] = None
+    align_steps: Optional[int] = None
+    align_from: Optional[Tensor] = None
+    align_moved_t: Optional[float] = None
+    align_moved_r_deg: Optional[float] = None
+    align_scores: Optional[tuple] = None
 
 
 def _step(axis: int, rot_deg: float = 0.0, trans: float = 0.0) -> Tensor:
@@ -243,7 +258,16 @@ class Localizer:
     estimate -- after the relocalisation flow, before the band is checked and before anything is rendered, refined,
     stamped or inserted -- fills ``LocalizeResult.cov`` / ``sigma_t`` / ``sigma_r`` / ``info_used`` / ``info_min_eig`` /
     ``weak``.  It reads the map and the depth image and writes neither: poses, steps, added rows and the map are bit
-    for bit those of the run without the option.  Everything else
+    for bit those of the run without the option.
+    ``map_config.align``: before the pair is built, ``GaussianMap.align_pose`` aligns the motion model's start pose to
+    the map against the frame's depth image.  A pose it moved (status CONVERGED or STEPPED) is scored beside the start
+    in one ``score_poses`` call and taken when it confirms some row and its share agree / (agree + front) is at least
+    the start's; a pose that is taken is what ``select_view``, ``build_pair`` and the tracker start from, it is
+    ``init_c2w``, and the relocalisation grid, the insertion, refinement and information see it wherever they saw the
+    start.  A pose that is not taken is dropped and the frame runs as without the option.  ``LocalizeResult.aligned`` /
+    ``align_status`` / ``align_steps`` / ``align_from`` (the motion model's pose) / ``align_moved_t`` /
+    ``align_moved_r_deg`` / ``align_scores`` say what happened.  Nothing in the map is written.  With the option off
+    there is no call, and poses, step counts and the map are bit for bit those of the run without it.  Everything else
     -- normalisation, the re-rendered query depth, the scales, the hand-over, ``best_c2w`` -- is the frame mode's."""
 
     def __init__(self, K: Tensor, width: int, height: int, config: TrackerConfig = TrackerConfig(),
@@ -279,6 +303,7 @@ class Localizer:
         self._keyframes = False  # MapConfig.keyframes
         self._refine = False  # MapConfig.refine
         self._info = False  # MapConfig.info
+        self._align = False  # MapConfig.align
         self._tracked = 0  # calls of track since reset
         self.merged_at_reset = None  # merge_voxel: rows the merge after reset's insertion removed
         if self.map_mode:
@@ -291,6 +316,7 @@ class Localizer:
             self._merge_every = int(map_config.merge_every) if map_config.merge_voxel is not None else 0
             self._refine = bool(map_config.refine)
             self._info = bool(map_config.info)
+            self._align = bool(map_config.align)
             if map_config.reloc:
                 self._reloc = map_config
                 self._min_tested = (map_config.reloc_min_tested if map_config.reloc_min_tested is not None
@@ -354,6 +380,27 @@ class Localizer:
         tested, agree, front = verdict
         return (res.best_step != -1 and tested >= self._min_tested
                 and agree >= self._reloc.reloc_min_agree * (agree + front))
+
+    def _aligned_start(self, depth: Tensor, init: Tensor):
+        """align: the motion model's pose aligned to the map (``GaussianMap.align_pose``), and taken when the alignment
+        moved it (status CONVERGED or STEPPED) and the map scores it no worse -- one ``score_poses`` call on the two:
+        the aligned pose confirms some row, and of the rows it judges against the frame's own surface (those that
+        agree and those in front) the share that agrees is at least the start's, agree_a * front_s >= agree_s * front_a
+        in integers.  The share, the quantity ``reloc`` accepts an estimate by, and not the difference agree - front:
+        a camera that moves loses rows over the image's edge, and the difference counts every one of them against
+        the pose that follows the motion (NOTES.md, "Pose alignment").  Returns (the ``LocalizeResult`` fields aligned,
+        align_status, align_steps, align_from, align_moved_t, align_moved_r_deg, align_scores; the pose to start
+        from)."""
+        near = self.cfg.gs.near_plane
+        al = self.map.align_pose(depth, self.K, init, near)
+        taken, moved_t, moved_r, scores = False, 0.0, 0.0, None
+        if al.status in ("CONVERGED", "STEPPED"):
+            to = al.c2w.to(self.device)
+            moved_t, moved_r = float(calculate_translation_error(to, init)), float(calculate_rotation_error(to, init))
+            scores = tuple(tuple(int(c) for c in s) for s in self.map.score_poses(depth, self.K, [init, to], near))
+            (_, agree_s, front_s), (_, agree_a, front_a) = scores
+            taken = agree_a > 0 and agree_a * front_s >= agree_s * front_a
+        return (taken, al.status, al.steps, init, moved_t, moved_r, scores), (to if taken else init)
 
     @staticmethod
     def _report_information(out: LocalizeResult, info) -> None:
@@ -430,10 +477,13 @@ class Localizer:
         else:
             init = predict_pose(self._poses[-2], placed)
         gt = None if gt_c2w is None else torch.as_tensor(gt_c2w, dtype=torch.float32, device=self.device)
+        alignment = None
         # the pair's reference pose is the tracker's error read-out only: without ground truth, the starting pose
         if self.map_mode:
             if self.map.n_live == 0:
                 raise RuntimeError("Localizer.track: the map is empty (the first frame had no valid depth)")
+            if self._align:
+                alignment, init = self._aligned_start(depth, init)
             frame = (pts, col, depth, rgb, placed, gt if gt is not None else init)
             d = self._map_pair(init, frame)
         else:
@@ -468,6 +518,9 @@ class Localizer:
         if verdict is not None:
             out.relocalised, (out.tested, out.agree, out.front) = relocalised, verdict
             out.recognised = recognised
+        if alignment is not None:
+            (out.aligned, out.align_status, out.align_steps, out.align_from, out.align_moved_t,
+             out.align_moved_r_deg, out.align_scores) = alignment
         if self.map_mode:
             out.added, out.tracked = 0, N
             out.removed = 0 if self._free else None

@@ -55,7 +55,15 @@ Pose information (``MapConfig.info``, csrc/map_info.hip): ``pose_information`` s
 of a pose over the live rows that agree with a depth frame on a planar patch -- the 6 x 6 information matrix, the
 gradient and the residual sum, in fixed point, the same integers on every run -- and ``PoseInformation`` makes the
 covariance of the pose, the verdict ``weak`` and, for the tests, the Gauss-Newton step of them (``apply_twist``).  It
-changes nothing in the map.  One more entry point; one read-back."""
+changes nothing in the map.  One more entry point; one read-back.
+
+Pose alignment (``MapConfig.align``, csrc/map_align.hip): ``align_pose`` iterates that step on the device -- up to
+``align_steps`` times the sums at the working pose and a one-thread float64 kernel that solves the damped normal
+equations, bounds the step, moves the pose (the Cayley map, not ``apply_twist``'s exponential: it needs no sine or
+cosine, so the tests' numpy mirror gives the same bits) and writes the float32 copy the next sums are taken at -- and
+returns a ``PoseAlignment``: the pose, a status and the history of the steps.  ``Localizer(mode="map")`` aligns the
+motion model's start pose with it before the splat tracker runs.  It changes nothing in the map.  One more entry point,
+one fixed sequence of launches; one read-back."""
 from __future__ import annotations
 
 import functools
@@ -83,6 +91,10 @@ INFO_ONE = float(2 ** 20)  # their fixed point
 # along a wall), for a rotation that of p x n in m^2.  1e-3 is normals within 1.8 degrees (rms) of perpendicular to a
 # direction -- a wall, to the eye -- and 2000 times the 2^-21 that the rounding of a fixed-point term can add to a mean
 INFO_MIN_EIG = 1e-3
+ALIGN_MAX_STEPS = 32  # iterations one call of csrc/map_align.hip runs at the most (gsl_map_align_max_steps())
+ALIGN_STATE_WORDS, ALIGN_ROW_WORDS = 14, 10  # 8-byte words of its state and of a history row (include/gsloc_hip.h)
+ALIGN_MIN_USED = 7  # rows: six unknowns and one to spare, as PoseInformation.weak
+ALIGN_STATUS = ("STEPPED", "CONVERGED", "FEW", "SINGULAR", "TOO_FAR")  # GSL_MAP_ALIGN_*
 
 
 @dataclass
@@ -122,6 +134,30 @@ class PoseInformation:
         if self.weak():
             return None
         return -np.linalg.solve(self.H, self.g)
+
+
+@dataclass
+class PoseAlignment:
+    """What ``GaussianMap.align_pose`` returns.  c2w: float32 [4,4] on the map's device, the float64 inverse of w2c64
+    rounded once; w2c64: float64 [4,4] numpy, the device's world-to-camera pose after the last applied step (the exact
+    widening of the float32 start when none was); status: the last iteration's, one of ``ALIGN_STATUS`` -- STEPPED
+    (every iteration moved the pose and the last step was still above the stop tolerance), CONVERGED (a step within it
+    was applied), FEW (fewer than 7 rows used), SINGULAR (a pivot of the damped normal equations not above 0), TOO_FAR
+    (a step beyond the bound; not applied); the last three leave the pose where the step before them put it.  steps:
+    the steps applied; used / tested: the rows of the last iteration's sums, at the final pose when the run stopped
+    early; history: per iteration (status, used, tested, rss [m^2], xi [6] float64 = (omega [rad], upsilon [m]))."""
+    c2w: Tensor
+    w2c64: np.ndarray
+    status: str
+    steps: int
+    used: int
+    tested: int
+    history: list
+
+    @property
+    def moved(self) -> bool:
+        """The pose is a new one: at least one step was applied and no iteration refused."""
+        return self.steps > 0 and self.status in ("STEPPED", "CONVERGED")
 
 
 def apply_twist(c2w, xi) -> Tensor:
@@ -230,10 +266,47 @@ class MapConfig:
     # a frame is weak when fewer than 7 rows were used or the smallest eigenvalue of H / used is below this (None:
     # INFO_MIN_EIG)
     info_min_eig: Optional[float] = None
+    # Localizer(mode="map"): pose alignment.  Before the pair is built, the motion model's start pose is aligned to the
+    # map by up to align_steps Gauss-Newton steps on those normal equations (GaussianMap.align_pose), and the aligned
+    # pose is what the frame starts from when the map scores it no worse than the start (localizer.py).  8 steps: the
+    # float64 prototype of a start 5 cm / 3 degrees off was converged at step 7 (NOTES.md, "Pose alignment")
+    align: bool = False
+    align_steps: int = 8
+    # added, times the rows used, to the diagonal of H: the quantity INFO_MIN_EIG bounds -- an eigenvalue of H / used
+    # below it belongs to a direction the frame does not pin down, and the damping keeps the step out of it
+    align_damping: float = INFO_MIN_EIG
+    align_rho: Optional[float] = None  # as info_rho (None: depth_rho); the planarity bound is info_kappa
+    # a single step beyond these is not trusted and not taken: the jump between two frames that the tracker was measured
+    # to absorb (NOTES.md, "Relocalisation")
+    align_max_rot_deg: float = 12.8
+    align_max_trans: float = 0.32
+    # a step within both has converged: a tenth of the smallest per-frame error of the 160x120 sequence (NOTES.md)
+    align_eps_rot_deg: float = 1.5e-4
+    align_eps_trans: float = 3e-5
 
     def __post_init__(self):
         whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
         number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer))  # noqa: E731
+        if not isinstance(self.align, bool):
+            raise ValueError(f"align {self.align!r}: True or False")
+        if not whole(self.align_steps) or not 1 <= self.align_steps <= ALIGN_MAX_STEPS:
+            raise ValueError(f"align_steps {self.align_steps!r}: a whole number of iterations, 1 .. {ALIGN_MAX_STEPS}")
+        if not number(self.align_damping) or not (np.isfinite(self.align_damping) and self.align_damping >= 0):
+            raise ValueError(f"align_damping {self.align_damping!r}: an eigenvalue of H / used, finite and not negative")
+        if self.align_rho is not None and (not number(self.align_rho) or not 0.0 <= self.align_rho < 1.0):
+            raise ValueError(f"align_rho {self.align_rho!r}: a fraction of the observed depth, inside [0, 1) (or None: "
+                             "depth_rho)")
+        if self.align and self.align_rho is None and not 0.0 <= self.depth_rho < 1.0:
+            raise ValueError(f"depth_rho {self.depth_rho}: align holds a row against the observed depth within this "
+                             "fraction, inside [0, 1) (or set align_rho)")
+        for name, unit in (("align_max_rot_deg", "degrees"), ("align_max_trans", "metres")):
+            v = getattr(self, name)
+            if not number(v) or not (np.isfinite(v) and v > 0):
+                raise ValueError(f"{name} {v!r}: {unit}, finite and above 0")
+        for name, unit in (("align_eps_rot_deg", "degrees"), ("align_eps_trans", "metres")):
+            v = getattr(self, name)
+            if not number(v) or not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"{name} {v!r}: {unit}, finite and not negative")
         if not isinstance(self.info, bool):
             raise ValueError(f"info {self.info!r}: True or False")
         if self.info_rho is not None and (not number(self.info_rho) or not 0.0 <= self.info_rho < 1.0):
@@ -402,6 +475,8 @@ class GaussianMap:
             self._refine_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
         # pose_information: its 30 sums, on first use
         self._info = None
+        # align_pose: one buffer of 8-byte words -- state, history, working pose, sums -- and the start pose, on first use
+        self._align = None
 
     def _alloc_ws(self):
         if self.device.type != "cuda":
@@ -821,6 +896,89 @@ class GaussianMap:
                 k += 1
         return PoseInformation(H, sums[21:27].astype(np.float64) / INFO_ONE, float(sums[27]) / INFO_ONE, int(sums[28]),
                                int(sums[29]), min_eig)
+
+    # ---- pose alignment: Gauss-Newton steps on those normal equations, iterated on the device (csrc/map_align.hip) ----
+    def _align_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, keep: float,
+                      beyond: float, kappa: float, near: float, steps: int, damping: float, min_used: int,
+                      max_rot: float, max_trans: float, eps_rot: float, eps_trans: float):
+        """w2c [4,4] float32 on the host.  Its copy to the device, the entry point and the read-back of one buffer, the
+        call's one synchronisation: (pose [3,4] float64, working pose [4,4] float32, steps applied, rows [steps,4] int64
+        = (status, used, tested, rss_fixed), xi [steps,6] float64)."""
+        assert depth.is_cuda, "GaussianMap.align_pose: the pose is aligned by HIP kernels, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        n_state, n_hist = ALIGN_STATE_WORDS, ALIGN_MAX_STEPS * ALIGN_ROW_WORDS
+        if self._align is None:
+            self._align = dict(words=torch.zeros(n_state + n_hist + 8 + INFO_VALUES, dtype=torch.int64, device=self.device),
+                               start=torch.empty(16, device=self.device))
+        a = self._align
+        words, base = a["words"], a["words"].data_ptr()
+        a["start"].copy_(w2c.reshape(16))
+        _lib.check(lib.gsl_map_pose_align(ptr(self.means), self.n_live, ptr(a["start"]), *intr, ptr(depth), self.W, self.H,
+                                          keep, beyond, kappa, near, steps, damping, min_used, max_rot, max_trans,
+                                          eps_rot, eps_trans, base + 8 * (n_state + n_hist + 8), base + 8 * (n_state + n_hist),
+                                          base, base + 8 * n_state, st), "gsl_map_pose_align")
+        host = words.cpu().numpy()
+        hist = host[n_state:n_state + steps * ALIGN_ROW_WORDS].reshape(steps, ALIGN_ROW_WORDS)
+        return (host[:12].view(np.float64).reshape(3, 4).copy(),
+                host[n_state + n_hist:n_state + n_hist + 8].view(np.float32).reshape(4, 4).copy(), int(host[12]),
+                hist[:, :4].copy(), hist[:, 4:].copy().view(np.float64))
+
+    @torch.no_grad()
+    def align_pose(self, depth, K, c2w, near_plane: float, steps: Optional[int] = None, rho: Optional[float] = None,
+                   kappa: Optional[float] = None, damping: Optional[float] = None, max_rot_deg: Optional[float] = None,
+                   max_trans: Optional[float] = None, eps_rot_deg: Optional[float] = None,
+                   eps_trans: Optional[float] = None, min_used: int = ALIGN_MIN_USED) -> PoseAlignment:
+        """The pose c2w [4,4] aligned to the map against the depth frame [H,W] (metres): up to ``steps`` (None:
+        ``align_steps``) damped Gauss-Newton steps on the normal equations of ``pose_information`` -- the rows chosen
+        with ``rho`` (None: ``align_rho``, and ``depth_rho`` when that is None) and ``kappa`` (None: ``info_kappa``),
+        ``damping`` (None: ``align_damping``) times the rows used on the diagonal -- each of them solved, bounded
+        (``max_rot_deg`` / ``max_trans``), applied and tested for convergence (``eps_rot_deg`` / ``eps_trans``) on the
+        device in float64 (the rule: include/gsloc_hip.h).  The start is rounded to float32 as every pose a kernel is
+        given.  Changes nothing in the map.  One fixed sequence of 1 + 3 ``steps`` launches, one read-back; an empty
+        map gives status FEW without a launch.  The result has to be checked by the caller: a start too far off can
+        settle elsewhere (NOTES.md, "Pose alignment")."""
+        cfg = self.cfg
+        steps = int(cfg.align_steps if steps is None else steps)
+        if not 1 <= steps <= ALIGN_MAX_STEPS:
+            raise ValueError(f"steps {steps!r}: a whole number of iterations, 1 .. {ALIGN_MAX_STEPS}")
+        if rho is None:
+            rho = cfg.depth_rho if cfg.align_rho is None else cfg.align_rho
+        if not 0.0 <= rho < 1.0:
+            raise ValueError(f"rho {rho!r}: a fraction of the observed depth, inside [0, 1)")
+        kappa = float(cfg.info_kappa if kappa is None else kappa)
+        if not (math.isfinite(kappa) and kappa >= 0.0):
+            raise ValueError(f"kappa {kappa!r}: a fraction of the inverse depth, finite and not negative")
+        damping = float(cfg.align_damping if damping is None else damping)
+        if not (math.isfinite(damping) and damping >= 0.0):
+            raise ValueError(f"damping {damping!r}: an eigenvalue of H / used, finite and not negative")
+        max_rot = math.radians(float(cfg.align_max_rot_deg if max_rot_deg is None else max_rot_deg))
+        max_trans = float(cfg.align_max_trans if max_trans is None else max_trans)
+        eps_rot = math.radians(float(cfg.align_eps_rot_deg if eps_rot_deg is None else eps_rot_deg))
+        eps_trans = float(cfg.align_eps_trans if eps_trans is None else eps_trans)
+        if not (math.isfinite(max_rot) and max_rot > 0.0 and math.isfinite(max_trans) and max_trans > 0.0):
+            raise ValueError(f"max_rot_deg / max_trans {max_rot_deg!r} / {max_trans!r}: finite and above 0")
+        if not (math.isfinite(eps_rot) and eps_rot >= 0.0 and math.isfinite(eps_trans) and eps_trans >= 0.0):
+            raise ValueError(f"eps_rot_deg / eps_trans {eps_rot_deg!r} / {eps_trans!r}: finite and not negative")
+        min_used = int(min_used)
+        if min_used < ALIGN_MIN_USED:
+            raise ValueError(f"min_used {min_used!r}: at least {ALIGN_MIN_USED} rows")
+        depth = self._depth_image(depth)
+        intr, c2w = _intr_and_pose(K, c2w)
+        w2c = _world_to_camera(c2w)
+        if self.n_live == 0:
+            pose, n, rows, xis = w2c.numpy()[:3].astype(np.float64), 0, np.zeros((1, 4), np.int64), np.zeros((1, 6))
+            rows[0, 0] = ALIGN_STATUS.index("FEW")
+        else:
+            keep, beyond = float(np.float32(1.0) - np.float32(rho)), float(np.float32(1.0) + np.float32(rho))
+            pose, _, n, rows, xis = self._align_launch(depth, intr, w2c.contiguous(), keep, beyond,
+                                                       float(np.float32(kappa)), float(near_plane), steps, damping,
+                                                       min_used, max_rot, max_trans, eps_rot, eps_trans)
+        w2c64 = np.eye(4)
+        w2c64[:3] = pose
+        history = [(ALIGN_STATUS[int(r[0])], int(r[1]), int(r[2]), float(r[3]) / INFO_ONE, np.array(x, dtype=np.float64))
+                   for r, x in zip(rows, xis)]
+        aligned = torch.from_numpy(np.linalg.inv(w2c64).astype(np.float32)).to(self.device)
+        return PoseAlignment(aligned, w2c64, history[-1][0], int(n), history[-1][1], history[-1][2], history)
 
     # ---- refinement: the rows a depth frame observes again move to the running mean of their depths (csrc/map_refine.hip)
     def _refine_launch(self, depth: Tensor, rgb: Optional[Tensor], intr: Tuple[float, float, float, float], w2c: Tensor,

@@ -363,6 +363,47 @@ int gsl_map_pose_info(const float* means, int64_t n_rows, const float* w2c, floa
                       const float* depth, int width, int height, float keep, float beyond, float kappa,
                       float near_plane, int64_t* out, void* stream);
 
+/* ---- pose alignment: Gauss-Newton on the normal equations above, iterated on the device (csrc/map_align.hip) ----
+ * means, n_rows, w2c, fx .. near_plane as for gsl_map_pose_info; w2c[16] is the start pose and is not written.
+ * sums[GSL_MAP_INFO_VALUES] int64, work[16] float32, state[GSL_MAP_ALIGN_STATE_WORDS] and
+ * history[max_steps][GSL_MAP_ALIGN_ROW_WORDS] 8-byte words, all on the device, none of which need be initialised and
+ * none of which may overlap another or w2c:
+ *   state   = the pose P, the upper 3 x 4 of the world-to-camera matrix row-major as 12 float64 (initially the exact
+ *             widening of w2c's 12 float32 entries), then int64 steps_taken (the steps applied), then int64 done;
+ *   work    = (float)P, round to nearest even, and the row (0, 0, 0, 1): what the sums of an iteration are taken at;
+ *   history = per iteration int64 (status, rows used, rows tested, sum of fix(r, r)), then float64 xi[6] = (omega [rad],
+ *             upsilon [m]).
+ * One initialising launch; then for each of max_steps iterations the two launches of gsl_map_pose_info at work and a
+ * one-thread kernel that, in float64 with one rounding per operation in the order csrc/map_align.hip writes down:
+ *   done already: repeats the previous row's status (xi = 0; used, tested and the residual sum are this launch's);
+ *   used < min_used: status FEW, done;
+ *   solves (H + damping * used * I) xi = -g by LDL^T without pivoting, H and g the sums / 2^20; a pivot that is not
+ *     above 0 (a NaN included): status SINGULAR, done;
+ *   not (omega . omega <= max_rot^2 and upsilon . upsilon <= max_trans^2): status TOO_FAR (xi is recorded), done;
+ *   otherwise P <- [R | upsilon] P with R the Cayley map of omega, ((1 - s) I + 2 a a^T + 2 [a]x) / (1 + s), a = omega
+ *     / 2, s = a . a -- an exact rotation that agrees with exp(omega^) to first order and needs no sine or cosine --
+ *     work is written, steps_taken goes up by one, and the status is CONVERGED (done) when omega . omega <= eps_rot^2
+ *     and upsilon . upsilon <= eps_trans^2, else STEPPED.
+ * FEW, SINGULAR and TOO_FAR leave P and work as they were.  The status of the call is that of the last history row.
+ * The launches after done cannot be skipped (nothing is read back) and still run.  No allocation, no synchronisation.
+ * Returns GSL_ERR_BAD_ARG before any launch for whatever gsl_map_pose_info refuses, a NULL sums, work, state or
+ * history, max_steps outside 1 .. GSL_MAP_ALIGN_MAX_STEPS (gsl_map_align_max_steps()), min_used < 7, damping not in
+ * [0, inf), max_rot or max_trans not in (0, inf), eps_rot or eps_trans not in [0, inf). */
+#define GSL_MAP_ALIGN_MAX_STEPS 32
+#define GSL_MAP_ALIGN_STATE_WORDS 14
+#define GSL_MAP_ALIGN_ROW_WORDS 10
+#define GSL_MAP_ALIGN_STEPPED 0
+#define GSL_MAP_ALIGN_CONVERGED 1
+#define GSL_MAP_ALIGN_FEW 2
+#define GSL_MAP_ALIGN_SINGULAR 3
+#define GSL_MAP_ALIGN_TOO_FAR 4
+int gsl_map_align_max_steps(void);
+int gsl_map_pose_align(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx, float cy,
+                       const float* depth, int width, int height, float keep, float beyond, float kappa,
+                       float near_plane, int max_steps, double damping, int min_used, double max_rot, double max_trans,
+                       double eps_rot, double eps_trans, int64_t* sums, float* work, void* state, void* history,
+                       void* stream);
+
 /* ---- place recognition: a 16 x 12 descriptor of a depth frame, and its match against keyframes (csrc/map_place.hip) ----
  * gsl_map_place_describe: depth[height,width] float32 on the device, row-major, metres; desc[192] int32 on the device,
  * row-major over GSL_MAP_PLACE_GH lines of GSL_MAP_PLACE_GW cells (gsl_map_place_cells() = 192).  It need not be

@@ -13,10 +13,13 @@ of the whole insertion per frame.  The merge rows ("Map resolution" in NOTES.md,
 there-and-back sequence and the sweep, map mode unmerged beside map mode with MapConfig.merge_voxel, and the host cost
 of the merge per frame.  The refine rows ("Refinement" in NOTES.md, printed only with --only refine): the constant twist
 and the there-and-back sequence with Gaussian depth noise, map mode without beside map mode with MapConfig.refine --
-ATE / AAE and the RMS distance of the live rows to the box's planes -- and the host cost of refine per frame.
+ATE / AAE and the RMS distance of the live rows to the box's planes -- and the host cost of refine per frame.  The align
+rows ("Pose alignment" in NOTES.md, printed only with --only align): the random walk and the constant twist, map mode
+without beside map mode with MapConfig.align -- mean steps, frames per second, ATE, the error of the aligned start --
+and the device time of the alignment's loop beside as many calls of the sums alone.
 
     python scripts/map_figures.py [--frames 20] [--size 640 480] [--no-cost]
-                                  [--only there_and_back | sweep | vanish | evict | merge | refine]
+                                  [--only there_and_back | sweep | vanish | evict | merge | refine | align]
                                   [--refine-sigma M]
                                   [--sweep DEG FRAMES GUARD_PX] [--vanish FRAMES WITH RHO WINDOW_PX]
                                   [--merge-voxel M] [--merge-every K]"""
@@ -327,6 +330,100 @@ def refine(W, H, n, sigma, cost=True):
                                                "map_gaussians": r["map_gaussians"]}), flush=True)
 
 
+def align_cost(sizes=((320, 240), (640, 480)), steps=8, calls=20, warm=3, windows=5):
+    """Pose alignment, the cost of the loop: gsl_map_pose_align with ``steps`` iterations beside ``steps`` back-to-back
+    calls of gsl_map_pose_info, in the same run, on a map that is one frame's back-projection (76 800 and 307 200 rows)
+    and a query 1 cm / 0.5 degrees away: device events around ``calls`` calls after ``warm`` warm-ups, ``windows``
+    windows of each, alternating; and the same loop cut at the step it converges at, whose difference to the whole one
+    is what the launches after convergence cost."""
+    import math
+
+    import numpy as np
+
+    from gsplatloc_amd import _lib
+    from gsplatloc_amd.mapping import ALIGN_STATUS, GaussianMap
+    from gsplatloc_amd.synthetic import replica_intrinsics
+
+    lib, ptr = _lib.load_library(), _lib.ptr
+
+    def yaw(position, deg):
+        c, s = math.cos(math.radians(deg)), math.sin(math.radians(deg))
+        T = torch.eye(4, dtype=torch.float64)
+        T[:3, :3] = torch.tensor([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]], dtype=torch.float64)
+        T[:3, 3] = torch.tensor(position, dtype=torch.float64)
+        return T
+
+    at_map, at_query = yaw((0.6, 0.1, 0.8), 35.0), yaw((0.608, 0.1, 0.794), 35.5)
+    for W, H in sizes:
+        K = replica_intrinsics(W, H)
+        m = GaussianMap(W, H, MapConfig(align=True), "cuda")
+        m.insert_frame(room_depth(W, H, K, at_map.float()).cuda(), torch.zeros(H, W, 3, device="cuda"), K, at_map.float())
+        depth = room_depth(W, H, K, at_query.float()).cuda().contiguous()
+        al = m.align_pose(depth, K, at_map, 0.01, steps=steps)
+        taken = max(1, [h[0] for h in al.history].index("CONVERGED") + 1 if "CONVERGED" in [h[0] for h in al.history]
+                    else steps)
+        intr = tuple(float(v) for v in (K[0, 0], K[1, 1], K[0, 2], K[1, 2]))
+        w2c = torch.from_numpy(np.linalg.inv(at_map.numpy()).astype(np.float32)).cuda().reshape(16)
+        keep, beyond = float(np.float32(1) - np.float32(0.05)), float(np.float32(1) + np.float32(0.05))
+        sums = torch.zeros(30, dtype=torch.int64, device="cuda")
+        work, state = torch.zeros(16, device="cuda"), torch.zeros(14, dtype=torch.int64, device="cuda")
+        history = torch.zeros(32 * 10, dtype=torch.int64, device="cuda")
+        st = _lib.current_stream()
+
+        def aligned(k):
+            _lib.check(lib.gsl_map_pose_align(ptr(m.means), m.n_live, ptr(w2c), *intr, ptr(depth), W, H, keep, beyond, 1e-3,
+                                              0.01, k, 1e-3, 7, math.radians(12.8), 0.32, math.radians(1.5e-4), 3e-5,
+                                              ptr(sums), ptr(work), ptr(state), ptr(history), st), "gsl_map_pose_align")
+
+        def infos():
+            for _ in range(steps):
+                _lib.check(lib.gsl_map_pose_info(ptr(m.means), m.n_live, ptr(w2c), *intr, ptr(depth), W, H, keep, beyond,
+                                                 1e-3, 0.01, ptr(sums), st), "gsl_map_pose_info")
+
+        def window(fn):
+            for _ in range(warm):
+                fn()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            return 1e3 * a.elapsed_time(b) / calls  # microseconds per call
+
+        kinds = (("align", lambda: aligned(steps)), ("info_x_steps", infos), ("align_cut", lambda: aligned(taken)))
+        us = {name: [] for name, _ in kinds}
+        for _ in range(windows):
+            for name, fn in kinds:
+                us[name].append(round(window(fn), 1))
+        med = {name: sorted(v)[len(v) // 2] for name, v in us.items()}
+        print("ALIGN_COST " + json.dumps({"rows": m.n_live, "size": [W, H], "steps": steps, "status": al.status,
+                                          "converged_at_step": taken, "used": al.used, "us_per_call": us, "median_us": med,
+                                          "after_convergence_us": round(med["align"] - med["align_cut"], 1),
+                                          "statuses": list(ALIGN_STATUS)}), flush=True)
+
+
+def align(W, H, n, cost=True):
+    """Pose alignment (MapConfig.align) on the random walk and the constant twist (``n`` frames): map mode without the
+    option beside map mode with it, alternating in one process, the second pass of each reported -- mean steps, frames
+    per second, ATE, and with the option the error of the motion model's pose and of the aligned start beside the
+    frame's final error; then the cost of the loop (``align_cost``)."""
+    writers = (("random_walk", lambda root: write_replica_sequence(root, W, H, n)),
+               ("constant_twist", lambda root: write_replica_constant_twist(root, W, H, n)))
+    for name, writer in writers:
+        root = pathlib.Path(tempfile.mkdtemp())
+        writer(root)
+        for _ in range(2):
+            rows = [evaluate_room(Parser("Replica", "room0", normalize=True, input_folder=str(root)), 2000, None,
+                                  sequential=True, map_mode=True, map_align=on) for on in (False, True)]
+        for on, r in zip((False, True), rows):
+            for k in ("added_per_frame", "tracked_per_frame"):
+                r.pop(k, None)
+            print("MAP_FIG " + json.dumps({"sequence": name, "map": True, "align": on, **r}), flush=True)
+    if cost:
+        align_cost()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20)
@@ -350,6 +447,9 @@ def main():
                     help="the refine rows (--only refine): sigma of the Gaussian depth noise, metres")
     a = ap.parse_args()
     (W, H), n = a.size, a.frames
+    if a.only == "align":
+        align(W, H, n, cost=not a.no_cost)
+        return
     if a.only == "refine":
         refine(W, H, n, a.refine_sigma, cost=not a.no_cost)
         return
