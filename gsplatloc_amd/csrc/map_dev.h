@@ -2,7 +2,8 @@
 // selection (map_view.hip), free space (map_free.hip), the observation stamps (map_evict.hip), the pose scores
 // (map_score.hip), the refinement (map_refine.hip, which takes z, u, v and leaves the rounded uf, vf alone) and the pose
 // information (map_info.hip, which takes the camera x and y as well); what each of them does with the projected row --
-// its depth predicates, its counts -- is in its file.
+// its depth predicates, its counts -- is in its file.  The trajectory correction (map_correct.hip) projects nothing: it
+// takes the row load and its store twin, and writes the bracket order of the rule out once more for its 3 x 4 entries.
 //
 // Row i of means[n,3], with w the rows of w2c (world to camera, row-major):
 //   x = ((w0 px + w1 py) + w2 pz) + w3, y and z likewise;  u = fx x / z + cx, v = fy y / z + cy;
@@ -46,6 +47,13 @@ struct MapWindow {  // u0 .. u1 x v0 .. v1, inclusive
 
 __device__ static inline float3 map_load_row(const float* __restrict__ means, long long g) {
   return {means[3 * (size_t)g], means[3 * (size_t)g + 1], means[3 * (size_t)g + 2]};
+}
+
+// The store twin: a lane writes its own row with one global_store_dwordx3.
+__device__ static inline void map_store_row(float* __restrict__ means, long long g, float3 r) {
+  means[3 * (size_t)g] = r.x;
+  means[3 * (size_t)g + 1] = r.y;
+  means[3 * (size_t)g + 2] = r.z;
 }
 
 // w: the twelve leading entries of a row-major world-to-camera matrix.  cam_x, cam_y: the row's camera x and y, which

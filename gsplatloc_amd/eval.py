@@ -42,7 +42,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   map_reloc_trans: Optional[float] = None, map_keyframes: bool = False,
                   map_keyframe_rot_deg: Optional[float] = None, map_keyframe_trans: Optional[float] = None,
                   map_refine: bool = False, map_refine_max_weight: Optional[int] = None,
-                  map_info: bool = False, map_align: bool = False, map_align_steps: Optional[int] = None) -> Dict:
+                  map_info: bool = False, map_align: bool = False, map_align_steps: Optional[int] = None,
+                  map_origins: bool = False) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -92,6 +93,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         raise ValueError("map_refine_max_weight: an option of map_refine=True")
     if map_info and not map_mode:
         raise ValueError("map_info belongs to the map mode (map_mode=True)")
+    if map_origins and not map_mode:
+        raise ValueError("map_origins belongs to the map mode (map_mode=True)")
     if (map_align or map_align_steps is not None) and not map_mode:
         raise ValueError("map_align belongs to the map mode (map_mode=True)")
     if map_align_steps is not None and not map_align:
@@ -108,7 +111,7 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                                    map_free_rho, map_free_window, map_evict, map_merge_voxel, map_merge_every,
                                    dict(reloc, reloc=True) if map_reloc else None,
                                    dict(keyframes, keyframes=True) if map_keyframes else None, map_refine=refine,
-                                   map_info=bool(map_info), map_align=align)
+                                   map_info=bool(map_info), map_align=align, map_origins=bool(map_origins))
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -174,7 +177,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                         map_evict: bool = False, map_merge_voxel: Optional[float] = None,
                         map_merge_every: int = 1, map_reloc: Optional[Dict] = None,
                         map_keyframes: Optional[Dict] = None, map_refine: Optional[Dict] = None,
-                        map_info: bool = False, map_align: Optional[Dict] = None) -> Dict:
+                        map_info: bool = False, map_align: Optional[Dict] = None, map_origins: bool = False) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
     map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
@@ -195,7 +198,9 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     alignment (align=True and, where wanted, align_steps); every frame prints what the alignment did, and the report gains
     aligned_per_frame (the aligned start was taken), align_steps_per_frame, align_status_per_frame, aligned_frames, and
     the translation errors motion_eT_per_frame / start_eT_per_frame of the motion model's pose and of the pose the
-    tracker started from."""
+    tracker started from.  map_origins: MapConfig.origins, every row carries the index of the frame that appended it; the
+    report gains origins_non_decreasing (checked after every frame) and rows_per_origin (the live rows at the end that
+    came from frame 0, 1, ...).  No correction is applied: that is the caller's decision (``Localizer.close_loop``)."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
@@ -206,7 +211,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                                                        evict=bool(map_evict), merge_voxel=map_merge_voxel,
                                                        merge_every=map_merge_every, **(map_reloc or {}),
                                                        **(map_keyframes or {}), **(map_refine or {}),
-                                                       info=bool(map_info), **(map_align or {})))
+                                                       info=bool(map_info), **(map_align or {}),
+                                                       origins=bool(map_origins)))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
@@ -216,6 +222,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     relocalised, shares, recognised, refined = 0, [], 0, []
     sigma_t, sigma_r, info_used, info_eig, weak = [], [], [], [], 0
     aligned, align_steps, align_status, motion_eT, start_eT = [], [], [], [], []
+    ordered = True
     for i in range(1, n + 1):
         depth, rgb, pose = parser.frame(i)
         r = loc.track(depth, rgb, gt_c2w=pose)
@@ -256,6 +263,9 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             start_eT.append(float(torch.norm(r.init_c2w[:3, 3] - gt_t)))
             print(f"frame {i}: pose alignment: {r.align_status} after {r.align_steps} steps, moved {r.align_moved_t:.3e} m "
                   f"{r.align_moved_r_deg:.3e} deg, taken {r.aligned}: start eT {motion_eT[-1]:.3e} -> {start_eT[-1]:.3e}")
+        if map_origins:
+            o = loc.map.origins[: loc.map.n_live]
+            ordered = ordered and bool((o[1:] >= o[:-1]).all())
         path += float(torch.norm(pose[:3, 3] - last_t))
         last_t = pose[:3, 3]
         if verbose:
@@ -283,7 +293,10 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                if map_info else {}),
             **({"align": True, "aligned_per_frame": aligned, "align_steps_per_frame": align_steps,
                 "align_status_per_frame": align_status, "aligned_frames": sum(aligned),
-                "motion_eT_per_frame": motion_eT, "start_eT_per_frame": start_eT} if map_align else {})}
+                "motion_eT_per_frame": motion_eT, "start_eT_per_frame": start_eT} if map_align else {}),
+            **({"origins": True, "origins_non_decreasing": ordered,
+                "rows_per_origin": torch.bincount(loc.map.origins[: loc.map.n_live].long().cpu(),
+                                                  minlength=n + 1).tolist()} if map_origins else {})}
 
 
 def main(argv=None):
@@ -347,6 +360,10 @@ def main(argv=None):
                          "running mean of the depths observed there (default: a point keeps its first depth)")
     ap.add_argument("--map-refine-max-weight", type=int, default=None, metavar="N",
                     help="--map-refine: the number of depths from which on the mean is an exponential one (default 64)")
+    ap.add_argument("--map-origins", action="store_true",
+                    help="--map: every point of the map carries the index of the frame that appended it, so that the map "
+                         "can follow a corrected trajectory; the report says that the origins stayed non-decreasing in map "
+                         "order and how many live points came from each frame (no correction is applied)")
     ap.add_argument("--map-info", action="store_true",
                     help="--map: pose information -- every frame that is not lost prints the standard deviations of its "
                          "pose (metres, degrees) from the map's points against its depth image, the points used, the "
@@ -391,6 +408,8 @@ def main(argv=None):
         ap.error("--map-refine-max-weight needs --map-refine")
     if a.map_info and not a.map:
         ap.error("--map-info needs --map")
+    if a.map_origins and not a.map:
+        ap.error("--map-origins needs --map")
     if a.map_align and not a.map:
         ap.error("--map-align needs --map")
     if a.map_align_steps is not None and not a.map_align:
@@ -407,7 +426,8 @@ def main(argv=None):
                           map_reloc_trans=a.map_reloc_trans, map_keyframes=a.map_keyframes,
                           map_keyframe_rot_deg=a.map_keyframe_rot_deg, map_keyframe_trans=a.map_keyframe_trans,
                           map_refine=a.map_refine, map_refine_max_weight=a.map_refine_max_weight,
-                          map_info=a.map_info, map_align=a.map_align, map_align_steps=a.map_align_steps)
+                          map_info=a.map_info, map_align=a.map_align, map_align_steps=a.map_align_steps,
+                          map_origins=a.map_origins)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

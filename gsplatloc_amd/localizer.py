@@ -50,6 +50,10 @@ it is weak.  Nothing is gated on it.
 With ``MapConfig.align`` step 3 looks at the frame: the motion model's start pose is aligned to the map by a few
 Gauss-Newton steps on those normal equations, iterated on the device (``GaussianMap.align_pose``), and the aligned pose
 is what the frame starts from when the map scores it no worse than the motion model's (``GaussianMap.score_poses``).
+With ``MapConfig.origins`` the map can follow a corrected trajectory: every row carries the index its frame's pose has
+in ``trajectory``, and ``correct_trajectory`` (any new poses) or ``close_loop`` (one constraint on one frame, spread over
+the frames of the loop) moves the rows, the keyframe poses and the poses themselves (``GaussianMap.correct``).  Neither
+is called by ``track``: when a loop is closed is the caller's decision.
 """
 from __future__ import annotations
 
@@ -57,12 +61,13 @@ import math
 from dataclasses import dataclass
 from typing import Callable, List, Optional
 
+import numpy as np
 import torch
 from torch import Tensor
 
 from .data.dataset import build_pair
 from .data.normalize import denormalize_camera, transform_cameras
-from .mapping import SCORE_MAX_POSES, GaussianMap, MapConfig
+from .mapping import SCORE_MAX_POSES, GaussianMap, MapConfig, spread_correction
 from .my_gsplat.geometry import construct_full_pose, depth_to_points, init_gs_scales, render_depth_alpha
 from .my_gsplat.trainer import TrackerConfig, calculate_rotation_error, calculate_translation_error
 from .my_gsplat.transform import normalize_quaternion, quat_to_rotation_matrix, rotation_matrix_to_quaternion
@@ -139,6 +144,19 @@ class LocalizeResult:
     align_moved_t: Optional[float] = None
     align_moved_r_deg: Optional[float] = None
     align_scores: Optional[tuple] = None
+
+
+@dataclass
+class TrajectoryCorrection:
+    """What ``Localizer.correct_trajectory`` / ``close_loop`` did.  moved: the map's rows that were moved; outside: the
+    rows whose origin lies outside the trajectory (0 for a map this localizer built); frames: the poses whose
+    correction D_k = new_k old_k^-1 is not the identity; max_trans [m] / max_rot_deg: the largest translation and the
+    largest rotation angle over the D_k."""
+    moved: int
+    outside: int
+    frames: int
+    max_trans: float
+    max_rot_deg: float
 
 
 def _step(axis: int, rot_deg: float = 0.0, trans: float = 0.0) -> Tensor:
@@ -304,6 +322,7 @@ class Localizer:
         self._refine = False  # MapConfig.refine
         self._info = False  # MapConfig.info
         self._align = False  # MapConfig.align
+        self._origins = False  # MapConfig.origins
         self._tracked = 0  # calls of track since reset
         self.merged_at_reset = None  # merge_voxel: rows the merge after reset's insertion removed
         if self.map_mode:
@@ -317,6 +336,7 @@ class Localizer:
             self._refine = bool(map_config.refine)
             self._info = bool(map_config.info)
             self._align = bool(map_config.align)
+            self._origins = bool(map_config.origins)
             if map_config.reloc:
                 self._reloc = map_config
                 self._min_tested = (map_config.reloc_min_tested if map_config.reloc_min_tested is not None
@@ -424,12 +444,13 @@ class Localizer:
         self._poses = [pose.to(self.device).clone()]
         if self.map_mode:
             self.map.clear()
-            self.map.insert_frame(depth, rgb, self.K, self._poses[0])  # no render yet: every valid pixel
+            first = dict(origin=0) if self._origins else {}  # the index of the frame's pose in the trajectory
+            self.map.insert_frame(depth, rgb, self.K, self._poses[0], **first)  # no render yet: every valid pixel
             self._tracked = 0
             if self._merge_every:
                 self.merged_at_reset = self.map.merge()[0]
             if self._keyframes:
-                self.map.add_keyframe(depth, self._poses[0])  # keyframe 0: clear() has forgotten the others
+                self.map.add_keyframe(depth, self._poses[0], **first)  # keyframe 0: clear() has forgotten the others
 
     def _retry(self, depth: Tensor, frame, bases, kept, failed_start: bool = False):
         """One more run for a frame whose estimate the map rejected.  The ``reloc_candidates`` around the bases are scored
@@ -552,7 +573,8 @@ class Localizer:
                 if self._evict:
                     # stamp before the insertion: what this frame observes must not make room for its own rows
                     self.map.observe(depth, self.K, est, self.cfg.gs.near_plane, self.cfg.gs.far_plane)
-                _, out.added = self.map.insert_frame(depth, rgb, self.K, est, render, alphas)
+                index = dict(origin=len(self._poses) - 1) if self._origins else {}  # of est in the trajectory
+                _, out.added = self.map.insert_frame(depth, rgb, self.K, est, render, alphas, **index)
                 if self._evict:
                     out.evicted = self.map.last_evicted
                 if self._free:
@@ -563,8 +585,60 @@ class Localizer:
                     out.merged, _ = self.map.merge()
                 if self._keyframes:
                     # after the frame is done: the descriptor reads the depth image only, nothing above depends on it
-                    out.keyframe = self.map.add_keyframe(depth, est)
+                    out.keyframe = self.map.add_keyframe(depth, est, **index)
             out.map_size = self.map.n_live
         if gt is not None:
             out.eT, out.eR = calculate_translation_error(est, gt), calculate_rotation_error(est, gt)
         return out
+
+    # ---- trajectory correction (MapConfig.origins) ------------------------------------------------------------------
+    def _old_poses(self, what: str) -> np.ndarray:
+        if not self.map_mode or not self._origins:
+            raise RuntimeError(f"Localizer.{what}: needs mode='map' and MapConfig.origins=True -- without the frame every "
+                               "row came from there is nothing a corrected trajectory could move")
+        if not self._poses:
+            raise RuntimeError(f"Localizer.{what} before reset(): there is no trajectory yet")
+        return torch.stack(self._poses).detach().cpu().double().numpy()
+
+    @torch.no_grad()
+    def correct_trajectory(self, new_poses) -> TrajectoryCorrection:
+        """Replaces the trajectory by new_poses [n,4,4], one pose per pose so far, and moves the map with it: the rows
+        that frame k appended, and the keyframe made of frame k, move by D_k = new_k old_k^-1 (float64;
+        ``GaussianMap.correct``).  A pose that is given back as it is has the identity as its D_k, and its rows keep
+        every bit.  The next frame's motion model reads the corrected poses."""
+        old = self._old_poses("correct_trajectory")
+        new = torch.as_tensor(new_poses).detach().cpu().double().numpy()
+        if new.shape != old.shape:
+            raise ValueError(f"new_poses are {new.shape}, the trajectory is {old.shape}: one pose per pose so far")
+        if not np.isfinite(new).all():
+            raise ValueError("new_poses: some entry is not finite")
+        D = np.tile(np.eye(4), (len(old), 1, 1))
+        for k in range(len(old)):
+            if not np.array_equal(new[k], old[k]):
+                D[k] = new[k] @ np.linalg.inv(old[k])
+                D[k, 3] = (0.0, 0.0, 0.0, 1.0)
+        moved, outside = self.map.correct(D)
+        self._poses = [torch.from_numpy(p.astype(np.float32)).to(self.device) for p in new]
+        changed = [k for k in range(len(D)) if not np.array_equal(D[k], np.eye(4))]
+        cos = np.clip((np.trace(D[:, :3, :3], axis1=1, axis2=2) - 1.0) / 2.0, -1.0, 1.0)
+        return TrajectoryCorrection(moved=moved, outside=outside, frames=len(changed),
+                                    max_trans=float(np.linalg.norm(D[:, :3, 3], axis=1).max()),
+                                    max_rot_deg=float(np.degrees(np.arccos(cos)).max()))
+
+    @torch.no_grad()
+    def close_loop(self, first: int, last: int, c2w_last, by: str = "path") -> TrajectoryCorrection:
+        """One loop constraint: frame ``last`` of the trajectory really stood at c2w_last [4,4] (from
+        ``GaussianMap.loop_constraint``, a place recogniser, a pose graph), and frame ``first`` and the frames before it
+        are right as they are.  The correction delta = c2w_last c2w_old(last)^-1 is spread over the frames in between
+        (``spread_correction``: by the camera's path length, or by="index"), the frames after ``last`` move with it,
+        and the trajectory and the map are corrected (``correct_trajectory``)."""
+        old = self._old_poses("close_loop")
+        target = torch.as_tensor(c2w_last).detach().cpu().double().numpy()
+        if target.shape != (4, 4):
+            raise ValueError(f"c2w_last is {target.shape}, not (4, 4)")
+        if isinstance(last, bool) or not isinstance(last, (int, np.integer)) or not 0 <= last < len(old):
+            raise ValueError(f"last {last!r}: an index into the {len(old)} poses")
+        # the pose the frame already has is no correction at all, not one of the size of a rounding error
+        delta = np.eye(4) if np.array_equal(target, old[last]) else target @ np.linalg.inv(old[last])
+        D = spread_correction(old, first, last, delta, by)
+        return self.correct_trajectory(D @ old)

@@ -63,7 +63,16 @@ equations, bounds the step, moves the pose (the Cayley map, not ``apply_twist``'
 cosine, so the tests' numpy mirror gives the same bits) and writes the float32 copy the next sums are taken at -- and
 returns a ``PoseAlignment``: the pose, a status and the history of the steps.  ``Localizer(mode="map")`` aligns the
 motion model's start pose with it before the splat tracker runs.  It changes nothing in the map.  One more entry point,
-one fixed sequence of launches; one read-back."""
+one fixed sequence of launches; one read-back.
+
+Trajectory correction (``MapConfig.origins``, csrc/map_correct.hip): a row is written into the world once, at the
+estimate of the frame that saw it.  With the option every row carries the index of that frame (``origins``), and
+``correct`` moves the rows of every frame by that frame's rigid transform -- the one that takes its old pose to its
+corrected one -- in place, with the stored keyframe poses.  ``spread_correction`` makes such transforms of one loop
+constraint (the correction of the last frame, spread over the frames since the first by path length);
+``loop_constraint`` measures one against the old part of the map (``align_pose`` and ``score_poses`` on the rows up
+to a frame, a prefix of the map).  When to close a loop stays the caller's decision.  One more entry point; ``correct``
+reads back once."""
 from __future__ import annotations
 
 import functools
@@ -183,6 +192,104 @@ def apply_twist(c2w, xi) -> Tensor:
 
 
 @dataclass
+class LoopConstraint:
+    """What ``GaussianMap.loop_constraint`` returns.  alignment: the ``PoseAlignment`` of the given pose against the
+    prefix; rows: the prefix, ``rows_up_to(upto_frame)``; scores / aligned_scores: int64 [3] (tested, agree, front) of
+    the given and of the aligned pose against that prefix."""
+    alignment: PoseAlignment
+    rows: int
+    scores: np.ndarray
+    aligned_scores: np.ndarray
+
+
+def _hat(w) -> np.ndarray:
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def _se3_log(T: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """(omega, upsilon) with exp((omega, upsilon)^) = T, for a rotation below 90 degrees: float64, closed form, the
+    series where the angle is tiny."""
+    R, t = T[:3, :3], T[:3, 3]
+    s = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])  # sin(th) * axis
+    sin, cos = float(np.linalg.norm(s)), 0.5 * (float(np.trace(R)) - 1.0)
+    th = math.atan2(sin, cos)
+    if th < 1e-4:
+        w = s * (1.0 + th * th / 6.0 + 7.0 * th ** 4 / 360.0)
+        c = 1.0 / 12.0 + th * th / 720.0 + th ** 4 / 30240.0
+    else:
+        w = s * (th / sin)
+        # of th alone, not of sin and cos: a rotation that is orthonormal to float32 only has a sine and a cosine that
+        # disagree in the eighth digit, and 1 - cos would carry that into the fourth
+        c = (1.0 - 0.5 * th / math.tan(0.5 * th)) / (th * th)
+    Kw = _hat(w)
+    return w, (np.eye(3) - 0.5 * Kw + c * (Kw @ Kw)) @ t
+
+
+def _se3_exp(w: np.ndarray, v: np.ndarray) -> np.ndarray:
+    """[4,4] float64: the exponential of the twist (omega, upsilon) (Rodrigues; the series where |omega| is tiny)."""
+    th = float(np.linalg.norm(w))
+    Kw = _hat(w)
+    if th < 1e-4:
+        a, b, c = 1.0 - th * th / 6.0, 0.5 - th * th / 24.0, 1.0 / 6.0 - th * th / 120.0
+    else:
+        a, b, c = math.sin(th) / th, (1.0 - math.cos(th)) / (th * th), (th - math.sin(th)) / (th ** 3)
+    E = np.eye(4)
+    E[:3, :3] = np.eye(3) + a * Kw + b * (Kw @ Kw)
+    E[:3, 3] = (np.eye(3) + b * Kw + c * (Kw @ Kw)) @ v
+    return E
+
+
+def spread_correction(poses, first: int, last: int, delta, by: str = "path") -> np.ndarray:
+    """One loop constraint spread over a trajectory.  poses [n,4,4]: the camera-to-world poses so far; delta [4,4]: the
+    correction of frame ``last`` in the world, c2w_new(last) = delta c2w_old(last); frame ``first`` and the frames before
+    it are right as they are.  Returns D [n,4,4] float64 with c2w_new(k) = D_k c2w_old(k), D_k = exp(s_k log(delta)) on
+    SE(3): s_k = 0 for k <= first -- those D_k are the identity matrix itself, so that the rows of these frames keep
+    every bit in ``GaussianMap.correct`` -- s_k = 1 for k >= last, and in between the length of the path of the camera
+    centres from ``first`` to k over that from ``first`` to ``last`` (by="path"), or (k - first) / (last - first)
+    (by="index", and when the path has no length).  The drift of a tracker accumulates with the motion it tracked,
+    not with the count of frames: a camera that stood still for a while has not drifted there.  A ValueError for
+    first >= last, an index outside the poses, a delta that is not a rigid transform, or one that turns by 90 degrees
+    or more (no loop constraint worth closing is that far off, and the logarithm stays well conditioned)."""
+    P = torch.as_tensor(poses).detach().cpu().double().numpy()
+    if P.ndim != 3 or P.shape[1:] != (4, 4):
+        raise ValueError(f"poses are {P.shape}, not (n, 4, 4)")
+    n = len(P)
+    for name, v in (("first", first), ("last", last)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < n:
+            raise ValueError(f"{name} {v!r}: an index into the {n} poses")
+    first, last = int(first), int(last)
+    if first >= last:
+        raise ValueError(f"first {first} is not before last {last}")
+    if by not in ("path", "index"):
+        raise ValueError(f"by {by!r}: 'path' or 'index'")
+    D = torch.as_tensor(delta).detach().cpu().double().numpy()
+    if D.shape != (4, 4) or not np.isfinite(D).all():
+        raise ValueError("delta is not a finite [4,4] matrix")
+    R = D[:3, :3]
+    if (np.abs(R.T @ R - np.eye(3)).max() > 1e-5 or np.linalg.det(R) <= 0.0
+            or np.abs(D[3] - np.array([0.0, 0.0, 0.0, 1.0])).max() > 1e-9):
+        raise ValueError("delta is not a rigid transform (R^T R = 1 within 1e-5, det R > 0, last row 0 0 0 1)")
+    if not np.trace(R) - 1.0 > 1e-9:  # cos(angle) = (trace - 1) / 2; a quarter turn's own rounding does not pass
+        raise ValueError("delta turns by 90 degrees or more")
+    w, v = _se3_log(D)
+    span = np.arange(first, last + 1)
+    s = (span - first) / float(last - first)
+    if by == "path":
+        centres = P[first:last + 1, :3, 3]
+        along = np.concatenate([[0.0], np.cumsum(np.linalg.norm(np.diff(centres, axis=0), axis=1))])
+        if not np.isfinite(along).all():
+            raise ValueError("poses: a camera centre between first and last is not finite")
+        if along[-1] > 0.0:
+            s = along / along[-1]
+    out = np.tile(np.eye(4), (n, 1, 1))
+    for k in range(first + 1, n):
+        sk = 1.0 if k >= last else float(s[k - first])
+        if sk > 0.0:
+            out[k] = _se3_exp(sk * w, sk * v)
+    return out
+
+
+@dataclass
 class MapConfig:
     alpha_min: float = 0.5  # a pixel the map renders with less alpha is not covered
     depth_rho: float = 0.05  # a pixel observed more than this fraction in front of the map's depth is a new surface
@@ -283,10 +390,15 @@ class MapConfig:
     # a step within both has converged: a tenth of the smallest per-frame error of the 160x120 sequence (NOTES.md)
     align_eps_rot_deg: float = 1.5e-4
     align_eps_trans: float = 3e-5
+    # trajectory correction: every row carries the index of the frame that appended it (GaussianMap.origins), so that
+    # the rows can follow a corrected trajectory (GaussianMap.correct, Localizer.correct_trajectory / close_loop)
+    origins: bool = False
 
     def __post_init__(self):
         whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
         number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer))  # noqa: E731
+        if not isinstance(self.origins, bool):
+            raise ValueError(f"origins {self.origins!r}: True or False")
         if not isinstance(self.align, bool):
             raise ValueError(f"align {self.align!r}: True or False")
         if not whole(self.align_steps) or not 1 <= self.align_steps <= ALIGN_MAX_STEPS:
@@ -477,6 +589,15 @@ class GaussianMap:
         self._info = None
         # align_pose: one buffer of 8-byte words -- state, history, working pose, sums -- and the start pose, on first use
         self._align = None
+        # origins: the index of the frame that appended each row; nothing of it without the option.  The insertions
+        # since clear() and the last one's origin; the frame index of the keyframe in every slot (-1: not recorded);
+        # correct's two 64-bit counters on first use
+        self.origins = None
+        if config.origins:
+            self.origins = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
+        self._n_inserts, self._last_origin = 0, -1
+        self._kf_origins = np.full(int(config.keyframe_max), -1, dtype=np.int64)
+        self._correct_counters = None
 
     def _alloc_ws(self):
         if self.device.type != "cuda":
@@ -506,6 +627,8 @@ class GaussianMap:
         self._view_rows = -1
         self._n_survivors = 0
         self._kf_made = 0
+        self._n_inserts, self._last_origin = 0, -1
+        self._kf_origins[:] = -1
 
     def _image(self, a, shape, what: str) -> Tensor:
         """a as a contiguous float32 tensor of that shape on the map's device, refused unless it has that many elements."""
@@ -547,16 +670,30 @@ class GaussianMap:
 
     @torch.no_grad()
     def insert_frame(self, depth, rgb, K, c2w, render: Optional[Tensor] = None,
-                     alphas: Optional[Tensor] = None) -> Tuple[int, int]:
+                     alphas: Optional[Tensor] = None, origin: Optional[int] = None) -> Tuple[int, int]:
         """depth [H,W] metres, rgb [H,W,3] in 0..255, K [3,3], c2w [4,4] the frame's pose in the world; render / alphas
         [H,W]: the map's expected depth (metres) and alpha at that pose -- both None: every pixel with a valid depth is
         new (the first frame).  Returns (pixels selected, rows appended); they differ when the map is full.  The rows
         appended are stamped with ``frame_index``.  ``MapConfig.evict``: a frame that may not fit (n_live + W * H above
         the capacity) reads its selection's count back before the append and, when it is short of room, first evicts
         that many rows plus ``evict_headroom`` (``evict``; ``last_evicted`` counts them).  ``MapConfig.refine``: the rows
-        appended get the weight 1."""
+        appended get the weight 1.  ``MapConfig.origins``: the rows appended get the origin ``origin`` -- the index of
+        the frame in the caller's trajectory; None: the number of insert_frame calls since ``clear()`` -- which must be
+        at least 0 and at least the origin of the insertion before (a ValueError before any launch).  Every removal
+        compacts in map order and every append goes to the end, so ``origins[:n_live]`` is non-decreasing at all
+        times, and the rows of the frames up to k are a prefix of the map (``rows_up_to``).  Without the option
+        ``origin`` is not looked at."""
         if (render is None) != (alphas is None):
             raise ValueError("insert_frame: render and alphas come together (or neither, for the first frame)")
+        if self.origins is not None:
+            if origin is None:
+                origin = self._n_inserts
+            if isinstance(origin, bool) or not isinstance(origin, (int, np.integer)):
+                raise ValueError(f"origin {origin!r}: a whole frame index")
+            origin = int(origin)
+            if not 0 <= origin < 2 ** 31 or origin < self._last_origin:
+                raise ValueError(f"origin {origin}: at least 0 and at least the origin of the insertion before "
+                                 f"({self._last_origin}): the origins are non-decreasing in map order")
         hw = (self.H, self.W)
         depth, rgb = self._depth_image(depth), self._image(torch.as_tensor(rgb)[..., :3], hw + (3,), "rgb")
         if render is not None:
@@ -576,6 +713,11 @@ class GaussianMap:
             self.stamps[self.n_live:self.n_live + appended] = self.frame_index
             if self.weights is not None:
                 self.weights[self.n_live:self.n_live + appended] = 1
+            if self.origins is not None:
+                self.origins[self.n_live:self.n_live + appended] = origin
+        if self.origins is not None:
+            self._last_origin = origin
+        self._n_inserts += 1
         self.n_live += appended
         self.full = self.full or appended < selected
         return selected, appended
@@ -647,6 +789,7 @@ class GaussianMap:
             self._free = dict(means=torch.zeros(cap, 3, device=dev), colors=torch.zeros(cap, 3, device=dev),
                               stamps=torch.zeros(cap, dtype=torch.int32, device=dev),
                               weights=None if self.weights is None else torch.zeros(cap, dtype=torch.int32, device=dev),
+                              origins=None if self.origins is None else torch.zeros(cap, dtype=torch.int32, device=dev),
                               ids=torch.zeros(cap, dtype=torch.int32, device=dev),
                               counters=torch.zeros(3, dtype=torch.int32, device=dev), ws=ws)
         return self._free
@@ -658,7 +801,8 @@ class GaussianMap:
         call's one synchronisation.  stamps_early: the stamps go before the read-back, every live row at most (the count
         is not known on the host yet, and the rows past it are never read); otherwise after it, the rows stored, and
         only when something goes -- the buffers will be swapped, the stamps follow their rows.  ``MapConfig.refine``:
-        the weights follow them in the same way, by the same gather."""
+        the weights follow them in the same way, by the same gather; ``MapConfig.origins``: and so do the origins (a
+        fused voxel keeps the origin of the row that stays, the first in map order)."""
         lib, st, ptr, f = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._free_buffers()
 
         def stamps(n):
@@ -666,6 +810,9 @@ class GaussianMap:
                        "gsl_map_gather_i32")
             if self.weights is not None:
                 _lib.check(lib.gsl_map_gather_i32(ptr(self.weights), self.n_live, ptr(f["ids"]), n, ptr(f["weights"]),
+                                                  st), "gsl_map_gather_i32")
+            if self.origins is not None:
+                _lib.check(lib.gsl_map_gather_i32(ptr(self.origins), self.n_live, ptr(f["ids"]), n, ptr(f["origins"]),
                                                   st), "gsl_map_gather_i32")
 
         _lib.check(lib.gsl_map_view_gather(ptr(self.means), ptr(self.colors), self.n_live, ptr(f["means"]),
@@ -693,6 +840,8 @@ class GaussianMap:
             self.stamps, f["stamps"] = f["stamps"], self.stamps
             if self.weights is not None:
                 self.weights, f["weights"] = f["weights"], self.weights
+            if self.origins is not None:
+                self.origins, f["origins"] = f["origins"], self.origins
             self.n_live = stay
             self._view_rows = -1  # the view ballots describe other rows
         return gone, stay
@@ -816,9 +965,12 @@ class GaussianMap:
         return self._keep_survivors(stay, removed, stored)
 
     # ---- pose scores: how many live rows a depth frame confirms from each of a set of poses (csrc/map_score.hip) ----
-    def _score_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, near: float) -> np.ndarray:
+    def _score_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, near: float,
+                      n_rows: Optional[int] = None) -> np.ndarray:
         """w2c [k,4,4] float32 on the host.  The poses' copy to the device, the entry point (which zeroes the counts) and
-        the read-back of int64 [k,3]: (tested, agree, front) per pose."""
+        the read-back of int64 [k,3]: (tested, agree, front) per pose.  n_rows: the first rows of the map that are
+        judged (None: the live ones)."""
+        n_rows = self.n_live if n_rows is None else int(n_rows)
         assert depth.is_cuda, "GaussianMap.score_poses: the rows are judged and counted by a HIP kernel, no CPU path"
         lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
         if self._score is None:
@@ -826,30 +978,42 @@ class GaussianMap:
                                poses=torch.empty(SCORE_MAX_POSES, 16, device=self.device))
         k, s = w2c.shape[0], self._score
         s["poses"][:k].copy_(w2c.reshape(k, 16))
-        _lib.check(lib.gsl_map_score(ptr(self.means), self.n_live, ptr(s["poses"]), k, *intr, ptr(depth), self.W, self.H,
+        _lib.check(lib.gsl_map_score(ptr(self.means), n_rows, ptr(s["poses"]), k, *intr, ptr(depth), self.W, self.H,
                                      self.keep, self.beyond, near, ptr(s["counts"]), st), "gsl_map_score")
         return s["counts"][:k].cpu().numpy().astype(np.int64)  # the call's one synchronisation
 
     @torch.no_grad()
-    def score_poses(self, depth, K, c2ws, near: float) -> np.ndarray:
+    def score_poses(self, depth, K, c2ws, near: float, rows: Optional[int] = None) -> np.ndarray:
         """How the depth frame [H,W] (metres) agrees with the live rows from each of the poses c2ws [k,4,4] (a tensor,
         or a sequence of [4,4] poses; k <= 64).  Returns int64 [k,3]: per pose the rows TESTED (in the image, beyond the
         near plane, their own pixel has a depth), those that AGREE (within ``depth_rho`` of that depth either way) and
         those in FRONT of it (the rule: include/gsloc_hip.h); tested - agree - front lie behind, where a frame that
         sees a nearer surface says nothing against them.  One launch for all poses, one read-back; an empty map gives
-        zeros without a launch."""
+        zeros without a launch.  rows: only the first that many rows of the map are judged (``loop_constraint``; None:
+        every live row)."""
+        rows = self._prefix(rows)
         poses = [torch.as_tensor(c) for c in c2ws]
         for c in poses:
             if c.shape != (4, 4):
                 raise ValueError(f"a pose is {tuple(c.shape)}, not (4, 4)")
         if len(poses) > SCORE_MAX_POSES:
             raise ValueError(f"{len(poses)} poses: one call scores at most {SCORE_MAX_POSES}")
-        if self.n_live == 0 or not poses:
+        if (self.n_live if rows is None else rows) == 0 or not poses:
             return np.zeros((len(poses), 3), dtype=np.int64)
         depth = self._depth_image(depth)
         intr, _ = _intr_and_pose(K, poses[0])
-        return self._score_launch(depth, intr, _world_to_camera(torch.stack([c.detach().cpu().double() for c in poses])),
-                                  float(near))
+        w2c = _world_to_camera(torch.stack([c.detach().cpu().double() for c in poses]))
+        if rows is None:
+            return self._score_launch(depth, intr, w2c, float(near))
+        return self._score_launch(depth, intr, w2c, float(near), n_rows=rows)
+
+    def _prefix(self, rows: Optional[int]) -> Optional[int]:
+        """rows as a count of leading live rows (None stays None), refused outside 0 .. n_live."""
+        if rows is None:
+            return None
+        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 0 <= int(rows) <= self.n_live:
+            raise ValueError(f"rows {rows!r}: a whole number of leading rows, 0 .. {self.n_live}")
+        return int(rows)
 
     # ---- pose information: the normal equations of a pose from the rows against a depth frame (csrc/map_info.hip) ------
     def _info_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, keep: float,
@@ -900,10 +1064,11 @@ class GaussianMap:
     # ---- pose alignment: Gauss-Newton steps on those normal equations, iterated on the device (csrc/map_align.hip) ----
     def _align_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, keep: float,
                       beyond: float, kappa: float, near: float, steps: int, damping: float, min_used: int,
-                      max_rot: float, max_trans: float, eps_rot: float, eps_trans: float):
+                      max_rot: float, max_trans: float, eps_rot: float, eps_trans: float, n_rows: Optional[int] = None):
         """w2c [4,4] float32 on the host.  Its copy to the device, the entry point and the read-back of one buffer, the
         call's one synchronisation: (pose [3,4] float64, working pose [4,4] float32, steps applied, rows [steps,4] int64
-        = (status, used, tested, rss_fixed), xi [steps,6] float64)."""
+        = (status, used, tested, rss_fixed), xi [steps,6] float64).  n_rows: the first rows of the map that are summed
+        over (None: the live ones)."""
         assert depth.is_cuda, "GaussianMap.align_pose: the pose is aligned by HIP kernels, no CPU path"
         lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
         n_state, n_hist = ALIGN_STATE_WORDS, ALIGN_MAX_STEPS * ALIGN_ROW_WORDS
@@ -911,9 +1076,10 @@ class GaussianMap:
             self._align = dict(words=torch.zeros(n_state + n_hist + 8 + INFO_VALUES, dtype=torch.int64, device=self.device),
                                start=torch.empty(16, device=self.device))
         a = self._align
+        n_rows = self.n_live if n_rows is None else int(n_rows)
         words, base = a["words"], a["words"].data_ptr()
         a["start"].copy_(w2c.reshape(16))
-        _lib.check(lib.gsl_map_pose_align(ptr(self.means), self.n_live, ptr(a["start"]), *intr, ptr(depth), self.W, self.H,
+        _lib.check(lib.gsl_map_pose_align(ptr(self.means), n_rows, ptr(a["start"]), *intr, ptr(depth), self.W, self.H,
                                           keep, beyond, kappa, near, steps, damping, min_used, max_rot, max_trans,
                                           eps_rot, eps_trans, base + 8 * (n_state + n_hist + 8), base + 8 * (n_state + n_hist),
                                           base, base + 8 * n_state, st), "gsl_map_pose_align")
@@ -927,7 +1093,8 @@ class GaussianMap:
     def align_pose(self, depth, K, c2w, near_plane: float, steps: Optional[int] = None, rho: Optional[float] = None,
                    kappa: Optional[float] = None, damping: Optional[float] = None, max_rot_deg: Optional[float] = None,
                    max_trans: Optional[float] = None, eps_rot_deg: Optional[float] = None,
-                   eps_trans: Optional[float] = None, min_used: int = ALIGN_MIN_USED) -> PoseAlignment:
+                   eps_trans: Optional[float] = None, min_used: int = ALIGN_MIN_USED,
+                   rows: Optional[int] = None) -> PoseAlignment:
         """The pose c2w [4,4] aligned to the map against the depth frame [H,W] (metres): up to ``steps`` (None:
         ``align_steps``) damped Gauss-Newton steps on the normal equations of ``pose_information`` -- the rows chosen
         with ``rho`` (None: ``align_rho``, and ``depth_rho`` when that is None) and ``kappa`` (None: ``info_kappa``),
@@ -936,8 +1103,10 @@ class GaussianMap:
         device in float64 (the rule: include/gsloc_hip.h).  The start is rounded to float32 as every pose a kernel is
         given.  Changes nothing in the map.  One fixed sequence of 1 + 3 ``steps`` launches, one read-back; an empty
         map gives status FEW without a launch.  The result has to be checked by the caller: a start too far off can
-        settle elsewhere (NOTES.md, "Pose alignment")."""
+        settle elsewhere (NOTES.md, "Pose alignment").  rows: only the first that many rows of the map are used
+        (``loop_constraint``; None: every live row)."""
         cfg = self.cfg
+        rows = self._prefix(rows)
         steps = int(cfg.align_steps if steps is None else steps)
         if not 1 <= steps <= ALIGN_MAX_STEPS:
             raise ValueError(f"steps {steps!r}: a whole number of iterations, 1 .. {ALIGN_MAX_STEPS}")
@@ -965,20 +1134,93 @@ class GaussianMap:
         depth = self._depth_image(depth)
         intr, c2w = _intr_and_pose(K, c2w)
         w2c = _world_to_camera(c2w)
-        if self.n_live == 0:
-            pose, n, rows, xis = w2c.numpy()[:3].astype(np.float64), 0, np.zeros((1, 4), np.int64), np.zeros((1, 6))
-            rows[0, 0] = ALIGN_STATUS.index("FEW")
+        if (self.n_live if rows is None else rows) == 0:
+            pose, n, hist, xis = w2c.numpy()[:3].astype(np.float64), 0, np.zeros((1, 4), np.int64), np.zeros((1, 6))
+            hist[0, 0] = ALIGN_STATUS.index("FEW")
         else:
             keep, beyond = float(np.float32(1.0) - np.float32(rho)), float(np.float32(1.0) + np.float32(rho))
-            pose, _, n, rows, xis = self._align_launch(depth, intr, w2c.contiguous(), keep, beyond,
+            prefix = {} if rows is None else dict(n_rows=rows)
+            pose, _, n, hist, xis = self._align_launch(depth, intr, w2c.contiguous(), keep, beyond,
                                                        float(np.float32(kappa)), float(near_plane), steps, damping,
-                                                       min_used, max_rot, max_trans, eps_rot, eps_trans)
+                                                       min_used, max_rot, max_trans, eps_rot, eps_trans, **prefix)
         w2c64 = np.eye(4)
         w2c64[:3] = pose
         history = [(ALIGN_STATUS[int(r[0])], int(r[1]), int(r[2]), float(r[3]) / INFO_ONE, np.array(x, dtype=np.float64))
-                   for r, x in zip(rows, xis)]
+                   for r, x in zip(hist, xis)]
         aligned = torch.from_numpy(np.linalg.inv(w2c64).astype(np.float32)).to(self.device)
         return PoseAlignment(aligned, w2c64, history[-1][0], int(n), history[-1][1], history[-1][2], history)
+
+    # ---- trajectory correction: the rows follow the frame they came from (csrc/map_correct.hip) ----------------------
+    @torch.no_grad()
+    def rows_up_to(self, frame: int) -> int:
+        """How many live rows have an origin <= frame.  The origins are non-decreasing in map order, so these rows are
+        the first that many of the map: one ``torch.searchsorted`` and one read-back."""
+        if self.origins is None:
+            raise RuntimeError("rows_up_to: MapConfig.origins is False, the map keeps no origins")
+        if self.n_live == 0:
+            return 0
+        frame = max(min(int(frame), 2 ** 31 - 1), -1)
+        key = torch.tensor([frame], dtype=torch.int32, device=self.origins.device)
+        return int(torch.searchsorted(self.origins[: self.n_live], key, right=True).item())
+
+    def _correct_launch(self, table: Tensor) -> Tuple[int, int]:
+        """table [n_frames,12] float32 on the host.  Its copy to the device, the entry point (which zeroes the counters)
+        over the live rows, in place, and the read-back of (rows moved, rows with an origin outside the table), the
+        call's one synchronisation."""
+        assert self.means.is_cuda, "GaussianMap.correct: the rows are moved by a HIP kernel, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        if self._correct_counters is None:
+            self._correct_counters = torch.zeros(2, dtype=torch.int64, device=self.device)
+        on_device = table.to(self.device).contiguous()
+        _lib.check(lib.gsl_map_correct(ptr(self.means), ptr(self.origins), self.n_live, ptr(on_device),
+                                       int(table.shape[0]), ptr(self._correct_counters), st), "gsl_map_correct")
+        moved, outside = self._correct_counters.tolist()
+        return moved, outside
+
+    @torch.no_grad()
+    def correct(self, transforms) -> Tuple[int, int]:
+        """Moves the live rows with their frames: transforms [n_frames,4,4], per frame of the trajectory the rigid
+        transform of the world that takes its old pose to its corrected one (c2w_new = D c2w_old); a row with the
+        origin k becomes D_k applied to it, in float32 (the rule: include/gsloc_hip.h).  A row whose D_k is exactly
+        the identity, a row that is not finite and a row whose origin lies outside the transforms keeps every bit.
+        Only the means move: colours, stamps, weights and origins stay.  In place: ``points`` stays valid and shows the
+        moved rows.  The pose of every keyframe with a recorded frame index (``add_keyframe``'s origin) inside the
+        transforms moves as well, pose <- D_k pose in float64, stored as float32.  Returns (rows moved, rows with an
+        origin outside the transforms).  One copy of the float32 [n_frames,12] table to the device, one zeroing launch,
+        one kernel, one read-back; an empty map gives (0, 0) without a launch.  When a row moved, the next
+        ``view_violations`` needs a fresh ``select_view``, as after a removal."""
+        if self.origins is None:
+            raise RuntimeError("correct: MapConfig.origins is False, the map keeps no origins")
+        T = torch.as_tensor(transforms).detach().cpu().double().numpy()
+        if T.ndim != 3 or T.shape[0] < 1 or T.shape[1:] != (4, 4):
+            raise ValueError(f"transforms are {T.shape}, not (n_frames >= 1, 4, 4)")
+        if not np.isfinite(T).all():
+            raise ValueError("transforms: some entry is not finite")
+        moved, outside = 0, 0
+        if self.n_live > 0:
+            table = np.ascontiguousarray(T[:, :3, :].astype(np.float32).reshape(-1, 12))
+            moved, outside = self._correct_launch(torch.from_numpy(table))
+        if moved > 0:
+            self._view_rows = -1  # the view ballots describe rows that lay elsewhere
+        for slot in range(self.n_keyframes):
+            k = int(self._kf_origins[slot])
+            if 0 <= k < len(T):
+                self._kf_poses[slot] = (T[k] @ self._kf_poses[slot].astype(np.float64)).astype(np.float32)
+        return int(moved), int(outside)
+
+    @torch.no_grad()
+    def loop_constraint(self, depth, K, c2w, upto_frame: int, near_plane: float, **align) -> "LoopConstraint":
+        """A loop constraint from the map itself: the pose c2w [4,4] of a frame that sees an old part of the map again,
+        aligned against the rows of the frames up to ``upto_frame`` only -- ``rows_up_to(upto_frame)``, a prefix of the
+        map; the rows the drifted frames since then wrote beside it take no part -- by ``align_pose`` (``align``: its
+        keyword arguments), and the scores (``score_poses``) of the given and of the aligned pose against the same
+        prefix.  Changes nothing in the map.  Whether to trust the result, and what to do with it
+        (``spread_correction``, ``correct``), is the caller's decision."""
+        n = self.rows_up_to(upto_frame)
+        al = self.align_pose(depth, K, c2w, near_plane, rows=n, **align)
+        scores = self.score_poses(depth, K, [torch.as_tensor(c2w).detach().cpu(), al.c2w.detach().cpu()], near_plane,
+                                  rows=n)
+        return LoopConstraint(al, n, scores[0], scores[1])
 
     # ---- refinement: the rows a depth frame observes again move to the running mean of their depths (csrc/map_refine.hip)
     def _refine_launch(self, depth: Tensor, rgb: Optional[Tensor], intr: Tuple[float, float, float, float], w2c: Tensor,
@@ -1059,7 +1301,7 @@ class GaussianMap:
         return desc
 
     @torch.no_grad()
-    def add_keyframe(self, depth, c2w) -> Optional[int]:
+    def add_keyframe(self, depth, c2w, origin: Optional[int] = None) -> Optional[int]:
         """Keeps the frame -- its pose c2w [4,4] on the host, its descriptor on the device -- as a keyframe when the
         pose is further than ``keyframe_rot_deg`` degrees or further than ``keyframe_trans`` metres from the pose of
         every stored keyframe (the first frame always is one); decided on the host from the stored poses alone, and
@@ -1068,7 +1310,12 @@ class GaussianMap:
 
         Keyframes describe frames, not rows: eviction, free space and merging leave them alone.  A keyframe whose rows
         have all gone is harmless -- the candidate poses around it test too few rows and are rejected by the rule that
-        every estimate is held against (``reloc_min_tested``)."""
+        every estimate is held against (``reloc_min_tested``).
+
+        origin: the index of the frame in the caller's trajectory; ``correct`` moves the pose of a keyframe that has
+        one with its frame, and leaves a keyframe without one (None) alone."""
+        if origin is not None and (isinstance(origin, bool) or not isinstance(origin, (int, np.integer)) or origin < 0):
+            raise ValueError(f"origin {origin!r}: a whole frame index, at least 0 (or None)")
         if not self.cfg.keyframes:
             raise RuntimeError("add_keyframe: MapConfig.keyframes is False, the map keeps no keyframes")
         depth = self._depth_image(depth)
@@ -1089,6 +1336,7 @@ class GaussianMap:
         slot = self._kf_made % int(self.cfg.keyframe_max)
         self._describe_launch(depth, self._place_buffers()["table"][slot])
         self._kf_poses[slot] = pose
+        self._kf_origins[slot] = -1 if origin is None else int(origin)
         self._kf_made += 1
         return slot
 

@@ -472,6 +472,31 @@ int gsl_map_refine(float* means, float* colors, int32_t* weights, int64_t n_rows
                    const float* rgb, int width, int height, float keep, float near_plane, int max_weight,
                    int32_t* counters, void* stream);
 
+/* ---- trajectory correction: the rows follow the frame they came from (csrc/map_correct.hip) ----
+ * means[n_rows,3] float32 and origins[n_rows] int32 on the device, as in the map: origins[i] is the index, in the
+ * trajectory, of the frame that appended row i.  table[n_frames,12] float32 on the device: per frame a row-major 3 x 4
+ * [R | t], the rigid transform of the world that takes the frame's old pose to its corrected one.  counters is
+ * int64[2]; it need not be initialised, the entry point zeroes it on the stream.  Row i with mean (x, y, z),
+ * o = origins[i] and e = table[12 o .. 12 o + 11]:
+ *   OUTSIDE   when o < 0 or o >= n_frames;
+ *   MOVED     when not outside, x, y and z are finite, and e is not the identity: some of the twelve comparisons
+ *             e0 == 1, e1 == 0, e2 == 0, e3 == 0, e4 == 0, e5 == 1, e6 == 0, e7 == 0, e8 == 0, e9 == 0, e10 == 1,
+ *             e11 == 0 is false (-0.0 counts as 0);
+ *   a moved row becomes  x' = ((e0 x + e1 y) + e2 z) + e3,  y' = ((e4 x + e5 y) + e6 z) + e7,
+ *             z' = ((e8 x + e9 y) + e10 z) + e11;
+ *   every other row keeps every bit of its mean: a NaN or inf row, a -0.0 coordinate under an identity entry, an
+ *             origin outside the table.  Only the means are ever written;
+ *   counters[0] = rows moved, counters[1] = rows outside (integer sums: they do not depend on the order of rows, waves
+ *             or workgroups).
+ * float32, evaluated exactly as written (one rounding per operation, no fused operation), comparisons false for a NaN.
+ * In place: a thread reads and writes its own row only.  One zeroing launch and one kernel; the number of global
+ * atomics is bounded by the kernel's grid cap, not by n_rows.  n_rows == 0 is GSL_OK without a launch (the counters
+ * are then not touched).
+ * Returns GSL_ERR_BAD_ARG before any launch for a NULL means, origins, table or counters, n_frames < 1, n_rows < 0 or
+ * >= 2^31. */
+int gsl_map_correct(float* means, const int32_t* origins, int64_t n_rows, const float* table, int n_frames,
+                    int64_t* counters, void* stream);
+
 /* ---- spherical harmonics: gsplat.spherical_harmonics fwd/bwd (IDX:14306, IDX:14297) ----
  * dirs[M,3], coeffs[M,K,3] with K >= (degree+1)^2, masks[M] (uint8, may be NULL).
  * degree 0..3.  v_dirs may be NULL. */
