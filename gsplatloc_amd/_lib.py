@@ -74,6 +74,8 @@ _SIGNATURES = {
     "gsl_map_refine": (c_int, [P, P, P, c_int64, P, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P, P,
                                c_int, c_int, c_float, c_float, c_int, P, P]),
     "gsl_map_correct": (c_int, [P, P, c_int64, P, c_int, P, P]),
+    "gsl_map_covis": (c_int, [P, P, c_int64, P, c_float, c_float, c_float, c_float, P, c_int, c_int, c_float, c_float,
+                              c_float, c_int, P, P, P]),
     "gsl_sh_fwd": (c_int, [c_int, P, P, P, c_int, c_int, P, P]),
     "gsl_sh_bwd": (c_int, [c_int, P, P, P, c_int, c_int, P, P, P, P]),
     "gsl_isect_ws_bytes": (c_size_t, [c_int]),

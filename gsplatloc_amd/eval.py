@@ -43,7 +43,7 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   map_keyframe_rot_deg: Optional[float] = None, map_keyframe_trans: Optional[float] = None,
                   map_refine: bool = False, map_refine_max_weight: Optional[int] = None,
                   map_info: bool = False, map_align: bool = False, map_align_steps: Optional[int] = None,
-                  map_origins: bool = False) -> Dict:
+                  map_origins: bool = False, map_loop: bool = False, map_loop_min_gap: Optional[int] = None) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -95,6 +95,13 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         raise ValueError("map_info belongs to the map mode (map_mode=True)")
     if map_origins and not map_mode:
         raise ValueError("map_origins belongs to the map mode (map_mode=True)")
+    if (map_loop or map_loop_min_gap is not None) and not map_mode:
+        raise ValueError("map_loop belongs to the map mode (map_mode=True)")
+    if map_loop_min_gap is not None and not map_loop:
+        raise ValueError("map_loop_min_gap: an option of map_loop=True")
+    loop = None
+    if map_loop:
+        loop = dict(loop=True, **({} if map_loop_min_gap is None else {"loop_min_gap": map_loop_min_gap}))
     if (map_align or map_align_steps is not None) and not map_mode:
         raise ValueError("map_align belongs to the map mode (map_mode=True)")
     if map_align_steps is not None and not map_align:
@@ -111,7 +118,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                                    map_free_rho, map_free_window, map_evict, map_merge_voxel, map_merge_every,
                                    dict(reloc, reloc=True) if map_reloc else None,
                                    dict(keyframes, keyframes=True) if map_keyframes else None, map_refine=refine,
-                                   map_info=bool(map_info), map_align=align, map_origins=bool(map_origins))
+                                   map_info=bool(map_info), map_align=align, map_origins=bool(map_origins) or bool(map_loop),
+                                   map_loop=loop)
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -177,7 +185,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                         map_evict: bool = False, map_merge_voxel: Optional[float] = None,
                         map_merge_every: int = 1, map_reloc: Optional[Dict] = None,
                         map_keyframes: Optional[Dict] = None, map_refine: Optional[Dict] = None,
-                        map_info: bool = False, map_align: Optional[Dict] = None, map_origins: bool = False) -> Dict:
+                        map_info: bool = False, map_align: Optional[Dict] = None, map_origins: bool = False,
+                        map_loop: Optional[Dict] = None) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
     map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
@@ -200,7 +209,12 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     the translation errors motion_eT_per_frame / start_eT_per_frame of the motion model's pose and of the pose the
     tracker started from.  map_origins: MapConfig.origins, every row carries the index of the frame that appended it; the
     report gains origins_non_decreasing (checked after every frame) and rows_per_origin (the live rows at the end that
-    came from frame 0, 1, ...).  No correction is applied: that is the caller's decision (``Localizer.close_loop``)."""
+    came from frame 0, 1, ...).  No correction is applied: that is the caller's decision (``Localizer.close_loop``) --
+    unless map_loop: MapConfig fields of the loop closure in ``track()`` (loop=True and, where wanted, loop_min_gap; it
+    needs map_origins); every frame that attempts a loop prints what became of it, and the report gains
+    loop_status_per_frame, loop_closures (the frames that closed a loop), loop_anchors (the frame each of those edges
+    starts at), loop_edge_residuals (of every kept edge after the last solve) and ate_corrected (the RMSE of the final,
+    corrected trajectory's translation errors; ATE is that of the estimates as they were made)."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
@@ -212,7 +226,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                                                        merge_every=map_merge_every, **(map_reloc or {}),
                                                        **(map_keyframes or {}), **(map_refine or {}),
                                                        info=bool(map_info), **(map_align or {}),
-                                                       origins=bool(map_origins)))
+                                                       origins=bool(map_origins), **(map_loop or {})))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
@@ -223,6 +237,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     sigma_t, sigma_r, info_used, info_eig, weak = [], [], [], [], 0
     aligned, align_steps, align_status, motion_eT, start_eT = [], [], [], [], []
     ordered = True
+    loop_status, closures, anchors, gts = [], [], [], [pose]
     for i in range(1, n + 1):
         depth, rgb, pose = parser.frame(i)
         r = loc.track(depth, rgb, gt_c2w=pose)
@@ -263,6 +278,16 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             start_eT.append(float(torch.norm(r.init_c2w[:3, 3] - gt_t)))
             print(f"frame {i}: pose alignment: {r.align_status} after {r.align_steps} steps, moved {r.align_moved_t:.3e} m "
                   f"{r.align_moved_r_deg:.3e} deg, taken {r.aligned}: start eT {motion_eT[-1]:.3e} -> {start_eT[-1]:.3e}")
+        if map_loop:
+            gts.append(pose)
+            loop_status.append(r.loop_status)
+            if r.loop:
+                closures.append(i)
+                anchors.append(r.loop_anchor)
+            if r.loop_status not in (None, "waiting"):
+                moved = "" if r.loop_moved_t is None else f", moved {r.loop_moved_t:.3e} m {r.loop_moved_r_deg:.3e} deg"
+                print(f"frame {i}: loop: {r.loop_status}, {r.loop_old_tested} old rows tested{moved}"
+                      + (f", anchor {r.loop_anchor}, {r.loop_correction.moved} rows moved" if r.loop else ""))
         if map_origins:
             o = loc.map.origins[: loc.map.n_live]
             ordered = ordered and bool((o[1:] >= o[:-1]).all())
@@ -296,7 +321,13 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                 "motion_eT_per_frame": motion_eT, "start_eT_per_frame": start_eT} if map_align else {}),
             **({"origins": True, "origins_non_decreasing": ordered,
                 "rows_per_origin": torch.bincount(loc.map.origins[: loc.map.n_live].long().cpu(),
-                                                  minlength=n + 1).tolist()} if map_origins else {})}
+                                                  minlength=n + 1).tolist()} if map_origins else {}),
+            **({"loop": True, "loop_status_per_frame": loop_status, "loop_closures": closures, "loop_anchors": anchors,
+                "loop_edge_residuals": ([] if loc.last_pose_graph is None
+                                        else [float(v) for v in loc.last_pose_graph.loop_residuals]),
+                "ate_corrected": float(torch.sqrt(torch.mean(torch.stack(
+                    [torch.sum((a[:3, 3].cpu() - b[:3, 3].cpu()) ** 2) for a, b in zip(loc.trajectory[1:], gts[1:])]))))
+                } if map_loop else {})}
 
 
 def main(argv=None):
@@ -364,6 +395,13 @@ def main(argv=None):
                     help="--map: every point of the map carries the index of the frame that appended it, so that the map "
                          "can follow a corrected trajectory; the report says that the origins stayed non-decreasing in map "
                          "order and how many live points came from each frame (no correction is applied)")
+    ap.add_argument("--map-loop", action="store_true",
+                    help="--map: loops are closed while tracking -- a frame that sees the points of much older frames again "
+                         "is aligned against those alone, and a pose graph over the tracked odometry and every such "
+                         "constraint corrects the trajectory and the map (implies --map-origins); the report lists the "
+                         "closures and their anchors")
+    ap.add_argument("--map-loop-min-gap", type=int, default=None, metavar="G",
+                    help="--map-loop: only frames at least G behind the current one count as old (default 30)")
     ap.add_argument("--map-info", action="store_true",
                     help="--map: pose information -- every frame that is not lost prints the standard deviations of its "
                          "pose (metres, degrees) from the map's points against its depth image, the points used, the "
@@ -410,6 +448,10 @@ def main(argv=None):
         ap.error("--map-info needs --map")
     if a.map_origins and not a.map:
         ap.error("--map-origins needs --map")
+    if a.map_loop and not a.map:
+        ap.error("--map-loop needs --map")
+    if a.map_loop_min_gap is not None and not a.map_loop:
+        ap.error("--map-loop-min-gap needs --map-loop")
     if a.map_align and not a.map:
         ap.error("--map-align needs --map")
     if a.map_align_steps is not None and not a.map_align:
@@ -427,7 +469,8 @@ def main(argv=None):
                           map_keyframe_rot_deg=a.map_keyframe_rot_deg, map_keyframe_trans=a.map_keyframe_trans,
                           map_refine=a.map_refine, map_refine_max_weight=a.map_refine_max_weight,
                           map_info=a.map_info, map_align=a.map_align, map_align_steps=a.map_align_steps,
-                          map_origins=a.map_origins)
+                          map_origins=a.map_origins or a.map_loop, map_loop=a.map_loop,
+                          map_loop_min_gap=a.map_loop_min_gap)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

@@ -53,7 +53,12 @@ is what the frame starts from when the map scores it no worse than the motion mo
 With ``MapConfig.origins`` the map can follow a corrected trajectory: every row carries the index its frame's pose has
 in ``trajectory``, and ``correct_trajectory`` (any new poses) or ``close_loop`` (one constraint on one frame, spread over
 the frames of the loop) moves the rows, the keyframe poses and the poses themselves (``GaussianMap.correct``).  Neither
-is called by ``track``: when a loop is closed is the caller's decision.
+is called by ``track``: when a loop is closed is the caller's decision -- unless
+``MapConfig.loop`` is on: then ``track`` looks for a loop itself.  Every ``loop_every``-th frame that is not lost, before
+anything touches the map, is held against the rows of the frames at least ``loop_min_gap`` behind it
+(``GaussianMap.covisibility``, ``loop_constraint``); an alignment against those rows alone that converged, agrees with
+them and moved the estimate becomes a loop edge (``add_loop``) of a pose graph over the tracked odometry and every edge
+so far (``optimise_pose_graph``), and the trajectory and the map follow its solution.
 """
 from __future__ import annotations
 
@@ -67,7 +72,7 @@ from torch import Tensor
 
 from .data.dataset import build_pair
 from .data.normalize import denormalize_camera, transform_cameras
-from .mapping import SCORE_MAX_POSES, GaussianMap, MapConfig, spread_correction
+from .mapping import SCORE_MAX_POSES, GaussianMap, MapConfig, optimise_pose_graph, spread_correction
 from .my_gsplat.geometry import construct_full_pose, depth_to_points, init_gs_scales, render_depth_alpha
 from .my_gsplat.trainer import TrackerConfig, calculate_rotation_error, calculate_translation_error
 from .my_gsplat.transform import normalize_quaternion, quat_to_rotation_matrix, rotation_matrix_to_quaternion
@@ -144,6 +149,19 @@ class LocalizeResult:
     align_moved_t: Optional[float] = None
     align_moved_r_deg: Optional[float] = None
     align_scores: Optional[tuple] = None
+    # loop (None with the option off): loop -- this frame closed a loop; loop_status: what the policy ended with, one of
+    # ``LOOP_STATUS`` (None on a lost frame, which is not asked); loop_old_tested: the rows of the frames at least
+    # loop_min_gap behind that the frame tests from its estimate; loop_anchor: the frame the loop edge starts at;
+    # loop_moved_t [m] / loop_moved_r_deg: from the estimate to the pose aligned against the old rows;
+    # loop_correction: the ``TrajectoryCorrection`` of the closure.  On a frame that closed a loop c2w is the corrected
+    # pose of the frame
+    loop: Optional[bool] = None
+    loop_status: Optional[str] = None
+    loop_old_tested: Optional[int] = None
+    loop_anchor: Optional[int] = None
+    loop_moved_t: Optional[float] = None
+    loop_moved_r_deg: Optional[float] = None
+    loop_correction: Optional["TrajectoryCorrection"] = None
 
 
 @dataclass
@@ -157,6 +175,9 @@ class TrajectoryCorrection:
     frames: int
     max_trans: float
     max_rot_deg: float
+
+
+LOOP_STATUS = ("waiting", "few_rows", "not_converged", "rejected", "small", "closed")
 
 
 def _step(axis: int, rot_deg: float = 0.0, trans: float = 0.0) -> Tensor:
@@ -285,7 +306,15 @@ class Localizer:
     start.  A pose that is not taken is dropped and the frame runs as without the option.  ``LocalizeResult.aligned`` /
     ``align_status`` / ``align_steps`` / ``align_from`` (the motion model's pose) / ``align_moved_t`` /
     ``align_moved_r_deg`` / ``align_scores`` say what happened.  Nothing in the map is written.  With the option off
-    there is no call, and poses, step counts and the map are bit for bit those of the run without it.  Everything else
+    there is no call, and poses, step counts and the map are bit for bit those of the run without it.
+    ``map_config.origins``: every appended pose is recorded with its odometry measurement, the float64 relative pose to
+    the pose before it as it was appended (``reset`` clears the record, ``correct_trajectory`` leaves it alone), which
+    is what ``add_loop`` builds its pose graph on.  ``map_config.loop``: for a frame that is not lost, before the pose
+    information and before anything is rendered, refined, stamped, inserted or removed, ``track`` looks for a loop
+    (``_try_loop`` has the steps; ``LocalizeResult.loop`` / ``loop_status`` / ``loop_old_tested`` / ``loop_anchor`` /
+    ``loop_moved_t`` / ``loop_moved_r_deg`` / ``loop_correction``).  A frame that closes one has the corrected pose as
+    its ``c2w``, and its insertion render is made from a new pair at that pose.  With no closure poses, step counts and
+    the map are bit for bit those of the run without the option.  Everything else
     -- normalisation, the re-rendered query depth, the scales, the hand-over, ``best_c2w`` -- is the frame mode's."""
 
     def __init__(self, K: Tensor, width: int, height: int, config: TrackerConfig = TrackerConfig(),
@@ -323,6 +352,13 @@ class Localizer:
         self._info = False  # MapConfig.info
         self._align = False  # MapConfig.align
         self._origins = False  # MapConfig.origins
+        self._loop = None  # the MapConfig when MapConfig.loop is on
+        self._loop_min_rows = 0  # MapConfig.loop_min_rows, or its default for this image size
+        self._loop_weight, self._loop_by = 1e4, "index"  # MapConfig.loop_weight / loop_by (add_loop)
+        self._odometry: List[np.ndarray] = []  # origins: float64 [4,4] per appended pose, inv(poses[-2]) poses[-1]
+        self._loops: list = []  # the loop edges so far: (anchor, last, Z, weight)
+        self._loop_last = 0  # the frame of the last attempt at a loop
+        self.last_pose_graph = None  # the ``PoseGraphResult`` of the last add_loop
         self._tracked = 0  # calls of track since reset
         self.merged_at_reset = None  # merge_voxel: rows the merge after reset's insertion removed
         if self.map_mode:
@@ -337,6 +373,11 @@ class Localizer:
             self._info = bool(map_config.info)
             self._align = bool(map_config.align)
             self._origins = bool(map_config.origins)
+            self._loop_weight, self._loop_by = float(map_config.loop_weight), map_config.loop_by
+            if map_config.loop:
+                self._loop = map_config
+                self._loop_min_rows = (map_config.loop_min_rows if map_config.loop_min_rows is not None
+                                       else (self.W * self.H) // 8)
             if map_config.reloc:
                 self._reloc = map_config
                 self._min_tested = (map_config.reloc_min_tested if map_config.reloc_min_tested is not None
@@ -442,6 +483,7 @@ class Localizer:
         pose = torch.eye(4) if c2w is None else torch.as_tensor(c2w, dtype=torch.float32)
         self._prev = (pts, col)
         self._poses = [pose.to(self.device).clone()]
+        self._odometry, self._loops, self._loop_last, self.last_pose_graph = [], [], 0, None
         if self.map_mode:
             self.map.clear()
             first = dict(origin=0) if self._origins else {}  # the index of the frame's pose in the trajectory
@@ -534,6 +576,10 @@ class Localizer:
             (N, scales, res, best, est), d, init, verdict = kept
         self._prev = (pts, col)
         self._poses.append(est)
+        if self._origins:
+            # the odometry measurement, taken when the pose is appended: what was tracked, whatever is corrected later
+            a, b = (p.detach().cpu().double().numpy() for p in self._poses[-2:])
+            self._odometry.append(np.linalg.inv(a) @ b)
         out = LocalizeResult(c2w=est, init_c2w=init, steps=steps, best_step=res.best_step, best_loss=res.best_loss,
                              lost=lost)
         if verdict is not None:
@@ -549,11 +595,25 @@ class Localizer:
             out.merged = 0 if self._merge_every else None
             out.refined = 0 if self._refine else None
             self._tracked += 1
+            if self._loop is not None:
+                out.loop = False
             if not out.lost:  # a lost frame's pose is a guess: it adds nothing
+                if self._loop is not None:
+                    # before anything touches the map: at a drifted pose the free-space rule would take correct old
+                    # rows for ghosts, and the rows this frame appends should land where the closed loop puts them
+                    self._try_loop(out, depth, est)
+                    if out.loop:
+                        est = out.c2w = self._poses[-1]
                 if self._info:
                     # the frame's final estimate against the map as it was tracked: before anything below touches it
                     self._report_information(out, self.map.pose_information(depth, self.K, est, self.cfg.gs.near_plane))
                 at = best
+                if out.loop:
+                    # the rows have moved and the estimate with them: the insertion render is made from a new pair at
+                    # the corrected pose (no second tracking), as below where the band did not hold
+                    d = self._map_pair(est, frame)
+                    scales = init_gs_scales(d.tar_points)
+                    at = transform_cameras(d.norm_T, est.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else est
                 if self._view_guard is not None:
                     # the band is checked against the estimate, not assumed: rows that reach into the view from there
                     # and were not tracked would render as an empty border, and insert_frame would add them a second
@@ -624,6 +684,73 @@ class Localizer:
         return TrajectoryCorrection(moved=moved, outside=outside, frames=len(changed),
                                     max_trans=float(np.linalg.norm(D[:, :3, 3], axis=1).max()),
                                     max_rot_deg=float(np.degrees(np.arccos(cos)).max()))
+
+    @torch.no_grad()
+    def add_loop(self, anchor: int, last: int, c2w_last, weight: Optional[float] = None) -> TrajectoryCorrection:
+        """One more loop constraint for the pose graph, the counterpart of ``close_loop`` that several constraints can
+        share a trajectory through: frame ``last`` stood at c2w_last [4,4] as seen from frame ``anchor`` where it is now
+        -- the edge (anchor, last, pose(anchor)^-1 c2w_last, weight; None: ``MapConfig.loop_weight``) joins the edges
+        kept since ``reset``.  The graph of the tracked odometry (the relative pose of every appended pose to the one
+        before, as it was appended) and all loop edges is optimised from the current trajectory
+        (``optimise_pose_graph``, odometry weights by ``MapConfig.loop_by``), the frames up to the smallest anchor of
+        any edge held, and the trajectory and the map are corrected (``correct_trajectory``).  ``last_pose_graph`` keeps
+        the ``PoseGraphResult``.  An edge the graph refuses is not kept."""
+        old = self._old_poses("add_loop")
+        target = torch.as_tensor(c2w_last).detach().cpu().double().numpy()
+        if target.shape != (4, 4):
+            raise ValueError(f"c2w_last is {target.shape}, not (4, 4)")
+        for name, v in (("anchor", anchor), ("last", last)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < len(old):
+                raise ValueError(f"{name} {v!r}: an index into the {len(old)} poses")
+        if anchor >= last:
+            raise ValueError(f"anchor {anchor} is not before last {last}")
+        edge = (int(anchor), int(last), np.linalg.inv(old[anchor]) @ target,
+                float(self._loop_weight if weight is None else weight))
+        loops = self._loops + [edge]
+        result = optimise_pose_graph(old, self._odometry, loops, min(e[0] for e in loops), by=self._loop_by)
+        self._loops, self.last_pose_graph = loops, result
+        return self.correct_trajectory(result.poses)
+
+    def _try_loop(self, out: LocalizeResult, depth: Tensor, est: Tensor) -> None:
+        """MapConfig.loop: the policy of one frame that is not lost, whose estimate ``est`` is the last pose of the
+        trajectory and whose rows are not in the map yet; fills the ``loop`` fields of its result.
+        (a) ``waiting``: fewer than ``loop_every`` frames since the last attempt.  (b) The covisibility at the estimate;
+        the old frames are those up to n - ``loop_min_gap``: ``few_rows`` when they are tested fewer than
+        ``loop_min_rows`` times.  (c) ``loop_constraint`` against the rows of the old frames: ``not_converged`` unless the
+        alignment moved and CONVERGED.  (d) ``rejected`` unless the aligned pose agrees with at least ``loop_min_agree`` of
+        the old rows it tests and with no smaller a share than the estimate (in integers).  (e) ``small``: the move is
+        below ``loop_min_trans`` and below ``loop_min_rot_deg``.  (f) ``closed``: the anchor is the old frame with the
+        most rows agreeing from the aligned pose (the lowest index among equals), and ``add_loop`` does the rest."""
+        cfg, near, n = self._loop, self.cfg.gs.near_plane, len(self._poses) - 1
+        if n - self._loop_last < cfg.loop_every:
+            out.loop_status = "waiting"
+            return
+        self._loop_last = n
+        upto = n - cfg.loop_min_gap  # the last old frame
+        out.loop_old_tested = 0
+        if upto >= 0:
+            out.loop_old_tested = int(self.map.covisibility(depth, self.K, est, near, n_frames=n)[:upto + 1, 0].sum())
+        if out.loop_old_tested < self._loop_min_rows:
+            out.loop_status = "few_rows"
+            return
+        c = self.map.loop_constraint(depth, self.K, est, upto, near)
+        if not (c.alignment.moved and c.alignment.status == "CONVERGED"):
+            out.loop_status = "not_converged"
+            return
+        (tested_e, agree_e, _), (tested_a, agree_a, _) = (tuple(int(v) for v in s) for s in (c.scores, c.aligned_scores))
+        if not (tested_a > 0 and agree_a >= cfg.loop_min_agree * tested_a and agree_a * tested_e >= agree_e * tested_a):
+            out.loop_status = "rejected"
+            return
+        aligned = c.alignment.c2w.to(self.device)
+        out.loop_moved_t = float(calculate_translation_error(aligned, est))
+        out.loop_moved_r_deg = float(calculate_rotation_error(aligned, est))
+        if out.loop_moved_t < cfg.loop_min_trans and out.loop_moved_r_deg < cfg.loop_min_rot_deg:
+            out.loop_status = "small"
+            return
+        agree = self.map.covisibility(depth, self.K, aligned, near, n_frames=n)[:upto + 1, 1]
+        out.loop_anchor = int(np.argmax(agree))  # the lowest index among equals
+        out.loop_correction = self.add_loop(out.loop_anchor, n, aligned)
+        out.loop, out.loop_status = True, "closed"
 
     @torch.no_grad()
     def close_loop(self, first: int, last: int, c2w_last, by: str = "path") -> TrajectoryCorrection:

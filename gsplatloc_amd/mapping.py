@@ -72,7 +72,13 @@ corrected one -- in place, with the stored keyframe poses.  ``spread_correction`
 constraint (the correction of the last frame, spread over the frames since the first by path length);
 ``loop_constraint`` measures one against the old part of the map (``align_pose`` and ``score_poses`` on the rows up
 to a frame, a prefix of the map).  When to close a loop stays the caller's decision.  One more entry point; ``correct``
-reads back once."""
+reads back once.
+
+Covisibility and the pose graph (``MapConfig.loop``, csrc/map_covis.hip): ``covisibility`` bins the three verdicts of
+``score_poses`` for one pose by the frame every row came from -- which frames' rows a depth frame sees, and whether they
+agree with it -- in one launch with one read-back; ``optimise_pose_graph`` makes a trajectory consistent with its
+tracked odometry and any number of loop constraints at once, least squares on SE(3) in float64 on the host.
+``Localizer(mode="map")`` finds, measures and closes loops with the two (localizer.py)."""
 from __future__ import annotations
 
 import functools
@@ -290,6 +296,224 @@ def spread_correction(poses, first: int, last: int, delta, by: str = "path") -> 
 
 
 @dataclass
+class PoseGraphResult:
+    """What ``optimise_pose_graph`` returns.  poses: float64 [n,4,4]; cost_before / cost_after: the weighted sum of
+    squared residuals sum w r^T r over all edges at the given and at the returned poses; iterations: the linear solves
+    whose step was taken; converged: the last step stayed within the tolerance (False: ``iters`` ran out, or no damping
+    made the cost fall); loop_residuals: float64 [len(loops)], the norm of every loop edge's residual (rad and m in one
+    vector, as the cost has them) at the returned poses."""
+    poses: np.ndarray
+    cost_before: float
+    cost_after: float
+    iterations: int
+    converged: bool
+    loop_residuals: np.ndarray
+
+
+class _TooFar(ValueError):
+    pass
+
+
+def _bernoulli_over_factorial(upto: int) -> list:
+    """B_n / n! for n = 0 .. upto (B_1 = -1/2), exact fractions rounded once."""
+    from fractions import Fraction
+
+    B, fact, out = [], Fraction(1), []
+    for m in range(upto + 1):
+        B.append(Fraction(1) if m == 0 else -sum(Fraction(math.comb(m + 1, k)) * B[k] for k in range(m)) / (m + 1))
+        fact = fact * m if m > 0 else fact
+        out.append(float(B[m] / fact))
+    return out
+
+
+_B_OVER_FACT = _bernoulli_over_factorial(30)
+
+
+def _jr_inv(r: np.ndarray) -> np.ndarray:
+    """[6,6]: the inverse right Jacobian of SE(3) at the twist r = (omega, upsilon), log(exp(r^) exp(d^)) = r + Jr^-1 d
+    to first order: the series sum B_n / n! (-ad_r)^n, which converges for |omega| < 2 pi and is at rounding after 30
+    terms for the rotations below 90 degrees that an edge is allowed."""
+    ad = np.zeros((6, 6))
+    ad[:3, :3] = ad[3:, 3:] = _hat(r[:3])
+    ad[3:, :3] = _hat(r[3:])
+    out, sq = np.eye(6) + 0.5 * ad, ad @ ad
+    term = sq
+    for n in range(2, len(_B_OVER_FACT), 2):
+        out = out + _B_OVER_FACT[n] * term
+        term = term @ sq
+    return out
+
+
+def _adjoint(T: np.ndarray) -> np.ndarray:
+    """[6,6]: T exp(x^) T^-1 = exp((Ad x)^) for twists x = (omega, upsilon)."""
+    R, out = T[:3, :3], np.zeros((6, 6))
+    out[:3, :3] = out[3:, 3:] = R
+    out[3:, :3] = _hat(T[:3, 3]) @ R
+    return out
+
+
+def _rigid(M, what: str) -> np.ndarray:
+    """M as a float64 [4,4] rigid transform, refused otherwise (the bounds of ``spread_correction``)."""
+    M = torch.as_tensor(M).detach().cpu().double().numpy()
+    if M.shape != (4, 4) or not np.isfinite(M).all():
+        raise ValueError(f"{what} is not a finite [4,4] matrix")
+    R = M[:3, :3]
+    if (np.abs(R.T @ R - np.eye(3)).max() > 1e-5 or np.linalg.det(R) <= 0.0
+            or np.abs(M[3] - np.array([0.0, 0.0, 0.0, 1.0])).max() > 1e-9):
+        raise ValueError(f"{what} is not a rigid transform (R^T R = 1 within 1e-5, det R > 0, last row 0 0 0 1)")
+    return M
+
+
+def optimise_pose_graph(poses, odometry, loops, fixed_upto: int, by: str = "index", iters: int = 30,
+                        tol: float = 1e-12, solver: Optional[str] = None) -> PoseGraphResult:
+    """A trajectory made consistent with several loop constraints at once: least squares over a pose graph on SE(3),
+    float64, on the host (the nodes number in the hundreds, once per closure).
+
+    poses [n,4,4]: the camera-to-world poses so far, the start.  odometry [n-1,4,4]: Z_k, the relative pose
+    T_k^-1 T_k+1 as it was tracked.  loops: (i, j, Z, weight) with i < j, Z [4,4] the measured T_i^-1 T_j and weight
+    above 0.  The residual of an edge (i, j, Z) is r = log(Z^-1 T_i^-1 T_j) = (omega, upsilon), and sum w r^T r is
+    minimised by Gauss-Newton with the right perturbation T_k <- T_k exp(d_k^) and the exact Jacobians (the inverse
+    right Jacobian of SE(3): the residuals of a drifted trajectory do not vanish at the minimum, and a first-order
+    Jacobian would stop beside it); a step under which the cost would rise is taken again with Levenberg's damping,
+    lambda diag(H), ten times stronger each time.  Odometry weights: 1 (by="index"); or the mean step length over the
+    edge's own -- the length of Z_k's translation, floored at 1 % of the mean -- (by="path", and "index" when the path
+    has no length): drift accumulates with the motion that was tracked.  The nodes k <= fixed_upto are not variables
+    and come back with every bit.  It stops when a step was taken under which the cost fell by no more than ``tol`` of
+    itself, or a step within 1e-11 (rad, m), or after ``iters`` steps.  solver: "sparse" (scipy.sparse, the normal
+    equations are block-banded but for the loops), "dense" (numpy), None: sparse where scipy imports.
+
+    A ValueError for poses, Z that are not finite rigid transforms, a wrong count of odometry edges, an index outside the
+    poses, i >= j, a weight that is not finite and above 0, and for an edge whose residual at the start turns by 90
+    degrees or more (``spread_correction``: no constraint worth closing is that far off)."""
+    P = torch.as_tensor(poses).detach().cpu().double().numpy()
+    if P.ndim != 3 or P.shape[0] < 1 or P.shape[1:] != (4, 4):
+        raise ValueError(f"poses are {P.shape}, not (n >= 1, 4, 4)")
+    if not np.isfinite(P).all():
+        raise ValueError("poses: some entry is not finite")
+    n = len(P)
+    if isinstance(fixed_upto, bool) or not isinstance(fixed_upto, (int, np.integer)) or not 0 <= fixed_upto < n:
+        raise ValueError(f"fixed_upto {fixed_upto!r}: an index into the {n} poses (some node has to hold the graph)")
+    if by not in ("path", "index"):
+        raise ValueError(f"by {by!r}: 'path' or 'index'")
+    if solver not in (None, "sparse", "dense"):
+        raise ValueError(f"solver {solver!r}: 'sparse', 'dense' or None")
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 1:
+        raise ValueError(f"iters {iters!r}: a whole number of steps, at least 1")
+    if not (isinstance(tol, (int, float)) and math.isfinite(tol) and tol >= 0):
+        raise ValueError(f"tol {tol!r}: finite and not negative")
+    odo = [_rigid(Z, f"odometry[{k}]") for k, Z in enumerate(odometry)]
+    if len(odo) != n - 1:
+        raise ValueError(f"{len(odo)} odometry edges for {n} poses: one per step, {n - 1}")
+    weights = np.ones(n - 1)
+    if by == "path" and n > 1:
+        steps = np.array([np.linalg.norm(Z[:3, 3]) for Z in odo])
+        if steps.mean() > 0.0:
+            weights = steps.mean() / np.maximum(steps, 0.01 * steps.mean())
+    edges = [(k, k + 1, np.linalg.inv(odo[k]), float(weights[k])) for k in range(n - 1)]
+    for e, loop in enumerate(loops):
+        if len(loop) != 4:
+            raise ValueError(f"loops[{e}]: (i, j, Z, weight)")
+        i, j, Z, w = loop
+        for name, v in (("i", i), ("j", j)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < n:
+                raise ValueError(f"loops[{e}]: {name} {v!r} is no index into the {n} poses")
+        if i >= j:
+            raise ValueError(f"loops[{e}]: i {i} is not before j {j}")
+        if isinstance(w, bool) or not isinstance(w, (int, float, np.floating, np.integer)) \
+                or not (math.isfinite(w) and w > 0):
+            raise ValueError(f"loops[{e}]: weight {w!r}: finite and above 0")
+        edges.append((int(i), int(j), np.linalg.inv(_rigid(Z, f"loops[{e}]: Z")), float(w)))
+    first, m = int(fixed_upto) + 1, n - int(fixed_upto) - 1  # the variables: nodes first .. n - 1
+
+    def residuals(T, jacobians: bool):
+        """(cost, [r per edge], [(Ji, Jj) per edge])."""
+        cost, rs, Js = 0.0, [], []
+        for i, j, Zinv, w in edges:
+            E = Zinv @ np.linalg.inv(T[i]) @ T[j]
+            if not np.trace(E[:3, :3]) - 1.0 > 1e-9:
+                raise _TooFar(f"the edge ({i}, {j}) is off by a turn of 90 degrees or more")
+            r = np.concatenate(_se3_log(E))
+            cost += w * float(r @ r)
+            rs.append(r)
+            if jacobians:
+                Jj = _jr_inv(r)
+                Js.append((-Jj @ _adjoint(np.linalg.inv(T[j]) @ T[i]), Jj))
+        return cost, rs, Js
+
+    def solve(blocks, g, lam):
+        """(H + lam diag H) d = -g, H from its 6 x 6 blocks (a, b, block), duplicates summed."""
+        use_sparse = solver == "sparse"
+        if solver is None:
+            try:
+                import scipy.sparse  # noqa: F401
+                use_sparse = True
+            except ImportError:
+                use_sparse = False
+        if use_sparse:
+            from scipy.sparse import coo_matrix, diags
+            from scipy.sparse.linalg import spsolve
+
+            rows = np.concatenate([(6 * a + np.arange(6))[:, None].repeat(6, 1).ravel() for a, _, _ in blocks])
+            cols = np.concatenate([(6 * b + np.arange(6))[None, :].repeat(6, 0).ravel() for _, b, _ in blocks])
+            H = coo_matrix((np.concatenate([B.ravel() for _, _, B in blocks]), (rows, cols)), shape=(6 * m, 6 * m)).tocsc()
+            if lam > 0.0:
+                H = H + diags(lam * H.diagonal()).tocsc()
+            return np.asarray(spsolve(H, -g)).reshape(-1)
+        H = np.zeros((6 * m, 6 * m))
+        for a, b, B in blocks:
+            H[6 * a:6 * a + 6, 6 * b:6 * b + 6] += B
+        if lam > 0.0:
+            H[np.diag_indices(6 * m)] *= 1.0 + lam
+        return np.linalg.solve(H, -g)
+
+    T = P.copy()
+    try:
+        cost, rs, Js = residuals(T, True)
+    except _TooFar as err:
+        raise ValueError(str(err)) from None
+    before, done, converged, lam = cost, 0, m == 0, 0.0
+    while not converged and done < int(iters):
+        blocks, g = [], np.zeros(6 * m)
+        for (i, j, _, w), r, (Ji, Jj) in zip(edges, rs, Js):
+            var = [(k - first, J) for k, J in ((i, Ji), (j, Jj)) if k >= first]
+            for a, Ja in var:
+                g[6 * a:6 * a + 6] += w * (Ja.T @ r)
+                for b, Jb in var:
+                    blocks.append((a, b, w * (Ja.T @ Jb)))
+        if not blocks:
+            converged = True
+            break
+        taken = False
+        while True:
+            d = solve(blocks, g, lam).reshape(m, 6)
+            size = float(np.abs(d).max()) if np.isfinite(d).all() else math.inf
+            cand = T.copy()
+            for a in range(m):
+                cand[first + a] = T[first + a] @ _se3_exp(d[a, :3], d[a, 3:])
+            try:
+                c_cost, c_rs, c_Js = residuals(cand, True) if math.isfinite(size) else (math.inf, None, None)
+            except _TooFar:
+                c_cost = math.inf
+            if c_cost <= cost:
+                fell = cost - c_cost
+                T, cost, rs, Js, taken = cand, c_cost, c_rs, c_Js, True
+                converged = fell <= tol * (cost + fell) or size <= 1e-11
+                lam = lam / 10.0 if lam > 1e-12 else 0.0
+                break
+            if size <= 1e-11:  # the cost cannot fall any further: what is left is its rounding
+                converged = True
+                break
+            lam = max(10.0 * lam, 1e-6)
+            if lam > 1e12:
+                break
+        if not taken:
+            break
+        done += 1
+    loop_r = np.array([float(np.linalg.norm(r)) for r in rs[n - 1:]])
+    return PoseGraphResult(T, float(before), float(cost), done, bool(converged), loop_r)
+
+
+@dataclass
 class MapConfig:
     alpha_min: float = 0.5  # a pixel the map renders with less alpha is not covered
     depth_rho: float = 0.05  # a pixel observed more than this fraction in front of the map's depth is a new surface
@@ -393,12 +617,49 @@ class MapConfig:
     # trajectory correction: every row carries the index of the frame that appended it (GaussianMap.origins), so that
     # the rows can follow a corrected trajectory (GaussianMap.correct, Localizer.correct_trajectory / close_loop)
     origins: bool = False
+    # Localizer(mode="map"), with origins: loops closed in track().  Every loop_every-th frame that is not lost, before
+    # anything touches the map, the frame's covisibility with the frames at least loop_min_gap behind it is taken
+    # (GaussianMap.covisibility); when those frames' rows are tested loop_min_rows times or more (None: W * H // 8) the
+    # estimate is aligned against them alone (GaussianMap.loop_constraint), and the aligned pose becomes a loop edge of
+    # the pose graph (Localizer.add_loop, optimise_pose_graph) when it converged, agrees with at least loop_min_agree
+    # of the old rows it tests and with no smaller a share than the estimate, and lies at least loop_min_trans metres
+    # or loop_min_rot_deg degrees from the estimate.  loop_weight: the weight of a loop edge, an odometry edge has 1 --
+    # a constraint measured against the map itself is worth many tracked steps; loop_by: the odometry weights, by
+    # "index" or by "path" length (optimise_pose_graph)
+    loop: bool = False
+    loop_min_gap: int = 30
+    loop_every: int = 10
+    loop_min_rows: Optional[int] = None
+    loop_min_agree: float = 0.9
+    loop_min_trans: float = 0.005
+    loop_min_rot_deg: float = 0.1
+    loop_weight: float = 1e4
+    loop_by: str = "index"
 
     def __post_init__(self):
         whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
         number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer))  # noqa: E731
         if not isinstance(self.origins, bool):
             raise ValueError(f"origins {self.origins!r}: True or False")
+        if not isinstance(self.loop, bool):
+            raise ValueError(f"loop {self.loop!r}: True or False")
+        if self.loop and not self.origins:
+            raise ValueError("loop=True needs origins=True: a closed loop moves every row with the frame it came from")
+        for name in ("loop_min_gap", "loop_every"):
+            if not whole(getattr(self, name)) or getattr(self, name) < 1:
+                raise ValueError(f"{name} {getattr(self, name)!r}: a whole number of frames, at least 1")
+        if self.loop_min_rows is not None and (not whole(self.loop_min_rows) or self.loop_min_rows < 1):
+            raise ValueError(f"loop_min_rows {self.loop_min_rows!r}: a whole number of rows, at least 1 (or None)")
+        if not number(self.loop_min_agree) or not 0.0 < self.loop_min_agree <= 1.0:
+            raise ValueError(f"loop_min_agree {self.loop_min_agree!r}: a share of the rows tested, inside (0, 1]")
+        for name, unit in (("loop_min_trans", "metres"), ("loop_min_rot_deg", "degrees")):
+            v = getattr(self, name)
+            if not number(v) or not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"{name} {v!r}: {unit}, finite and not negative")
+        if not number(self.loop_weight) or not (np.isfinite(self.loop_weight) and self.loop_weight > 0):
+            raise ValueError(f"loop_weight {self.loop_weight!r}: finite and above 0")
+        if self.loop_by not in ("index", "path"):
+            raise ValueError(f"loop_by {self.loop_by!r}: 'index' or 'path'")
         if not isinstance(self.align, bool):
             raise ValueError(f"align {self.align!r}: True or False")
         if not whole(self.align_steps) or not 1 <= self.align_steps <= ALIGN_MAX_STEPS:
@@ -598,6 +859,9 @@ class GaussianMap:
         self._n_inserts, self._last_origin = 0, -1
         self._kf_origins = np.full(int(config.keyframe_max), -1, dtype=np.int64)
         self._correct_counters = None
+        # covisibility: its buffer and the pose on first use; the rows the last call found outside its table
+        self._covis = None
+        self.last_covis_outside = 0
 
     def _alloc_ws(self):
         if self.device.type != "cuda":
@@ -1221,6 +1485,58 @@ class GaussianMap:
         scores = self.score_poses(depth, K, [torch.as_tensor(c2w).detach().cpu(), al.c2w.detach().cpu()], near_plane,
                                   rows=n)
         return LoopConstraint(al, n, scores[0], scores[1])
+
+    # ---- covisibility: the pose scores' verdicts, binned by the frame a row came from (csrc/map_covis.hip) -----------
+    def _covis_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, near: float,
+                      n_frames: int, n_rows: Optional[int] = None) -> Tuple[np.ndarray, int]:
+        """w2c [4,4] float32 on the host.  Its copy to the device, the entry point (which zeroes the counts and the
+        count of rows outside) and the read-back of one buffer, the call's one synchronisation: (int64 [n_frames,3],
+        rows whose origin lies outside the table).  n_rows: the first rows of the map that are judged (None: the live
+        ones)."""
+        n_rows = self.n_live if n_rows is None else int(n_rows)
+        assert depth.is_cuda, "GaussianMap.covisibility: the rows are judged and counted by a HIP kernel, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        if self._covis is None or self._covis["words"].numel() < 2 + 3 * n_frames:
+            # one buffer of 4-byte words: [the rows outside, one 64-bit word][counts, 3 per frame]
+            self._covis = dict(words=torch.empty(2 + 3 * max(n_frames, 64), dtype=torch.int32, device=self.device),
+                               pose=torch.empty(16, device=self.device))
+        c = self._covis
+        c["pose"].copy_(w2c.reshape(16))
+        base = c["words"].data_ptr()
+        _lib.check(lib.gsl_map_covis(ptr(self.means), ptr(self.origins), n_rows, ptr(c["pose"]), *intr, ptr(depth),
+                                     self.W, self.H, self.keep, self.beyond, near, n_frames, base + 8, base, st),
+                   "gsl_map_covis")
+        host = c["words"][: 2 + 3 * n_frames].cpu().numpy()
+        return host[2:].astype(np.int64).reshape(n_frames, 3), int(host[:2].copy().view(np.int64)[0])
+
+    @torch.no_grad()
+    def covisibility(self, depth, K, c2w, near_plane: float, n_frames: Optional[int] = None,
+                     rows: Optional[int] = None) -> np.ndarray:
+        """Which frames' rows the depth frame [H,W] (metres) sees from the pose c2w [4,4], and whether they agree with
+        it: int64 [n_frames,3], per frame of the trajectory the rows it appended (``origins``) that the frame TESTS,
+        those that AGREE and those in FRONT -- the verdicts of ``score_poses`` for that one pose, with the map's own
+        ``keep`` and ``beyond``, binned by origin, so that the sum over the frames is ``score_poses(depth, K, [c2w],
+        near_plane)[0]`` whenever no origin lies outside.  n_frames: the frames of the table (None: the last origin
+        written + 1); a row with an origin outside it is counted in ``last_covis_outside`` and nowhere else.  rows:
+        only the first that many rows of the map are judged (None: every live row).  Changes nothing in the map.  Two
+        zeroing launches, one kernel, one read-back; an empty map gives zeros without a launch."""
+        if self.origins is None:
+            raise RuntimeError("covisibility: MapConfig.origins is False, the map keeps no origins")
+        rows = self._prefix(rows)
+        if n_frames is None:
+            n_frames = max(self._last_origin + 1, 1)
+        if isinstance(n_frames, bool) or not isinstance(n_frames, (int, np.integer)) or not 1 <= n_frames <= 2 ** 24:
+            raise ValueError(f"n_frames {n_frames!r}: a whole number of frames, 1 .. 2^24")
+        n_frames = int(n_frames)
+        depth = self._depth_image(depth)
+        intr, c2w = _intr_and_pose(K, c2w)
+        self.last_covis_outside = 0
+        if (self.n_live if rows is None else rows) == 0:
+            return np.zeros((n_frames, 3), dtype=np.int64)
+        prefix = {} if rows is None else dict(n_rows=rows)
+        counts, self.last_covis_outside = self._covis_launch(depth, intr, _world_to_camera(c2w).contiguous(),
+                                                             float(near_plane), n_frames, **prefix)
+        return counts
 
     # ---- refinement: the rows a depth frame observes again move to the running mean of their depths (csrc/map_refine.hip)
     def _refine_launch(self, depth: Tensor, rgb: Optional[Tensor], intr: Tuple[float, float, float, float], w2c: Tensor,

@@ -497,6 +497,29 @@ int gsl_map_refine(float* means, float* colors, int32_t* weights, int64_t n_rows
 int gsl_map_correct(float* means, const int32_t* origins, int64_t n_rows, const float* table, int n_frames,
                     int64_t* counters, void* stream);
 
+/* ---- covisibility: the verdicts of the pose scores, binned by the frame a row came from (csrc/map_covis.hip) ----
+ * means[n_rows,3] float32 and origins[n_rows] int32 on the device, as in the map; w2c[16] (world to camera, row-major;
+ * twelve entries are read) and depth[height,width] float32 (the observed depth, metres) on the device.
+ * counts[n_frames,3] int32 and outside[1] int64 on the device; they need not be initialised, the entry point zeroes them
+ * on the stream.  Row i with o = origins[i] -- the origin is looked at first:
+ *   OUTSIDE when o < 0 or o >= n_frames: outside[0] += 1 and nothing else, whatever the row's mean is;
+ *   otherwise TESTED, AGREE, FRONT and BEHIND are those of gsl_map_score for the one pose w2c, operation for operation
+ *           (above: the projection, the row's own pixel, keep and beyond, comparisons false for a NaN), and
+ *   counts[o] += (tested, agree, front).
+ * The sums are integers: they do not depend on the order of rows, waves or workgroups, nor on the order of the
+ * origins -- a map has them non-decreasing, which the kernel uses for speed only.  The sum of counts over the frames is
+ * what gsl_map_score leaves for the same pose whenever no row is outside.  Two zeroing launches and one kernel; a
+ * workgroup combines its waves over a window of 64 consecutive origins before it adds to counts, a run of equal origins
+ * outside that window is added with one integer atomic per non-zero predicate; no atomic per row.  n_rows == 0 is
+ * GSL_OK without a launch (counts and outside are then not touched).
+ * Returns GSL_ERR_BAD_ARG before any launch for a NULL means, origins, w2c, depth, counts or outside, n_frames outside
+ * 1 .. GSL_MAP_COVIS_MAX_FRAMES, n_rows < 0 or >= 2^31, width or height <= 0 or width * height > 2^31 - 1, fx or fy not
+ * non-zero, keep outside (0, 1], beyond not >= 1. */
+#define GSL_MAP_COVIS_MAX_FRAMES 16777216
+int gsl_map_covis(const float* means, const int32_t* origins, int64_t n_rows, const float* w2c, float fx, float fy,
+                  float cx, float cy, const float* depth, int width, int height, float keep, float beyond,
+                  float near_plane, int n_frames, int32_t* counts, int64_t* outside, void* stream);
+
 /* ---- spherical harmonics: gsplat.spherical_harmonics fwd/bwd (IDX:14306, IDX:14297) ----
  * dirs[M,3], coeffs[M,K,3] with K >= (degree+1)^2, masks[M] (uint8, may be NULL).
  * degree 0..3.  v_dirs may be NULL. */
