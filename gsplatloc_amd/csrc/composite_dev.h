@@ -141,7 +141,14 @@ __device__ __forceinline__ void clear_tile_counter(int32_t* __restrict__ clear_c
 // in six operations and  alpha = opacity exp2(-that)  without the scaling multiply of expf.  The forward (praster_walk)
 // and every backward that replays it (k_tiny_bwd, qraster_bwd_body, k_absgrad) call these two and nothing else: both sides
 // evaluate alpha with the very same operations and take the same alpha >= 1/255 decision for every (pixel, entry) pair.
-// (The deterministic and the staged kernels pair with forwards of the __expf form and do not use this.)
+// The staged kernels (raster.hip) do not use this: k_raster_bwd pairs with k_raster_fwd, both of the __expf form.
+// The deterministic backward (raster_det.hip, k_mraster_bwd) does not use it either, but it is NOT paired with a forward
+// of its own form: a deterministic RenderContext runs praster_walk (exp2, staged conic) forward and k_mraster_bwd
+// (__expf, plain conic) backward.  The two alphas differ in the last bits (a few 1e-7 relative), so on a (pixel, entry)
+// pair whose alpha sits within that of 1/255 the backward can skip an entry the forward composited, or the reverse: T
+// behind that entry is then off by the factor 1 - 1/255 in that pixel's gradient terms.  No test has met such a pair (the
+// stop-ladder scenes keep every decision 1e-3 away, and on the random scenes NOTES.md counts the pixels below 1.5e-5);
+// the bound on last_ids still trims the walk identically.  Cure, if it ever matters: sigma_log2e in k_mraster_bwd.
 __device__ __forceinline__ float3 stage_conic(const float4& q1) {
   return make_float3(q1.x * (0.5f * GSL_LOG2E), q1.y * GSL_LOG2E, q1.z * (0.5f * GSL_LOG2E));
 }

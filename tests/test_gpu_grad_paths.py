@@ -17,6 +17,7 @@ import functools
 import pytest
 import torch
 
+from tests import walk_ref as WR
 from tests.grad_paths import compare_grads, failing_subsets, oracle_render, roll_within
 from tests.parity import POSE_GRAD_TOL, agreeing_pixels, rel_inf, report
 from tests.scenes import small_pose
@@ -148,6 +149,7 @@ def _ladder_scene(variant, c2w=None):
 
 
 _ORACLE = {}
+_EXPLAINED = set()
 
 
 def _oracle(variant, mode, half, c2w=None):
@@ -269,6 +271,14 @@ def run_path_case(path, mode, upstream, monkeypatch, c2w=None, label="grad paths
     flipped = 1.0 - ok[y0:y1].double().mean().item()
     tag = f"{label} {path} {mode} {upstream}"
     assert flipped <= MAX_FLIPPED, f"{tag}: {flipped:.2e} of the pixels differ from the oracle"
+    if (label, path, mode, c2w) not in _EXPLAINED:  # once per (scene, path, mode), not once per upstream kind
+        # every pixel rejected above, and every pixel that differs from the walk of the context's own records, sits on a
+        # compositing threshold and is what the walk gives with that decision taken the other way (tests/walk_ref.py)
+        suspects = ~ok
+        suspects[:y0] = False
+        suspects[y1:] = False
+        WR.assert_flips_explained(f"{label} {path} {mode}", rc, render, alphas, suspects, oracle=(r_o, a_o))
+        _EXPLAINED.add((label, path, mode, c2w))
     if staging == "fp16" and base == "general" and upstream == "random":
         # the rounding is what is modelled: against the unrounded oracle the fp16 render misses 1e-4 somewhere
         with torch.no_grad():

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from oracle import gsplat_oracle as G
+from tests import walk_ref as WR
 from tests.grad_paths import compare_grads, failing_subsets, oracle_render
 from tests.parity import POSE_GRAD_TOL, agreeing_pixels, report
 from tests.scenes import random_scene, sh_from_rgb, small_pose
@@ -612,6 +613,10 @@ def test_fuzz_render_context_against_the_oracle(seed):
     mostly_close(render[None, y0:y1], r_o[:, y0:y1], rtol=1e-4, atol=2e-5, max_bad_frac=5e-3, what=tag + " render")
     mostly_close(alphas[None, y0:y1], a_o[:, y0:y1], rtol=1e-4, atol=2e-5, max_bad_frac=5e-3, what=tag + " alpha")
     ok = agreeing_pixels(render[None], alphas[None], r_o, a_o)
+    suspects = ~ok[0]
+    suspects[:y0] = False
+    suspects[y1:] = False
+    WR.assert_flips_explained(tag, rc, render, alphas, suspects, oracle=(r_o[0], a_o[0]))  # every rejected pixel sits on a threshold (tests/walk_ref.py)
     ok[:, :y0] = False
     ok[:, y1:] = False
     v_c = torch.randn(r_o.shape, generator=gen) * ok[..., None]
