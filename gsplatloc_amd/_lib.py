@@ -68,6 +68,10 @@ _SIGNATURES = {
     "gsl_map_pose_align": (c_int, [P, c_int64, P, c_float, c_float, c_float, c_float, P, c_int, c_int, c_float, c_float,
                                    c_float, c_float, c_int, c_double, c_int, c_double, c_double, c_double, c_double, P, P,
                                    P, P, P]),
+    "gsl_map_align_batch_max_poses": (c_int, []),
+    "gsl_map_pose_align_batch": (c_int, [P, c_int64, P, c_int, c_float, c_float, c_float, c_float, P, c_int, c_int,
+                                         c_float, c_float, c_float, c_float, c_int, c_double, c_int, c_double, c_double,
+                                         c_double, c_double, P, P, P, P, P]),
     "gsl_map_place_cells": (c_int, []),
     "gsl_map_place_describe": (c_int, [P, c_int, c_int, P, P]),
     "gsl_map_place_match": (c_int, [P, P, c_int, P, P]),

@@ -47,123 +47,24 @@
 // (six xor-shuffle steps per value), lane 0 adds them to a table of 30 in LDS (ds_add_u64; 240 B), and the workgroup
 // adds its non-zero entries to out with one 64-bit integer atomic each: at most INFO_MAX_BLOCKS x 30 global atomics
 // whatever n_rows is.  No float atomics.  out is zeroed by a launch of zero_u32 in front (never a memset node).
+//
+// All of that, from map_project_point(...) to the atomics on out, is info_sum_rows of map_info_dev.h: the one copy, which
+// the batched alignment (map_align_batch.hip) runs for several poses in one launch.
 #include "gsloc_internal.h"
-#include "map_dev.h"
+#include "map_info_dev.h"
 
 namespace gsl {
 
 constexpr int INFO_THREADS = 256;
 constexpr int INFO_MAX_BLOCKS = 1024;  // four workgroups of 256 threads for each of the 256 CUs
-constexpr int INFO_SUMS = 28;          // 21 + 6 + 1 fixed-point sums; then the two counts
-constexpr float INFO_MAX_DEPTH = 64.f;
-constexpr float INFO_ONE = 1048576.f;  // 2^20
-static_assert(INFO_SUMS + 2 == GSL_MAP_INFO_VALUES, "out is the sums and the two counts");
-static_assert(GSL_MAP_INFO_VALUES <= INFO_THREADS, "one thread per entry of the table flushes it");
-
-// Where fix(J_a, J_b), a <= b <= 6 with J_6 = r, goes in out.
-__host__ __device__ constexpr int info_slot(int a, int b) {
-  return b < 6 ? a * 6 - a * (a - 1) / 2 + (b - a) : a < 6 ? 21 + a : 27;
-}
-static_assert(info_slot(0, 0) == 0 && info_slot(0, 5) == 5 && info_slot(1, 1) == 6 && info_slot(5, 5) == 20 &&
-                  info_slot(0, 6) == 21 && info_slot(5, 6) == 26 && info_slot(6, 6) == 27,
-              "the upper triangle row-major, then g, then the residual sum");
-
-__device__ static inline long long info_fix(float s, float t) {
-#pragma clang fp contract(off)
-  return llrintf((s * t) * INFO_ONE);
-}
-
-__device__ static inline bool info_neighbour_ok(float d, float lo, float hi) {
-  return d > 0.f && d < INFINITY && d >= lo && d <= hi;
-}
 
 __global__ __launch_bounds__(INFO_THREADS) void k_map_pose_info(
     const float* __restrict__ means, long long n_rows, const float* __restrict__ w2c, float fx, float fy, float cx,
     float cy, const float* __restrict__ depth, int width, float u_inner, float v_inner, float keep, float beyond,
     float kappa, float near_plane, unsigned long long* __restrict__ out) {
-  __shared__ unsigned long long table[GSL_MAP_INFO_VALUES];
-  if ((int)threadIdx.x < GSL_MAP_INFO_VALUES) table[threadIdx.x] = 0ull;
-  __syncthreads();
-  long long acc[INFO_SUMS];
-#pragma unroll
-  for (int i = 0; i < INFO_SUMS; ++i) acc[i] = 0;
-  uint32_t n_used = 0u, n_tested = 0u;  // the wave's: wave-uniform
-  const long long stride = (long long)gridDim.x * INFO_THREADS;
-  // the trip count is the workgroup's: every lane of a wave reaches every ballot
-  for (long long base = (long long)blockIdx.x * INFO_THREADS; base < n_rows; base += stride) {
 #pragma clang fp contract(off)
-    const long long g = base + threadIdx.x;
-    const bool live = g < n_rows;
-    float3 row = {0.f, 0.f, 0.f};
-    if (live) row = map_load_row(means, g);
-    float x, y;
-    const MapPixel p = map_project_point(w2c, row, fx, fy, cx, cy, x, y);
-    bool tested = live && p.z > near_plane && p.uf >= 1.f && p.uf <= u_inner && p.vf >= 1.f && p.vf <= v_inner;
-    bool used = false;
-    float J[7];
-    if (tested) {  // the five indices are inside
-      const size_t at = (size_t)(int)p.vf * (size_t)width + (size_t)(int)p.uf;
-      const float d0 = depth[at];
-      tested = d0 > 0.f && d0 < INFINITY;
-      const float lo = d0 * keep, hi = d0 * beyond;
-      if (tested && p.z >= lo && p.z <= hi && p.z < INFO_MAX_DEPTH) {
-        const float dl = depth[at - 1], dr = depth[at + 1], du = depth[at - (size_t)width], dd = depth[at + (size_t)width];
-        if (info_neighbour_ok(dl, lo, hi) && info_neighbour_ok(dr, lo, hi) && info_neighbour_ok(du, lo, hi) &&
-            info_neighbour_ok(dd, lo, hi)) {
-          const float i0 = 1.f / d0, s0 = i0 + i0, tol = kappa * i0;
-          const float su = 1.f / dl + 1.f / dr, sv = 1.f / du + 1.f / dd;
-          if (fabsf(su - s0) <= tol && fabsf(sv - s0) <= tol) {
-            // q(u, v, d): the back-projection of k_map_append
-            const float kx0 = (p.uf - cx) / fx, ky0 = (p.vf - cy) / fy;
-            const float kxl = ((p.uf - 1.f) - cx) / fx, kxr = ((p.uf + 1.f) - cx) / fx;
-            const float kyu = ((p.vf - 1.f) - cy) / fy, kyd = ((p.vf + 1.f) - cy) / fy;
-            const float ax = kxr * dr - kxl * dl, ay = ky0 * dr - ky0 * dl, az = dr - dl;
-            const float bx = kx0 * dd - kx0 * du, by = kyd * dd - kyu * du, bz = dd - du;
-            const float c0 = ay * bz - az * by, c1 = az * bx - ax * bz, c2 = ax * by - ay * bx;
-            const float len = sqrtf((c0 * c0 + c1 * c1) + c2 * c2);
-            if (len > 0.f) {
-              const float n0 = c0 / len, n1 = c1 / len, n2 = c2 / len;
-              const float e0 = x - kx0 * d0, e1 = y - ky0 * d0, e2 = p.z - d0;
-              J[0] = y * n2 - p.z * n1;
-              J[1] = p.z * n0 - x * n2;
-              J[2] = x * n1 - y * n0;
-              J[3] = n0;
-              J[4] = n1;
-              J[5] = n2;
-              J[6] = (n0 * e0 + n1 * e1) + n2 * e2;
-              used = true;
-            }
-          }
-        }
-      }
-    }
-    if (used) {
-#pragma unroll
-      for (int a = 0; a < 7; ++a)
-#pragma unroll
-        for (int b = a; b < 7; ++b) acc[info_slot(a, b)] += info_fix(J[a], J[b]);
-    }
-    n_tested += (uint32_t)__popcll(__ballot(tested));
-    n_used += (uint32_t)__popcll(__ballot(used));
-  }
-  // per wave, then LDS
-  const bool first_lane = (threadIdx.x & 63) == 0;
-#pragma unroll
-  for (int i = 0; i < INFO_SUMS; ++i) {
-    long long v = acc[i];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    if (first_lane && v != 0) atomicAdd(&table[i], (unsigned long long)v);
-  }
-  if (first_lane && n_tested != 0u) {
-    atomicAdd(&table[INFO_SUMS + 1], (unsigned long long)n_tested);
-    if (n_used != 0u) atomicAdd(&table[INFO_SUMS], (unsigned long long)n_used);
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < GSL_MAP_INFO_VALUES) {
-    const unsigned long long c = table[threadIdx.x];
-    if (c != 0ull) atomicAdd(&out[threadIdx.x], c);
-  }
+  info_sum_rows<INFO_THREADS>(means, n_rows, w2c, fx, fy, cx, cy, depth, width, u_inner, v_inner, keep, beyond, kappa,
+                              near_plane, out);
 }
 
 // The zeroing of out and the launch of k_map_pose_info, for arguments that gsl_map_pose_info has checked: its own two

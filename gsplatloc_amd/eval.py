@@ -43,7 +43,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   map_keyframe_rot_deg: Optional[float] = None, map_keyframe_trans: Optional[float] = None,
                   map_refine: bool = False, map_refine_max_weight: Optional[int] = None,
                   map_info: bool = False, map_align: bool = False, map_align_steps: Optional[int] = None,
-                  map_origins: bool = False, map_loop: bool = False, map_loop_min_gap: Optional[int] = None) -> Dict:
+                  map_origins: bool = False, map_loop: bool = False, map_loop_min_gap: Optional[int] = None,
+                  map_align_accept: bool = False, map_reloc_align_top: Optional[int] = None) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -65,7 +66,10 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     ``map_refine_max_weight`` for MapConfig.refine_max_weight where not None; ``map_info``: MapConfig.info, every frame
     that is not lost reports the covariance of its pose from the map's rows against its depth image; ``map_align``:
     MapConfig.align, every frame's start pose is aligned to the map by Gauss-Newton steps before the tracker runs, with
-    ``map_align_steps`` for MapConfig.align_steps where not None)."""
+    ``map_align_steps`` for MapConfig.align_steps where not None; ``map_align_accept``: MapConfig.align_accept, a
+    converged alignment that the map's rows pin down is the frame's pose and the tracker does not run;
+    ``map_reloc_align_top``: MapConfig.reloc_align_top, that many of the best relocalisation candidates are aligned to
+    the map before the winner is chosen)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
     if map_merge_voxel is not None and not map_mode:
         raise ValueError("map_merge_voxel belongs to the map mode (map_mode=True)")
@@ -76,7 +80,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     if map_evict and not map_mode:
         raise ValueError("map_evict belongs to the map mode (map_mode=True)")
     reloc = {k: v for k, v in (("reloc_min_agree", map_reloc_min_agree), ("reloc_rot_deg", map_reloc_rot_deg),
-                               ("reloc_trans", map_reloc_trans)) if v is not None}
+                               ("reloc_trans", map_reloc_trans), ("reloc_align_top", map_reloc_align_top))
+             if v is not None}
     if (map_reloc or reloc) and not map_mode:
         raise ValueError("map_reloc belongs to the map mode (map_mode=True)")
     if reloc and not map_reloc:
@@ -106,9 +111,12 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         raise ValueError("map_align belongs to the map mode (map_mode=True)")
     if map_align_steps is not None and not map_align:
         raise ValueError("map_align_steps: an option of map_align=True")
+    if map_align_accept and not map_align:
+        raise ValueError("map_align_accept: an option of map_align=True")
     align = None
     if map_align:
-        align = dict(align=True, **({} if map_align_steps is None else {"align_steps": map_align_steps}))
+        align = dict(align=True, **({} if map_align_steps is None else {"align_steps": map_align_steps}),
+                     **({"align_accept": True} if map_align_accept else {}))
     refine = None
     if map_refine:
         refine = dict(refine=True, **({} if map_refine_max_weight is None else
@@ -236,6 +244,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     relocalised, shares, recognised, refined = 0, [], 0, []
     sigma_t, sigma_r, info_used, info_eig, weak = [], [], [], [], 0
     aligned, align_steps, align_status, motion_eT, start_eT = [], [], [], [], []
+    direct, direct_reason, reloc_aligned = [], [], []
     ordered = True
     loop_status, closures, anchors, gts = [], [], [], [pose]
     for i in range(1, n + 1):
@@ -277,7 +286,12 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             motion_eT.append(float(torch.norm(r.align_from[:3, 3] - gt_t)))
             start_eT.append(float(torch.norm(r.init_c2w[:3, 3] - gt_t)))
             print(f"frame {i}: pose alignment: {r.align_status} after {r.align_steps} steps, moved {r.align_moved_t:.3e} m "
-                  f"{r.align_moved_r_deg:.3e} deg, taken {r.aligned}: start eT {motion_eT[-1]:.3e} -> {start_eT[-1]:.3e}")
+                  f"{r.align_moved_r_deg:.3e} deg, taken {r.aligned}: start eT {motion_eT[-1]:.3e} -> {start_eT[-1]:.3e}"
+                  + ("" if r.direct is None else f", direct {r.direct}" + (f" ({r.direct_reason})" if r.direct_reason else "")))
+            direct.append(r.direct)
+            direct_reason.append(r.direct_reason)
+        if map_reloc and map_reloc.get("reloc_align_top"):
+            reloc_aligned.append(r.reloc_aligned)
         if map_loop:
             gts.append(pose)
             loop_status.append(r.loop_status)
@@ -294,8 +308,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
         path += float(torch.norm(pose[:3, 3] - last_t))
         last_t = pose[:3, 3]
         if verbose:
-            print(f"frame {i}: steps {r.steps} best step {r.best_step} loss {r.best_loss:.3e} eT {r.eT:.3e} "
-                  f"eR {r.eR:.3e}")
+            loss = "none" if r.best_loss is None else f"{r.best_loss:.3e}"  # a direct frame has no loss
+            print(f"frame {i}: steps {r.steps} best step {r.best_step} loss {loss} eT {r.eT:.3e} eR {r.eR:.3e}")
     dt = time.perf_counter() - t0
     return {"mode": "sequential", "motion": motion, "ATE": rmse(eTs), "AAE": rmse(eRs),
             "final_eT": eTs[-1] if eTs else float("nan"), "final_eR": eRs[-1] if eRs else float("nan"),
@@ -319,6 +333,10 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             **({"align": True, "aligned_per_frame": aligned, "align_steps_per_frame": align_steps,
                 "align_status_per_frame": align_status, "aligned_frames": sum(aligned),
                 "motion_eT_per_frame": motion_eT, "start_eT_per_frame": start_eT} if map_align else {}),
+            **({"align_accept": True, "direct_per_frame": direct, "direct_reason_per_frame": direct_reason,
+                "direct_frames": sum(bool(d) for d in direct)} if map_align and map_align.get("align_accept") else {}),
+            **({"reloc_align_top": map_reloc["reloc_align_top"], "reloc_aligned_per_frame": reloc_aligned}
+               if map_reloc and map_reloc.get("reloc_align_top") else {}),
             **({"origins": True, "origins_non_decreasing": ordered,
                 "rows_per_origin": torch.bincount(loc.map.origins[: loc.map.n_live].long().cpu(),
                                                   minlength=n + 1).tolist()} if map_origins else {}),
@@ -412,6 +430,13 @@ def main(argv=None):
                          "on the device before the tracker runs, and taken when the map scores it no worse")
     ap.add_argument("--map-align-steps", type=int, default=None, metavar="K",
                     help="--map-align: iterations per frame, 1 .. 32 (default 8)")
+    ap.add_argument("--map-align-accept", action="store_true",
+                    help="--map-align: a converged alignment that the map scores no worse than the start and that the "
+                         "map's points pin down in every direction is the frame's pose -- the tracker does not run; the "
+                         "report counts these direct frames")
+    ap.add_argument("--map-reloc-align-top", type=int, default=None, metavar="K",
+                    help="--map-reloc: the K best candidates of a relocalisation grid (1 .. 16) are aligned to the map "
+                         "in one call before the winner is chosen (default 0: none)")
     a = ap.parse_args(argv)
     if a.map_merge_voxel is not None and not a.map:
         ap.error("--map-merge-voxel needs --map")
@@ -456,6 +481,10 @@ def main(argv=None):
         ap.error("--map-align needs --map")
     if a.map_align_steps is not None and not a.map_align:
         ap.error("--map-align-steps needs --map-align")
+    if a.map_align_accept and not a.map_align:
+        ap.error("--map-align-accept needs --map-align")
+    if a.map_reloc_align_top is not None and not a.map_reloc:
+        ap.error("--map-reloc-align-top needs --map-reloc")
     out = {}
     for room in a.rooms:
         parser = Parser(a.dataset, room, normalize=not a.no_normalize, input_folder=a.root)
@@ -469,6 +498,7 @@ def main(argv=None):
                           map_keyframe_rot_deg=a.map_keyframe_rot_deg, map_keyframe_trans=a.map_keyframe_trans,
                           map_refine=a.map_refine, map_refine_max_weight=a.map_refine_max_weight,
                           map_info=a.map_info, map_align=a.map_align, map_align_steps=a.map_align_steps,
+                          map_align_accept=a.map_align_accept, map_reloc_align_top=a.map_reloc_align_top,
                           map_origins=a.map_origins or a.map_loop, map_loop=a.map_loop,
                           map_loop_min_gap=a.map_loop_min_gap)
         out[room] = {"gsplatloc_amd": r}

@@ -50,6 +50,11 @@ it is weak.  Nothing is gated on it.
 With ``MapConfig.align`` step 3 looks at the frame: the motion model's start pose is aligned to the map by a few
 Gauss-Newton steps on those normal equations, iterated on the device (``GaussianMap.align_pose``), and the aligned pose
 is what the frame starts from when the map scores it no worse than the motion model's (``GaussianMap.score_poses``).
+With ``MapConfig.align_accept`` that alignment may be the whole frame: it goes through ``GaussianMap.align_poses``, which
+leaves the normal equations at the aligned pose, and an alignment that converged, that the map scores no worse than the
+start and that enough rows pin down in every direction is the frame's estimate -- the tracker does not run
+(``LocalizeResult.direct``).  With ``MapConfig.reloc_align_top`` the best candidates of a relocalisation grid are aligned
+the same way, in one call, before the winner is chosen.
 With ``MapConfig.origins`` the map can follow a corrected trajectory: every row carries the index its frame's pose has
 in ``trajectory``, and ``correct_trajectory`` (any new poses) or ``close_loop`` (one constraint on one frame, spread over
 the frames of the loop) moves the rows, the keyframe poses and the poses themselves (``GaussianMap.correct``).  Neither
@@ -72,9 +77,9 @@ from torch import Tensor
 
 from .data.dataset import build_pair
 from .data.normalize import denormalize_camera, transform_cameras
-from .mapping import SCORE_MAX_POSES, GaussianMap, MapConfig, optimise_pose_graph, spread_correction
+from .mapping import INFO_MIN_EIG, SCORE_MAX_POSES, GaussianMap, MapConfig, optimise_pose_graph, spread_correction
 from .my_gsplat.geometry import construct_full_pose, depth_to_points, init_gs_scales, render_depth_alpha
-from .my_gsplat.trainer import TrackerConfig, calculate_rotation_error, calculate_translation_error
+from .my_gsplat.trainer import TrackerConfig, TrackResult, calculate_rotation_error, calculate_translation_error
 from .my_gsplat.transform import normalize_quaternion, quat_to_rotation_matrix, rotation_matrix_to_quaternion
 
 MOTIONS = ("constant_velocity", "hold")
@@ -102,7 +107,7 @@ class LocalizeResult:
     init_c2w: Tensor  # [4,4] the pose the optimisation started from, in the world
     steps: int
     best_step: int
-    best_loss: float
+    best_loss: Optional[float]  # None on a direct frame (align_accept)
     lost: bool  # no minimum was ever recorded (best_step == -1)
     eT: Optional[float] = None  # metres / degrees against gt_c2w, when one was given
     eR: Optional[float] = None
@@ -149,6 +154,18 @@ class LocalizeResult:
     align_moved_t: Optional[float] = None
     align_moved_r_deg: Optional[float] = None
     align_scores: Optional[tuple] = None
+    # align_accept (both None with the option off): direct -- the aligned pose is the frame's estimate and the tracker
+    # did not run (steps 0, best_step -1, best_loss None; lost is the map's verdict alone); direct_reason: None on a
+    # direct frame, otherwise the first rule that failed -- "status" (the alignment is not CONVERGED), "open" (it
+    # converged on its last iteration: no sums at the final pose), "share" (the map scores the start better), "used"
+    # (fewer than align_accept_min_used rows in the final sums), "weak" (their smallest eigenvalue is below
+    # align_accept_min_eig) -- or "rejected": reloc did not confirm the aligned pose, and the frame was tracked from
+    # the motion model's start
+    direct: Optional[bool] = None
+    direct_reason: Optional[str] = None
+    # reloc_align_top (None with the option at 0, or on a frame that needed no retry): the candidates of the last retry
+    # whose alignment took their place
+    reloc_aligned: Optional[int] = None
     # loop (None with the option off): loop -- this frame closed a loop; loop_status: what the policy ended with, one of
     # ``LOOP_STATUS`` (None on a lost frame, which is not asked); loop_old_tested: the rows of the frames at least
     # loop_min_gap behind that the frame tests from its estimate; loop_anchor: the frame the loop edge starts at;
@@ -351,6 +368,7 @@ class Localizer:
         self._refine = False  # MapConfig.refine
         self._info = False  # MapConfig.info
         self._align = False  # MapConfig.align
+        self._accept = None  # (align_accept_min_used, align_accept_min_eig) when MapConfig.align_accept is on
         self._origins = False  # MapConfig.origins
         self._loop = None  # the MapConfig when MapConfig.loop is on
         self._loop_min_rows = 0  # MapConfig.loop_min_rows, or its default for this image size
@@ -372,6 +390,10 @@ class Localizer:
             self._refine = bool(map_config.refine)
             self._info = bool(map_config.info)
             self._align = bool(map_config.align)
+            if map_config.align_accept:
+                self._accept = (
+                    (self.W * self.H) // 16 if map_config.align_accept_min_used is None else map_config.align_accept_min_used,
+                    INFO_MIN_EIG if map_config.align_accept_min_eig is None else float(map_config.align_accept_min_eig))
             self._origins = bool(map_config.origins)
             self._loop_weight, self._loop_by = float(map_config.loop_weight), map_config.loop_by
             if map_config.loop:
@@ -419,7 +441,7 @@ class Localizer:
     def _run_tracker(self, d, init: Tensor):
         """Steps 4 - 6 on the pair ``d`` from the world pose ``init``: (Gaussians tracked, their scales, the tracker's
         result, its minimum-loss pose in the pair's frame, that pose in the world)."""
-        init_n = transform_cameras(d.norm_T, init.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else init
+        init_n = self._pair_pose(d, init)
         N = d.tar_points.shape[0]
         if self.tracker is None or self._tracker_N != N:
             self.tracker, self._tracker_N = self._factory(N, self.W, self.H, self.cfg, self.device, self.render_mode), N
@@ -435,12 +457,46 @@ class Localizer:
         """(tested, agree, front), Python ints: the map's rows that the depth frame judges from the world pose c2w."""
         return tuple(int(c) for c in self.map.score_poses(depth, self.K, [c2w], self.cfg.gs.near_plane)[0])
 
-    def _accepted(self, res, verdict) -> bool:
-        """reloc: the tracker recorded a minimum, enough rows were tested, and of those the frame judges against its
-        own surface -- in front of it or on it -- at least ``reloc_min_agree`` are on it."""
+    def _accepted(self, res, verdict, direct: bool = False) -> bool:
+        """reloc: the tracker recorded a minimum (direct: it did not run, the map's verdict decides alone), enough rows
+        were tested, and of those the frame judges against its own surface -- in front of it or on it -- at least
+        ``reloc_min_agree`` are on it."""
         tested, agree, front = verdict
-        return (res.best_step != -1 and tested >= self._min_tested
+        return ((direct or res.best_step != -1) and tested >= self._min_tested
                 and agree >= self._reloc.reloc_min_agree * (agree + front))
+
+    def _pair_pose(self, d, c2w: Tensor) -> Tensor:
+        """The world pose c2w in the frame of the pair ``d``."""
+        return transform_cameras(d.norm_T, c2w.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else c2w
+
+    def _direct_run(self, d, est: Tensor):
+        """What ``_run_tracker`` returns, for a frame whose estimate is the aligned pose ``est`` and whose pair ``d`` was
+        built there: no step, no minimum, no loss."""
+        at = self._pair_pose(d, est)
+        res = TrackResult(best_loss=None, steps=0, final_c2w=at, best_c2w=at, best_step=-1)
+        return d.tar_points.shape[0], init_gs_scales(d.tar_points), res, at, est.clone()
+
+    def _share_rule(self, start, aligned) -> bool:
+        """An aligned pose against the pose it started from, by their (tested, agree, front): the aligned pose confirms
+        some row, and its share of agreeing rows is at least the start's (``_aligned_start``)."""
+        (_, agree_s, front_s), (_, agree_a, front_a) = start, aligned
+        return agree_a > 0 and agree_a * front_s >= agree_s * front_a
+
+    def _direct_reason(self, al, taken: bool) -> Optional[str]:
+        """align_accept: None when the alignment ``al`` (of ``GaussianMap.align_poses``), which the share rule took or
+        did not, may be the frame's estimate; otherwise the first rule that failed."""
+        min_used, min_eig = self._accept
+        if al.status != "CONVERGED":
+            return "status"
+        if not al.closed:
+            return "open"
+        if not taken:
+            return "share"
+        if al.final.used < min_used:
+            return "used"
+        if al.final.weak(min_eig):
+            return "weak"
+        return None
 
     def _aligned_start(self, depth: Tensor, init: Tensor):
         """align: the motion model's pose aligned to the map (``GaussianMap.align_pose``), and taken when the alignment
@@ -451,17 +507,21 @@ class Localizer:
         a camera that moves loses rows over the image's edge, and the difference counts every one of them against
         the pose that follows the motion (NOTES.md, "Pose alignment").  Returns (the ``LocalizeResult`` fields aligned,
         align_status, align_steps, align_from, align_moved_t, align_moved_r_deg, align_scores; the pose to start
-        from)."""
+        from; align_accept: None when that pose may be the frame's estimate, else ``_direct_reason``'s word -- None
+        with the option off)."""
         near = self.cfg.gs.near_plane
-        al = self.map.align_pose(depth, self.K, init, near)
+        if self._accept is None:
+            al = self.map.align_pose(depth, self.K, init, near)
+        else:  # the same pose bit for bit, and the sums at it
+            al = self.map.align_poses(depth, self.K, [init], near)[0]
         taken, moved_t, moved_r, scores = False, 0.0, 0.0, None
         if al.status in ("CONVERGED", "STEPPED"):
             to = al.c2w.to(self.device)
             moved_t, moved_r = float(calculate_translation_error(to, init)), float(calculate_rotation_error(to, init))
             scores = tuple(tuple(int(c) for c in s) for s in self.map.score_poses(depth, self.K, [init, to], near))
-            (_, agree_s, front_s), (_, agree_a, front_a) = scores
-            taken = agree_a > 0 and agree_a * front_s >= agree_s * front_a
-        return (taken, al.status, al.steps, init, moved_t, moved_r, scores), (to if taken else init)
+            taken = self._share_rule(*scores)
+        reason = None if self._accept is None else self._direct_reason(al, taken)
+        return (taken, al.status, al.steps, init, moved_t, moved_r, scores), (to if taken else init), reason
 
     @staticmethod
     def _report_information(out: LocalizeResult, info) -> None:
@@ -499,22 +559,44 @@ class Localizer:
         in one call; the one with the largest ``agree - front`` (the lowest index among equals) is tracked from, on a
         pair built at that pose, and the estimate is held against the map.  kept: (run as ``_run_tracker`` returns it,
         pair, start pose, verdict) of the run kept so far.  Returns (that candidate's index, accepted, the run's steps,
-        the state to keep now) -- or None when failed_start says that candidate 0 is the start that has just failed,
-        and it scores highest."""
-        cfg = self._reloc
+        the state to keep now, (candidates replaced by their alignment -- None with reloc_align_top at 0 --, the run
+        was a direct one)) -- or None when failed_start says that candidate 0 is the start that has just failed, and
+        it scores highest.
+        reloc_align_top: the candidates with the largest margins, that many (the lowest index among equals), are
+        aligned in one ``align_poses`` call and the aligned poses scored in one more; an alignment that moved and that
+        passes ``_share_rule`` against its own candidate takes the candidate's place and margin before the winner is
+        chosen.  With align_accept a winner that is such an alignment and passes ``_direct_reason`` is the estimate
+        without a tracking, when the map accepts it."""
+        cfg, near = self._reloc, self.cfg.gs.near_plane
         cands = reloc_candidates(bases, cfg.reloc_rot_deg, cfg.reloc_trans, cfg.reloc_levels).to(self.device)
-        scores = self.map.score_poses(depth, self.K, cands, self.cfg.gs.near_plane)
+        scores = self.map.score_poses(depth, self.K, cands, near)
         margins = [int(s[1]) - int(s[2]) for s in scores]
+        aligned = {}  # candidate -> the alignment that took its place
+        if cfg.reloc_align_top > 0:
+            top = sorted(range(len(margins)), key=lambda i: (-margins[i], i))[: cfg.reloc_align_top]
+            als = self.map.align_poses(depth, self.K, [cands[i] for i in top], near)
+            tos = [al.c2w.to(self.device) for al in als]
+            cands = cands.clone()
+            for i, al, to, sc in zip(top, als, tos, self.map.score_poses(depth, self.K, tos, near)):
+                if al.moved and self._share_rule(tuple(int(c) for c in scores[i]), tuple(int(c) for c in sc)):
+                    cands[i], margins[i], aligned[i] = to.to(cands.dtype), int(sc[1]) - int(sc[2]), al
+        replaced = len(aligned) if cfg.reloc_align_top > 0 else None
         winner = margins.index(max(margins))  # the lowest index among equals
-        if failed_start and winner == 0:
+        if failed_start and winner == 0 and 0 not in aligned:
             return None
         pair = self._map_pair(cands[winner], frame)
-        run = self._run_tracker(pair, cands[winner])
-        verdict = self._verdict(depth, run[4])
-        accepted = self._accepted(run[2], verdict)
+        run, direct = None, False
+        if self._accept is not None and winner in aligned and self._direct_reason(aligned[winner], True) is None:
+            run = self._direct_run(pair, cands[winner])
+            verdict = self._verdict(depth, run[4])
+            direct = self._accepted(run[2], verdict, direct=True)
+        if not direct:
+            run = self._run_tracker(pair, cands[winner])
+            verdict = self._verdict(depth, run[4])
+        accepted = direct or self._accepted(run[2], verdict)
         if accepted or verdict[1] - verdict[2] > kept[3][1] - kept[3][2]:  # better-scoring, rejected: still handed on
             kept = (run, pair, cands[winner], verdict)
-        return winner, accepted, run[2].steps, kept
+        return winner, accepted, run[2].steps, kept, (replaced, direct)
 
     def _recognise(self, depth: Tensor, frame, kept):
         """Place recognition for a frame that the grid around its start poses has left lost: ``_retry`` around the turned
@@ -540,39 +622,55 @@ class Localizer:
         else:
             init = predict_pose(self._poses[-2], placed)
         gt = None if gt_c2w is None else torch.as_tensor(gt_c2w, dtype=torch.float32, device=self.device)
-        alignment = None
+        alignment, direct, reason = None, None, None
         # the pair's reference pose is the tracker's error read-out only: without ground truth, the starting pose
         if self.map_mode:
             if self.map.n_live == 0:
                 raise RuntimeError("Localizer.track: the map is empty (the first frame had no valid depth)")
             if self._align:
-                alignment, init = self._aligned_start(depth, init)
+                alignment, init, reason = self._aligned_start(depth, init)
+                direct = None if self._accept is None else reason is None
             frame = (pts, col, depth, rgb, placed, gt if gt is not None else init)
             d = self._map_pair(init, frame)
         else:
             d = build_pair(self._prev[0], self._prev[1], pts, col, depth, rgb, placed, gt if gt is not None else init,
                            self.K, self.normalize)
-        N, scales, res, best, est = self._run_tracker(d, init)
-        steps, lost, verdict, relocalised, recognised = res.steps, res.best_step == -1, None, None, None
+        run, verdict = None, None
+        if direct:
+            # the aligned pose is the estimate, on the pair built there.  reloc holds it against the map as any estimate;
+            # one it rejects is dropped, and the frame runs from the motion model's start as without the options
+            run = self._direct_run(d, init)
+            if self._reloc is not None:
+                verdict = self._verdict(depth, run[4])
+                if not self._accepted(run[2], verdict, direct=True):
+                    run, verdict, direct, reason, init = None, None, False, "rejected", alignment[3]
+                    frame = (pts, col, depth, rgb, placed, gt if gt is not None else init)
+                    d = self._map_pair(init, frame)
+        N, scales, res, best, est = run if run is not None else self._run_tracker(d, init)
+        steps, lost, relocalised, recognised, reloc_aligned = res.steps, res.best_step == -1 and not direct, None, None, None
         if self._reloc is not None:
             # before anything touches the map: does it confirm the estimate?  If not, the best-scoring pose of a grid
             # around the start poses is tracked from once more; an estimate the map still rejects is a lost frame's
-            verdict, relocalised = self._verdict(depth, est), False
-            lost = not self._accepted(res, verdict)
+            verdict, relocalised = self._verdict(depth, est) if verdict is None else verdict, False
+            lost = not self._accepted(res, verdict, direct=bool(direct))
             kept = ((N, scales, res, best, est), d, init, verdict)
             if lost:
                 again = self._retry(depth, frame, [init] if torch.equal(placed, init) else [init, placed], kept, True)
                 if again is not None:
-                    _, relocalised, more, kept = again
+                    _, relocalised, more, kept, (reloc_aligned, took) = again
                     steps, lost = steps + more, not relocalised
+                    if took:
+                        direct, reason = True, None
             if self._keyframes:
                 recognised = -1
                 found = self._recognise(depth, frame, kept) if lost and self.map.n_keyframes > 0 else None
                 if found is not None:
-                    slot, accepted, more, kept = found
+                    slot, accepted, more, kept, (reloc_aligned, took) = found
                     steps += more
                     if accepted:
                         lost, relocalised, recognised = False, True, slot
+                        if took:
+                            direct, reason = True, None
             (N, scales, res, best, est), d, init, verdict = kept
         self._prev = (pts, col)
         self._poses.append(est)
@@ -584,10 +682,11 @@ class Localizer:
                              lost=lost)
         if verdict is not None:
             out.relocalised, (out.tested, out.agree, out.front) = relocalised, verdict
-            out.recognised = recognised
+            out.recognised, out.reloc_aligned = recognised, reloc_aligned
         if alignment is not None:
             (out.aligned, out.align_status, out.align_steps, out.align_from, out.align_moved_t,
              out.align_moved_r_deg, out.align_scores) = alignment
+            out.direct, out.direct_reason = direct, reason
         if self.map_mode:
             out.added, out.tracked = 0, N
             out.removed = 0 if self._free else None
@@ -613,7 +712,7 @@ class Localizer:
                     # the corrected pose (no second tracking), as below where the band did not hold
                     d = self._map_pair(est, frame)
                     scales = init_gs_scales(d.tar_points)
-                    at = transform_cameras(d.norm_T, est.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else est
+                    at = self._pair_pose(d, est)
                 if self._view_guard is not None:
                     # the band is checked against the estimate, not assumed: rows that reach into the view from there
                     # and were not tracked would render as an empty border, and insert_frame would add them a second
@@ -623,7 +722,7 @@ class Localizer:
                     if out.view_violations > 0:
                         d = self._map_pair(est, frame)
                         scales = init_gs_scales(d.tar_points)
-                        at = transform_cameras(d.norm_T, est.unsqueeze(0))[0].squeeze(0) if d.norm_T is not None else est
+                        at = self._pair_pose(d, est)
                 render, alphas = self._map_render(d, scales, at)
                 if self._refine:
                     # after the render, before the insertion: every live row is an old one, and the render above is of

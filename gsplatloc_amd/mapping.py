@@ -108,6 +108,7 @@ INFO_ONE = float(2 ** 20)  # their fixed point
 INFO_MIN_EIG = 1e-3
 ALIGN_MAX_STEPS = 32  # iterations one call of csrc/map_align.hip runs at the most (gsl_map_align_max_steps())
 ALIGN_STATE_WORDS, ALIGN_ROW_WORDS = 14, 10  # 8-byte words of its state and of a history row (include/gsloc_hip.h)
+ALIGN_BATCH_MAX_POSES = 16  # poses one call of csrc/map_align_batch.hip aligns (gsl_map_align_batch_max_poses())
 ALIGN_MIN_USED = 7  # rows: six unknowns and one to spare, as PoseInformation.weak
 ALIGN_STATUS = ("STEPPED", "CONVERGED", "FEW", "SINGULAR", "TOO_FAR")  # GSL_MAP_ALIGN_*
 
@@ -151,6 +152,19 @@ class PoseInformation:
         return -np.linalg.solve(self.H, self.g)
 
 
+def information_from_sums(sums, min_eig: float = INFO_MIN_EIG) -> PoseInformation:
+    """The ``PoseInformation`` of the 30 int64 sums of csrc/map_info.hip (the upper triangle of H row-major, g, the
+    residual sum, the rows used and tested)."""
+    sums = np.asarray(sums, dtype=np.int64)
+    H, k = np.zeros((6, 6)), 0
+    for a in range(6):
+        for b in range(a, 6):
+            H[a, b] = H[b, a] = float(sums[k]) / INFO_ONE
+            k += 1
+    return PoseInformation(H, sums[21:27].astype(np.float64) / INFO_ONE, float(sums[27]) / INFO_ONE, int(sums[28]),
+                           int(sums[29]), min_eig)
+
+
 @dataclass
 class PoseAlignment:
     """What ``GaussianMap.align_pose`` returns.  c2w: float32 [4,4] on the map's device, the float64 inverse of w2c64
@@ -168,6 +182,10 @@ class PoseAlignment:
     used: int
     tested: int
     history: list
+    # ``align_poses`` only: closed -- the device took the sums once more at the final pose (its ``done`` word reads 2);
+    # final: the ``PoseInformation`` of those sums, the normal equations at c2w, present when closed
+    closed: bool = False
+    final: Optional[PoseInformation] = None
 
     @property
     def moved(self) -> bool:
@@ -558,6 +576,10 @@ class MapConfig:
     reloc_rot_deg: float = 2.0
     reloc_trans: float = 0.05
     reloc_levels: int = 2
+    # with reloc: the reloc_align_top best-scoring candidates of a grid (0: none, at most 16) are aligned to the map in
+    # one call (GaussianMap.align_poses) and scored once more; an alignment that moved and that the map scores no worse
+    # than its candidate takes the candidate's place before the winner is chosen
+    reloc_align_top: int = 0
     # Localizer(mode="map"), with reloc: place recognition.  The map keeps up to keyframe_max keyframes (a ring: the
     # oldest goes first) -- the pose of an inserted frame and a 16 x 12 integer descriptor of its depth image
     # (GaussianMap.add_keyframe) -- and a frame that the relocalisation above leaves lost is compared with all of them
@@ -614,6 +636,14 @@ class MapConfig:
     # a step within both has converged: a tenth of the smallest per-frame error of the 160x120 sequence (NOTES.md)
     align_eps_rot_deg: float = 1.5e-4
     align_eps_trans: float = 3e-5
+    # with align: a converged alignment may be the frame's pose.  The start goes through GaussianMap.align_poses, and
+    # when the alignment is CONVERGED and closed, the map scores it no worse than the start, its final sums used at
+    # least align_accept_min_used rows (None: W * H // 16, the default of reloc_min_tested) and are not weak at
+    # align_accept_min_eig (None: INFO_MIN_EIG), the aligned pose is the estimate and the tracker does not run
+    # (localizer.py; NOTES.md, "Batched alignment")
+    align_accept: bool = False
+    align_accept_min_used: Optional[int] = None
+    align_accept_min_eig: Optional[float] = None
     # trajectory correction: every row carries the index of the frame that appended it (GaussianMap.origins), so that
     # the rows can follow a corrected trajectory (GaussianMap.correct, Localizer.correct_trajectory / close_loop)
     origins: bool = False
@@ -680,6 +710,19 @@ class MapConfig:
             v = getattr(self, name)
             if not number(v) or not (np.isfinite(v) and v >= 0):
                 raise ValueError(f"{name} {v!r}: {unit}, finite and not negative")
+        if not isinstance(self.align_accept, bool):
+            raise ValueError(f"align_accept {self.align_accept!r}: True or False")
+        if self.align_accept and not self.align:
+            raise ValueError("align_accept=True needs align=True: the pose that is accepted is the aligned start")
+        if self.align_accept_min_used is not None and (not whole(self.align_accept_min_used)
+                                                       or self.align_accept_min_used < ALIGN_MIN_USED):
+            raise ValueError(f"align_accept_min_used {self.align_accept_min_used!r}: a whole number of rows, at least "
+                             f"{ALIGN_MIN_USED} (or None)")
+        if self.align_accept_min_eig is not None and (
+                not number(self.align_accept_min_eig)
+                or not (np.isfinite(self.align_accept_min_eig) and self.align_accept_min_eig > 0)):
+            raise ValueError(f"align_accept_min_eig {self.align_accept_min_eig!r}: an eigenvalue of H / used, finite and "
+                             "above 0 (or None)")
         if not isinstance(self.info, bool):
             raise ValueError(f"info {self.info!r}: True or False")
         if self.info_rho is not None and (not number(self.info_rho) or not 0.0 <= self.info_rho < 1.0):
@@ -731,6 +774,11 @@ class MapConfig:
             raise ValueError(f"reloc_trans {self.reloc_trans!r}: metres, finite and above 0")
         if not whole(self.reloc_levels) or not 1 <= self.reloc_levels <= 2:
             raise ValueError(f"reloc_levels {self.reloc_levels!r}: a whole number of steps per direction, 1 .. 2")
+        if not whole(self.reloc_align_top) or not 0 <= self.reloc_align_top <= ALIGN_BATCH_MAX_POSES:
+            raise ValueError(f"reloc_align_top {self.reloc_align_top!r}: a whole number of candidates, 0 .. "
+                             f"{ALIGN_BATCH_MAX_POSES}")
+        if self.reloc_align_top and not self.reloc:
+            raise ValueError("reloc_align_top needs reloc=True: the candidates that are aligned are the relocalisation's")
         if self.place_top * (1 + 12 * self.reloc_levels) > SCORE_MAX_POSES:
             raise ValueError(f"place_top {self.place_top!r}: with reloc_levels {self.reloc_levels} that many bases make "
                              f"{self.place_top * (1 + 12 * self.reloc_levels)} candidate poses, one scoring call takes "
@@ -850,6 +898,7 @@ class GaussianMap:
         self._info = None
         # align_pose: one buffer of 8-byte words -- state, history, working pose, sums -- and the start pose, on first use
         self._align = None
+        self._align_batch = None  # align_poses: the same for 16 poses, on first use
         # origins: the index of the frame that appended each row; nothing of it without the option.  The insertions
         # since clear() and the last one's origin; the frame index of the keyframe in every slot (-1: not recorded);
         # correct's two 64-bit counters on first use
@@ -1316,14 +1365,7 @@ class GaussianMap:
         keep, beyond = float(np.float32(1.0) - np.float32(rho)), float(np.float32(1.0) + np.float32(rho))
         sums = self._info_launch(depth, intr, _world_to_camera(c2w).to(self.device).contiguous(), keep, beyond,
                                  float(np.float32(kappa)), float(near_plane))
-        sums = np.asarray(sums, dtype=np.int64)
-        H, k = np.zeros((6, 6)), 0
-        for a in range(6):
-            for b in range(a, 6):
-                H[a, b] = H[b, a] = float(sums[k]) / INFO_ONE
-                k += 1
-        return PoseInformation(H, sums[21:27].astype(np.float64) / INFO_ONE, float(sums[27]) / INFO_ONE, int(sums[28]),
-                               int(sums[29]), min_eig)
+        return information_from_sums(sums, min_eig)
 
     # ---- pose alignment: Gauss-Newton steps on those normal equations, iterated on the device (csrc/map_align.hip) ----
     def _align_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, keep: float,
@@ -1353,24 +1395,11 @@ class GaussianMap:
                 host[n_state + n_hist:n_state + n_hist + 8].view(np.float32).reshape(4, 4).copy(), int(host[12]),
                 hist[:, :4].copy(), hist[:, 4:].copy().view(np.float64))
 
-    @torch.no_grad()
-    def align_pose(self, depth, K, c2w, near_plane: float, steps: Optional[int] = None, rho: Optional[float] = None,
-                   kappa: Optional[float] = None, damping: Optional[float] = None, max_rot_deg: Optional[float] = None,
-                   max_trans: Optional[float] = None, eps_rot_deg: Optional[float] = None,
-                   eps_trans: Optional[float] = None, min_used: int = ALIGN_MIN_USED,
-                   rows: Optional[int] = None) -> PoseAlignment:
-        """The pose c2w [4,4] aligned to the map against the depth frame [H,W] (metres): up to ``steps`` (None:
-        ``align_steps``) damped Gauss-Newton steps on the normal equations of ``pose_information`` -- the rows chosen
-        with ``rho`` (None: ``align_rho``, and ``depth_rho`` when that is None) and ``kappa`` (None: ``info_kappa``),
-        ``damping`` (None: ``align_damping``) times the rows used on the diagonal -- each of them solved, bounded
-        (``max_rot_deg`` / ``max_trans``), applied and tested for convergence (``eps_rot_deg`` / ``eps_trans``) on the
-        device in float64 (the rule: include/gsloc_hip.h).  The start is rounded to float32 as every pose a kernel is
-        given.  Changes nothing in the map.  One fixed sequence of 1 + 3 ``steps`` launches, one read-back; an empty
-        map gives status FEW without a launch.  The result has to be checked by the caller: a start too far off can
-        settle elsewhere (NOTES.md, "Pose alignment").  rows: only the first that many rows of the map are used
-        (``loop_constraint``; None: every live row)."""
+    def _align_params(self, steps, rho, kappa, damping, max_rot_deg, max_trans, eps_rot_deg, eps_trans, min_used):
+        """The keyword arguments of ``align_pose`` / ``align_poses`` with their defaults filled in, checked, in the units
+        of the entry points: (steps, keep, beyond, kappa, damping, min_used, max_rot [rad], max_trans, eps_rot [rad],
+        eps_trans)."""
         cfg = self.cfg
-        rows = self._prefix(rows)
         steps = int(cfg.align_steps if steps is None else steps)
         if not 1 <= steps <= ALIGN_MAX_STEPS:
             raise ValueError(f"steps {steps!r}: a whole number of iterations, 1 .. {ALIGN_MAX_STEPS}")
@@ -1395,6 +1424,28 @@ class GaussianMap:
         min_used = int(min_used)
         if min_used < ALIGN_MIN_USED:
             raise ValueError(f"min_used {min_used!r}: at least {ALIGN_MIN_USED} rows")
+        keep, beyond = float(np.float32(1.0) - np.float32(rho)), float(np.float32(1.0) + np.float32(rho))
+        return (steps, keep, beyond, float(np.float32(kappa)), damping, min_used, max_rot, max_trans, eps_rot, eps_trans)
+
+    @torch.no_grad()
+    def align_pose(self, depth, K, c2w, near_plane: float, steps: Optional[int] = None, rho: Optional[float] = None,
+                   kappa: Optional[float] = None, damping: Optional[float] = None, max_rot_deg: Optional[float] = None,
+                   max_trans: Optional[float] = None, eps_rot_deg: Optional[float] = None,
+                   eps_trans: Optional[float] = None, min_used: int = ALIGN_MIN_USED,
+                   rows: Optional[int] = None) -> PoseAlignment:
+        """The pose c2w [4,4] aligned to the map against the depth frame [H,W] (metres): up to ``steps`` (None:
+        ``align_steps``) damped Gauss-Newton steps on the normal equations of ``pose_information`` -- the rows chosen
+        with ``rho`` (None: ``align_rho``, and ``depth_rho`` when that is None) and ``kappa`` (None: ``info_kappa``),
+        ``damping`` (None: ``align_damping``) times the rows used on the diagonal -- each of them solved, bounded
+        (``max_rot_deg`` / ``max_trans``), applied and tested for convergence (``eps_rot_deg`` / ``eps_trans``) on the
+        device in float64 (the rule: include/gsloc_hip.h).  The start is rounded to float32 as every pose a kernel is
+        given.  Changes nothing in the map.  One fixed sequence of 1 + 3 ``steps`` launches, one read-back; an empty
+        map gives status FEW without a launch.  The result has to be checked by the caller: a start too far off can
+        settle elsewhere (NOTES.md, "Pose alignment").  rows: only the first that many rows of the map are used
+        (``loop_constraint``; None: every live row)."""
+        rows = self._prefix(rows)
+        (steps, keep, beyond, kappa, damping, min_used, max_rot, max_trans, eps_rot,
+         eps_trans) = self._align_params(steps, rho, kappa, damping, max_rot_deg, max_trans, eps_rot_deg, eps_trans, min_used)
         depth = self._depth_image(depth)
         intr, c2w = _intr_and_pose(K, c2w)
         w2c = _world_to_camera(c2w)
@@ -1402,17 +1453,99 @@ class GaussianMap:
             pose, n, hist, xis = w2c.numpy()[:3].astype(np.float64), 0, np.zeros((1, 4), np.int64), np.zeros((1, 6))
             hist[0, 0] = ALIGN_STATUS.index("FEW")
         else:
-            keep, beyond = float(np.float32(1.0) - np.float32(rho)), float(np.float32(1.0) + np.float32(rho))
             prefix = {} if rows is None else dict(n_rows=rows)
-            pose, _, n, hist, xis = self._align_launch(depth, intr, w2c.contiguous(), keep, beyond,
-                                                       float(np.float32(kappa)), float(near_plane), steps, damping,
-                                                       min_used, max_rot, max_trans, eps_rot, eps_trans, **prefix)
+            pose, _, n, hist, xis = self._align_launch(depth, intr, w2c.contiguous(), keep, beyond, kappa,
+                                                       float(near_plane), steps, damping, min_used, max_rot, max_trans,
+                                                       eps_rot, eps_trans, **prefix)
+        return self._alignment(pose, n, hist, xis)
+
+    def _alignment(self, pose, n, hist, xis, final: Optional[PoseInformation] = None) -> PoseAlignment:
+        """The ``PoseAlignment`` of what a launch read back: the pose [3,4] float64, the steps applied, the history's
+        integers [steps,4] and xi [steps,6]; final: the information at the final pose of a closed pose."""
         w2c64 = np.eye(4)
         w2c64[:3] = pose
         history = [(ALIGN_STATUS[int(r[0])], int(r[1]), int(r[2]), float(r[3]) / INFO_ONE, np.array(x, dtype=np.float64))
                    for r, x in zip(hist, xis)]
         aligned = torch.from_numpy(np.linalg.inv(w2c64).astype(np.float32)).to(self.device)
-        return PoseAlignment(aligned, w2c64, history[-1][0], int(n), history[-1][1], history[-1][2], history)
+        return PoseAlignment(aligned, w2c64, history[-1][0], int(n), history[-1][1], history[-1][2], history,
+                             closed=final is not None, final=final)
+
+    # ---- the same for several poses in one call, a finished pose closed by its final sums (csrc/map_align_batch.hip) ---
+    def _align_batch_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, keep: float,
+                            beyond: float, kappa: float, near: float, steps: int, damping: float, min_used: int,
+                            max_rot: float, max_trans: float, eps_rot: float, eps_trans: float,
+                            n_rows: Optional[int] = None) -> list:
+        """w2c [k,4,4] float32 on the host, k <= 16.  Their copy to the device, the entry point and the read-back of one
+        buffer, the call's one synchronisation.  Per pose: (pose [3,4] float64, working pose [4,4] float32, steps
+        applied, done, rows [steps,4] int64, xi [steps,6] float64, sums [30] int64)."""
+        assert depth.is_cuda, "GaussianMap.align_poses: the poses are aligned by HIP kernels, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        cap, k = ALIGN_BATCH_MAX_POSES, int(w2c.shape[0])
+        n_hist = steps * ALIGN_ROW_WORDS  # the history is laid out for this call's steps
+        at_state, at_hist = 0, cap * ALIGN_STATE_WORDS  # offsets in 8-byte words; the sections are sized for 16 poses
+        at_work = at_hist + cap * ALIGN_MAX_STEPS * ALIGN_ROW_WORDS
+        at_sums = at_work + cap * 8
+        if self._align_batch is None:
+            self._align_batch = dict(words=torch.zeros(at_sums + cap * INFO_VALUES, dtype=torch.int64, device=self.device),
+                                     start=torch.empty(cap, 16, device=self.device))
+        a = self._align_batch
+        n_rows = self.n_live if n_rows is None else int(n_rows)
+        words, base = a["words"], a["words"].data_ptr()
+        a["start"][:k].copy_(w2c.reshape(k, 16))
+        _lib.check(lib.gsl_map_pose_align_batch(ptr(self.means), n_rows, ptr(a["start"]), k, *intr, ptr(depth), self.W,
+                                                self.H, keep, beyond, kappa, near, steps, damping, min_used, max_rot,
+                                                max_trans, eps_rot, eps_trans, base + 8 * at_sums, base + 8 * at_work,
+                                                base + 8 * at_state, base + 8 * at_hist, st), "gsl_map_pose_align_batch")
+        host = words.cpu().numpy()
+        out = []
+        for p in range(k):
+            state = host[at_state + p * ALIGN_STATE_WORDS:at_state + (p + 1) * ALIGN_STATE_WORDS]
+            hist = host[at_hist + p * n_hist:at_hist + (p + 1) * n_hist].reshape(steps, ALIGN_ROW_WORDS)
+            out.append((state[:12].view(np.float64).reshape(3, 4).copy(),
+                        host[at_work + p * 8:at_work + (p + 1) * 8].view(np.float32).reshape(4, 4).copy(),
+                        int(state[12]), int(state[13]), hist[:, :4].copy(), hist[:, 4:].copy().view(np.float64),
+                        host[at_sums + p * INFO_VALUES:at_sums + (p + 1) * INFO_VALUES].copy()))
+        return out
+
+    @torch.no_grad()
+    def align_poses(self, depth, K, c2ws, near_plane: float, steps: Optional[int] = None, rho: Optional[float] = None,
+                    kappa: Optional[float] = None, damping: Optional[float] = None, max_rot_deg: Optional[float] = None,
+                    max_trans: Optional[float] = None, eps_rot_deg: Optional[float] = None,
+                    eps_trans: Optional[float] = None, min_used: int = ALIGN_MIN_USED,
+                    rows: Optional[int] = None) -> list:
+        """``align_pose`` for each of the poses c2ws [k,4,4] (a tensor, or a sequence of [4,4] poses) against the same
+        frame, with the same keyword arguments and defaults: one call of 1 + 3 ``steps`` launches and one read-back for
+        up to 16 poses (more go in chunks of 16).  Pose, status, steps and history of every ``PoseAlignment`` are bit
+        for bit ``align_pose``'s.  On the device a pose that has finished stops paying for its sums, after one more
+        pass at its final pose: the result is then ``closed`` and ``final`` holds those sums as a ``PoseInformation``
+        (with ``info_min_eig``) -- what ``pose_information`` gives at c2w, without another launch.  A pose that
+        converges on the last iteration is not closed.  An empty map gives status FEW, not closed, without a launch."""
+        rows = self._prefix(rows)
+        (steps, keep, beyond, kappa, damping, min_used, max_rot, max_trans, eps_rot,
+         eps_trans) = self._align_params(steps, rho, kappa, damping, max_rot_deg, max_trans, eps_rot_deg, eps_trans, min_used)
+        poses = [torch.as_tensor(c) for c in c2ws]
+        for c in poses:
+            if c.shape != (4, 4):
+                raise ValueError(f"a pose is {tuple(c.shape)}, not (4, 4)")
+        if not poses:
+            return []
+        depth = self._depth_image(depth)
+        intr, _ = _intr_and_pose(K, poses[0])
+        w2c = _world_to_camera(torch.stack([c.detach().cpu().double() for c in poses]))
+        if (self.n_live if rows is None else rows) == 0:
+            hist = np.zeros((1, 4), np.int64)
+            hist[0, 0] = ALIGN_STATUS.index("FEW")
+            return [self._alignment(w.numpy()[:3].astype(np.float64), 0, hist, np.zeros((1, 6))) for w in w2c]
+        min_eig = INFO_MIN_EIG if self.cfg.info_min_eig is None else float(self.cfg.info_min_eig)
+        prefix = {} if rows is None else dict(n_rows=rows)
+        out = []
+        for at in range(0, len(poses), ALIGN_BATCH_MAX_POSES):
+            chunk = w2c[at:at + ALIGN_BATCH_MAX_POSES].contiguous()
+            for pose, _, n, done, hist, xis, sums in self._align_batch_launch(
+                    depth, intr, chunk, keep, beyond, kappa, float(near_plane), steps, damping, min_used, max_rot,
+                    max_trans, eps_rot, eps_trans, **prefix):
+                out.append(self._alignment(pose, n, hist, xis, information_from_sums(sums, min_eig) if done == 2 else None))
+        return out
 
     # ---- trajectory correction: the rows follow the frame they came from (csrc/map_correct.hip) ----------------------
     @torch.no_grad()

@@ -404,6 +404,33 @@ int gsl_map_pose_align(const float* means, int64_t n_rows, const float* w2c, flo
                        double eps_rot, double eps_trans, int64_t* sums, float* work, void* state, void* history,
                        void* stream);
 
+/* ---- pose alignment of several poses in one call, with an early exit per pose (csrc/map_align_batch.hip) ----
+ * n_poses (1 .. GSL_MAP_ALIGN_BATCH_MAX_POSES = gsl_map_align_batch_max_poses()) world-to-camera start poses
+ * w2c[n_poses][16] are aligned against the same rows, depth frame and parameters, each as gsl_map_pose_align aligns it
+ * alone.  The buffers are gsl_map_pose_align's per pose, pose-major, on the device, not initialised, not overlapping:
+ * sums[n_poses][GSL_MAP_INFO_VALUES] int64, work[n_poses][16] float32, state[n_poses][GSL_MAP_ALIGN_STATE_WORDS] and
+ * history[n_poses][max_steps][GSL_MAP_ALIGN_ROW_WORDS] 8-byte words.
+ * One initialising launch; then per iteration a launch that zeroes the sums, one that takes the sums of all poses (the
+ * pose on the second grid dimension) and a kernel with one thread per pose that takes gsl_map_pose_align's step.
+ * A pose's done word has three values: 0 running; 1 finished, its sums at the final pose still to be taken; 2 closed.
+ * A CONVERGED step sets 1: the next iteration takes the sums once more at the pose the step left, records the row (the
+ * previous status, xi = 0, as gsl_map_pose_align does after done) and sets 2.  FEW, SINGULAR and TOO_FAR did not move
+ * the pose and set 2 at once.  For a closed pose the sums' workgroups leave after reading the word, its 30 sums are not
+ * zeroed, and the step kernel repeats the previous row's four integers with xi = 0.
+ * For every pose state (done apart), work and every history row are bit for bit what gsl_map_pose_align leaves for that
+ * pose alone (it recomputes identical integers at an unchanged pose).  With done == 2, sums[p] are what
+ * gsl_map_pose_info gives at work[p]: the normal equations at the final pose.  A pose that converges on the last
+ * iteration is left at 1, and its sums are those of the pose before that step.
+ * No allocation, no synchronisation, no read-back, no memset node.  Returns GSL_ERR_BAD_ARG before any launch for
+ * whatever gsl_map_pose_align refuses and for n_poses outside 1 .. GSL_MAP_ALIGN_BATCH_MAX_POSES. */
+#define GSL_MAP_ALIGN_BATCH_MAX_POSES 16
+int gsl_map_align_batch_max_poses(void);
+int gsl_map_pose_align_batch(const float* means, int64_t n_rows, const float* w2c, int n_poses, float fx, float fy,
+                             float cx, float cy, const float* depth, int width, int height, float keep, float beyond,
+                             float kappa, float near_plane, int max_steps, double damping, int min_used, double max_rot,
+                             double max_trans, double eps_rot, double eps_trans, int64_t* sums, float* work, void* state,
+                             void* history, void* stream);
+
 /* ---- place recognition: a 16 x 12 descriptor of a depth frame, and its match against keyframes (csrc/map_place.hip) ----
  * gsl_map_place_describe: depth[height,width] float32 on the device, row-major, metres; desc[192] int32 on the device,
  * row-major over GSL_MAP_PLACE_GH lines of GSL_MAP_PLACE_GW cells (gsl_map_place_cells() = 192).  It need not be

@@ -403,25 +403,108 @@ def align_cost(sizes=((320, 240), (640, 480)), steps=8, calls=20, warm=3, window
                                           "statuses": list(ALIGN_STATUS)}), flush=True)
 
 
+def align_batch_cost(sizes=((320, 240), (640, 480)), steps=8, calls=20, warm=3, windows=5):
+    """Batched pose alignment, the cost of a call: gsl_map_pose_align_batch on 1, 4 and 16 poses beside as many single
+    calls of gsl_map_pose_align, on the map and the query of ``align_cost``, the start poses a millimetre apart; and the
+    16-pose call once more with a stop tolerance of 0 -- no pose finishes, every iteration pays for every pose's sums --
+    whose difference to the first is what the early exit saves.  Device events around ``calls`` calls after ``warm``
+    warm-ups, ``windows`` windows of each, alternating; medians in microseconds per call."""
+    import math
+
+    import numpy as np
+
+    from gsplatloc_amd import _lib
+    from gsplatloc_amd.mapping import ALIGN_BATCH_MAX_POSES, GaussianMap
+    from gsplatloc_amd.synthetic import replica_intrinsics
+
+    lib, ptr, cap = _lib.load_library(), _lib.ptr, ALIGN_BATCH_MAX_POSES
+
+    def yaw(position, deg):
+        c, s = math.cos(math.radians(deg)), math.sin(math.radians(deg))
+        T = np.eye(4)
+        T[:3, :3] = [[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]]
+        T[:3, 3] = position
+        return T
+
+    for W, H in sizes:
+        K = replica_intrinsics(W, H)
+        at_map = torch.from_numpy(yaw((0.6, 0.1, 0.8), 35.0))
+        m = GaussianMap(W, H, MapConfig(align=True), "cuda")
+        m.insert_frame(room_depth(W, H, K, at_map.float()).cuda(), torch.zeros(H, W, 3, device="cuda"), K, at_map.float())
+        depth = room_depth(W, H, K, torch.from_numpy(yaw((0.608, 0.1, 0.794), 35.5)).float()).cuda().contiguous()
+        starts = [yaw((0.6 + 1e-3 * (p % 4), 0.1, 0.8 + 1e-3 * (p // 4)), 35.0) for p in range(cap)]
+        als = m.align_poses(depth, K, [torch.from_numpy(c) for c in starts], 0.01, steps=steps)
+        w2c = torch.from_numpy(np.stack([np.linalg.inv(c).astype(np.float32) for c in starts])).cuda().reshape(cap, 16)
+        intr = tuple(float(v) for v in (K[0, 0], K[1, 1], K[0, 2], K[1, 2]))
+        keep, beyond = float(np.float32(1) - np.float32(0.05)), float(np.float32(1) + np.float32(0.05))
+        sums = torch.zeros(cap * 30, dtype=torch.int64, device="cuda")
+        work, state = torch.zeros(cap * 16, device="cuda"), torch.zeros(cap * 14, dtype=torch.int64, device="cuda")
+        history = torch.zeros(cap * 32 * 10, dtype=torch.int64, device="cuda")
+        st = _lib.current_stream()
+        common = (1e-3, 7, math.radians(12.8), 0.32)
+
+        def batch(k, eps=(math.radians(1.5e-4), 3e-5)):
+            _lib.check(lib.gsl_map_pose_align_batch(ptr(m.means), m.n_live, ptr(w2c), k, *intr, ptr(depth), W, H, keep,
+                                                    beyond, 1e-3, 0.01, steps, *common, *eps, ptr(sums), ptr(work),
+                                                    ptr(state), ptr(history), st), "gsl_map_pose_align_batch")
+
+        def singles(k):
+            for p in range(k):
+                _lib.check(lib.gsl_map_pose_align(ptr(m.means), m.n_live, w2c[p].data_ptr(), *intr, ptr(depth), W, H, keep,
+                                                  beyond, 1e-3, 0.01, steps, *common, math.radians(1.5e-4), 3e-5, ptr(sums),
+                                                  ptr(work), ptr(state), ptr(history), st), "gsl_map_pose_align")
+
+        def window(fn):
+            for _ in range(warm):
+                fn()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            return 1e3 * a.elapsed_time(b) / calls  # microseconds per call
+
+        kinds = [(f"batch_{k}", lambda k=k: batch(k)) for k in (1, 4, cap)]
+        kinds += [(f"single_x{k}", lambda k=k: singles(k)) for k in (1, 4, cap)]
+        kinds += [(f"batch_{cap}_no_exit", lambda: batch(cap, (0.0, 0.0)))]
+        us = {name: [] for name, _ in kinds}
+        for _ in range(windows):
+            for name, fn in kinds:
+                us[name].append(round(window(fn), 1))
+        med = {name: sorted(v)[len(v) // 2] for name, v in us.items()}
+        print("ALIGN_BATCH_COST " + json.dumps({
+            "rows": m.n_live, "size": [W, H], "steps": steps, "statuses": [al.status for al in als],
+            "steps_applied": [al.steps for al in als], "closed": [al.closed for al in als], "us_per_call": us,
+            "median_us": med, "early_exit_saves_us": round(med[f"batch_{cap}_no_exit"] - med[f"batch_{cap}"], 1)}),
+            flush=True)
+
+
 def align(W, H, n, cost=True):
     """Pose alignment (MapConfig.align) on the random walk and the constant twist (``n`` frames): map mode without the
-    option beside map mode with it, alternating in one process, the second pass of each reported -- mean steps, frames
-    per second, ATE, and with the option the error of the motion model's pose and of the aligned start beside the
-    frame's final error; then the cost of the loop (``align_cost``)."""
+    option beside map mode with it and beside map mode with align_accept as well (a converged alignment is the frame's
+    pose), alternating in one process, the second pass of each reported -- mean steps, frames per second, ATE, with the
+    option the error of the motion model's pose and of the aligned start beside the frame's final error, with
+    align_accept the direct frames; then the cost of the loop (``align_cost``) and of the batched call
+    (``align_batch_cost``)."""
     writers = (("random_walk", lambda root: write_replica_sequence(root, W, H, n)),
                ("constant_twist", lambda root: write_replica_constant_twist(root, W, H, n)))
     for name, writer in writers:
         root = pathlib.Path(tempfile.mkdtemp())
         writer(root)
+        kinds = ((False, False), (True, False), (True, True))
         for _ in range(2):
             rows = [evaluate_room(Parser("Replica", "room0", normalize=True, input_folder=str(root)), 2000, None,
-                                  sequential=True, map_mode=True, map_align=on) for on in (False, True)]
-        for on, r in zip((False, True), rows):
+                                  sequential=True, map_mode=True, map_align=on, map_align_accept=accept)
+                    for on, accept in kinds]
+        for (on, accept), r in zip(kinds, rows):
             for k in ("added_per_frame", "tracked_per_frame"):
                 r.pop(k, None)
-            print("MAP_FIG " + json.dumps({"sequence": name, "map": True, "align": on, **r}), flush=True)
+            print("MAP_FIG " + json.dumps({"sequence": name, "map": True, "align": on, "align_accept": accept, **r}),
+                  flush=True)
     if cost:
         align_cost()
+        align_batch_cost()
 
 
 def main():
