@@ -47,6 +47,12 @@ _SIGNATURES = {
     "gsl_map_view_select": (c_int, [P, c_int64, P, c_float, c_float, c_float, c_float, c_int, c_int, c_float, c_float,
                                     c_float, P, P, P, c_size_t, P]),
     "gsl_map_view_gather": (c_int, [P, P, c_int64, P, P, P, c_int64, P, P, c_size_t, P]),
+    "gsl_map_occl_zbuf_bytes": (c_size_t, [c_int, c_int, c_float, c_int]),
+    "gsl_map_occl_ws_bytes": (c_size_t, [c_int64]),
+    "gsl_map_occl_depth": (c_int, [P, c_int64, P, c_float, c_float, c_float, c_float, c_int, c_int, c_float, c_int,
+                                   c_float, c_float, P, c_size_t, P]),
+    "gsl_map_occl_select": (c_int, [P, c_int64, P, c_float, c_float, c_float, c_float, c_int, c_int, c_float, c_float,
+                                    c_float, c_int, c_int, c_float, P, c_size_t, P, P, P, c_size_t, P]),
     "gsl_map_free_select": (c_int, [P, c_int64, P, c_float, c_float, c_float, c_float, P, c_int, c_int, c_float, c_int,
                                     c_float, P, P, c_size_t, P]),
     "gsl_map_observe": (c_int, [P, c_int64, P, c_float, c_float, c_float, c_float, P, c_int, c_int, c_float, c_int,

@@ -44,7 +44,9 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   map_refine: bool = False, map_refine_max_weight: Optional[int] = None,
                   map_info: bool = False, map_align: bool = False, map_align_steps: Optional[int] = None,
                   map_origins: bool = False, map_loop: bool = False, map_loop_min_gap: Optional[int] = None,
-                  map_align_accept: bool = False, map_reloc_align_top: Optional[int] = None) -> Dict:
+                  map_align_accept: bool = False, map_reloc_align_top: Optional[int] = None,
+                  map_view_occlusion: Optional[float] = None, map_view_occlusion_cell: Optional[int] = None,
+                  map_view_occlusion_window: Optional[int] = None) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -69,8 +71,18 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     ``map_align_steps`` for MapConfig.align_steps where not None; ``map_align_accept``: MapConfig.align_accept, a
     converged alignment that the map's rows pin down is the frame's pose and the tracker does not run;
     ``map_reloc_align_top``: MapConfig.reloc_align_top, that many of the best relocalisation candidates are aligned to
-    the map before the winner is chosen)."""
+    the map before the winner is chosen; ``map_view_occlusion``: MapConfig.view_occlusion_rho, the rows of the guarded
+    view that nearer rows of the map hide are not tracked, with ``map_view_occlusion_cell`` /
+    ``map_view_occlusion_window`` for MapConfig.view_occlusion_cell_px / view_occlusion_window where not None)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
+    occlusion = {k: v for k, v in (("view_occlusion_cell_px", map_view_occlusion_cell),
+                                   ("view_occlusion_window", map_view_occlusion_window)) if v is not None}
+    if (map_view_occlusion is not None or occlusion) and map_view_guard is None:
+        raise ValueError("map_view_occlusion belongs to the guarded view (map_view_guard)")
+    if occlusion and map_view_occlusion is None:
+        raise ValueError(f"{', '.join('map_' + k for k in occlusion)}: options of map_view_occlusion")
+    if map_view_occlusion is not None:
+        occlusion["view_occlusion_rho"] = map_view_occlusion
     if map_merge_voxel is not None and not map_mode:
         raise ValueError("map_merge_voxel belongs to the map mode (map_mode=True)")
     if map_view_guard is not None and not map_mode:
@@ -127,7 +139,7 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                                    dict(reloc, reloc=True) if map_reloc else None,
                                    dict(keyframes, keyframes=True) if map_keyframes else None, map_refine=refine,
                                    map_info=bool(map_info), map_align=align, map_origins=bool(map_origins) or bool(map_loop),
-                                   map_loop=loop)
+                                   map_loop=loop, map_view_occlusion=occlusion or None)
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -194,7 +206,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                         map_merge_every: int = 1, map_reloc: Optional[Dict] = None,
                         map_keyframes: Optional[Dict] = None, map_refine: Optional[Dict] = None,
                         map_info: bool = False, map_align: Optional[Dict] = None, map_origins: bool = False,
-                        map_loop: Optional[Dict] = None) -> Dict:
+                        map_loop: Optional[Dict] = None, map_view_occlusion: Optional[Dict] = None) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
     map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
@@ -222,7 +234,9 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     needs map_origins); every frame that attempts a loop prints what became of it, and the report gains
     loop_status_per_frame, loop_closures (the frames that closed a loop), loop_anchors (the frame each of those edges
     starts at), loop_edge_residuals (of every kept edge after the last solve) and ate_corrected (the RMSE of the final,
-    corrected trajectory's translation errors; ATE is that of the estimates as they were made)."""
+    corrected trajectory's translation errors; ATE is that of the estimates as they were made).  map_view_occlusion: the
+    MapConfig fields of occlusion culling (view_occlusion_rho and, where wanted, view_occlusion_cell_px /
+    view_occlusion_window; it needs map_view_guard); the report gains view_culled_per_frame."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
@@ -234,13 +248,15 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                                                        merge_every=map_merge_every, **(map_reloc or {}),
                                                        **(map_keyframes or {}), **(map_refine or {}),
                                                        info=bool(map_info), **(map_align or {}),
-                                                       origins=bool(map_origins), **(map_loop or {})))
+                                                       origins=bool(map_origins), **(map_loop or {}),
+                                                       **(map_view_occlusion or {})))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
     merged_at_reset = loc.merged_at_reset
     eTs, eRs, steps, lost, path, last_t = [], [], [], 0, 0.0, pose[:3, 3]
     added, tracked, violations, removed, evicted, merged = [], [], [], [], [], []
+    culled = []
     relocalised, shares, recognised, refined = 0, [], 0, []
     sigma_t, sigma_r, info_used, info_eig, weak = [], [], [], [], 0
     aligned, align_steps, align_status, motion_eT, start_eT = [], [], [], [], []
@@ -257,6 +273,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
         added.append(r.added)
         tracked.append(r.tracked)
         violations.append(r.view_violations)
+        culled.append(r.view_culled)
         removed.append(r.removed)
         evicted.append(r.evicted)
         merged.append(r.merged)
@@ -319,6 +336,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                 "map_full": loc.map.full} if map_mode else {}),
             **({"view_guard_px": map_view_guard, "view_violations_per_frame": violations}
                if map_view_guard is not None else {}),
+            **({**map_view_occlusion, "view_culled_per_frame": culled} if map_view_occlusion else {}),
             **({"free_rho": map_free_rho, "free_window_px": map_free_window, "removed_per_frame": removed}
                if map_free_rho is not None else {}),
             **({"evict": True, "evicted_per_frame": evicted} if map_evict else {}),
@@ -373,6 +391,15 @@ def main(argv=None):
     ap.add_argument("--map-view-guard", type=float, default=None, metavar="PX",
                     help="--map: track every frame against the map's points in view from its start pose, the image "
                          "widened by PX pixels on every side (default: against all of them)")
+    ap.add_argument("--map-view-occlusion", type=float, default=None, metavar="RHO",
+                    help="--map-view-guard: leave out the points in view that nearer points of the map hide, those more "
+                         "than this fraction behind the nearest depth of every z-buffer cell around their own "
+                         "(default: the frustum is the only test)")
+    ap.add_argument("--map-view-occlusion-cell", type=int, default=None, metavar="PX",
+                    help="--map-view-occlusion: the side of a z-buffer cell, 1, 2, 4, 8 or 16 pixels (default 4)")
+    ap.add_argument("--map-view-occlusion-window", type=int, default=None, metavar="N",
+                    help="--map-view-occlusion: the cells around a point's cell that must all hold a nearer depth, "
+                         "0 .. 3 (default 1)")
     ap.add_argument("--map-free-rho", type=float, default=None, metavar="RHO",
                     help="--map: after every frame's insertion remove the map's points that the frame sees through, "
                          "those more than this fraction in front of everything it observes around their pixel "
@@ -446,6 +473,12 @@ def main(argv=None):
         ap.error("--map needs --sequential")
     if a.map_view_guard is not None and not a.map:
         ap.error("--map-view-guard needs --map")
+    if a.map_view_occlusion is not None and a.map_view_guard is None:
+        ap.error("--map-view-occlusion needs --map-view-guard")
+    for flag, value in (("--map-view-occlusion-cell", a.map_view_occlusion_cell),
+                        ("--map-view-occlusion-window", a.map_view_occlusion_window)):
+        if value is not None and a.map_view_occlusion is None:
+            ap.error(f"{flag} needs --map-view-occlusion")
     if a.map_free_rho is not None and not a.map:
         ap.error("--map-free-rho needs --map")
     if a.map_evict and not a.map:
@@ -500,7 +533,9 @@ def main(argv=None):
                           map_info=a.map_info, map_align=a.map_align, map_align_steps=a.map_align_steps,
                           map_align_accept=a.map_align_accept, map_reloc_align_top=a.map_reloc_align_top,
                           map_origins=a.map_origins or a.map_loop, map_loop=a.map_loop,
-                          map_loop_min_gap=a.map_loop_min_gap)
+                          map_loop_min_gap=a.map_loop_min_gap, map_view_occlusion=a.map_view_occlusion,
+                          map_view_occlusion_cell=a.map_view_occlusion_cell,
+                          map_view_occlusion_window=a.map_view_occlusion_window)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

@@ -21,6 +21,8 @@ the world, which every tracked frame extends by the pixels the map does not expl
 With ``MapConfig.view_guard_px`` they are the live points in view from the start pose of step 3, the image widened by
 that guard band; after the frame the band is checked against the estimate (``GaussianMap.view_violations``), and where
 it did not hold the render the new pixels are judged against is made from a selection at the estimate.
+With ``MapConfig.view_occlusion_rho`` the points in view that nearer points of the map hide are left out as well, and the
+check at the estimate counts the points visible from there.
 With ``MapConfig.free_rho`` the map also shrinks: after the insertion of a frame that is not lost, the live rows that
 frame sees through -- in front of everything it observes around their pixel -- are removed
 (``GaussianMap.remove_seen_through``).  The hole a removed ghost leaves is filled by the NEXT frame's insertion.
@@ -115,6 +117,7 @@ class LocalizeResult:
     added: Optional[int] = None
     tracked: Optional[int] = None  # mode="map": rows the tracker saw (all live rows, or those in the guarded view)
     view_violations: Optional[int] = None  # view_guard_px: rows in reach of the view from c2w that were not tracked
+    view_culled: Optional[int] = None  # view_occlusion_rho: rows of the tracked band left out as hidden by nearer rows
     removed: Optional[int] = None  # free_rho: live rows this frame saw through, removed after its insertion
     evicted: Optional[int] = None  # evict: least recently observed rows that made room for this frame's insertion
     merged: Optional[int] = None  # merge_voxel: rows removed by fusing the rows that share a voxel, after the insertion
@@ -271,7 +274,10 @@ class Localizer:
     rebuilt when the live count changes.  ``map_config.view_guard_px``: the Gaussians of a frame are the live points in
     view from its start pose only (``GaussianMap.select_view``; ``LocalizeResult.tracked``), the tracker is keyed on
     their count, and ``LocalizeResult.view_violations`` says how many rows in reach of the view from the estimate they
-    left out (above 0: the render is made from a selection at the estimate).  ``map_config.free_rho``: after the
+    left out (above 0: the render is made from a selection at the estimate).  ``map_config.view_occlusion_rho``: of the
+    rows in that view, those hidden behind nearer rows of the map are left out as well (``LocalizeResult.view_culled``),
+    and the check at the estimate counts the rows visible from there: it also repairs an occlusion that no longer
+    holds.  ``map_config.free_rho``: after the
     insertion (insert first, then remove: the insertion render is of the cloud that was tracked, and the rows just
     appended sit at their own pixel's observed depth and cannot go) the rows the frame sees through are removed,
     ``LocalizeResult.removed`` counts them and ``map_size`` is the count after the removal; the pixels behind a removed
@@ -359,6 +365,7 @@ class Localizer:
         self.map_mode = mode == "map"
         self.map = None
         self._view_guard = None  # MapConfig.view_guard_px
+        self._view_occlusion = None  # MapConfig.view_occlusion_rho
         self._free = False  # MapConfig.free_rho is set
         self._evict = False  # MapConfig.evict
         self._merge_every = 0  # MapConfig.merge_every when merge_voxel is set, else 0
@@ -384,6 +391,7 @@ class Localizer:
             map_config = map_config if map_config is not None else MapConfig()
             self.map = make(self.W, self.H, map_config, self.device)
             self._view_guard = map_config.view_guard_px
+            self._view_occlusion = map_config.view_occlusion_rho
             self._free = map_config.free_rho is not None
             self._evict = bool(map_config.evict)
             self._merge_every = int(map_config.merge_every) if map_config.merge_voxel is not None else 0
@@ -424,13 +432,20 @@ class Localizer:
         ``view_guard_px`` -- those in view from the world pose ``at``, the image widened by the guard band (an empty
         selection: all of them)."""
         t_pts, t_col = self.map.points, self.map.point_colors
+        culled = None
         if self._view_guard is not None:
+            # (the keyword only with the option: without it the call is the one a map without the option gets)
+            occlusion = {} if self._view_occlusion is None else dict(occlusion_rho=self._view_occlusion)
             v_pts, v_col, _, n = self.map.select_view(self.K, at, self._view_guard, self.cfg.gs.near_plane,
-                                                      self.cfg.gs.far_plane)
+                                                      self.cfg.gs.far_plane, **occlusion)
             if n > 0:
                 t_pts, t_col = v_pts, v_col
+            if self._view_occlusion is not None:
+                culled = self.map.last_view_culled
         pts, col, depth, rgb, placed, ref = frame
-        return build_pair(t_pts, t_col, pts, col, depth, rgb, placed, ref, self.K, self.normalize, t_placed=True)
+        d = build_pair(t_pts, t_col, pts, col, depth, rgb, placed, ref, self.K, self.normalize, t_placed=True)
+        d.view_culled = culled  # travels with the pair: the frame reports the selection that was tracked
+        return d
 
     def _map_render(self, d, scales: Tensor, c2w_n: Tensor):
         """What the pair's cloud shows from the pose ``c2w_n`` in the pair's frame (a rigid move of the world: depths in
@@ -689,6 +704,7 @@ class Localizer:
             out.direct, out.direct_reason = direct, reason
         if self.map_mode:
             out.added, out.tracked = 0, N
+            out.view_culled = getattr(d, "view_culled", None)
             out.removed = 0 if self._free else None
             out.evicted = 0 if self._evict else None
             out.merged = 0 if self._merge_every else None

@@ -14,6 +14,11 @@ pose, the image widened by a guard band, in map order into working buffers -- wh
 tracks instead of every live row -- and ``view_violations`` counts the rows in reach of the view from another pose that
 this selection left out.  Two more entry points; each of the two calls reads its counters back once.
 
+Occlusion culling (``MapConfig.view_occlusion_rho``, csrc/map_occl.hip): ``select_view(occlusion_rho=)`` first splats the
+rows in the band into a coarse z-buffer of the map's own nearest depths and leaves out the rows that every cell around
+their own hides; ``view_violations`` then counts the rows VISIBLE from the other pose that were left out, and
+``view_depth`` returns the buffer.  Two entry points in front of the local map's gather; still one read-back per call.
+
 Free space (``MapConfig.free_rho``, csrc/map_free.hip): ``remove_seen_through`` removes the live rows a depth frame sees
 through -- rows that project into the image and lie more than ``free_rho`` in front of everything the frame observes in
 a window of ``free_window_px`` pixels around their pixel -- and compacts the survivors, in map order, into a spare pair
@@ -531,6 +536,9 @@ def optimise_pose_graph(poses, odometry, loops, fixed_upto: int, by: str = "inde
     return PoseGraphResult(T, float(before), float(cost), done, bool(converged), loop_r)
 
 
+OCCL_CELLS = (1, 2, 4, 8, 16)  # the cell sizes of the occlusion z-buffer, pixels (csrc/map_occl.hip)
+
+
 @dataclass
 class MapConfig:
     alpha_min: float = 0.5  # a pixel the map renders with less alpha is not covered
@@ -542,6 +550,14 @@ class MapConfig:
     # ... and afterwards count the rows in view from the ESTIMATE, the image widened by this, that the tracked set left
     # out.  A 3 sigma footprint of these clouds is about 7 px wide: a centre up to about 4 px outside still paints inside
     view_reach_px: float = 4.0
+    # with view_guard_px: occlusion culling.  The rows in the band are splatted into a z-buffer of view_occlusion_cell_px
+    # pixel cells (1, 2, 4, 8 or 16) that keeps the nearest depth per cell, and a row is left out when EVERY cell within
+    # view_occlusion_window cells of its own (0 .. 3) holds a depth nearer than (1 - view_occlusion_rho) times the row's:
+    # an empty cell, the silhouette of an occluder and a lone ghost row keep it (csrc/map_occl.hip).  A window of 0 lets a
+    # slanted surface cull its own far side within a cell, hence 1 (None: the frustum is the only test)
+    view_occlusion_rho: Optional[float] = None
+    view_occlusion_cell_px: int = 4
+    view_occlusion_window: int = 1
     # Localizer(mode="map"): after a frame's insertion, remove the live rows that project into the frame and lie more
     # than this fraction in front of every observed depth within free_window_px pixels of their pixel (None: a map only
     # grows).  The window is what keeps the edge of a surface that is still there when the pose is a little off
@@ -822,6 +838,16 @@ class MapConfig:
         if self.view_guard_px is not None and not self.view_guard_px >= self.view_reach_px:
             raise ValueError(f"view_guard_px {self.view_guard_px} is below view_reach_px {self.view_reach_px}: the band "
                              "that is tracked must hold the band that is checked")
+        if self.view_occlusion_rho is not None:
+            if not number(self.view_occlusion_rho) or not 0.0 < self.view_occlusion_rho < 1.0:
+                raise ValueError(f"view_occlusion_rho {self.view_occlusion_rho!r}: a fraction of a row's depth, inside "
+                                 "(0, 1)")
+            if self.view_guard_px is None:
+                raise ValueError("view_occlusion_rho culls the rows of the guarded view: it needs view_guard_px")
+        if not whole(self.view_occlusion_cell_px) or self.view_occlusion_cell_px not in OCCL_CELLS:
+            raise ValueError(f"view_occlusion_cell_px {self.view_occlusion_cell_px!r}: one of {OCCL_CELLS} pixels")
+        if not whole(self.view_occlusion_window) or not 0 <= self.view_occlusion_window <= 3:
+            raise ValueError(f"view_occlusion_window {self.view_occlusion_window!r}: a whole number of cells, 0 .. 3")
 
 
 def _intr_and_pose(K, c2w) -> Tuple[Tuple[float, float, float, float], Tensor]:
@@ -866,6 +892,12 @@ class GaussianMap:
         # select_view: capacity-sized working buffers and two workspaces, allocated on first use
         self._view = None
         self._view_rows = -1  # n_live at the last select_view: what its ballots describe
+        # select_view(occlusion_rho=): two workspaces, four counters and a z-buffer per grid size, allocated on first
+        # use; the rho of the last select_view (None: the frustum alone), which view_violations applies as well, and
+        # the rows in the band that it left out as occluded
+        self._occl = None
+        self._view_rho = None
+        self.last_view_culled = 0
         # remove_seen_through: the spare pair of buffers, the ids and a workspace, allocated on first use
         self._free = None
         self._free_keep = None if config.free_rho is None else float(np.float32(1.0) - np.float32(config.free_rho))
@@ -1069,28 +1101,118 @@ class GaussianMap:
         intr, c2w = _intr_and_pose(K, c2w)
         return intr, _world_to_camera(c2w).to(self.device).contiguous()
 
+    # ---- occlusion culling of the local map: a z-buffer of the map's own rows (csrc/map_occl.hip) --------------------
+    def occlusion_grid(self, guard_px: float) -> Tuple[int, int, int]:
+        """(gi, CH, CW) of the z-buffer for this guard band and ``view_occlusion_cell_px``: the image widened by
+        gi = ceil(guard_px) pixels, in cells."""
+        cell = int(self.cfg.view_occlusion_cell_px)
+        if not float(guard_px) >= 0.0 or not float(guard_px) < 2 ** 24:
+            raise ValueError(f"guard_px {guard_px}: not negative, below 2^24")
+        gi = int(math.ceil(np.float32(guard_px)))
+        return gi, (self.H - 1 + 2 * gi) // cell + 1, (self.W - 1 + 2 * gi) // cell + 1
+
+    def _occl_buffers(self):
+        if self._occl is None:
+            cap, dev, ws = self.capacity, self.device, []
+            if dev.type == "cuda":
+                n = _lib.load_library().gsl_map_occl_ws_bytes(cap)
+                ws = [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self._occl = dict(counters=torch.zeros(4, dtype=torch.int32, device=dev), ws=ws, zbufs={})
+        return self._occl
+
+    def _occl_zbuf(self, guard_px: float) -> Tensor:
+        """The z-buffer [CH, CW] of this guard band's grid (the uint32 keys as int32), allocated once per grid size."""
+        _, ch, cw = self.occlusion_grid(guard_px)
+        zbufs = self._occl_buffers()["zbufs"]
+        if (ch, cw) not in zbufs:
+            if ch * cw > 2 ** 26:
+                raise ValueError(f"occlusion z-buffer of {ch} x {cw} cells: at most 2^26")
+            zbufs[(ch, cw)] = torch.zeros(ch, cw, dtype=torch.int32, device=self.device)
+        return zbufs[(ch, cw)]
+
+    def _occl_depth_launch(self, intr: Tuple[float, float, float, float], w2c: Tensor, guard_px: float, near: float,
+                           far: float) -> Tensor:
+        """The z-buffer of the live rows from this pose; no read-back."""
+        assert self.means.is_cuda, "GaussianMap.select_view: the rows are selected by HIP kernels, no CPU path"
+        lib, st, ptr, zb = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._occl_zbuf(guard_px)
+        _lib.check(lib.gsl_map_occl_depth(ptr(self.means), self.n_live, ptr(w2c), *intr, self.W, self.H, guard_px,
+                                          int(self.cfg.view_occlusion_cell_px), near, far, ptr(zb), 4 * zb.numel(), st),
+                   "gsl_map_occl_depth")
+        return zb
+
+    def _occl_launch(self, intr: Tuple[float, float, float, float], w2c: Tensor, guard_px: float, near: float,
+                     far: float, check: bool, rho: float) -> Tuple[int, int, int, int]:
+        """``_view_launch`` with the occlusion rule: the z-buffer at this pose, the selection and, unless ``check``, the
+        gather.  The read-back of the counters (selected, selected and not in the first workspace's selection, gathered,
+        in the band and occluded)."""
+        zb = self._occl_depth_launch(intr, w2c, guard_px, near, far)
+        lib, st, ptr, v, o = _lib.load_library(), _lib.current_stream(), _lib.ptr, self._view_buffers(), self._occl
+        ws, prev = (o["ws"][1], o["ws"][0]) if check else (o["ws"][0], None)
+        keep = float(np.float32(1.0) - np.float32(rho))
+        _lib.check(lib.gsl_map_occl_select(ptr(self.means), self.n_live, ptr(w2c), *intr, self.W, self.H, guard_px, near,
+                                           far, int(self.cfg.view_occlusion_cell_px),
+                                           int(self.cfg.view_occlusion_window), keep, ptr(zb), 4 * zb.numel(), ptr(prev),
+                                           ptr(o["counters"]), ptr(ws), ws.numel(), st), "gsl_map_occl_select")
+        if not check:
+            _lib.check(lib.gsl_map_view_gather(ptr(self.means), ptr(self.colors), self.n_live, ptr(v["means"]),
+                                               ptr(v["colors"]), ptr(v["ids"]), self.capacity, ptr(o["counters"]),
+                                               ptr(ws), ws.numel(), st), "gsl_map_view_gather")
+        selected, fresh, gathered, culled = o["counters"].tolist()  # the call's one synchronisation
+        return selected, fresh, gathered, culled
+
     @torch.no_grad()
-    def select_view(self, K, c2w, guard_px: float, near: float, far: float) -> Tuple[Tensor, Tensor, Tensor, int]:
+    def view_depth(self, K, c2w, guard_px: float, near: float, far: float) -> Tuple[Tensor, Tensor]:
+        """The occlusion z-buffer of the live rows from the pose c2w, for tests and figures: (depth float32 [CH, CW],
+        the nearest depth of the rows in each cell, inf where a cell is empty; the raw keys int32 [CH, CW], the uint32
+        the kernel keeps -- 0 or the complement of the depth's bits -- reinterpreted).  Copies."""
+        if self.n_live == 0:
+            _, ch, cw = self.occlusion_grid(guard_px)
+            return (torch.full((ch, cw), float("inf"), device=self.device),
+                    torch.zeros(ch, cw, dtype=torch.int32, device=self.device))
+        intr, w2c = self._view_args(K, c2w)
+        raw = self._occl_depth_launch(intr, w2c, float(guard_px), float(near), float(far)).clone()
+        depth = torch.where(raw == 0, torch.full_like(raw, float("inf"), dtype=torch.float32),
+                            torch.bitwise_not(raw).view(torch.float32))
+        return depth, raw
+
+    @torch.no_grad()
+    def select_view(self, K, c2w, guard_px: float, near: float, far: float,
+                    occlusion_rho: Optional[float] = None) -> Tuple[Tensor, Tensor, Tensor, int]:
         """The live rows in view from the pose c2w [4,4] -- inside the image widened by guard_px on every side, between
         the depth planes (the rule: include/gsloc_hip.h) -- in map order.  Returns (points [n,3], colors [n,3],
-        ids [n] int32, n): views of the prefix of capacity-sized working buffers that the next call overwrites."""
+        ids [n] int32, n): views of the prefix of capacity-sized working buffers that the next call overwrites.
+        ``occlusion_rho``: of those rows, the ones that no nearer surface of the map hides (``MapConfig.
+        view_occlusion_rho`` has the rule; the cell size and the window are the configuration's); ``last_view_culled``
+        then counts the rows in the band that were left out, and is 0 without it."""
+        if occlusion_rho is not None and not 0.0 < float(occlusion_rho) < 1.0:
+            raise ValueError(f"occlusion_rho {occlusion_rho!r}: inside (0, 1)")
         v = self._view_buffers()
-        n = 0
+        n, culled = 0, 0
         if self.n_live > 0:
             intr, w2c = self._view_args(K, c2w)
-            n = self._view_launch(intr, w2c, float(guard_px), float(near), float(far), False)[2]
-        self._view_rows = self.n_live
+            if occlusion_rho is None:
+                n = self._view_launch(intr, w2c, float(guard_px), float(near), float(far), False)[2]
+            else:
+                _, _, n, culled = self._occl_launch(intr, w2c, float(guard_px), float(near), float(far), False,
+                                                    float(occlusion_rho))
+        self._view_rows, self._view_rho, self.last_view_culled = self.n_live, occlusion_rho, culled
         return v["means"][:n], v["colors"][:n], v["ids"][:n], n
 
     @torch.no_grad()
     def view_violations(self, K, c2w, near: float, far: float) -> int:
         """How many live rows are in view from c2w, the image widened by ``view_reach_px``, that the last select_view
-        left out: 0 says that selection covers the view from c2w."""
+        left out: 0 says that selection covers the view from c2w.  The rule is the one that select_view used: after one
+        with ``occlusion_rho`` the z-buffer is built at c2w, with ``view_reach_px`` as guard, and the rows counted are
+        those VISIBLE from there -- a row that parallax has uncovered counts, a row occluded from both poses does
+        not."""
         if self._view_rows != self.n_live:
             raise RuntimeError("view_violations: no select_view of the rows that are live now")
         if self.n_live == 0:
             return 0
         intr, w2c = self._view_args(K, c2w)
+        if self._view_rho is not None:
+            return self._occl_launch(intr, w2c, float(self.cfg.view_reach_px), float(near), float(far), True,
+                                     float(self._view_rho))[1]
         return self._view_launch(intr, w2c, float(self.cfg.view_reach_px), float(near), float(far), True)[1]
 
     # ---- free space: the live rows a depth frame sees through are removed (csrc/map_free.hip) ------------------------

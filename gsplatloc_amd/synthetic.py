@@ -257,6 +257,29 @@ def write_replica_vanishing_panel(root, W, H, n, n_with, rot_deg: float = 1.0, t
     return _write_replica_poses(root, W, H, poses, depth_of)
 
 
+def write_replica_passing_panel(root, W, H, n, step: float = 0.02, center=(0.0, 0.0), size=(0.8, 0.6), z: float = 1.0,
+                                rot_deg: float = 0.0, axis=(0.0, 1.0, 0.0), and_back: bool = False):
+    """A camera that passes a panel (``panel_depth``) in the room: it looks along +z from the plane z = 0 and slides
+    ``step`` metres per frame along x, n frames centred on x = 0 -- and turns by ``rot_deg`` about ``axis`` per frame,
+    0 at the middle of the sequence (default: no turn).  The wall behind the panel is covered by parallax as the camera
+    moves: what a map keeps of it lies behind the panel's rows, inside the frustum.  ``and_back``: then the same poses
+    back to the first, 2 n - 1 frames -- what was covered on the way out is uncovered again.  Returns the poses
+    (float64)."""
+    poses = []
+    for i in range(n):
+        k = i - (n - 1) / 2.0
+        c2w = _twist(rot_deg * k, 0.0, axis, (1.0, 0.0, 0.0))
+        c2w[:3, 3] = [step * k, 0.0, 0.0]
+        poses.append(c2w)
+    if and_back:
+        poses = poses + [p.copy() for p in poses[-2::-1]]
+
+    def depth_of(i, K, pose):
+        return panel_depth(W, H, K, pose, center, size, z)
+
+    return _write_replica_poses(root, W, H, poses, depth_of)
+
+
 def _twist(rot_deg, trans, axis, direction):
     """4x4 step: rot_deg about ``axis``, ``trans`` metres along ``direction`` (float64)."""
     import numpy as np

@@ -180,6 +180,41 @@ int gsl_map_view_gather(const float* means, const float* colors, int64_t n_rows,
                         float* out_colors, int32_t* out_ids, int64_t out_capacity, int32_t* counters, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ---- local map, occlusion culling: the rows in view that no nearer surface of the map hides (csrc/map_occl.hip) ----
+ * The rule of gsl_map_view_select (IN THE BAND below) and a z-buffer of the map's own rows on a coarse grid:
+ *   gi = (int)ceilf(guard_px);  cell_px is 1, 2, 4, 8 or 16;  CW = (width - 1 + 2 gi) / cell_px + 1 and
+ *   CH = (height - 1 + 2 gi) / cell_px + 1 (integer division);  a row in the band lies in the cell
+ *   cu = (int)floorf((u + (float)gi) * (1 / cell_px)), cv = (int)floorf((v + (float)gi) * (1 / cell_px)), which is
+ *   inside the grid.  The widened image, width - 1 + 2 gi and height - 1 + 2 gi, must stay below 2^24 pixels a side
+ *   and CW * CH at or below 2^26.
+ * gsl_map_occl_zbuf_bytes: 4 CW CH, or 0 for arguments the entry points refuse.
+ * gsl_map_occl_depth: zbuf[CH,CW] uint32 = 0 where no row in the band falls into the cell, else the maximum of
+ *   ~bits(z) over those rows: the complement of the bit pattern of the NEAREST depth (near_plane >= 0, so z > 0 and
+ *   its bits order as the float does).  Integer atomics: the same buffer in every run and for every order of the rows.
+ * gsl_map_occl_select: with m the minimum of zbuf over the cells (cu + du, cv + dv), |du|, |dv| <= window, a cell
+ *   outside the grid counting as 0, a row in the band is OCCLUDED when m != 0 and rho_keep * z > asfloat(~m) (one
+ *   rounded product; rho_keep is 1 - rho, the float32 difference taken by the caller), and SELECTED when it is in the
+ *   band and not occluded.  Leaves in ws (gsl_map_occl_ws_bytes(n_rows): the layout of gsl_map_view_select, which it
+ *   is at least as large as, and two more columns) one ballot per wave of the selected rows and the row offset of every
+ *   workgroup, so that gsl_map_view_gather on the same rows and the same, untouched ws moves them.  counters is
+ *   int32[4]: [0] rows selected, [1] rows selected whose bit is CLEAR in the ballots of prev_ws (as
+ *   gsl_map_view_select; 0 when prev_ws is NULL), [2] = 0 (the gather's), [3] rows in the band and occluded.  zbuf is
+ *   only read; it is what gsl_map_occl_depth left for the same image, guard_px and cell_px.
+ * float32, evaluated exactly as written, comparisons false for a NaN.  Both return GSL_ERR_BAD_ARG before any launch
+ * for a NULL array, n_rows <= 0 or >= 2^31, width or height <= 0 or width * height > 2^31 - 1, fx or fy not non-zero,
+ * guard_px negative or NaN, near_plane negative or NaN or >= far_plane, a cell_px other than the five, a grid beyond
+ * the limits above, window outside 0..3, rho_keep outside (0, 1), prev_ws == ws; and GSL_ERR_WORKSPACE for a zbuf
+ * smaller than gsl_map_occl_zbuf_bytes or a workspace smaller than gsl_map_occl_ws_bytes. */
+size_t gsl_map_occl_zbuf_bytes(int width, int height, float guard_px, int cell_px);
+size_t gsl_map_occl_ws_bytes(int64_t n_rows);
+int gsl_map_occl_depth(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx, float cy,
+                       int width, int height, float guard_px, int cell_px, float near_plane, float far_plane,
+                       void* zbuf, size_t zbuf_bytes, void* stream);
+int gsl_map_occl_select(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx, float cy,
+                        int width, int height, float guard_px, float near_plane, float far_plane, int cell_px,
+                        int window, float rho_keep, const void* zbuf, size_t zbuf_bytes, const void* prev_ws,
+                        int32_t* counters, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- free space: the rows of the map that a depth frame sees through are removed (csrc/map_free.hip) ----
  * depth[height,width] float32 on the device, row-major: the observed depth, metres.  Row i of means[n_rows,3], with
  * w2c[16] (world to camera, row-major, on the device):
