@@ -78,6 +78,17 @@ _SIGNATURES = {
     "gsl_map_pose_align_batch": (c_int, [P, c_int64, P, c_int, c_float, c_float, c_float, c_float, P, c_int, c_int,
                                          c_float, c_float, c_float, c_float, c_int, c_double, c_int, c_double, c_double,
                                          c_double, c_double, P, P, P, P, P]),
+    "gsl_map_photo_intensity": (c_int, [P, c_int, c_int, P, P]),
+    "gsl_map_info_photo_max_rows": (c_int64, [c_float, c_float, c_float, c_float, c_int, c_int, c_float, c_float,
+                                              c_float]),
+    "gsl_map_pose_info_photo": (c_int, [P, c_int64, P, c_float, c_float, c_float, c_float, P, c_int, c_int, c_float,
+                                        c_float, c_float, c_float, P, P, P, c_float, c_float, P, P]),
+    "gsl_map_pose_align_photo": (c_int, [P, c_int64, P, c_float, c_float, c_float, c_float, P, c_int, c_int, c_float,
+                                         c_float, c_float, c_float, c_int, c_double, c_int, c_double, c_double, c_double,
+                                         c_double, P, P, P, P, P, P, c_float, c_float, P]),
+    "gsl_map_pose_align_batch_photo": (c_int, [P, c_int64, P, c_int, c_float, c_float, c_float, c_float, P, c_int, c_int,
+                                               c_float, c_float, c_float, c_float, c_int, c_double, c_int, c_double,
+                                               c_double, c_double, c_double, P, P, P, P, P, P, c_float, c_float, P]),
     "gsl_map_place_cells": (c_int, []),
     "gsl_map_place_describe": (c_int, [P, c_int, c_int, P, P]),
     "gsl_map_place_match": (c_int, [P, P, c_int, P, P]),

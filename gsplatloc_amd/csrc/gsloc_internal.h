@@ -6,7 +6,8 @@
 
 namespace gsl {
 
-struct LongWs;  // long_dev.h
+struct LongWs;     // long_dev.h
+struct InfoPhoto;  // map_info_dev.h
 
 // misc.hip: zero n dwords with a kernel of the library (never hipMemsetAsync: see the note there)
 int zero_u32(void* p, size_t n_dwords, hipStream_t st);
@@ -51,6 +52,13 @@ int launch_mraster_bwd(const float* Q0, const float* Q1, const float* Q2, int ch
 int map_pose_info_launch(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx, float cy,
                          const float* depth, int width, int height, float keep, float beyond, float kappa,
                          float near_plane, int64_t* out, hipStream_t st);
+
+// map_photo.hip: the same with k_map_pose_info_photo, for arguments checked as gsl_map_pose_info_photo checks them;
+// extra NULL or the two words, which are then zeroed as well
+int map_pose_info_photo_launch(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx,
+                               float cy, const float* depth, int width, int height, float keep, float beyond,
+                               float kappa, float near_plane, int64_t* out, const InfoPhoto& photo, int64_t* extra,
+                               hipStream_t st);
 
 // ---- workspace of the fused pipeline (sized by gsl_fused_ws_bytes, fused_project.hip) -------------------------------
 // ws = [tile_counts n_tiles][cursors n_tiles][pad to 16 bytes][pose-gradient rows ceil(N/256) x 16 floats][stage rows]

@@ -47,9 +47,12 @@
 // One workgroup of one wave; lane 0 does the work and the other lanes leave at once.  Every loop is unrolled, L, D and
 // the rest live in registers (no scratch).  Everything is written with ordinary vector stores.
 // The code of that sequence is align_step of map_align_dev.h, the one copy: map_align_batch.hip runs it for several poses.
+// gsl_map_pose_align_photo is the same sequence with the sums of map_photo.hip (geometry plus colour) in place of
+// k_map_pose_info's: the 30 integers have one layout, and nothing here reads more than them.
 #include "gsloc_internal.h"
 #include "map_align_dev.h"
 #include "map_dev.h"
+#include "map_info_dev.h"
 
 namespace gsl {
 
@@ -71,6 +74,29 @@ __global__ __launch_bounds__(ALIGN_THREADS) void k_map_align_step(
 
 extern "C" int gsl_map_align_max_steps(void) { return GSL_MAP_ALIGN_MAX_STEPS; }
 
+// The launch sequence of gsl_map_pose_align for checked arguments; photo NULL: the geometric sums, otherwise the
+// photometric ones (map_photo.hip) in their place -- the init and step kernels do not know which.
+static int map_pose_align_run(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx,
+                              float cy, const float* depth, int width, int height, float keep, float beyond, float kappa,
+                              float near_plane, int max_steps, double damping, int min_used, double max_rot,
+                              double max_trans, double eps_rot, double eps_trans, int64_t* sums, float* work, void* state,
+                              void* history, const gsl::InfoPhoto* photo, hipStream_t st) {
+  hipLaunchKernelGGL(gsl::k_map_align_init, dim3(1), dim3(gsl::ALIGN_THREADS), 0, st, w2c, work, (double*)state);
+  GSL_CHECK_LAUNCH();
+  for (int k = 0; k < max_steps; ++k) {
+    const int rc = photo ? gsl::map_pose_info_photo_launch(means, n_rows, work, fx, fy, cx, cy, depth, width, height,
+                                                           keep, beyond, kappa, near_plane, sums, *photo, nullptr, st)
+                         : gsl::map_pose_info_launch(means, n_rows, work, fx, fy, cx, cy, depth, width, height, keep,
+                                                     beyond, kappa, near_plane, sums, st);
+    if (rc != GSL_OK) return rc;
+    hipLaunchKernelGGL(gsl::k_map_align_step, dim3(1), dim3(gsl::ALIGN_THREADS), 0, st, (const long long*)sums, k,
+                       damping, (long long)min_used, max_rot, max_trans, eps_rot, eps_trans, work, (double*)state,
+                       (long long*)history);
+    GSL_CHECK_LAUNCH();
+  }
+  return GSL_OK;
+}
+
 extern "C" int gsl_map_pose_align(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx,
                                   float cy, const float* depth, int width, int height, float keep, float beyond,
                                   float kappa, float near_plane, int max_steps, double damping, int min_used,
@@ -80,17 +106,27 @@ extern "C" int gsl_map_pose_align(const float* means, int64_t n_rows, const floa
   if (!gsl::align_args_ok(means, n_rows, fx, fy, cx, cy, depth, width, height, keep, beyond, kappa, max_steps, damping,
                           min_used, max_rot, max_trans, eps_rot, eps_trans))
     return GSL_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(gsl::k_map_align_init, dim3(1), dim3(gsl::ALIGN_THREADS), 0, st, w2c, work, (double*)state);
-  GSL_CHECK_LAUNCH();
-  for (int k = 0; k < max_steps; ++k) {
-    const int rc = gsl::map_pose_info_launch(means, n_rows, work, fx, fy, cx, cy, depth, width, height, keep, beyond,
-                                             kappa, near_plane, sums, st);
-    if (rc != GSL_OK) return rc;
-    hipLaunchKernelGGL(gsl::k_map_align_step, dim3(1), dim3(gsl::ALIGN_THREADS), 0, st, (const long long*)sums, k,
-                       damping, (long long)min_used, max_rot, max_trans, eps_rot, eps_trans, work, (double*)state,
-                       (long long*)history);
-    GSL_CHECK_LAUNCH();
-  }
-  return GSL_OK;
+  return map_pose_align_run(means, n_rows, w2c, fx, fy, cx, cy, depth, width, height, keep, beyond, kappa, near_plane,
+                            max_steps, damping, min_used, max_rot, max_trans, eps_rot, eps_trans, sums, work, state,
+                            history, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int gsl_map_pose_align_photo(const float* means, int64_t n_rows, const float* w2c, float fx, float fy,
+                                        float cx, float cy, const float* depth, int width, int height, float keep,
+                                        float beyond, float kappa, float near_plane, int max_steps, double damping,
+                                        int min_used, double max_rot, double max_trans, double eps_rot, double eps_trans,
+                                        int64_t* sums, float* work, void* state, void* history, const float* colors,
+                                        const float* intensity, float photo_scale, float photo_max_residual,
+                                        void* stream) {
+  if (!w2c || !sums || !work || !state || !history) return GSL_ERR_BAD_ARG;
+  if (!gsl::align_args_ok(means, n_rows, fx, fy, cx, cy, depth, width, height, keep, beyond, kappa, max_steps, damping,
+                          min_used, max_rot, max_trans, eps_rot, eps_trans))
+    return GSL_ERR_BAD_ARG;
+  const gsl::InfoPhoto photo = {colors, intensity, photo_scale, photo_max_residual};
+  if (!gsl::info_photo_args_ok(photo)) return GSL_ERR_BAD_ARG;
+  if (n_rows > gsl_map_info_photo_max_rows(fx, fy, cx, cy, width, height, keep, photo_scale, photo_max_residual))
+    return GSL_ERR_BAD_ARG;  // a sum could overflow
+  return map_pose_align_run(means, n_rows, w2c, fx, fy, cx, cy, depth, width, height, keep, beyond, kappa, near_plane,
+                            max_steps, damping, min_used, max_rot, max_trans, eps_rot, eps_trans, sums, work, state,
+                            history, &photo, (hipStream_t)stream);
 }

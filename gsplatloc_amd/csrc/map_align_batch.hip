@@ -22,6 +22,8 @@
 // gsl_map_pose_align recomputes identical integers at an unchanged pose, so state (done apart), work and every history
 // row are bit for bit what it leaves for that pose alone; after the call sums[p] are the normal equations at work[p],
 // unless the pose converged on the last iteration and done is left at 1.  Ordinary vector stores only.
+// gsl_map_pose_align_batch_photo is the same sequence with k_map_batch_photo_info -- the sums of map_photo.hip, geometry
+// plus colour -- in place of k_map_batch_info.
 #include "gsloc_internal.h"
 #include "map_align_dev.h"
 #include "map_info_dev.h"
@@ -59,8 +61,24 @@ __global__ __launch_bounds__(BATCH_INFO_THREADS) void k_map_batch_info(
 #pragma clang fp contract(off)
   const int p = (int)blockIdx.y;
   if (batch_done(state, p) == 2) return;  // the workgroup's: every thread leaves
-  info_sum_rows<BATCH_INFO_THREADS>(means, n_rows, work + 16 * (size_t)p, fx, fy, cx, cy, depth, width, u_inner, v_inner,
-                                    keep, beyond, kappa, near_plane, sums + GSL_MAP_INFO_VALUES * (size_t)p);
+  info_sum_rows<BATCH_INFO_THREADS, false>(means, n_rows, work + 16 * (size_t)p, fx, fy, cx, cy, depth, width, u_inner,
+                                           v_inner, keep, beyond, kappa, near_plane,
+                                           sums + GSL_MAP_INFO_VALUES * (size_t)p, nullptr, nullptr, 0.f, 0.f, nullptr);
+}
+
+// k_map_batch_info with the photometric term of map_photo.hip in the sums (info_sum_rows with PHOTO; no extra).
+__global__ __launch_bounds__(BATCH_INFO_THREADS) void k_map_batch_photo_info(
+    const float* __restrict__ means, long long n_rows, const float* __restrict__ work, const double* __restrict__ state,
+    float fx, float fy, float cx, float cy, const float* __restrict__ depth, int width, float u_inner, float v_inner,
+    float keep, float beyond, float kappa, float near_plane, unsigned long long* __restrict__ sums,
+    const float* __restrict__ colors, const float* __restrict__ intensity, float photo_scale, float photo_max_residual) {
+#pragma clang fp contract(off)
+  const int p = (int)blockIdx.y;
+  if (batch_done(state, p) == 2) return;  // the workgroup's: every thread leaves
+  info_sum_rows<BATCH_INFO_THREADS, true>(means, n_rows, work + 16 * (size_t)p, fx, fy, cx, cy, depth, width, u_inner,
+                                          v_inner, keep, beyond, kappa, near_plane,
+                                          sums + GSL_MAP_INFO_VALUES * (size_t)p, colors, intensity, photo_scale,
+                                          photo_max_residual, nullptr);
 }
 
 __global__ __launch_bounds__(ALIGN_THREADS) void k_map_batch_step(
@@ -91,6 +109,42 @@ __global__ __launch_bounds__(ALIGN_THREADS) void k_map_batch_step(
 
 extern "C" int gsl_map_align_batch_max_poses(void) { return GSL_MAP_ALIGN_BATCH_MAX_POSES; }
 
+// The launch sequence of gsl_map_pose_align_batch for checked arguments; photo NULL: k_map_batch_info, otherwise
+// k_map_batch_photo_info in its place.
+static int map_pose_align_batch_run(const float* means, int64_t n_rows, const float* w2c, int n_poses, float fx, float fy,
+                                    float cx, float cy, const float* depth, int width, int height, float keep,
+                                    float beyond, float kappa, float near_plane, int max_steps, double damping,
+                                    int min_used, double max_rot, double max_trans, double eps_rot, double eps_trans,
+                                    int64_t* sums, float* work, void* state, void* history,
+                                    const gsl::InfoPhoto* photo, hipStream_t st) {
+  hipLaunchKernelGGL(gsl::k_map_batch_init, dim3(n_poses), dim3(gsl::ALIGN_THREADS), 0, st, w2c, work, (double*)state);
+  GSL_CHECK_LAUNCH();
+  const long long blocks = (n_rows + gsl::BATCH_INFO_THREADS - 1) / gsl::BATCH_INFO_THREADS;
+  const dim3 grid((unsigned)(blocks < gsl::BATCH_INFO_MAX_BLOCKS ? blocks : gsl::BATCH_INFO_MAX_BLOCKS), n_poses);
+  for (int k = 0; k < max_steps; ++k) {
+    hipLaunchKernelGGL(gsl::k_map_batch_zero, dim3(1), dim3(gsl::BATCH_ZERO_THREADS), 0, st, (const double*)state,
+                       n_poses, (long long*)sums);
+    GSL_CHECK_LAUNCH();
+    if (photo) {
+      hipLaunchKernelGGL(gsl::k_map_batch_photo_info, grid, dim3(gsl::BATCH_INFO_THREADS), 0, st, means,
+                         (long long)n_rows, (const float*)work, (const double*)state, fx, fy, cx, cy, depth, width,
+                         (float)(width - 2), (float)(height - 2), keep, beyond, kappa, near_plane,
+                         (unsigned long long*)sums, photo->colors, photo->intensity, photo->scale,
+                         photo->max_residual);
+    } else {
+      hipLaunchKernelGGL(gsl::k_map_batch_info, grid, dim3(gsl::BATCH_INFO_THREADS), 0, st, means, (long long)n_rows,
+                         (const float*)work, (const double*)state, fx, fy, cx, cy, depth, width, (float)(width - 2),
+                         (float)(height - 2), keep, beyond, kappa, near_plane, (unsigned long long*)sums);
+    }
+    GSL_CHECK_LAUNCH();
+    hipLaunchKernelGGL(gsl::k_map_batch_step, dim3(1), dim3(gsl::ALIGN_THREADS), 0, st, (const long long*)sums, n_poses,
+                       k, max_steps, damping, (long long)min_used, max_rot, max_trans, eps_rot, eps_trans, work,
+                       (double*)state, (long long*)history);
+    GSL_CHECK_LAUNCH();
+  }
+  return GSL_OK;
+}
+
 extern "C" int gsl_map_pose_align_batch(const float* means, int64_t n_rows, const float* w2c, int n_poses, float fx,
                                         float fy, float cx, float cy, const float* depth, int width, int height,
                                         float keep, float beyond, float kappa, float near_plane, int max_steps,
@@ -102,23 +156,28 @@ extern "C" int gsl_map_pose_align_batch(const float* means, int64_t n_rows, cons
   if (!gsl::align_args_ok(means, n_rows, fx, fy, cx, cy, depth, width, height, keep, beyond, kappa, max_steps, damping,
                           min_used, max_rot, max_trans, eps_rot, eps_trans))
     return GSL_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(gsl::k_map_batch_init, dim3(n_poses), dim3(gsl::ALIGN_THREADS), 0, st, w2c, work, (double*)state);
-  GSL_CHECK_LAUNCH();
-  const long long blocks = (n_rows + gsl::BATCH_INFO_THREADS - 1) / gsl::BATCH_INFO_THREADS;
-  const dim3 grid((unsigned)(blocks < gsl::BATCH_INFO_MAX_BLOCKS ? blocks : gsl::BATCH_INFO_MAX_BLOCKS), n_poses);
-  for (int k = 0; k < max_steps; ++k) {
-    hipLaunchKernelGGL(gsl::k_map_batch_zero, dim3(1), dim3(gsl::BATCH_ZERO_THREADS), 0, st, (const double*)state,
-                       n_poses, (long long*)sums);
-    GSL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gsl::k_map_batch_info, grid, dim3(gsl::BATCH_INFO_THREADS), 0, st, means, (long long)n_rows,
-                       (const float*)work, (const double*)state, fx, fy, cx, cy, depth, width, (float)(width - 2),
-                       (float)(height - 2), keep, beyond, kappa, near_plane, (unsigned long long*)sums);
-    GSL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gsl::k_map_batch_step, dim3(1), dim3(gsl::ALIGN_THREADS), 0, st, (const long long*)sums, n_poses,
-                       k, max_steps, damping, (long long)min_used, max_rot, max_trans, eps_rot, eps_trans, work,
-                       (double*)state, (long long*)history);
-    GSL_CHECK_LAUNCH();
-  }
-  return GSL_OK;
+  return map_pose_align_batch_run(means, n_rows, w2c, n_poses, fx, fy, cx, cy, depth, width, height, keep, beyond, kappa,
+                                  near_plane, max_steps, damping, min_used, max_rot, max_trans, eps_rot, eps_trans, sums,
+                                  work, state, history, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int gsl_map_pose_align_batch_photo(const float* means, int64_t n_rows, const float* w2c, int n_poses, float fx,
+                                              float fy, float cx, float cy, const float* depth, int width, int height,
+                                              float keep, float beyond, float kappa, float near_plane, int max_steps,
+                                              double damping, int min_used, double max_rot, double max_trans,
+                                              double eps_rot, double eps_trans, int64_t* sums, float* work, void* state,
+                                              void* history, const float* colors, const float* intensity,
+                                              float photo_scale, float photo_max_residual, void* stream) {
+  if (!w2c || !sums || !work || !state || !history) return GSL_ERR_BAD_ARG;
+  if (n_poses < 1 || n_poses > GSL_MAP_ALIGN_BATCH_MAX_POSES) return GSL_ERR_BAD_ARG;
+  if (!gsl::align_args_ok(means, n_rows, fx, fy, cx, cy, depth, width, height, keep, beyond, kappa, max_steps, damping,
+                          min_used, max_rot, max_trans, eps_rot, eps_trans))
+    return GSL_ERR_BAD_ARG;
+  const gsl::InfoPhoto photo = {colors, intensity, photo_scale, photo_max_residual};
+  if (!gsl::info_photo_args_ok(photo)) return GSL_ERR_BAD_ARG;
+  if (n_rows > gsl_map_info_photo_max_rows(fx, fy, cx, cy, width, height, keep, photo_scale, photo_max_residual))
+    return GSL_ERR_BAD_ARG;  // a sum could overflow
+  return map_pose_align_batch_run(means, n_rows, w2c, n_poses, fx, fy, cx, cy, depth, width, height, keep, beyond, kappa,
+                                  near_plane, max_steps, damping, min_used, max_rot, max_trans, eps_rot, eps_trans, sums,
+                                  work, state, history, &photo, (hipStream_t)stream);
 }

@@ -63,8 +63,8 @@ __global__ __launch_bounds__(INFO_THREADS) void k_map_pose_info(
     float cy, const float* __restrict__ depth, int width, float u_inner, float v_inner, float keep, float beyond,
     float kappa, float near_plane, unsigned long long* __restrict__ out) {
 #pragma clang fp contract(off)
-  info_sum_rows<INFO_THREADS>(means, n_rows, w2c, fx, fy, cx, cy, depth, width, u_inner, v_inner, keep, beyond, kappa,
-                              near_plane, out);
+  info_sum_rows<INFO_THREADS, false>(means, n_rows, w2c, fx, fy, cx, cy, depth, width, u_inner, v_inner, keep, beyond,
+                                     kappa, near_plane, out, nullptr, nullptr, 0.f, 0.f, nullptr);
 }
 
 // The zeroing of out and the launch of k_map_pose_info, for arguments that gsl_map_pose_info has checked: its own two

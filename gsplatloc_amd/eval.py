@@ -46,7 +46,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   map_origins: bool = False, map_loop: bool = False, map_loop_min_gap: Optional[int] = None,
                   map_align_accept: bool = False, map_reloc_align_top: Optional[int] = None,
                   map_view_occlusion: Optional[float] = None, map_view_occlusion_cell: Optional[int] = None,
-                  map_view_occlusion_window: Optional[int] = None) -> Dict:
+                  map_view_occlusion_window: Optional[int] = None, map_photo_scale: Optional[float] = None,
+                  map_photo_max_residual: Optional[float] = None) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -73,7 +74,10 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     ``map_reloc_align_top``: MapConfig.reloc_align_top, that many of the best relocalisation candidates are aligned to
     the map before the winner is chosen; ``map_view_occlusion``: MapConfig.view_occlusion_rho, the rows of the guarded
     view that nearer rows of the map hide are not tracked, with ``map_view_occlusion_cell`` /
-    ``map_view_occlusion_window`` for MapConfig.view_occlusion_cell_px / view_occlusion_window where not None)."""
+    ``map_view_occlusion_window`` for MapConfig.view_occlusion_cell_px / view_occlusion_window where not None;
+    ``map_photo_scale``: MapConfig.photo_scale, the normal equations of map_info, map_align and map_loop gain a
+    photometric term from the rows' colours against the frame's image, with ``map_photo_max_residual`` for
+    MapConfig.photo_max_residual where not None)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
     occlusion = {k: v for k, v in (("view_occlusion_cell_px", map_view_occlusion_cell),
                                    ("view_occlusion_window", map_view_occlusion_window)) if v is not None}
@@ -116,6 +120,16 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         raise ValueError("map_loop belongs to the map mode (map_mode=True)")
     if map_loop_min_gap is not None and not map_loop:
         raise ValueError("map_loop_min_gap: an option of map_loop=True")
+    if (map_photo_scale is not None or map_photo_max_residual is not None) and not map_mode:
+        raise ValueError("map_photo_scale belongs to the map mode (map_mode=True)")
+    if map_photo_max_residual is not None and map_photo_scale is None:
+        raise ValueError("map_photo_max_residual: an option of map_photo_scale")
+    if map_photo_scale is not None and not (map_info or map_align or map_loop):
+        raise ValueError("map_photo_scale: the photometric term of map_info, map_align or map_loop -- one of them")
+    photo_term = None
+    if map_photo_scale is not None:
+        photo_term = dict(photo_scale=map_photo_scale, **({} if map_photo_max_residual is None else
+                                                          {"photo_max_residual": map_photo_max_residual}))
     loop = None
     if map_loop:
         loop = dict(loop=True, **({} if map_loop_min_gap is None else {"loop_min_gap": map_loop_min_gap}))
@@ -139,7 +153,7 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                                    dict(reloc, reloc=True) if map_reloc else None,
                                    dict(keyframes, keyframes=True) if map_keyframes else None, map_refine=refine,
                                    map_info=bool(map_info), map_align=align, map_origins=bool(map_origins) or bool(map_loop),
-                                   map_loop=loop, map_view_occlusion=occlusion or None)
+                                   map_loop=loop, map_view_occlusion=occlusion or None, map_photo=photo_term)
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -206,7 +220,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                         map_merge_every: int = 1, map_reloc: Optional[Dict] = None,
                         map_keyframes: Optional[Dict] = None, map_refine: Optional[Dict] = None,
                         map_info: bool = False, map_align: Optional[Dict] = None, map_origins: bool = False,
-                        map_loop: Optional[Dict] = None, map_view_occlusion: Optional[Dict] = None) -> Dict:
+                        map_loop: Optional[Dict] = None, map_view_occlusion: Optional[Dict] = None,
+                        map_photo: Optional[Dict] = None) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
     map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
@@ -236,7 +251,9 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     starts at), loop_edge_residuals (of every kept edge after the last solve) and ate_corrected (the RMSE of the final,
     corrected trajectory's translation errors; ATE is that of the estimates as they were made).  map_view_occlusion: the
     MapConfig fields of occlusion culling (view_occlusion_rho and, where wanted, view_occlusion_cell_px /
-    view_occlusion_window; it needs map_view_guard); the report gains view_culled_per_frame."""
+    view_occlusion_window; it needs map_view_guard); the report gains view_culled_per_frame.  map_photo: the MapConfig
+    fields of the photometric term (photo_scale and, where wanted, photo_max_residual; it needs map_info, map_align or
+    map_loop); the report gains photo_scale and, with map_info, info_photo_used_per_frame."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
@@ -249,7 +266,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                                                        **(map_keyframes or {}), **(map_refine or {}),
                                                        info=bool(map_info), **(map_align or {}),
                                                        origins=bool(map_origins), **(map_loop or {}),
-                                                       **(map_view_occlusion or {})))
+                                                       **(map_view_occlusion or {}), **(map_photo or {})))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
@@ -259,6 +276,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     culled = []
     relocalised, shares, recognised, refined = 0, [], 0, []
     sigma_t, sigma_r, info_used, info_eig, weak = [], [], [], [], 0
+    photo_used = []
     aligned, align_steps, align_status, motion_eT, start_eT = [], [], [], [], []
     direct, direct_reason, reloc_aligned = [], [], []
     ordered = True
@@ -288,13 +306,14 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             sigma_r.append(r.sigma_r)
             info_used.append(r.info_used)
             info_eig.append(r.info_min_eig)
+            photo_used.append(r.info_photo_used)
             weak += int(bool(r.weak))
             if r.weak is None:
                 print(f"frame {i}: pose information: lost, not asked")
             else:
                 sig = "none" if r.cov is None else f"sigma_t {r.sigma_t:.3e} m sigma_r {r.sigma_r:.3e} deg"
                 print(f"frame {i}: pose information: {sig} rows used {r.info_used} min eig {r.info_min_eig:.3e} "
-                      f"weak {r.weak}")
+                      f"weak {r.weak}" + (f" photometric rows {r.info_photo_used}" if map_photo else ""))
         if map_align:
             aligned.append(bool(r.aligned))
             align_steps.append(r.align_steps)
@@ -348,6 +367,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             **({"info": True, "sigma_t_per_frame": sigma_t, "sigma_r_per_frame": sigma_r,
                 "info_used_per_frame": info_used, "info_min_eig_per_frame": info_eig, "weak_frames": weak}
                if map_info else {}),
+            **({**map_photo, **({"info_photo_used_per_frame": photo_used} if map_info else {})} if map_photo else {}),
             **({"align": True, "aligned_per_frame": aligned, "align_steps_per_frame": align_steps,
                 "align_status_per_frame": align_status, "aligned_frames": sum(aligned),
                 "motion_eT_per_frame": motion_eT, "start_eT_per_frame": start_eT} if map_align else {}),
@@ -464,6 +484,13 @@ def main(argv=None):
     ap.add_argument("--map-reloc-align-top", type=int, default=None, metavar="K",
                     help="--map-reloc: the K best candidates of a relocalisation grid (1 .. 16) are aligned to the map "
                          "in one call before the winner is chosen (default 0: none)")
+    ap.add_argument("--map-photo-scale", type=float, default=None, metavar="S",
+                    help="--map-info / --map-align / --map-loop: a photometric term in their normal equations -- every "
+                         "point that gives a depth equation also gives one from its colour against the frame's image, S "
+                         "metres per unit of intensity (0 .. 16; 0.2 is the documented value to start from)")
+    ap.add_argument("--map-photo-max-residual", type=float, default=None, metavar="R",
+                    help="--map-photo-scale: a point whose intensity misses the image's by more than R gives no "
+                         "photometric equation (0 .. 1, default 0.1)")
     a = ap.parse_args(argv)
     if a.map_merge_voxel is not None and not a.map:
         ap.error("--map-merge-voxel needs --map")
@@ -518,6 +545,10 @@ def main(argv=None):
         ap.error("--map-align-accept needs --map-align")
     if a.map_reloc_align_top is not None and not a.map_reloc:
         ap.error("--map-reloc-align-top needs --map-reloc")
+    if a.map_photo_scale is not None and not (a.map_info or a.map_align or a.map_loop):
+        ap.error("--map-photo-scale needs --map-info, --map-align or --map-loop")
+    if a.map_photo_max_residual is not None and a.map_photo_scale is None:
+        ap.error("--map-photo-max-residual needs --map-photo-scale")
     out = {}
     for room in a.rooms:
         parser = Parser(a.dataset, room, normalize=not a.no_normalize, input_folder=a.root)
@@ -535,7 +566,8 @@ def main(argv=None):
                           map_origins=a.map_origins or a.map_loop, map_loop=a.map_loop,
                           map_loop_min_gap=a.map_loop_min_gap, map_view_occlusion=a.map_view_occlusion,
                           map_view_occlusion_cell=a.map_view_occlusion_cell,
-                          map_view_occlusion_window=a.map_view_occlusion_window)
+                          map_view_occlusion_window=a.map_view_occlusion_window,
+                          map_photo_scale=a.map_photo_scale, map_photo_max_residual=a.map_photo_max_residual)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

@@ -145,6 +145,9 @@ class LocalizeResult:
     info_used: Optional[int] = None
     info_min_eig: Optional[float] = None
     weak: Optional[bool] = None
+    # info with MapConfig.photo_scale: the rows among info_used that also gave a photometric equation (cov, sigma_t,
+    # sigma_r, info_min_eig and weak are then those of geometry plus colour)
+    info_photo_used: Optional[int] = None
     # align: aligned -- the start pose the map's Gauss-Newton steps gave was taken (init_c2w is then that pose; False:
     # the alignment refused, or the map scored its pose worse than the motion model's, and the frame ran from that);
     # align_status / align_steps: ``PoseAlignment.status`` / ``steps``; align_from: the motion model's pose [4,4];
@@ -330,6 +333,12 @@ class Localizer:
     ``align_status`` / ``align_steps`` / ``align_from`` (the motion model's pose) / ``align_moved_t`` /
     ``align_moved_r_deg`` / ``align_scores`` say what happened.  Nothing in the map is written.  With the option off
     there is no call, and poses, step counts and the map are bit for bit those of the run without it.
+    ``map_config.photo_scale`` (with ``info``, ``align`` or ``loop``): ``track`` makes the frame's intensity image once
+    (``GaussianMap.intensity``; the frame then needs its ``rgb``) and hands it to every alignment, loop constraint and
+    pose information of the frame, whose normal equations gain a photometric equation per used row
+    (csrc/map_photo.hip); ``LocalizeResult.info_photo_used`` counts them.  A textured wall is then a frame that pins
+    its pose down: not ``weak``, and with ``align_accept`` a direct one.  With the field at None every launch, buffer
+    and number is as without it.
     ``map_config.origins``: every appended pose is recorded with its odometry measurement, the float64 relative pose to
     the pose before it as it was appended (``reset`` clears the record, ``correct_trajectory`` leaves it alone), which
     is what ``add_loop`` builds its pose graph on.  ``map_config.loop``: for a frame that is not lost, before the pose
@@ -376,6 +385,8 @@ class Localizer:
         self._info = False  # MapConfig.info
         self._align = False  # MapConfig.align
         self._accept = None  # (align_accept_min_used, align_accept_min_eig) when MapConfig.align_accept is on
+        self._photo_scale = None  # MapConfig.photo_scale
+        self._photo_kw: dict = {}  # with it, inside track(): intensity=<the frame's intensity image>, for the map's calls
         self._origins = False  # MapConfig.origins
         self._loop = None  # the MapConfig when MapConfig.loop is on
         self._loop_min_rows = 0  # MapConfig.loop_min_rows, or its default for this image size
@@ -398,6 +409,7 @@ class Localizer:
             self._refine = bool(map_config.refine)
             self._info = bool(map_config.info)
             self._align = bool(map_config.align)
+            self._photo_scale = map_config.photo_scale
             if map_config.align_accept:
                 self._accept = (
                     (self.W * self.H) // 16 if map_config.align_accept_min_used is None else map_config.align_accept_min_used,
@@ -526,9 +538,9 @@ class Localizer:
         with the option off)."""
         near = self.cfg.gs.near_plane
         if self._accept is None:
-            al = self.map.align_pose(depth, self.K, init, near)
+            al = self.map.align_pose(depth, self.K, init, near, **self._photo_kw)
         else:  # the same pose bit for bit, and the sums at it
-            al = self.map.align_poses(depth, self.K, [init], near)[0]
+            al = self.map.align_poses(depth, self.K, [init], near, **self._photo_kw)[0]
         taken, moved_t, moved_r, scores = False, 0.0, 0.0, None
         if al.status in ("CONVERGED", "STEPPED"):
             to = al.c2w.to(self.device)
@@ -559,6 +571,7 @@ class Localizer:
         self._prev = (pts, col)
         self._poses = [pose.to(self.device).clone()]
         self._odometry, self._loops, self._loop_last, self.last_pose_graph = [], [], 0, None
+        self._photo_kw = {}
         if self.map_mode:
             self.map.clear()
             first = dict(origin=0) if self._origins else {}  # the index of the frame's pose in the trajectory
@@ -589,7 +602,7 @@ class Localizer:
         aligned = {}  # candidate -> the alignment that took its place
         if cfg.reloc_align_top > 0:
             top = sorted(range(len(margins)), key=lambda i: (-margins[i], i))[: cfg.reloc_align_top]
-            als = self.map.align_poses(depth, self.K, [cands[i] for i in top], near)
+            als = self.map.align_poses(depth, self.K, [cands[i] for i in top], near, **self._photo_kw)
             tos = [al.c2w.to(self.device) for al in als]
             cands = cands.clone()
             for i, al, to, sc in zip(top, als, tos, self.map.score_poses(depth, self.K, tos, near)):
@@ -626,11 +639,22 @@ class Localizer:
         winner, *rest = self._retry(depth, frame, bases, kept)
         return (ranked[winner // (1 + 12 * self._reloc.reloc_levels)][0], *rest)
 
-    @torch.no_grad()
     def track(self, depth, rgb=None, gt_c2w: Optional[Tensor] = None) -> LocalizeResult:
+        try:
+            return self._track_frame(depth, rgb, gt_c2w)
+        finally:
+            self._photo_kw = {}  # the intensity image is the frame's: nothing outside its track() may read it
+
+    @torch.no_grad()
+    def _track_frame(self, depth, rgb, gt_c2w: Optional[Tensor]) -> LocalizeResult:
         if self._prev is None:
             raise RuntimeError("Localizer.track before reset(): the first frame comes with its pose")
+        if self._photo_scale is not None and rgb is None:
+            raise ValueError(f"photo_scale = {self._photo_scale}: the photometric term of the map's normal equations "
+                             "needs every frame's image (rgb=)")
         depth, rgb, pts, col = self._frame(depth, rgb)
+        # the frame's intensity image, once: every alignment, loop constraint and pose information of the frame reads it
+        self._photo_kw = {} if self._photo_scale is None else dict(intensity=self.map.intensity(rgb))
         placed = self._poses[-1]
         if self.motion == "hold" or len(self._poses) < 2:
             init = placed
@@ -721,7 +745,10 @@ class Localizer:
                         est = out.c2w = self._poses[-1]
                 if self._info:
                     # the frame's final estimate against the map as it was tracked: before anything below touches it
-                    self._report_information(out, self.map.pose_information(depth, self.K, est, self.cfg.gs.near_plane))
+                    info = self.map.pose_information(depth, self.K, est, self.cfg.gs.near_plane, **self._photo_kw)
+                    self._report_information(out, info)
+                    if self._photo_scale is not None:
+                        out.info_photo_used = info.photo_used
                 at = best
                 if out.loop:
                     # the rows have moved and the estimate with them: the insertion render is made from a new pair at
@@ -848,7 +875,7 @@ class Localizer:
         if out.loop_old_tested < self._loop_min_rows:
             out.loop_status = "few_rows"
             return
-        c = self.map.loop_constraint(depth, self.K, est, upto, near)
+        c = self.map.loop_constraint(depth, self.K, est, upto, near, **self._photo_kw)
         if not (c.alignment.moved and c.alignment.status == "CONVERGED"):
             out.loop_status = "not_converged"
             return

@@ -70,6 +70,13 @@ returns a ``PoseAlignment``: the pose, a status and the history of the steps.  `
 motion model's start pose with it before the splat tracker runs.  It changes nothing in the map.  One more entry point,
 one fixed sequence of launches; one read-back.
 
+Photometric term (``MapConfig.photo_scale``, csrc/map_photo.hip): those normal equations read nothing but depth, and a
+wall leaves three moves of the camera open.  With an ``intensity`` image of the frame (``intensity(rgb)``, one kernel)
+``pose_information``, ``align_pose``, ``align_poses`` and ``loop_constraint`` add one photometric equation per used row
+-- the row's colour against the image at its own pixel, ``photo_scale`` metres per unit of intensity -- into the same 30
+integers; the step kernels and everything on the host read them as before.  Three more entry points, the launch
+sequences of their twins; without an image the calls are exactly what they were.
+
 Trajectory correction (``MapConfig.origins``, csrc/map_correct.hip): a row is written into the world once, at the
 estimate of the frame that saw it.  With the option every row carries the index of that frame (``origins``), and
 ``correct`` moves the rows of every frame by that frame's rigid transform -- the one that takes its old pose to its
@@ -111,6 +118,7 @@ INFO_ONE = float(2 ** 20)  # their fixed point
 # along a wall), for a rotation that of p x n in m^2.  1e-3 is normals within 1.8 degrees (rms) of perpendicular to a
 # direction -- a wall, to the eye -- and 2000 times the 2^-21 that the rounding of a fixed-point term can add to a mean
 INFO_MIN_EIG = 1e-3
+INFO_PHOTO_MAX_SCALE = 16.0  # photo_scale one call of csrc/map_photo.hip takes at the most (its overflow bound)
 ALIGN_MAX_STEPS = 32  # iterations one call of csrc/map_align.hip runs at the most (gsl_map_align_max_steps())
 ALIGN_STATE_WORDS, ALIGN_ROW_WORDS = 14, 10  # 8-byte words of its state and of a history row (include/gsloc_hip.h)
 ALIGN_BATCH_MAX_POSES = 16  # poses one call of csrc/map_align_batch.hip aligns (gsl_map_align_batch_max_poses())
@@ -123,13 +131,17 @@ class PoseInformation:
     """The normal equations of a pose from the map's rows against a depth frame (``GaussianMap.pose_information``), for
     a left perturbation w2c' = exp(xi^) w2c with xi = (omega [rad], upsilon [m]) in the camera's frame: H = sum J J^T
     [6,6] and g = sum J r [6] over the rows used, float64 (the kernel's integers / 2^20); rss = sum r^2 in m^2; the rows
-    used and tested; min_eig: the bound ``weak`` takes by default."""
+    used and tested; min_eig: the bound ``weak`` takes by default.  With a photometric term (``intensity=``) H, g and
+    rss hold geometry plus colour, a colour residual counted as photo_scale metres per unit of intensity; photo_used:
+    the rows that gave a photometric equation (all of them among ``used``), photo_rss: their share of rss."""
     H: np.ndarray
     g: np.ndarray
     rss: float
     used: int
     tested: int
     min_eig: float = INFO_MIN_EIG
+    photo_used: int = 0
+    photo_rss: float = 0.0
 
     @property
     def eigenvalues(self) -> np.ndarray:
@@ -145,7 +157,9 @@ class PoseInformation:
         return self.used < 7 or not float(self.eigenvalues[0]) >= bound
 
     def covariance(self) -> Optional[np.ndarray]:
-        """sigma^2 H^-1 [6,6] with sigma^2 = rss / (used - 6), in (rad, m); None when weak."""
+        """sigma^2 H^-1 [6,6] with sigma^2 = rss / (used - 6), in (rad, m); None when weak.  With a photometric term
+        rss is the sum over used + photo_used equations while the divisor stays used - 6: sigma^2 is overstated by up
+        to a factor of two (every used row also gave a colour equation), never understated."""
         if self.weak():
             return None
         return (self.rss / float(self.used - 6)) * np.linalg.inv(self.H)
@@ -157,17 +171,18 @@ class PoseInformation:
         return -np.linalg.solve(self.H, self.g)
 
 
-def information_from_sums(sums, min_eig: float = INFO_MIN_EIG) -> PoseInformation:
+def information_from_sums(sums, min_eig: float = INFO_MIN_EIG, extra=None) -> PoseInformation:
     """The ``PoseInformation`` of the 30 int64 sums of csrc/map_info.hip (the upper triangle of H row-major, g, the
-    residual sum, the rows used and tested)."""
+    residual sum, the rows used and tested); extra: None, or the two int64 of gsl_map_pose_info_photo."""
     sums = np.asarray(sums, dtype=np.int64)
     H, k = np.zeros((6, 6)), 0
     for a in range(6):
         for b in range(a, 6):
             H[a, b] = H[b, a] = float(sums[k]) / INFO_ONE
             k += 1
+    photo = (0, 0.0) if extra is None else (int(extra[0]), float(extra[1]) / INFO_ONE)
     return PoseInformation(H, sums[21:27].astype(np.float64) / INFO_ONE, float(sums[27]) / INFO_ONE, int(sums[28]),
-                           int(sums[29]), min_eig)
+                           int(sums[29]), min_eig, *photo)
 
 
 @dataclass
@@ -681,10 +696,31 @@ class MapConfig:
     loop_min_rot_deg: float = 0.1
     loop_weight: float = 1e4
     loop_by: str = "index"
+    # Localizer(mode="map"): a photometric term in those normal equations (csrc/map_photo.hip).  With photo_scale set,
+    # every row that gives a point-to-plane equation also gives one from its colour against the frame's intensity
+    # image, in metres: photo_scale metres of depth residual per unit of intensity residual (intensities are 0 .. 1).
+    # It goes into the calls that info, align (align_accept, reloc_align_top) and loop already make, so one of the
+    # three has to be on.  A textured plane then pins the pose down where depth alone leaves three moves open.  On the
+    # textured wall of NOTES.md, "Photometric term", 0.2 -- the documented value to start from -- lifts the three open
+    # eigenvalues of H / used to 8e-3 .. 2e-2, eight times INFO_MIN_EIG, and converges in four steps; 0.1 needs seven;
+    # 0.05 stays below INFO_MIN_EIG.  None: off, every launch, buffer and number is what it is without the field
+    photo_scale: Optional[float] = None
+    # a row whose intensity misses the image's by more than this gives no photometric equation: an occluder, a
+    # highlight or a wrong row, not a pose error
+    photo_max_residual: float = 0.1
 
     def __post_init__(self):
         whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
         number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer))  # noqa: E731
+        if self.photo_scale is not None and (not number(self.photo_scale)
+                                             or not 0.0 <= self.photo_scale <= INFO_PHOTO_MAX_SCALE):
+            raise ValueError(f"photo_scale {self.photo_scale!r}: metres per unit of intensity, inside [0, "
+                             f"{INFO_PHOTO_MAX_SCALE:g}] (or None: no photometric term)")
+        if not number(self.photo_max_residual) or not 0.0 <= self.photo_max_residual <= 1.0:
+            raise ValueError(f"photo_max_residual {self.photo_max_residual!r}: an intensity difference, inside [0, 1]")
+        if self.photo_scale is not None and not (self.info is True or self.align is True or self.loop is True):
+            raise ValueError("photo_scale needs info=True, align=True or loop=True: the photometric term goes into the "
+                             "normal equations that those options sum")
         if not isinstance(self.origins, bool):
             raise ValueError(f"origins {self.origins!r}: True or False")
         if not isinstance(self.loop, bool):
@@ -928,6 +964,7 @@ class GaussianMap:
             self._refine_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
         # pose_information: its 30 sums, on first use
         self._info = None
+        self._info_photo = None  # pose_information with intensity=: the 30 sums and the two extra words, on first use
         # align_pose: one buffer of 8-byte words -- state, history, working pose, sums -- and the start pose, on first use
         self._align = None
         self._align_batch = None  # align_poses: the same for 16 poses, on first use
@@ -1463,15 +1500,72 @@ class GaussianMap:
                                          beyond, kappa, near, ptr(self._info), st), "gsl_map_pose_info")
         return self._info.cpu().numpy()
 
+    # ---- the photometric term of those normal equations (csrc/map_photo.hip) -------------------------------------------
+    def _intensity_launch(self, rgb: Tensor) -> Tensor:
+        """rgb [H,W,3] float32 on the device -> a new float32 [H,W]: one kernel, no synchronisation."""
+        assert rgb.is_cuda, "GaussianMap.intensity: the image is made by a HIP kernel, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        out = torch.empty(self.H, self.W, device=self.device)
+        _lib.check(lib.gsl_map_photo_intensity(ptr(rgb), self.W, self.H, ptr(out), st), "gsl_map_photo_intensity")
+        return out
+
+    @torch.no_grad()
+    def intensity(self, rgb) -> Tensor:
+        """The intensity image [H,W] float32, 0 .. 1, of a frame's rgb [H,W,3] in 0 .. 255 -- ((0.299 R + 0.587 G) +
+        0.114 B) / 255 in float32 -- on the map's device: what ``pose_information``, ``align_pose``, ``align_poses`` and
+        ``loop_constraint`` take as ``intensity``.  One kernel; make it once per frame."""
+        return self._intensity_launch(self._image(rgb, (self.H, self.W, 3), "rgb"))
+
+    def _photo_params(self, intensity, photo_scale, photo_max_residual):
+        """None without an intensity image; otherwise (the image [H,W] float32 on the device, photo_scale,
+        photo_max_residual as float32 values) with the configuration's values where None is given, checked."""
+        if intensity is None:
+            if photo_scale is not None or photo_max_residual is not None:
+                raise ValueError("photo_scale / photo_max_residual belong to a photometric term: they need intensity")
+            return None
+        scale = self.cfg.photo_scale if photo_scale is None else photo_scale
+        if scale is None:
+            raise ValueError("photo_scale: intensity is given and neither the call nor MapConfig sets the scale")
+        scale = float(scale)
+        if not 0.0 <= scale <= INFO_PHOTO_MAX_SCALE:
+            raise ValueError(f"photo_scale {scale!r}: metres per unit of intensity, inside [0, {INFO_PHOTO_MAX_SCALE:g}]")
+        rmax = float(self.cfg.photo_max_residual if photo_max_residual is None else photo_max_residual)
+        if not 0.0 <= rmax <= 1.0:
+            raise ValueError(f"photo_max_residual {rmax!r}: an intensity difference, inside [0, 1]")
+        return (self._image(intensity, (self.H, self.W), "intensity"), float(np.float32(scale)), float(np.float32(rmax)))
+
+    def _info_photo_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, keep: float,
+                           beyond: float, kappa: float, near: float, photo) -> Tuple[np.ndarray, np.ndarray]:
+        """``_info_launch`` with the photometric term, photo = (intensity, scale, max residual): the entry point (which
+        zeroes the sums and the two extra words) and the read-back of (int64 [30], int64 [2]), the call's one
+        synchronisation."""
+        assert depth.is_cuda, "GaussianMap.pose_information: the rows are judged and summed by a HIP kernel, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        if self._info_photo is None:
+            self._info_photo = torch.empty(INFO_VALUES + 2, dtype=torch.int64, device=self.device)
+        image, scale, rmax = photo
+        out = self._info_photo.data_ptr()
+        _lib.check(lib.gsl_map_pose_info_photo(ptr(self.means), self.n_live, ptr(w2c), *intr, ptr(depth), self.W, self.H,
+                                               keep, beyond, kappa, near, out, ptr(self.colors), ptr(image), scale, rmax,
+                                               out + 8 * INFO_VALUES, st), "gsl_map_pose_info_photo")
+        host = self._info_photo.cpu().numpy()
+        return host[:INFO_VALUES].copy(), host[INFO_VALUES:].copy()
+
     @torch.no_grad()
     def pose_information(self, depth, K, c2w, near_plane: float, rho: Optional[float] = None,
-                         kappa: Optional[float] = None) -> PoseInformation:
+                         kappa: Optional[float] = None, intensity=None, photo_scale: Optional[float] = None,
+                         photo_max_residual: Optional[float] = None) -> PoseInformation:
         """How well the depth frame [H,W] (metres) constrains the pose c2w [4,4]: the point-to-plane normal equations of
         a small move of the camera, summed over the live rows that project onto an inner pixel beyond ``near_plane``,
         agree with its depth within ``rho`` (None: ``info_rho``, and ``depth_rho`` when that is None) as do its four
         neighbours, and whose patch is planar within ``kappa`` (None: ``info_kappa``) -- the rule: include/gsloc_hip.h.
         Changes nothing in the map.  One zeroing launch, one kernel, one read-back; an empty map gives zeros (weak)
-        without a launch."""
+        without a launch.  intensity: None, or the frame's intensity image (``intensity(rgb)``): every used row then
+        also gives a photometric equation from its colour, ``photo_scale`` metres per unit of intensity (None:
+        ``MapConfig.photo_scale``) where it misses the image by at most ``photo_max_residual`` (None: the
+        configuration's), summed into the same H, g and rss (csrc/map_photo.hip); ``photo_used`` and ``photo_rss``
+        report its share.  One more zeroing launch."""
+        photo = self._photo_params(intensity, photo_scale, photo_max_residual)
         min_eig = INFO_MIN_EIG if self.cfg.info_min_eig is None else float(self.cfg.info_min_eig)
         if rho is None:
             rho = self.cfg.depth_rho if self.cfg.info_rho is None else self.cfg.info_rho
@@ -1485,18 +1579,23 @@ class GaussianMap:
         if self.n_live == 0:
             return PoseInformation(np.zeros((6, 6)), np.zeros(6), 0.0, 0, 0, min_eig)
         keep, beyond = float(np.float32(1.0) - np.float32(rho)), float(np.float32(1.0) + np.float32(rho))
-        sums = self._info_launch(depth, intr, _world_to_camera(c2w).to(self.device).contiguous(), keep, beyond,
-                                 float(np.float32(kappa)), float(near_plane))
+        w2c = _world_to_camera(c2w).to(self.device).contiguous()
+        if photo is not None:
+            sums, extra = self._info_photo_launch(depth, intr, w2c, keep, beyond, float(np.float32(kappa)),
+                                                  float(near_plane), photo)
+            return information_from_sums(sums, min_eig, extra)
+        sums = self._info_launch(depth, intr, w2c, keep, beyond, float(np.float32(kappa)), float(near_plane))
         return information_from_sums(sums, min_eig)
 
     # ---- pose alignment: Gauss-Newton steps on those normal equations, iterated on the device (csrc/map_align.hip) ----
     def _align_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, keep: float,
                       beyond: float, kappa: float, near: float, steps: int, damping: float, min_used: int,
-                      max_rot: float, max_trans: float, eps_rot: float, eps_trans: float, n_rows: Optional[int] = None):
+                      max_rot: float, max_trans: float, eps_rot: float, eps_trans: float, n_rows: Optional[int] = None,
+                      photo=None):
         """w2c [4,4] float32 on the host.  Its copy to the device, the entry point and the read-back of one buffer, the
         call's one synchronisation: (pose [3,4] float64, working pose [4,4] float32, steps applied, rows [steps,4] int64
         = (status, used, tested, rss_fixed), xi [steps,6] float64).  n_rows: the first rows of the map that are summed
-        over (None: the live ones)."""
+        over (None: the live ones).  photo: None, or (intensity, scale, max residual): gsl_map_pose_align_photo."""
         assert depth.is_cuda, "GaussianMap.align_pose: the pose is aligned by HIP kernels, no CPU path"
         lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
         n_state, n_hist = ALIGN_STATE_WORDS, ALIGN_MAX_STEPS * ALIGN_ROW_WORDS
@@ -1507,10 +1606,14 @@ class GaussianMap:
         n_rows = self.n_live if n_rows is None else int(n_rows)
         words, base = a["words"], a["words"].data_ptr()
         a["start"].copy_(w2c.reshape(16))
-        _lib.check(lib.gsl_map_pose_align(ptr(self.means), n_rows, ptr(a["start"]), *intr, ptr(depth), self.W, self.H,
-                                          keep, beyond, kappa, near, steps, damping, min_used, max_rot, max_trans,
-                                          eps_rot, eps_trans, base + 8 * (n_state + n_hist + 8), base + 8 * (n_state + n_hist),
-                                          base, base + 8 * n_state, st), "gsl_map_pose_align")
+        args = (ptr(self.means), n_rows, ptr(a["start"]), *intr, ptr(depth), self.W, self.H, keep, beyond, kappa, near,
+                steps, damping, min_used, max_rot, max_trans, eps_rot, eps_trans, base + 8 * (n_state + n_hist + 8),
+                base + 8 * (n_state + n_hist), base, base + 8 * n_state)
+        if photo is None:
+            _lib.check(lib.gsl_map_pose_align(*args, st), "gsl_map_pose_align")
+        else:
+            _lib.check(lib.gsl_map_pose_align_photo(*args, ptr(self.colors), ptr(photo[0]), photo[1], photo[2], st),
+                       "gsl_map_pose_align_photo")
         host = words.cpu().numpy()
         hist = host[n_state:n_state + steps * ALIGN_ROW_WORDS].reshape(steps, ALIGN_ROW_WORDS)
         return (host[:12].view(np.float64).reshape(3, 4).copy(),
@@ -1554,7 +1657,8 @@ class GaussianMap:
                    kappa: Optional[float] = None, damping: Optional[float] = None, max_rot_deg: Optional[float] = None,
                    max_trans: Optional[float] = None, eps_rot_deg: Optional[float] = None,
                    eps_trans: Optional[float] = None, min_used: int = ALIGN_MIN_USED,
-                   rows: Optional[int] = None) -> PoseAlignment:
+                   rows: Optional[int] = None, intensity=None, photo_scale: Optional[float] = None,
+                   photo_max_residual: Optional[float] = None) -> PoseAlignment:
         """The pose c2w [4,4] aligned to the map against the depth frame [H,W] (metres): up to ``steps`` (None:
         ``align_steps``) damped Gauss-Newton steps on the normal equations of ``pose_information`` -- the rows chosen
         with ``rho`` (None: ``align_rho``, and ``depth_rho`` when that is None) and ``kappa`` (None: ``info_kappa``),
@@ -1564,8 +1668,11 @@ class GaussianMap:
         given.  Changes nothing in the map.  One fixed sequence of 1 + 3 ``steps`` launches, one read-back; an empty
         map gives status FEW without a launch.  The result has to be checked by the caller: a start too far off can
         settle elsewhere (NOTES.md, "Pose alignment").  rows: only the first that many rows of the map are used
-        (``loop_constraint``; None: every live row)."""
+        (``loop_constraint``; None: every live row).  intensity, photo_scale, photo_max_residual: as for
+        ``pose_information`` -- the normal equations of every iteration then hold the photometric term
+        (gsl_map_pose_align_photo: the same launches, the sums of csrc/map_photo.hip)."""
         rows = self._prefix(rows)
+        photo = self._photo_params(intensity, photo_scale, photo_max_residual)
         (steps, keep, beyond, kappa, damping, min_used, max_rot, max_trans, eps_rot,
          eps_trans) = self._align_params(steps, rho, kappa, damping, max_rot_deg, max_trans, eps_rot_deg, eps_trans, min_used)
         depth = self._depth_image(depth)
@@ -1576,6 +1683,8 @@ class GaussianMap:
             hist[0, 0] = ALIGN_STATUS.index("FEW")
         else:
             prefix = {} if rows is None else dict(n_rows=rows)
+            if photo is not None:
+                prefix["photo"] = photo
             pose, _, n, hist, xis = self._align_launch(depth, intr, w2c.contiguous(), keep, beyond, kappa,
                                                        float(near_plane), steps, damping, min_used, max_rot, max_trans,
                                                        eps_rot, eps_trans, **prefix)
@@ -1596,10 +1705,11 @@ class GaussianMap:
     def _align_batch_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, keep: float,
                             beyond: float, kappa: float, near: float, steps: int, damping: float, min_used: int,
                             max_rot: float, max_trans: float, eps_rot: float, eps_trans: float,
-                            n_rows: Optional[int] = None) -> list:
+                            n_rows: Optional[int] = None, photo=None) -> list:
         """w2c [k,4,4] float32 on the host, k <= 16.  Their copy to the device, the entry point and the read-back of one
         buffer, the call's one synchronisation.  Per pose: (pose [3,4] float64, working pose [4,4] float32, steps
-        applied, done, rows [steps,4] int64, xi [steps,6] float64, sums [30] int64)."""
+        applied, done, rows [steps,4] int64, xi [steps,6] float64, sums [30] int64).  photo: None, or (intensity,
+        scale, max residual): gsl_map_pose_align_batch_photo."""
         assert depth.is_cuda, "GaussianMap.align_poses: the poses are aligned by HIP kernels, no CPU path"
         lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
         cap, k = ALIGN_BATCH_MAX_POSES, int(w2c.shape[0])
@@ -1614,10 +1724,14 @@ class GaussianMap:
         n_rows = self.n_live if n_rows is None else int(n_rows)
         words, base = a["words"], a["words"].data_ptr()
         a["start"][:k].copy_(w2c.reshape(k, 16))
-        _lib.check(lib.gsl_map_pose_align_batch(ptr(self.means), n_rows, ptr(a["start"]), k, *intr, ptr(depth), self.W,
-                                                self.H, keep, beyond, kappa, near, steps, damping, min_used, max_rot,
-                                                max_trans, eps_rot, eps_trans, base + 8 * at_sums, base + 8 * at_work,
-                                                base + 8 * at_state, base + 8 * at_hist, st), "gsl_map_pose_align_batch")
+        args = (ptr(self.means), n_rows, ptr(a["start"]), k, *intr, ptr(depth), self.W, self.H, keep, beyond, kappa, near,
+                steps, damping, min_used, max_rot, max_trans, eps_rot, eps_trans, base + 8 * at_sums, base + 8 * at_work,
+                base + 8 * at_state, base + 8 * at_hist)
+        if photo is None:
+            _lib.check(lib.gsl_map_pose_align_batch(*args, st), "gsl_map_pose_align_batch")
+        else:
+            _lib.check(lib.gsl_map_pose_align_batch_photo(*args, ptr(self.colors), ptr(photo[0]), photo[1], photo[2], st),
+                       "gsl_map_pose_align_batch_photo")
         host = words.cpu().numpy()
         out = []
         for p in range(k):
@@ -1634,15 +1748,19 @@ class GaussianMap:
                     kappa: Optional[float] = None, damping: Optional[float] = None, max_rot_deg: Optional[float] = None,
                     max_trans: Optional[float] = None, eps_rot_deg: Optional[float] = None,
                     eps_trans: Optional[float] = None, min_used: int = ALIGN_MIN_USED,
-                    rows: Optional[int] = None) -> list:
+                    rows: Optional[int] = None, intensity=None, photo_scale: Optional[float] = None,
+                    photo_max_residual: Optional[float] = None) -> list:
         """``align_pose`` for each of the poses c2ws [k,4,4] (a tensor, or a sequence of [4,4] poses) against the same
         frame, with the same keyword arguments and defaults: one call of 1 + 3 ``steps`` launches and one read-back for
         up to 16 poses (more go in chunks of 16).  Pose, status, steps and history of every ``PoseAlignment`` are bit
         for bit ``align_pose``'s.  On the device a pose that has finished stops paying for its sums, after one more
         pass at its final pose: the result is then ``closed`` and ``final`` holds those sums as a ``PoseInformation``
         (with ``info_min_eig``) -- what ``pose_information`` gives at c2w, without another launch.  A pose that
-        converges on the last iteration is not closed.  An empty map gives status FEW, not closed, without a launch."""
+        converges on the last iteration is not closed.  An empty map gives status FEW, not closed, without a launch.
+        intensity, photo_scale, photo_max_residual: as for ``align_pose`` (gsl_map_pose_align_batch_photo); ``final``
+        then holds geometry plus colour, without the photometric counts (``photo_used`` stays 0)."""
         rows = self._prefix(rows)
+        photo = self._photo_params(intensity, photo_scale, photo_max_residual)
         (steps, keep, beyond, kappa, damping, min_used, max_rot, max_trans, eps_rot,
          eps_trans) = self._align_params(steps, rho, kappa, damping, max_rot_deg, max_trans, eps_rot_deg, eps_trans, min_used)
         poses = [torch.as_tensor(c) for c in c2ws]
@@ -1660,6 +1778,8 @@ class GaussianMap:
             return [self._alignment(w.numpy()[:3].astype(np.float64), 0, hist, np.zeros((1, 6))) for w in w2c]
         min_eig = INFO_MIN_EIG if self.cfg.info_min_eig is None else float(self.cfg.info_min_eig)
         prefix = {} if rows is None else dict(n_rows=rows)
+        if photo is not None:
+            prefix["photo"] = photo
         out = []
         for at in range(0, len(poses), ALIGN_BATCH_MAX_POSES):
             chunk = w2c[at:at + ALIGN_BATCH_MAX_POSES].contiguous()
@@ -1734,7 +1854,9 @@ class GaussianMap:
         map; the rows the drifted frames since then wrote beside it take no part -- by ``align_pose`` (``align``: its
         keyword arguments), and the scores (``score_poses``) of the given and of the aligned pose against the same
         prefix.  Changes nothing in the map.  Whether to trust the result, and what to do with it
-        (``spread_correction``, ``correct``), is the caller's decision."""
+        (``spread_correction``, ``correct``), is the caller's decision.  ``intensity``, ``photo_scale`` and
+        ``photo_max_residual`` among ``align`` go to ``align_pose``: a constraint measured on a textured wall is then
+        closed in the wall's plane as well.  The scores stay depth only."""
         n = self.rows_up_to(upto_frame)
         al = self.align_pose(depth, K, c2w, near_plane, rows=n, **align)
         scores = self.score_poses(depth, K, [torch.as_tensor(c2w).detach().cpu(), al.c2w.detach().cpu()], near_plane,

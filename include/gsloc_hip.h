@@ -466,6 +466,56 @@ int gsl_map_pose_align_batch(const float* means, int64_t n_rows, const float* w2
                              double max_trans, double eps_rot, double eps_trans, int64_t* sums, float* work, void* state,
                              void* history, void* stream);
 
+/* ---- a photometric term in the normal equations above, and in the two alignments (csrc/map_photo.hip) ----
+ * gsl_map_photo_intensity: rgb[height,width,3] float32 in 0 .. 255 and intensity[height,width] float32 on the device;
+ *   intensity[v,u] = ((0.299f R + 0.587f G) + 0.114f B) / 255.f.  One kernel, one thread per pixel: once per frame.
+ *   Returns GSL_ERR_BAD_ARG before the launch for a NULL rgb or intensity, width or height <= 0 or width * height >
+ *   2^31 - 1.
+ * gsl_map_pose_info_photo: gsl_map_pose_info's arguments, then colors[n_rows,3] float32 (the rows' colours, 0 .. 1, as
+ *   gsl_map_append stores them), intensity[height,width] (above, of the frame that depth belongs to), photo_scale s
+ *   [metres per unit of intensity: how many metres of depth residual one unit of intensity residual is worth] and
+ *   photo_max_residual, then extra[2] int64 on the device, not initialised.  A row that is USED -- by the rule above,
+ *   untouched -- gives, beside its geometric equation, a photometric one when, with Y the intensity image, c the row's
+ *   colour and u, v, uf, vf, x, y, z as above, float32, one rounding per operation in the order written:
+ *     Yi = (0.299f c.r + 0.587f c.g) + 0.114f c.b;  Y0, Yl, Yr, Yu, Yd = Y[vf, uf], Y[vf, uf - 1], Y[vf, uf + 1],
+ *     Y[vf - 1, uf], Y[vf + 1, uf];  each of the six is >= 0 and <= 1 (false for a NaN);
+ *     gx = (Yr - Yl) * 0.5f, gy = (Yd - Yu) * 0.5f;  Yp = (Y0 + gx * (u - uf)) + gy * (v - vf);  rc = Yp - Yi;
+ *     |rc| <= photo_max_residual;
+ *     a0 = (s * gx) * fx / z, a1 = (s * gy) * fy / z, a2 = -((a0 * x + a1 * y) / z);  every |a_k| <= 8 and z < 16;
+ *     Jc = (y a2 - z a1, z a0 - x a2, x a1 - y a0, a0, a1, a2), Jc_6 = s * rc.
+ *   out[0 .. 27] are then the sums of fix(J_a, J_b) and of fix(Jc_a, Jc_b) together; out[28] and out[29] keep their
+ *   meaning.  extra[0] = the rows that gave a photometric equation, extra[1] = the sum of fix(s rc, s rc) over them.
+ *   photo_scale = 0 gives gsl_map_pose_info's 30 integers.  One or two zeroing launches and one kernel; nothing but out
+ *   and extra is written.
+ * gsl_map_info_photo_max_rows: the rows such a call takes -- with B and S of gsl_map_info_max_rows and
+ *   Bc = max(16 S 8 sqrt(3), s photo_max_residual): rows < 2^63 / (1.01^2 (B^2 + Bc^2) 2^20 + 2), 2^31 - 1 at the most; 0
+ *   for arguments the entry points refuse.
+ * gsl_map_pose_align_photo, gsl_map_pose_align_batch_photo: gsl_map_pose_align and gsl_map_pose_align_batch with these
+ *   sums in place of gsl_map_pose_info's in every iteration -- the same launch sequences, state, work and history; the
+ *   arguments of the twin, then colors, intensity, photo_scale, photo_max_residual in front of stream.
+ * Each returns GSL_ERR_BAD_ARG before any launch, writing nothing, for whatever its twin refuses, a NULL colors,
+ * intensity (or extra), photo_scale not in [0, 16], photo_max_residual not in [0, 1], n_rows above
+ * gsl_map_info_photo_max_rows. */
+int gsl_map_photo_intensity(const float* rgb, int width, int height, float* intensity, void* stream);
+int64_t gsl_map_info_photo_max_rows(float fx, float fy, float cx, float cy, int width, int height, float keep,
+                                    float photo_scale, float photo_max_residual);
+int gsl_map_pose_info_photo(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx, float cy,
+                            const float* depth, int width, int height, float keep, float beyond, float kappa,
+                            float near_plane, int64_t* out, const float* colors, const float* intensity,
+                            float photo_scale, float photo_max_residual, int64_t* extra, void* stream);
+int gsl_map_pose_align_photo(const float* means, int64_t n_rows, const float* w2c, float fx, float fy, float cx,
+                             float cy, const float* depth, int width, int height, float keep, float beyond, float kappa,
+                             float near_plane, int max_steps, double damping, int min_used, double max_rot,
+                             double max_trans, double eps_rot, double eps_trans, int64_t* sums, float* work, void* state,
+                             void* history, const float* colors, const float* intensity, float photo_scale,
+                             float photo_max_residual, void* stream);
+int gsl_map_pose_align_batch_photo(const float* means, int64_t n_rows, const float* w2c, int n_poses, float fx, float fy,
+                                   float cx, float cy, const float* depth, int width, int height, float keep,
+                                   float beyond, float kappa, float near_plane, int max_steps, double damping,
+                                   int min_used, double max_rot, double max_trans, double eps_rot, double eps_trans,
+                                   int64_t* sums, float* work, void* state, void* history, const float* colors,
+                                   const float* intensity, float photo_scale, float photo_max_residual, void* stream);
+
 /* ---- place recognition: a 16 x 12 descriptor of a depth frame, and its match against keyframes (csrc/map_place.hip) ----
  * gsl_map_place_describe: depth[height,width] float32 on the device, row-major, metres; desc[192] int32 on the device,
  * row-major over GSL_MAP_PLACE_GH lines of GSL_MAP_PLACE_GW cells (gsl_map_place_cells() = 192).  It need not be
