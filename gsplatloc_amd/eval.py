@@ -47,7 +47,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   map_align_accept: bool = False, map_reloc_align_top: Optional[int] = None,
                   map_view_occlusion: Optional[float] = None, map_view_occlusion_cell: Optional[int] = None,
                   map_view_occlusion_window: Optional[int] = None, map_photo_scale: Optional[float] = None,
-                  map_photo_max_residual: Optional[float] = None) -> Dict:
+                  map_photo_max_residual: Optional[float] = None, map_align_levels: Optional[int] = None,
+                  map_align_level_steps: Optional[int] = None) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -77,7 +78,9 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     ``map_view_occlusion_window`` for MapConfig.view_occlusion_cell_px / view_occlusion_window where not None;
     ``map_photo_scale``: MapConfig.photo_scale, the normal equations of map_info, map_align and map_loop gain a
     photometric term from the rows' colours against the frame's image, with ``map_photo_max_residual`` for
-    MapConfig.photo_max_residual where not None)."""
+    MapConfig.photo_max_residual where not None; ``map_align_levels``: MapConfig.align_levels, the alignments of
+    map_align and map_loop run coarse to fine on an image pyramid of the frame, with ``map_align_level_steps`` for
+    MapConfig.align_level_steps where not None)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
     occlusion = {k: v for k, v in (("view_occlusion_cell_px", map_view_occlusion_cell),
                                    ("view_occlusion_window", map_view_occlusion_window)) if v is not None}
@@ -126,6 +129,16 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         raise ValueError("map_photo_max_residual: an option of map_photo_scale")
     if map_photo_scale is not None and not (map_info or map_align or map_loop):
         raise ValueError("map_photo_scale: the photometric term of map_info, map_align or map_loop -- one of them")
+    if (map_align_levels is not None or map_align_level_steps is not None) and not map_mode:
+        raise ValueError("map_align_levels belongs to the map mode (map_mode=True)")
+    if map_align_level_steps is not None and map_align_levels is None:
+        raise ValueError("map_align_level_steps: an option of map_align_levels")
+    if map_align_levels is not None and not (map_align or map_loop):
+        raise ValueError("map_align_levels: the pyramid of the alignments of map_align or map_loop -- one of them")
+    pyramid = None
+    if map_align_levels is not None:
+        pyramid = dict(align_levels=map_align_levels, **({} if map_align_level_steps is None else
+                                                         {"align_level_steps": map_align_level_steps}))
     photo_term = None
     if map_photo_scale is not None:
         photo_term = dict(photo_scale=map_photo_scale, **({} if map_photo_max_residual is None else
@@ -153,7 +166,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                                    dict(reloc, reloc=True) if map_reloc else None,
                                    dict(keyframes, keyframes=True) if map_keyframes else None, map_refine=refine,
                                    map_info=bool(map_info), map_align=align, map_origins=bool(map_origins) or bool(map_loop),
-                                   map_loop=loop, map_view_occlusion=occlusion or None, map_photo=photo_term)
+                                   map_loop=loop, map_view_occlusion=occlusion or None, map_photo=photo_term,
+                                   map_pyramid=pyramid)
     if map_mode:
         raise ValueError("map_mode belongs to the sequential protocol (sequential=True)")
     photo = rgb_lambda != 0.0
@@ -221,7 +235,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                         map_keyframes: Optional[Dict] = None, map_refine: Optional[Dict] = None,
                         map_info: bool = False, map_align: Optional[Dict] = None, map_origins: bool = False,
                         map_loop: Optional[Dict] = None, map_view_occlusion: Optional[Dict] = None,
-                        map_photo: Optional[Dict] = None) -> Dict:
+                        map_photo: Optional[Dict] = None, map_pyramid: Optional[Dict] = None) -> Dict:
     """Frames 1..n of the room tracked by a Localizer that was given the ground-truth pose of frame 0 and nothing else.
     ATE / AAE: RMSE of the absolute translation / rotation errors of frames 1..n against ground truth, no alignment.
     map_mode: Localizer(mode="map"); the report gains map_gaussians (live points at the end), added_per_frame,
@@ -253,7 +267,10 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     MapConfig fields of occlusion culling (view_occlusion_rho and, where wanted, view_occlusion_cell_px /
     view_occlusion_window; it needs map_view_guard); the report gains view_culled_per_frame.  map_photo: the MapConfig
     fields of the photometric term (photo_scale and, where wanted, photo_max_residual; it needs map_info, map_align or
-    map_loop); the report gains photo_scale and, with map_info, info_photo_used_per_frame."""
+    map_loop); the report gains photo_scale and, with map_info, info_photo_used_per_frame.  map_pyramid: the MapConfig
+    fields of the coarse-to-fine alignment (align_levels and, where wanted, align_level_steps; it needs map_align or
+    map_loop); the report gains align_levels and, with map_align, align_level_steps_per_frame (the steps every level
+    applied, coarse to fine)."""
     n = len(parser) if max_frames is None else min(len(parser), max_frames)
     depth, rgb, pose = parser.frame(0)
     H, W = depth.shape
@@ -266,7 +283,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                                                        **(map_keyframes or {}), **(map_refine or {}),
                                                        info=bool(map_info), **(map_align or {}),
                                                        origins=bool(map_origins), **(map_loop or {}),
-                                                       **(map_view_occlusion or {}), **(map_photo or {})))
+                                                       **(map_view_occlusion or {}), **(map_photo or {}),
+                                                       **(map_pyramid or {})))
     loc = Localizer(parser.K, W, H, cfg, normalize=parser.normalize, motion=motion, device=parser.device, **extra)
     t0 = time.perf_counter()
     loc.reset(depth, rgb, pose)
@@ -278,6 +296,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     sigma_t, sigma_r, info_used, info_eig, weak = [], [], [], [], 0
     photo_used = []
     aligned, align_steps, align_status, motion_eT, start_eT = [], [], [], [], []
+    level_steps = []
     direct, direct_reason, reloc_aligned = [], [], []
     ordered = True
     loop_status, closures, anchors, gts = [], [], [], [pose]
@@ -318,10 +337,12 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             aligned.append(bool(r.aligned))
             align_steps.append(r.align_steps)
             align_status.append(r.align_status)
+            level_steps.append(r.align_level_steps)
             gt_t = pose[:3, 3].to(r.init_c2w.device)
             motion_eT.append(float(torch.norm(r.align_from[:3, 3] - gt_t)))
             start_eT.append(float(torch.norm(r.init_c2w[:3, 3] - gt_t)))
-            print(f"frame {i}: pose alignment: {r.align_status} after {r.align_steps} steps, moved {r.align_moved_t:.3e} m "
+            print(f"frame {i}: pose alignment: {r.align_status} after {r.align_steps} steps"
+                  + (f" (per level {r.align_level_steps})" if r.align_level_steps is not None else "") + f", moved {r.align_moved_t:.3e} m "
                   f"{r.align_moved_r_deg:.3e} deg, taken {r.aligned}: start eT {motion_eT[-1]:.3e} -> {start_eT[-1]:.3e}"
                   + ("" if r.direct is None else f", direct {r.direct}" + (f" ({r.direct_reason})" if r.direct_reason else "")))
             direct.append(r.direct)
@@ -368,6 +389,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
                 "info_used_per_frame": info_used, "info_min_eig_per_frame": info_eig, "weak_frames": weak}
                if map_info else {}),
             **({**map_photo, **({"info_photo_used_per_frame": photo_used} if map_info else {})} if map_photo else {}),
+            **({**map_pyramid, **({"align_level_steps_per_frame": level_steps} if map_align else {})}
+               if map_pyramid else {}),
             **({"align": True, "aligned_per_frame": aligned, "align_steps_per_frame": align_steps,
                 "align_status_per_frame": align_status, "aligned_frames": sum(aligned),
                 "motion_eT_per_frame": motion_eT, "start_eT_per_frame": start_eT} if map_align else {}),
@@ -491,6 +514,12 @@ def main(argv=None):
     ap.add_argument("--map-photo-max-residual", type=float, default=None, metavar="R",
                     help="--map-photo-scale: a point whose intensity misses the image's by more than R gives no "
                          "photometric equation (0 .. 1, default 0.1)")
+    ap.add_argument("--map-align-levels", type=int, default=None, metavar="L",
+                    help="--map-align / --map-loop: coarse-to-fine alignment -- every frame builds an image pyramid of L "
+                         "levels (1 .. 4) once, and its alignments start at the coarsest level: every level doubles the "
+                         "distance from which the photometric term converges (default 0: the frame alone)")
+    ap.add_argument("--map-align-level-steps", type=int, default=None, metavar="K",
+                    help="--map-align-levels: iterations at every coarse level, 1 .. 32 (default: those of the frame)")
     a = ap.parse_args(argv)
     if a.map_merge_voxel is not None and not a.map:
         ap.error("--map-merge-voxel needs --map")
@@ -549,6 +578,10 @@ def main(argv=None):
         ap.error("--map-photo-scale needs --map-info, --map-align or --map-loop")
     if a.map_photo_max_residual is not None and a.map_photo_scale is None:
         ap.error("--map-photo-max-residual needs --map-photo-scale")
+    if a.map_align_levels is not None and not (a.map_align or a.map_loop):
+        ap.error("--map-align-levels needs --map-align or --map-loop")
+    if a.map_align_level_steps is not None and a.map_align_levels is None:
+        ap.error("--map-align-level-steps needs --map-align-levels")
     out = {}
     for room in a.rooms:
         parser = Parser(a.dataset, room, normalize=not a.no_normalize, input_folder=a.root)
@@ -567,7 +600,8 @@ def main(argv=None):
                           map_loop_min_gap=a.map_loop_min_gap, map_view_occlusion=a.map_view_occlusion,
                           map_view_occlusion_cell=a.map_view_occlusion_cell,
                           map_view_occlusion_window=a.map_view_occlusion_window,
-                          map_photo_scale=a.map_photo_scale, map_photo_max_residual=a.map_photo_max_residual)
+                          map_photo_scale=a.map_photo_scale, map_photo_max_residual=a.map_photo_max_residual,
+                          map_align_levels=a.map_align_levels, map_align_level_steps=a.map_align_level_steps)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))
     with open(a.out, "w") as f:

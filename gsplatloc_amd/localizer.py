@@ -160,6 +160,9 @@ class LocalizeResult:
     align_moved_t: Optional[float] = None
     align_moved_r_deg: Optional[float] = None
     align_scores: Optional[tuple] = None
+    # MapConfig.align_levels (None with the option at 0): the steps every level of the start pose's alignment applied,
+    # from the coarsest level to the frame itself (``PoseAlignment.level_steps``; align_steps is the last of them)
+    align_level_steps: Optional[list] = None
     # align_accept (both None with the option off): direct -- the aligned pose is the frame's estimate and the tracker
     # did not run (steps 0, best_step -1, best_loss None; lost is the map's verdict alone); direct_reason: None on a
     # direct frame, otherwise the first rule that failed -- "status" (the alignment is not CONVERGED), "open" (it
@@ -337,7 +340,11 @@ class Localizer:
     (``GaussianMap.intensity``; the frame then needs its ``rgb``) and hands it to every alignment, loop constraint and
     pose information of the frame, whose normal equations gain a photometric equation per used row
     (csrc/map_photo.hip); ``LocalizeResult.info_photo_used`` counts them.  A textured wall is then a frame that pins
-    its pose down: not ``weak``, and with ``align_accept`` a direct one.  With the field at None every launch, buffer
+    its pose down: not ``weak``, and with ``align_accept`` a direct one.  ``map_config.align_levels`` (with ``align``
+    or ``loop``): ``track`` builds the frame's image pyramid once (``GaussianMap.pyramid``: depth and, with
+    ``photo_scale``, intensity) and every alignment of the frame -- of the start pose, of ``reloc_align_top``'s
+    candidates, of a loop constraint -- runs coarse to fine on it; ``LocalizeResult.align_level_steps`` holds the steps
+    per level.  With the field at None every launch, buffer
     and number is as without it.
     ``map_config.origins``: every appended pose is recorded with its odometry measurement, the float64 relative pose to
     the pose before it as it was appended (``reset`` clears the record, ``correct_trajectory`` leaves it alone), which
@@ -387,6 +394,9 @@ class Localizer:
         self._accept = None  # (align_accept_min_used, align_accept_min_eig) when MapConfig.align_accept is on
         self._photo_scale = None  # MapConfig.photo_scale
         self._photo_kw: dict = {}  # with it, inside track(): intensity=<the frame's intensity image>, for the map's calls
+        self._align_levels = 0  # MapConfig.align_levels
+        # inside track(): _photo_kw and, with align_levels, levels= and pyramid=<the frame's>, for the map's alignments
+        self._align_kw: dict = {}
         self._origins = False  # MapConfig.origins
         self._loop = None  # the MapConfig when MapConfig.loop is on
         self._loop_min_rows = 0  # MapConfig.loop_min_rows, or its default for this image size
@@ -410,6 +420,7 @@ class Localizer:
             self._info = bool(map_config.info)
             self._align = bool(map_config.align)
             self._photo_scale = map_config.photo_scale
+            self._align_levels = int(map_config.align_levels)
             if map_config.align_accept:
                 self._accept = (
                     (self.W * self.H) // 16 if map_config.align_accept_min_used is None else map_config.align_accept_min_used,
@@ -535,12 +546,13 @@ class Localizer:
         the pose that follows the motion (NOTES.md, "Pose alignment").  Returns (the ``LocalizeResult`` fields aligned,
         align_status, align_steps, align_from, align_moved_t, align_moved_r_deg, align_scores; the pose to start
         from; align_accept: None when that pose may be the frame's estimate, else ``_direct_reason``'s word -- None
-        with the option off)."""
+        with the option off).  With ``align_levels`` the alignment runs coarse to fine on the frame's pyramid, and the
+        fields gain the steps per level."""
         near = self.cfg.gs.near_plane
         if self._accept is None:
-            al = self.map.align_pose(depth, self.K, init, near, **self._photo_kw)
+            al = self.map.align_pose(depth, self.K, init, near, **self._align_kw)
         else:  # the same pose bit for bit, and the sums at it
-            al = self.map.align_poses(depth, self.K, [init], near, **self._photo_kw)[0]
+            al = self.map.align_poses(depth, self.K, [init], near, **self._align_kw)[0]
         taken, moved_t, moved_r, scores = False, 0.0, 0.0, None
         if al.status in ("CONVERGED", "STEPPED"):
             to = al.c2w.to(self.device)
@@ -548,7 +560,7 @@ class Localizer:
             scores = tuple(tuple(int(c) for c in s) for s in self.map.score_poses(depth, self.K, [init, to], near))
             taken = self._share_rule(*scores)
         reason = None if self._accept is None else self._direct_reason(al, taken)
-        return (taken, al.status, al.steps, init, moved_t, moved_r, scores), (to if taken else init), reason
+        return (taken, al.status, al.steps, init, moved_t, moved_r, scores, al.level_steps), (to if taken else init), reason
 
     @staticmethod
     def _report_information(out: LocalizeResult, info) -> None:
@@ -571,7 +583,7 @@ class Localizer:
         self._prev = (pts, col)
         self._poses = [pose.to(self.device).clone()]
         self._odometry, self._loops, self._loop_last, self.last_pose_graph = [], [], 0, None
-        self._photo_kw = {}
+        self._photo_kw, self._align_kw = {}, {}
         if self.map_mode:
             self.map.clear()
             first = dict(origin=0) if self._origins else {}  # the index of the frame's pose in the trajectory
@@ -602,7 +614,7 @@ class Localizer:
         aligned = {}  # candidate -> the alignment that took its place
         if cfg.reloc_align_top > 0:
             top = sorted(range(len(margins)), key=lambda i: (-margins[i], i))[: cfg.reloc_align_top]
-            als = self.map.align_poses(depth, self.K, [cands[i] for i in top], near, **self._photo_kw)
+            als = self.map.align_poses(depth, self.K, [cands[i] for i in top], near, **self._align_kw)
             tos = [al.c2w.to(self.device) for al in als]
             cands = cands.clone()
             for i, al, to, sc in zip(top, als, tos, self.map.score_poses(depth, self.K, tos, near)):
@@ -643,7 +655,8 @@ class Localizer:
         try:
             return self._track_frame(depth, rgb, gt_c2w)
         finally:
-            self._photo_kw = {}  # the intensity image is the frame's: nothing outside its track() may read it
+            # the intensity image and the pyramid are the frame's: nothing outside its track() may read them
+            self._photo_kw, self._align_kw = {}, {}
 
     @torch.no_grad()
     def _track_frame(self, depth, rgb, gt_c2w: Optional[Tensor]) -> LocalizeResult:
@@ -655,6 +668,11 @@ class Localizer:
         depth, rgb, pts, col = self._frame(depth, rgb)
         # the frame's intensity image, once: every alignment, loop constraint and pose information of the frame reads it
         self._photo_kw = {} if self._photo_scale is None else dict(intensity=self.map.intensity(rgb))
+        self._align_kw = self._photo_kw
+        if self._align_levels > 0:
+            # the frame's pyramid, once: every alignment of the frame starts at its coarsest level
+            self._align_kw = dict(self._photo_kw, levels=self._align_levels, pyramid=self.map.pyramid(
+                depth, self._align_levels, intensity=self._photo_kw.get("intensity")))
         placed = self._poses[-1]
         if self.motion == "hold" or len(self._poses) < 2:
             init = placed
@@ -724,7 +742,7 @@ class Localizer:
             out.recognised, out.reloc_aligned = recognised, reloc_aligned
         if alignment is not None:
             (out.aligned, out.align_status, out.align_steps, out.align_from, out.align_moved_t,
-             out.align_moved_r_deg, out.align_scores) = alignment
+             out.align_moved_r_deg, out.align_scores, out.align_level_steps) = alignment
             out.direct, out.direct_reason = direct, reason
         if self.map_mode:
             out.added, out.tracked = 0, N
@@ -875,7 +893,7 @@ class Localizer:
         if out.loop_old_tested < self._loop_min_rows:
             out.loop_status = "few_rows"
             return
-        c = self.map.loop_constraint(depth, self.K, est, upto, near, **self._photo_kw)
+        c = self.map.loop_constraint(depth, self.K, est, upto, near, **self._align_kw)
         if not (c.alignment.moved and c.alignment.status == "CONVERGED"):
             out.loop_status = "not_converged"
             return

@@ -124,6 +124,8 @@ ALIGN_STATE_WORDS, ALIGN_ROW_WORDS = 14, 10  # 8-byte words of its state and of 
 ALIGN_BATCH_MAX_POSES = 16  # poses one call of csrc/map_align_batch.hip aligns (gsl_map_align_batch_max_poses())
 ALIGN_MIN_USED = 7  # rows: six unknowns and one to spare, as PoseInformation.weak
 ALIGN_STATUS = ("STEPPED", "CONVERGED", "FEW", "SINGULAR", "TOO_FAR")  # GSL_MAP_ALIGN_*
+PYRAMID_MAX_LEVELS = 4  # levels above the frame one call of csrc/map_pyramid.hip builds (GSL_MAP_PYRAMID_MAX_LEVELS)
+PYRAMID_MIN_SIDE = 4  # pixels: the coarsest level is at least this wide and high
 
 
 @dataclass
@@ -206,11 +208,53 @@ class PoseAlignment:
     # final: the ``PoseInformation`` of those sums, the normal equations at c2w, present when closed
     closed: bool = False
     final: Optional[PoseInformation] = None
+    # coarse to fine (``levels=``): every field above is level 0's; level_history -- per level from the coarsest to
+    # level 0, that level's history in the format above (the last entry is ``history``); level_steps -- the steps each of
+    # them applied, in the same order.  Both None without levels
+    level_history: Optional[list] = None
+    level_steps: Optional[list] = None
 
     @property
     def moved(self) -> bool:
         """The pose is a new one: at least one step was applied and no iteration refused."""
         return self.steps > 0 and self.status in ("STEPPED", "CONVERGED")
+
+
+def pyramid_sizes(width: int, height: int, levels: int) -> list:
+    """[(W_l, H_l)] of levels 0 .. levels: every level halves the one before it, an odd last column or row dropped.
+    Refused (ValueError) for what gsl_map_pyramid refuses."""
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 1 <= int(levels) <= PYRAMID_MAX_LEVELS:
+        raise ValueError(f"levels {levels!r}: a whole number of pyramid levels, 1 .. {PYRAMID_MAX_LEVELS}")
+    levels = int(levels)
+    if (width >> levels) < PYRAMID_MIN_SIDE or (height >> levels) < PYRAMID_MIN_SIDE:
+        raise ValueError(f"levels {levels}: level {levels} of a {width} x {height} frame is {width >> levels} x "
+                         f"{height >> levels}, smaller than {PYRAMID_MIN_SIDE} x {PYRAMID_MIN_SIDE}")
+    return [(width >> l, height >> l) for l in range(levels + 1)]
+
+
+def pyramid_intrinsics(intr, levels: int) -> list:
+    """[(fx, fy, cx, cy)] of levels 0 .. levels as float32 values: pixel u lies at the integer u, the centre of a 2 x 2
+    block at 2 i + 0.5, so fx' = fx * 0.5f, cx' = (cx - 0.5f) * 0.5f (fy, cy likewise), each operation rounded once."""
+    half = np.float32(0.5)
+    out = [tuple(np.float32(a) for a in intr)]
+    for _ in range(int(levels)):
+        fx, fy, cx, cy = out[-1]
+        out.append((fx * half, fy * half, (cx - half) * half, (cy - half) * half))
+    return [tuple(float(a) for a in level) for level in out]
+
+
+@dataclass
+class FramePyramid:
+    """What ``GaussianMap.pyramid`` returns.  depths / intensities: per level 0 .. levels a float32 [H_l, W_l] tensor on
+    the map's device -- level 0 the inputs themselves, the others views into one packed buffer per image (intensities
+    None for a depth-only pyramid); sizes: (W_l, H_l) per level; keep: 1 - rho_p, the float32 value the kernel was given;
+    intrs: per level (fx, fy, cx, cy) as float32 values, when K was given (``pyramid_intrinsics``)."""
+    levels: int
+    depths: list
+    intensities: Optional[list]
+    sizes: list
+    keep: float
+    intrs: Optional[list] = None
 
 
 def apply_twist(c2w, xi) -> Tensor:
@@ -708,10 +752,36 @@ class MapConfig:
     # a row whose intensity misses the image's by more than this gives no photometric equation: an occluder, a
     # highlight or a wrong row, not a pose error
     photo_max_residual: float = 0.1
+    # Localizer(mode="map"): coarse-to-fine alignment on an image pyramid of the frame (csrc/map_pyramid.hip).  With
+    # align_levels in 1 .. 4 a frame builds the pyramid of its depth (and of its intensity image, with photo_scale) once,
+    # and every alignment of the frame -- of the start pose, of the relocalisation's candidates, of a loop constraint --
+    # runs at level align_levels first and then down to the frame itself, align_level_steps steps at the coarse levels
+    # (None: align_steps).  Every level halves the frame, and doubles the distance from which the photometric term
+    # pulls the right way: on the fine-textured wall of NOTES.md, "Image pyramid", three levels converge from 8 pixels
+    # off where one level stops converging between 2 and 4.  It goes into the calls that align (align_accept,
+    # reloc_align_top) and loop make, so one of the two has to be on.  pyramid_rho: a 2 x 2 block whose depths differ by
+    # more than this fraction of the largest gives no coarse pixel (None: the alignment's rho).  0: off, every launch,
+    # buffer and number is what it is without the field
+    align_levels: int = 0
+    align_level_steps: Optional[int] = None
+    pyramid_rho: Optional[float] = None
 
     def __post_init__(self):
         whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
         number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer))  # noqa: E731
+        if not whole(self.align_levels) or not 0 <= self.align_levels <= PYRAMID_MAX_LEVELS:
+            raise ValueError(f"align_levels {self.align_levels!r}: a whole number of pyramid levels, 0 .. "
+                             f"{PYRAMID_MAX_LEVELS}")
+        if self.align_level_steps is not None and (not whole(self.align_level_steps)
+                                                   or not 1 <= self.align_level_steps <= ALIGN_MAX_STEPS):
+            raise ValueError(f"align_level_steps {self.align_level_steps!r}: a whole number of iterations, 1 .. "
+                             f"{ALIGN_MAX_STEPS} (or None: align_steps)")
+        if self.pyramid_rho is not None and (not number(self.pyramid_rho) or not 0.0 <= self.pyramid_rho < 1.0):
+            raise ValueError(f"pyramid_rho {self.pyramid_rho!r}: a fraction of the largest depth of a block, inside "
+                             "[0, 1) (or None: the alignment's rho)")
+        if self.align_levels > 0 and not (self.align is True or self.loop is True):
+            raise ValueError("align_levels needs align=True or loop=True: the pyramid goes into the alignments that "
+                             "those options make")
         if self.photo_scale is not None and (not number(self.photo_scale)
                                              or not 0.0 <= self.photo_scale <= INFO_PHOTO_MAX_SCALE):
             raise ValueError(f"photo_scale {self.photo_scale!r}: metres per unit of intensity, inside [0, "
@@ -968,6 +1038,9 @@ class GaussianMap:
         # align_pose: one buffer of 8-byte words -- state, history, working pose, sums -- and the start pose, on first use
         self._align = None
         self._align_batch = None  # align_poses: the same for 16 poses, on first use
+        # align_pose / align_poses with levels=: that buffer and the start pose once per level, by level count, on first use
+        self._align_levels: dict = {}
+        self._align_batch_levels: dict = {}
         # origins: the index of the frame that appended each row; nothing of it without the option.  The insertions
         # since clear() and the last one's origin; the frame index of the keyframe in every slot (-1: not recorded);
         # correct's two 64-bit counters on first use
@@ -1587,6 +1660,194 @@ class GaussianMap:
         sums = self._info_launch(depth, intr, w2c, keep, beyond, float(np.float32(kappa)), float(near_plane))
         return information_from_sums(sums, min_eig)
 
+    # ---- the image pyramid of a frame, for coarse-to-fine alignment (csrc/map_pyramid.hip) ----------------------------
+    def _pyramid_launch(self, depth: Tensor, image: Optional[Tensor], levels: int, keep: float):
+        """depth [H,W] and, or None, image [H,W] float32 on the device -> (packed levels 1 .. levels of the depth, of the
+        image or None): two new buffers, one kernel, no synchronisation."""
+        assert depth.is_cuda, "GaussianMap.pyramid: the levels are made by a HIP kernel, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        n = int(lib.gsl_map_pyramid_floats(self.W, self.H, levels))
+        depth_out = torch.empty(n, device=self.device)
+        image_out = None if image is None else torch.empty(n, device=self.device)
+        _lib.check(lib.gsl_map_pyramid(ptr(depth), ptr(image), self.W, self.H, levels, keep, ptr(depth_out),
+                                       ptr(image_out), st), "gsl_map_pyramid")
+        return depth_out, image_out
+
+    def _pyramid_keep(self, rho, align_rho=None) -> float:
+        """1 - rho_p as the float32 value the kernel is given: rho, else ``pyramid_rho``, else the alignment's rho
+        (align_rho when a call resolved it, else ``align_rho``, and ``depth_rho`` when that is None)."""
+        if rho is None:
+            rho = self.cfg.pyramid_rho
+        if rho is None:
+            rho = align_rho
+        if rho is None:
+            rho = self.cfg.depth_rho if self.cfg.align_rho is None else self.cfg.align_rho
+        if not 0.0 <= rho < 1.0:
+            raise ValueError(f"rho {rho!r}: a fraction of the largest depth of a block, inside [0, 1)")
+        return float(np.float32(1.0) - np.float32(rho))
+
+    @torch.no_grad()
+    def pyramid(self, depth, levels: int, intensity=None, rho: Optional[float] = None, K=None) -> FramePyramid:
+        """The image pyramid of a frame: its depth [H,W] (metres) and, when given, its intensity image [H,W]
+        (``intensity(rgb)``) halved ``levels`` times (1 .. 4; the coarsest level at least 4 x 4).  A coarse depth is the
+        inverse of the mean inverse depth of its 2 x 2 block -- exact on a plane -- where all four are valid and within
+        ``rho`` of the largest (None: ``pyramid_rho``, and the alignment's rho when that is None), otherwise 0; a coarse
+        intensity is the mean of its block (the rule: include/gsloc_hip.h).  K: the frame's intrinsics, for
+        ``FramePyramid.intrs``.  What ``align_pose``, ``align_poses`` and ``loop_constraint`` take as ``pyramid``: build
+        it once per frame.  One kernel, no synchronisation."""
+        pyramid_sizes(self.W, self.H, levels)  # refuses what the entry point would
+        levels = int(levels)
+        keep = self._pyramid_keep(rho)
+        depth = self._depth_image(depth)
+        image = None if intensity is None else self._image(intensity, (self.H, self.W), "intensity")
+        out = self._build_pyramid(depth, image, levels, keep)
+        if K is not None:
+            out.intrs = pyramid_intrinsics(_intr_and_pose(K, torch.eye(4))[0], levels)
+        return out
+
+    def _build_pyramid(self, depth: Tensor, image: Optional[Tensor], levels: int, keep: float) -> FramePyramid:
+        """The launch and the per-level views into its two packed buffers, level 0 the inputs themselves."""
+        sizes = pyramid_sizes(self.W, self.H, levels)
+        depth_out, image_out = self._pyramid_launch(depth, image, levels, keep)
+        depths, images, at = [depth], None if image is None else [image], 0
+        for w, h in sizes[1:]:
+            depths.append(depth_out[at:at + w * h].view(h, w))
+            if image is not None:
+                images.append(image_out[at:at + w * h].view(h, w))
+            at += w * h
+        return FramePyramid(levels, depths, images, sizes, keep)
+
+    def _levels_params(self, levels, level_steps, steps: int):
+        """The ``levels`` / ``level_steps`` arguments of ``align_pose`` / ``align_poses`` with their defaults filled in
+        and checked: (levels, 0 for today's single level; the steps of a coarse level)."""
+        if levels is None:
+            levels = self.cfg.align_levels
+        if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 0 <= int(levels) <= PYRAMID_MAX_LEVELS:
+            raise ValueError(f"levels {levels!r}: a whole number of pyramid levels, 0 .. {PYRAMID_MAX_LEVELS}")
+        levels = int(levels)
+        if levels > 0:
+            pyramid_sizes(self.W, self.H, levels)
+        if level_steps is None:
+            level_steps = self.cfg.align_level_steps
+        level_steps = steps if level_steps is None else level_steps
+        if (isinstance(level_steps, bool) or not isinstance(level_steps, (int, np.integer))
+                or not 1 <= int(level_steps) <= ALIGN_MAX_STEPS):
+            raise ValueError(f"level_steps {level_steps!r}: a whole number of iterations, 1 .. {ALIGN_MAX_STEPS}")
+        return levels, int(level_steps)
+
+    def _level_frames(self, depth: Tensor, intr, photo, levels: int, pyramid: Optional[FramePyramid], keep: float) -> list:
+        """Per level from ``levels`` down to 0 what an alignment entry point is given there: (depth image, (W, H),
+        intrinsics, photo or None).  pyramid: a prebuilt one of this frame (at least ``levels`` levels, with intensities
+        when photo is given), or None: built here, one launch."""
+        if pyramid is None:
+            pyramid = self._build_pyramid(depth, None if photo is None else photo[0], levels, keep)
+        elif not isinstance(pyramid, FramePyramid) or pyramid.levels < levels or pyramid.sizes[0] != (self.W, self.H):
+            raise ValueError(f"pyramid: a FramePyramid of this map's {self.W} x {self.H} frames with at least {levels} "
+                             "levels")
+        elif photo is not None and pyramid.intensities is None:
+            raise ValueError("pyramid: it holds no intensities, and the call has a photometric term")
+        sizes, depths, images = pyramid.sizes, pyramid.depths, pyramid.intensities
+        intrs = pyramid_intrinsics(intr, levels)
+        return [(depth if l == 0 else depths[l], sizes[l], intrs[l],
+                 None if photo is None else ((photo[0] if l == 0 else images[l]), photo[1], photo[2]))
+                for l in range(levels, -1, -1)]
+
+    def _align_levels_launch(self, frames: list, w2c: Tensor, keep: float, beyond: float, kappa: float, near: float,
+                             steps: int, level_steps: int, damping: float, min_used: int, max_rot: float,
+                             max_trans: float, eps_rot: float, eps_trans: float, n_rows: Optional[int] = None) -> list:
+        """``_align_launch`` once per level of frames (``_level_frames``: coarse to fine), level_steps iterations at the
+        coarse levels and steps at level 0.  Every level has its own section of one buffer of 8-byte words, laid out as
+        ``_align_launch``'s, and its own start pose; a level's working pose is copied on the device into the next
+        level's start (the entry points forbid an overlap), and nothing is read back in between: the call's one
+        synchronisation is the read-back of the whole buffer at the end.  Returns ``_align_launch``'s tuple per level."""
+        assert frames[0][0].is_cuda, "GaussianMap.align_pose: the pose is aligned by HIP kernels, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        n_state, n_hist = ALIGN_STATE_WORDS, ALIGN_MAX_STEPS * ALIGN_ROW_WORDS
+        section, n = n_state + n_hist + 8 + INFO_VALUES, len(frames)
+        if n not in self._align_levels:
+            self._align_levels[n] = dict(words=torch.zeros(n * section, dtype=torch.int64, device=self.device),
+                                         start=torch.empty(n, 16, device=self.device))
+        a = self._align_levels[n]
+        n_rows = self.n_live if n_rows is None else int(n_rows)
+        words, start = a["words"], a["start"]
+        work = words.view(torch.float32).view(n, 2 * section)[:, 2 * (n_state + n_hist):2 * (n_state + n_hist) + 16]
+        start[0].copy_(w2c.reshape(16))
+        for j, (depth, (w, h), intr, photo) in enumerate(frames):
+            if j > 0:
+                start[j].copy_(work[j - 1])  # device to device, on the stream: the next level starts where this one stood
+            base = words.data_ptr() + 8 * j * section
+            args = (ptr(self.means), n_rows, ptr(start[j]), *intr, ptr(depth), w, h, keep, beyond, kappa, near,
+                    steps if j == n - 1 else level_steps, damping, min_used, max_rot, max_trans, eps_rot, eps_trans,
+                    base + 8 * (n_state + n_hist + 8), base + 8 * (n_state + n_hist), base, base + 8 * n_state)
+            if photo is None:
+                _lib.check(lib.gsl_map_pose_align(*args, st), "gsl_map_pose_align")
+            else:
+                _lib.check(lib.gsl_map_pose_align_photo(*args, ptr(self.colors), ptr(photo[0]), photo[1], photo[2], st),
+                           "gsl_map_pose_align_photo")
+        host = words.cpu().numpy().reshape(n, section)
+        out = []
+        for j in range(n):
+            taken = steps if j == n - 1 else level_steps
+            hist = host[j, n_state:n_state + taken * ALIGN_ROW_WORDS].reshape(taken, ALIGN_ROW_WORDS)
+            out.append((host[j, :12].view(np.float64).reshape(3, 4).copy(),
+                        host[j, n_state + n_hist:n_state + n_hist + 8].view(np.float32).reshape(4, 4).copy(),
+                        int(host[j, 12]), hist[:, :4].copy(), hist[:, 4:].copy().view(np.float64)))
+        return out
+
+    def _align_batch_levels_launch(self, frames: list, w2c: Tensor, keep: float, beyond: float, kappa: float,
+                                   near: float, steps: int, level_steps: int, damping: float, min_used: int,
+                                   max_rot: float, max_trans: float, eps_rot: float, eps_trans: float,
+                                   n_rows: Optional[int] = None) -> list:
+        """``_align_batch_launch`` once per level of frames, as ``_align_levels_launch`` does it for one pose: the k <=
+        16 working poses of a level are copied on the device into the next level's starts, one read-back at the end.
+        Returns per level ``_align_batch_launch``'s list."""
+        assert frames[0][0].is_cuda, "GaussianMap.align_poses: the poses are aligned by HIP kernels, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        cap, k, n = ALIGN_BATCH_MAX_POSES, int(w2c.shape[0]), len(frames)
+        at_state, at_hist = 0, cap * ALIGN_STATE_WORDS
+        at_work = at_hist + cap * ALIGN_MAX_STEPS * ALIGN_ROW_WORDS
+        at_sums = at_work + cap * 8
+        section = at_sums + cap * INFO_VALUES
+        if n not in self._align_batch_levels:
+            self._align_batch_levels[n] = dict(words=torch.zeros(n * section, dtype=torch.int64, device=self.device),
+                                               start=torch.empty(n, cap, 16, device=self.device))
+        a = self._align_batch_levels[n]
+        n_rows = self.n_live if n_rows is None else int(n_rows)
+        words, start = a["words"], a["start"]
+        work = words.view(torch.float32).view(n, 2 * section)[:, 2 * at_work:2 * at_work + 16 * cap].view(n, cap, 16)
+        start[0, :k].copy_(w2c.reshape(k, 16))
+        for j, (depth, (w, h), intr, photo) in enumerate(frames):
+            if j > 0:
+                start[j, :k].copy_(work[j - 1, :k])
+            base = words.data_ptr() + 8 * j * section
+            args = (ptr(self.means), n_rows, ptr(start[j]), k, *intr, ptr(depth), w, h, keep, beyond, kappa, near,
+                    steps if j == n - 1 else level_steps, damping, min_used, max_rot, max_trans, eps_rot, eps_trans,
+                    base + 8 * at_sums, base + 8 * at_work, base + 8 * at_state, base + 8 * at_hist)
+            if photo is None:
+                _lib.check(lib.gsl_map_pose_align_batch(*args, st), "gsl_map_pose_align_batch")
+            else:
+                _lib.check(lib.gsl_map_pose_align_batch_photo(*args, ptr(self.colors), ptr(photo[0]), photo[1], photo[2],
+                                                              st), "gsl_map_pose_align_batch_photo")
+        host = words.cpu().numpy().reshape(n, section)
+        out = []
+        for j in range(n):
+            taken = steps if j == n - 1 else level_steps
+            n_hist, level = taken * ALIGN_ROW_WORDS, []
+            for p in range(k):
+                state = host[j, at_state + p * ALIGN_STATE_WORDS:at_state + (p + 1) * ALIGN_STATE_WORDS]
+                hist = host[j, at_hist + p * n_hist:at_hist + (p + 1) * n_hist].reshape(taken, ALIGN_ROW_WORDS)
+                level.append((state[:12].view(np.float64).reshape(3, 4).copy(),
+                              host[j, at_work + p * 8:at_work + (p + 1) * 8].view(np.float32).reshape(4, 4).copy(),
+                              int(state[12]), int(state[13]), hist[:, :4].copy(), hist[:, 4:].copy().view(np.float64),
+                              host[j, at_sums + p * INFO_VALUES:at_sums + (p + 1) * INFO_VALUES].copy()))
+            out.append(level)
+        return out
+
+    def _history(self, hist, xis) -> list:
+        """The history's integers [steps,4] and xi [steps,6] in ``PoseAlignment.history``'s format."""
+        return [(ALIGN_STATUS[int(r[0])], int(r[1]), int(r[2]), float(r[3]) / INFO_ONE, np.array(x, dtype=np.float64))
+                for r, x in zip(hist, xis)]
+
     # ---- pose alignment: Gauss-Newton steps on those normal equations, iterated on the device (csrc/map_align.hip) ----
     def _align_launch(self, depth: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor, keep: float,
                       beyond: float, kappa: float, near: float, steps: int, damping: float, min_used: int,
@@ -1658,7 +1919,8 @@ class GaussianMap:
                    max_trans: Optional[float] = None, eps_rot_deg: Optional[float] = None,
                    eps_trans: Optional[float] = None, min_used: int = ALIGN_MIN_USED,
                    rows: Optional[int] = None, intensity=None, photo_scale: Optional[float] = None,
-                   photo_max_residual: Optional[float] = None) -> PoseAlignment:
+                   photo_max_residual: Optional[float] = None, levels: Optional[int] = None,
+                   level_steps: Optional[int] = None, pyramid: Optional[FramePyramid] = None) -> PoseAlignment:
         """The pose c2w [4,4] aligned to the map against the depth frame [H,W] (metres): up to ``steps`` (None:
         ``align_steps``) damped Gauss-Newton steps on the normal equations of ``pose_information`` -- the rows chosen
         with ``rho`` (None: ``align_rho``, and ``depth_rho`` when that is None) and ``kappa`` (None: ``info_kappa``),
@@ -1670,17 +1932,37 @@ class GaussianMap:
         settle elsewhere (NOTES.md, "Pose alignment").  rows: only the first that many rows of the map are used
         (``loop_constraint``; None: every live row).  intensity, photo_scale, photo_max_residual: as for
         ``pose_information`` -- the normal equations of every iteration then hold the photometric term
-        (gsl_map_pose_align_photo: the same launches, the sums of csrc/map_photo.hip)."""
+        (gsl_map_pose_align_photo: the same launches, the sums of csrc/map_photo.hip).  levels (None:
+        ``align_levels``): 0 is all of the above, bit for bit; 1 .. 4 aligns coarse to fine on the frame's image pyramid
+        (``pyramid``: a prebuilt one of this frame, or None: built here with ``pyramid_rho``, one more launch) -- the
+        pose is aligned at level ``levels`` first, ``level_steps`` iterations (None: ``align_level_steps``, and
+        ``steps`` when that is None), then at every level down to the frame itself, ``steps`` iterations there; every
+        level is the same entry point with that level's images, size and intrinsics, started on the device at the
+        float32 working pose the level before it left (a level that refused left it where it was), and the call keeps
+        its one read-back.  The fields of the result are level 0's; ``level_history`` and ``level_steps`` hold every
+        level's, coarse to fine."""
         rows = self._prefix(rows)
         photo = self._photo_params(intensity, photo_scale, photo_max_residual)
         (steps, keep, beyond, kappa, damping, min_used, max_rot, max_trans, eps_rot,
          eps_trans) = self._align_params(steps, rho, kappa, damping, max_rot_deg, max_trans, eps_rot_deg, eps_trans, min_used)
+        levels, level_steps = self._levels_params(levels, level_steps, steps)
+        pyramid_keep = self._pyramid_keep(None, rho) if levels > 0 else None
         depth = self._depth_image(depth)
         intr, c2w = _intr_and_pose(K, c2w)
         w2c = _world_to_camera(c2w)
         if (self.n_live if rows is None else rows) == 0:
             pose, n, hist, xis = w2c.numpy()[:3].astype(np.float64), 0, np.zeros((1, 4), np.int64), np.zeros((1, 6))
             hist[0, 0] = ALIGN_STATUS.index("FEW")
+        elif levels > 0:
+            frames = self._level_frames(depth, intr, photo, levels, pyramid, pyramid_keep)
+            per_level = self._align_levels_launch(frames, w2c.contiguous(), keep, beyond, kappa, float(near_plane), steps,
+                                                  level_steps, damping, min_used, max_rot, max_trans, eps_rot, eps_trans,
+                                                  n_rows=rows)
+            pose, _, n, hist, xis = per_level[-1]
+            out = self._alignment(pose, n, hist, xis)
+            out.level_history = [self._history(lv[3], lv[4]) for lv in per_level]
+            out.level_steps = [int(lv[2]) for lv in per_level]
+            return out
         else:
             prefix = {} if rows is None else dict(n_rows=rows)
             if photo is not None:
@@ -1695,8 +1977,7 @@ class GaussianMap:
         integers [steps,4] and xi [steps,6]; final: the information at the final pose of a closed pose."""
         w2c64 = np.eye(4)
         w2c64[:3] = pose
-        history = [(ALIGN_STATUS[int(r[0])], int(r[1]), int(r[2]), float(r[3]) / INFO_ONE, np.array(x, dtype=np.float64))
-                   for r, x in zip(hist, xis)]
+        history = self._history(hist, xis)
         aligned = torch.from_numpy(np.linalg.inv(w2c64).astype(np.float32)).to(self.device)
         return PoseAlignment(aligned, w2c64, history[-1][0], int(n), history[-1][1], history[-1][2], history,
                              closed=final is not None, final=final)
@@ -1749,7 +2030,8 @@ class GaussianMap:
                     max_trans: Optional[float] = None, eps_rot_deg: Optional[float] = None,
                     eps_trans: Optional[float] = None, min_used: int = ALIGN_MIN_USED,
                     rows: Optional[int] = None, intensity=None, photo_scale: Optional[float] = None,
-                    photo_max_residual: Optional[float] = None) -> list:
+                    photo_max_residual: Optional[float] = None, levels: Optional[int] = None,
+                    level_steps: Optional[int] = None, pyramid: Optional[FramePyramid] = None) -> list:
         """``align_pose`` for each of the poses c2ws [k,4,4] (a tensor, or a sequence of [4,4] poses) against the same
         frame, with the same keyword arguments and defaults: one call of 1 + 3 ``steps`` launches and one read-back for
         up to 16 poses (more go in chunks of 16).  Pose, status, steps and history of every ``PoseAlignment`` are bit
@@ -1758,11 +2040,15 @@ class GaussianMap:
         (with ``info_min_eig``) -- what ``pose_information`` gives at c2w, without another launch.  A pose that
         converges on the last iteration is not closed.  An empty map gives status FEW, not closed, without a launch.
         intensity, photo_scale, photo_max_residual: as for ``align_pose`` (gsl_map_pose_align_batch_photo); ``final``
-        then holds geometry plus colour, without the photometric counts (``photo_used`` stays 0)."""
+        then holds geometry plus colour, without the photometric counts (``photo_used`` stays 0).  levels,
+        level_steps, pyramid: as for ``align_pose``, every level one batched call for all the poses (the pyramid is the
+        frame's: built once); ``closed`` and ``final`` are level 0's."""
         rows = self._prefix(rows)
         photo = self._photo_params(intensity, photo_scale, photo_max_residual)
         (steps, keep, beyond, kappa, damping, min_used, max_rot, max_trans, eps_rot,
          eps_trans) = self._align_params(steps, rho, kappa, damping, max_rot_deg, max_trans, eps_rot_deg, eps_trans, min_used)
+        levels, level_steps = self._levels_params(levels, level_steps, steps)
+        pyramid_keep = self._pyramid_keep(None, rho) if levels > 0 else None
         poses = [torch.as_tensor(c) for c in c2ws]
         for c in poses:
             if c.shape != (4, 4):
@@ -1781,8 +2067,19 @@ class GaussianMap:
         if photo is not None:
             prefix["photo"] = photo
         out = []
+        frames = None if levels == 0 else self._level_frames(depth, intr, photo, levels, pyramid, pyramid_keep)
         for at in range(0, len(poses), ALIGN_BATCH_MAX_POSES):
             chunk = w2c[at:at + ALIGN_BATCH_MAX_POSES].contiguous()
+            if frames is not None:
+                per_level = self._align_batch_levels_launch(frames, chunk, keep, beyond, kappa, float(near_plane), steps,
+                                                            level_steps, damping, min_used, max_rot, max_trans, eps_rot,
+                                                            eps_trans, n_rows=rows)
+                for p, (pose, _, n, done, hist, xis, sums) in enumerate(per_level[-1]):
+                    al = self._alignment(pose, n, hist, xis, information_from_sums(sums, min_eig) if done == 2 else None)
+                    al.level_history = [self._history(lv[p][4], lv[p][5]) for lv in per_level]
+                    al.level_steps = [int(lv[p][2]) for lv in per_level]
+                    out.append(al)
+                continue
             for pose, _, n, done, hist, xis, sums in self._align_batch_launch(
                     depth, intr, chunk, keep, beyond, kappa, float(near_plane), steps, damping, min_used, max_rot,
                     max_trans, eps_rot, eps_trans, **prefix):
@@ -1856,7 +2153,8 @@ class GaussianMap:
         prefix.  Changes nothing in the map.  Whether to trust the result, and what to do with it
         (``spread_correction``, ``correct``), is the caller's decision.  ``intensity``, ``photo_scale`` and
         ``photo_max_residual`` among ``align`` go to ``align_pose``: a constraint measured on a textured wall is then
-        closed in the wall's plane as well.  The scores stay depth only."""
+        closed in the wall's plane as well; ``levels``, ``level_steps`` and ``pyramid`` go there too (coarse to fine, a
+        constraint at a drifted estimate has the wider basin).  The scores stay depth only."""
         n = self.rows_up_to(upto_frame)
         al = self.align_pose(depth, K, c2w, near_plane, rows=n, **align)
         scores = self.score_poses(depth, K, [torch.as_tensor(c2w).detach().cpu(), al.c2w.detach().cpu()], near_plane,

@@ -516,6 +516,31 @@ int gsl_map_pose_align_batch_photo(const float* means, int64_t n_rows, const flo
                                    int64_t* sums, float* work, void* state, void* history, const float* colors,
                                    const float* intensity, float photo_scale, float photo_max_residual, void* stream);
 
+/* ---- the image pyramid of a frame, for coarse-to-fine alignment (csrc/map_pyramid.hip) ----
+ * Level 0 is the frame, depth[height,width] and, when given, intensity[height,width] float32 on the device.  Level l + 1
+ * has W' = W / 2, H' = H / 2 (integer division: an odd last column or row is dropped); its pixel (i, j) is made from
+ * a, b, c, e = X[2j, 2i], X[2j, 2i+1], X[2j+1, 2i], X[2j+1, 2i+1] of level l, float32, one rounding per operation in the
+ * order written, no contraction, correctly rounded division, comparisons false for a NaN:
+ *   depth:     valid = each of the four > 0 and < inf, and max * keep <= min;
+ *              inv = ((1/a + 1/b) + (1/c + 1/e)) * 0.25f;  d' = 1 / inv where valid, otherwise 0;
+ *   intensity: Y' = ((a + b) + (c + e)) * 0.25f, unconditionally.
+ * The intrinsics of level l + 1 are the caller's, in float32: fx' = fx * 0.5f, fy' = fy * 0.5f, cx' = (cx - 0.5f) *
+ * 0.5f, cy' = (cy - 0.5f) * 0.5f (pixel u lies at the integer u, the centre of a block at 2i + 0.5).
+ * gsl_map_pyramid_floats: the floats of levels 1 .. levels packed one after another, each row-major; 0 for arguments
+ *   gsl_map_pyramid refuses.
+ * gsl_map_pyramid: depth_out and, with an intensity, intensity_out hold that many floats on the device, not initialised,
+ *   overlapping nothing; every one of them is written exactly once and nothing else is.  One kernel, a workgroup per 32 x
+ *   32 tile of level 0; no zeroing launch, no atomics, no allocation, no synchronisation.  intensity and intensity_out
+ *   are both NULL (depth only) or both given.  Returns GSL_ERR_BAD_ARG before the launch for a NULL depth or depth_out,
+ *   one of the intensity pair without the other, width or height <= 0 or width * height > 2^31 - 1, levels outside 1 ..
+ *   GSL_MAP_PYRAMID_MAX_LEVELS, keep not in (0, 1], a coarsest level smaller than 4 x 4.
+ * Nothing changes in gsl_map_pose_info* and gsl_map_pose_align*: they take width, height, the intrinsics and the images
+ * per call, and a level is another call. */
+#define GSL_MAP_PYRAMID_MAX_LEVELS 4
+int64_t gsl_map_pyramid_floats(int width, int height, int levels);
+int gsl_map_pyramid(const float* depth, const float* intensity, int width, int height, int levels, float keep,
+                    float* depth_out, float* intensity_out, void* stream);
+
 /* ---- place recognition: a 16 x 12 descriptor of a depth frame, and its match against keyframes (csrc/map_place.hip) ----
  * gsl_map_place_describe: depth[height,width] float32 on the device, row-major, metres; desc[192] int32 on the device,
  * row-major over GSL_MAP_PLACE_GH lines of GSL_MAP_PLACE_GW cells (gsl_map_place_cells() = 192).  It need not be
