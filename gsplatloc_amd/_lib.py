@@ -91,6 +91,11 @@ _SIGNATURES = {
                                                c_double, c_double, c_double, P, P, P, P, P, P, c_float, c_float, P]),
     "gsl_map_pyramid_floats": (c_int64, [c_int, c_int, c_int]),
     "gsl_map_pyramid": (c_int, [P, P, c_int, c_int, c_int, c_float, P, P, P]),
+    "gsl_map_exposure_values": (c_int, []),
+    "gsl_map_exposure_estimate": (c_int, [P, P, c_int64, P, c_float, c_float, c_float, c_float, P, P, c_int, c_int,
+                                          c_float, c_float, c_float, c_float, c_float, c_float, c_int, c_int, c_double,
+                                          c_double, c_double, c_double, P, P, P, P]),
+    "gsl_map_exposure_apply": (c_int, [P, c_int, c_int, P, P, P]),
     "gsl_map_place_cells": (c_int, []),
     "gsl_map_place_describe": (c_int, [P, c_int, c_int, P, P]),
     "gsl_map_place_match": (c_int, [P, P, c_int, P, P]),

@@ -48,7 +48,7 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
                   map_view_occlusion: Optional[float] = None, map_view_occlusion_cell: Optional[int] = None,
                   map_view_occlusion_window: Optional[int] = None, map_photo_scale: Optional[float] = None,
                   map_photo_max_residual: Optional[float] = None, map_align_levels: Optional[int] = None,
-                  map_align_level_steps: Optional[int] = None) -> Dict:
+                  map_align_level_steps: Optional[int] = None, map_photo_exposure: bool = False) -> Dict:
     """Runner.train (gs_trainer_total.py:45-282): frames 0..min(len, 1998).  profile=True: also the wall time per phase
     of a frame (synchronising at the phase boundaries): reading + back-projection + PCA normalisation, the query-depth
     render, the kNN scale initialisation, load_frame (copies + calibration pass), and the optimisation itself (graph
@@ -78,7 +78,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     ``map_view_occlusion_window`` for MapConfig.view_occlusion_cell_px / view_occlusion_window where not None;
     ``map_photo_scale``: MapConfig.photo_scale, the normal equations of map_info, map_align and map_loop gain a
     photometric term from the rows' colours against the frame's image, with ``map_photo_max_residual`` for
-    MapConfig.photo_max_residual where not None; ``map_align_levels``: MapConfig.align_levels, the alignments of
+    MapConfig.photo_max_residual where not None, and ``map_photo_exposure`` for MapConfig.photo_exposure (every frame's
+    gain and offset are estimated against the map and its image corrected; the report gains exposure_per_frame); ``map_align_levels``: MapConfig.align_levels, the alignments of
     map_align and map_loop run coarse to fine on an image pyramid of the frame, with ``map_align_level_steps`` for
     MapConfig.align_level_steps where not None)."""
     cfg = TrackerConfig(max_steps=num_iters, rgb_lambda=rgb_lambda, ssim_lambda=ssim_lambda)
@@ -129,6 +130,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
         raise ValueError("map_photo_max_residual: an option of map_photo_scale")
     if map_photo_scale is not None and not (map_info or map_align or map_loop):
         raise ValueError("map_photo_scale: the photometric term of map_info, map_align or map_loop -- one of them")
+    if map_photo_exposure and map_photo_scale is None:
+        raise ValueError("map_photo_exposure: an option of map_photo_scale")
     if (map_align_levels is not None or map_align_level_steps is not None) and not map_mode:
         raise ValueError("map_align_levels belongs to the map mode (map_mode=True)")
     if map_align_level_steps is not None and map_align_levels is None:
@@ -142,7 +145,8 @@ def evaluate_room(parser: Parser, num_iters: int = 2000, max_frames: Optional[in
     photo_term = None
     if map_photo_scale is not None:
         photo_term = dict(photo_scale=map_photo_scale, **({} if map_photo_max_residual is None else
-                                                          {"photo_max_residual": map_photo_max_residual}))
+                                                          {"photo_max_residual": map_photo_max_residual}),
+                          **({"photo_exposure": True} if map_photo_exposure else {}))
     loop = None
     if map_loop:
         loop = dict(loop=True, **({} if map_loop_min_gap is None else {"loop_min_gap": map_loop_min_gap}))
@@ -299,6 +303,7 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
     level_steps = []
     direct, direct_reason, reloc_aligned = [], [], []
     ordered = True
+    exposures = []
     loop_status, closures, anchors, gts = [], [], [], [pose]
     for i in range(1, n + 1):
         depth, rgb, pose = parser.frame(i)
@@ -320,6 +325,10 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             shares.append(r.agree / (r.agree + r.front) if r.agree + r.front > 0 else None)
         if map_keyframes:
             recognised += int(r.recognised >= 0)
+        if map_photo and map_photo.get("photo_exposure"):
+            exposures.append((r.exposure_gain, r.exposure_offset, r.exposure_status, r.exposure_used))
+            print(f"frame {i}: exposure: gain {r.exposure_gain:.5f} offset {r.exposure_offset:.5f} {r.exposure_status} "
+                  f"rows used {r.exposure_used}")
         if map_info:
             sigma_t.append(r.sigma_t)
             sigma_r.append(r.sigma_r)
@@ -388,7 +397,8 @@ def evaluate_sequential(parser: Parser, cfg: TrackerConfig, max_frames: Optional
             **({"info": True, "sigma_t_per_frame": sigma_t, "sigma_r_per_frame": sigma_r,
                 "info_used_per_frame": info_used, "info_min_eig_per_frame": info_eig, "weak_frames": weak}
                if map_info else {}),
-            **({**map_photo, **({"info_photo_used_per_frame": photo_used} if map_info else {})} if map_photo else {}),
+            **({**map_photo, **({"info_photo_used_per_frame": photo_used} if map_info else {}),
+                **({"exposure_per_frame": exposures} if map_photo.get("photo_exposure") else {})} if map_photo else {}),
             **({**map_pyramid, **({"align_level_steps_per_frame": level_steps} if map_align else {})}
                if map_pyramid else {}),
             **({"align": True, "aligned_per_frame": aligned, "align_steps_per_frame": align_steps,
@@ -514,6 +524,10 @@ def main(argv=None):
     ap.add_argument("--map-photo-max-residual", type=float, default=None, metavar="R",
                     help="--map-photo-scale: a point whose intensity misses the image's by more than R gives no "
                          "photometric equation (0 .. 1, default 0.1)")
+    ap.add_argument("--map-photo-exposure", action="store_true",
+                    help="--map-photo-scale: exposure compensation -- every frame's gain and offset are estimated against "
+                         "the map and its image is corrected before the photometric term, the refinement and the "
+                         "insertion read it (default: every frame is taken to have the first frame's exposure)")
     ap.add_argument("--map-align-levels", type=int, default=None, metavar="L",
                     help="--map-align / --map-loop: coarse-to-fine alignment -- every frame builds an image pyramid of L "
                          "levels (1 .. 4) once, and its alignments start at the coarsest level: every level doubles the "
@@ -578,6 +592,8 @@ def main(argv=None):
         ap.error("--map-photo-scale needs --map-info, --map-align or --map-loop")
     if a.map_photo_max_residual is not None and a.map_photo_scale is None:
         ap.error("--map-photo-max-residual needs --map-photo-scale")
+    if a.map_photo_exposure and a.map_photo_scale is None:
+        ap.error("--map-photo-exposure needs --map-photo-scale")
     if a.map_align_levels is not None and not (a.map_align or a.map_loop):
         ap.error("--map-align-levels needs --map-align or --map-loop")
     if a.map_align_level_steps is not None and a.map_align_levels is None:
@@ -601,6 +617,7 @@ def main(argv=None):
                           map_view_occlusion_cell=a.map_view_occlusion_cell,
                           map_view_occlusion_window=a.map_view_occlusion_window,
                           map_photo_scale=a.map_photo_scale, map_photo_max_residual=a.map_photo_max_residual,
+                          map_photo_exposure=a.map_photo_exposure,
                           map_align_levels=a.map_align_levels, map_align_level_steps=a.map_align_level_steps)
         out[room] = {"gsplatloc_amd": r}
         print(room, json.dumps(r))

@@ -148,6 +148,14 @@ class LocalizeResult:
     # info with MapConfig.photo_scale: the rows among info_used that also gave a photometric equation (cov, sigma_t,
     # sigma_r, info_min_eig and weak are then those of geometry plus colour)
     info_photo_used: Optional[int] = None
+    # MapConfig.photo_exposure: the exposure correction that the frame's image entered the map with -- gain * rgb + 255 *
+    # offset, estimated against the map at the frame's final estimate (a lost frame: at its start pose, and nothing
+    # entered the map); exposure_status: ``Exposure.status`` -- anything but "OK" is no estimate, and the frame went in
+    # as it was: gain 1, offset 0; exposure_used: the rows of the last pass
+    exposure_gain: Optional[float] = None
+    exposure_offset: Optional[float] = None
+    exposure_status: Optional[str] = None
+    exposure_used: Optional[int] = None
     # align: aligned -- the start pose the map's Gauss-Newton steps gave was taken (init_c2w is then that pose; False:
     # the alignment refused, or the map scored its pose worse than the motion model's, and the frame ran from that);
     # align_status / align_steps: ``PoseAlignment.status`` / ``steps``; align_from: the motion model's pose [4,4];
@@ -346,6 +354,16 @@ class Localizer:
     candidates, of a loop constraint -- runs coarse to fine on it; ``LocalizeResult.align_level_steps`` holds the steps
     per level.  With the field at None every launch, buffer
     and number is as without it.
+    ``map_config.photo_exposure`` (with ``photo_scale``): before any of that ``track`` estimates the frame's gain and
+    offset against the map at its start pose (``GaussianMap.estimate_exposure``) and corrects the image
+    (``apply_exposure``); the intensity image and the pyramid are made from the corrected image.  With ``align``, when
+    the aligned start is taken the exposure is estimated once more there, and where that changes the pair the images
+    are made again and the alignment is repeated from the aligned pose (``_realigned``).  For a frame that is
+    not lost, before anything of it enters the map, the RAW image is corrected once more with an estimate at the
+    frame's final pose: that image is what ``refine`` and ``insert_frame`` receive, and the estimate is what
+    ``LocalizeResult.exposure_gain`` / ``exposure_offset`` / ``exposure_status`` / ``exposure_used`` report.  An
+    estimate that is not OK corrects nothing.  The splat tracker's own pair keeps the raw image.  Off: every launch,
+    buffer and number is as without the field.
     ``map_config.origins``: every appended pose is recorded with its odometry measurement, the float64 relative pose to
     the pose before it as it was appended (``reset`` clears the record, ``correct_trajectory`` leaves it alone), which
     is what ``add_loop`` builds its pose graph on.  ``map_config.loop``: for a frame that is not lost, before the pose
@@ -395,6 +413,7 @@ class Localizer:
         self._photo_scale = None  # MapConfig.photo_scale
         self._photo_kw: dict = {}  # with it, inside track(): intensity=<the frame's intensity image>, for the map's calls
         self._align_levels = 0  # MapConfig.align_levels
+        self._exposure = False  # MapConfig.photo_exposure
         # inside track(): _photo_kw and, with align_levels, levels= and pyramid=<the frame's>, for the map's alignments
         self._align_kw: dict = {}
         self._origins = False  # MapConfig.origins
@@ -421,6 +440,7 @@ class Localizer:
             self._align = bool(map_config.align)
             self._photo_scale = map_config.photo_scale
             self._align_levels = int(map_config.align_levels)
+            self._exposure = bool(map_config.photo_exposure)
             if map_config.align_accept:
                 self._accept = (
                     (self.W * self.H) // 16 if map_config.align_accept_min_used is None else map_config.align_accept_min_used,
@@ -562,6 +582,42 @@ class Localizer:
         reason = None if self._accept is None else self._direct_reason(al, taken)
         return (taken, al.status, al.steps, init, moved_t, moved_r, scores, al.level_steps), (to if taken else init), reason
 
+    def _frame_images(self, depth: Tensor, rgb: Optional[Tensor]) -> None:
+        """What the map's calls of this frame read: the intensity image of rgb (None: no photometric term) and, with
+        ``align_levels``, the frame's pyramid, every alignment of the frame starts at its coarsest level."""
+        self._photo_kw = {} if rgb is None else dict(intensity=self.map.intensity(rgb))
+        self._align_kw = self._photo_kw
+        if self._align_levels > 0:
+            self._align_kw = dict(self._photo_kw, levels=self._align_levels, pyramid=self.map.pyramid(
+                depth, self._align_levels, intensity=self._photo_kw.get("intensity")))
+
+    def _realigned(self, depth: Tensor, rgb: Tensor, exposure, alignment, init: Tensor, reason):
+        """photo_exposure, after an aligned start was taken: the exposure is estimated once more, at the aligned pose.
+        The estimate reads every row's NEAREST pixel, so it depends on the pose through which pixel a row rounds to: a
+        start a fraction of a pixel off makes the frame's intensity a noisy regressor and the gain comes out 0.15 ..
+        0.25 % low, which costs the alignment a factor of three (NOTES.md, "Exposure compensation").  Where the second
+        estimate is OK and another pair than the first, the frame's images are made again from it and the alignment is
+        repeated from the aligned pose; its verdict (taken or not, ``align_accept``'s reason) is the frame's, the
+        steps add up, and ``align_from`` / ``align_moved_*`` stay relative to the motion model's pose.  Returns
+        (exposure, the ``_aligned_start`` fields, the pose to start from, the reason)."""
+        again, seen = self._corrected(depth, rgb, init)
+        if not again.ok or (exposure.ok and (again.gain, again.offset) == (exposure.gain, exposure.offset)):
+            return exposure, alignment, init, reason
+        self._frame_images(depth, seen)
+        second, to, why = self._aligned_start(depth, init)
+        start = alignment[3]
+        moved_t, moved_r = float(calculate_translation_error(to, start)), float(calculate_rotation_error(to, start))
+        levels = None if second[7] is None else [a + b for a, b in zip(alignment[7], second[7])]
+        fields = (True, second[1], alignment[2] + second[2], start, moved_t, moved_r,
+                  alignment[6] if second[6] is None else second[6], levels)
+        return again, fields, to, why
+
+    def _corrected(self, depth: Tensor, rgb: Tensor, c2w: Tensor):
+        """(the ``Exposure`` of the raw image rgb against the map at c2w, the image it corrects to: rgb itself when the
+        estimate is not OK)."""
+        exposure = self.map.estimate_exposure(depth, self.K, c2w, self.cfg.gs.near_plane, rgb=rgb)
+        return exposure, self.map.apply_exposure(rgb) if exposure.ok else rgb
+
     @staticmethod
     def _report_information(out: LocalizeResult, info) -> None:
         """The fields of a frame's result that ``MapConfig.info`` fills, from its ``PoseInformation``."""
@@ -667,12 +723,16 @@ class Localizer:
                              "needs every frame's image (rgb=)")
         depth, rgb, pts, col = self._frame(depth, rgb)
         # the frame's intensity image, once: every alignment, loop constraint and pose information of the frame reads it
-        self._photo_kw = {} if self._photo_scale is None else dict(intensity=self.map.intensity(rgb))
-        self._align_kw = self._photo_kw
-        if self._align_levels > 0:
-            # the frame's pyramid, once: every alignment of the frame starts at its coarsest level
-            self._align_kw = dict(self._photo_kw, levels=self._align_levels, pyramid=self.map.pyramid(
-                depth, self._align_levels, intensity=self._photo_kw.get("intensity")))
+        exposure = None
+        if self._exposure and self.map.n_live > 0:
+            # the frame's exposure against the map, at the pose the frame starts from: what every alignment, loop
+            # constraint and pose information of the frame reads is the corrected image's intensity
+            start = self._poses[-1] if self.motion == "hold" or len(self._poses) < 2 else predict_pose(
+                self._poses[-2], self._poses[-1])
+            exposure, seen = self._corrected(depth, rgb, start)
+            self._frame_images(depth, seen)
+        else:
+            self._frame_images(depth, None if self._photo_scale is None else rgb)
         placed = self._poses[-1]
         if self.motion == "hold" or len(self._poses) < 2:
             init = placed
@@ -686,6 +746,8 @@ class Localizer:
                 raise RuntimeError("Localizer.track: the map is empty (the first frame had no valid depth)")
             if self._align:
                 alignment, init, reason = self._aligned_start(depth, init)
+                if exposure is not None and alignment[0]:
+                    exposure, alignment, init, reason = self._realigned(depth, rgb, exposure, alignment, init, reason)
                 direct = None if self._accept is None else reason is None
             frame = (pts, col, depth, rgb, placed, gt if gt is not None else init)
             d = self._map_pair(init, frame)
@@ -767,6 +829,10 @@ class Localizer:
                     self._report_information(out, info)
                     if self._photo_scale is not None:
                         out.info_photo_used = info.photo_used
+                if self._exposure:
+                    # before anything of the frame enters the map: the raw image, corrected by the estimate at the
+                    # frame's final pose -- the map stays in the exposure of its first frame
+                    exposure, rgb = self._corrected(depth, rgb, est)
                 at = best
                 if out.loop:
                     # the rows have moved and the estimate with them: the insertion render is made from a new pair at
@@ -807,6 +873,10 @@ class Localizer:
                     # after the frame is done: the descriptor reads the depth image only, nothing above depends on it
                     out.keyframe = self.map.add_keyframe(depth, est, **index)
             out.map_size = self.map.n_live
+            if exposure is not None:
+                ok = exposure.ok
+                out.exposure_gain, out.exposure_offset = (exposure.gain, exposure.offset) if ok else (1.0, 0.0)
+                out.exposure_status, out.exposure_used = exposure.status, exposure.used
         if gt is not None:
             out.eT, out.eR = calculate_translation_error(est, gt), calculate_rotation_error(est, gt)
         return out

@@ -77,6 +77,12 @@ wall leaves three moves of the camera open.  With an ``intensity`` image of the 
 integers; the step kernels and everything on the host read them as before.  Three more entry points, the launch
 sequences of their twins; without an image the calls are exactly what they were.
 
+Exposure compensation (``MapConfig.photo_exposure``, csrc/map_exposure.hip): that term compares a row's stored colour
+with the frame's intensity as if every frame had one exposure.  ``estimate_exposure`` fits gain * Y_frame + offset to
+the colours of the rows the frame sees -- fixed-point sums over the rows and a one-thread float64 solve, a fixed
+sequence of launches with one read-back -- and ``apply_exposure`` corrects the frame's rgb with it on the device; the
+corrected image is what every consumer above receives.  Two more entry points; nothing else changes.
+
 Trajectory correction (``MapConfig.origins``, csrc/map_correct.hip): a row is written into the world once, at the
 estimate of the frame that saw it.  With the option every row carries the index of that frame (``origins``), and
 ``correct`` moves the rows of every frame by that frame's rigid transform -- the one that takes its old pose to its
@@ -126,6 +132,9 @@ ALIGN_MIN_USED = 7  # rows: six unknowns and one to spare, as PoseInformation.we
 ALIGN_STATUS = ("STEPPED", "CONVERGED", "FEW", "SINGULAR", "TOO_FAR")  # GSL_MAP_ALIGN_*
 PYRAMID_MAX_LEVELS = 4  # levels above the frame one call of csrc/map_pyramid.hip builds (GSL_MAP_PYRAMID_MAX_LEVELS)
 PYRAMID_MIN_SIDE = 4  # pixels: the coarsest level is at least this wide and high
+EXPOSURE_VALUES, EXPOSURE_RECORD_WORDS = 7, 6  # int64 sums and 8-byte words per pass of csrc/map_exposure.hip
+EXPOSURE_MAX_PASSES = 4  # passes one call of it runs at the most (GSL_MAP_EXPOSURE_MAX_PASSES)
+EXPOSURE_STATUS = ("OK", "FEW", "FLAT", "RANGE")  # GSL_MAP_EXPOSURE_*
 
 
 @dataclass
@@ -255,6 +264,29 @@ class FramePyramid:
     sizes: list
     keep: float
     intrs: Optional[list] = None
+
+
+@dataclass
+class Exposure:
+    """The affine brightness model of a frame against the map (``GaussianMap.estimate_exposure``): gain * Y_frame + offset
+    ~ Y_row over the rows the frame sees, the float32 pair the device holds and ``apply_exposure`` applies.  status: of
+    the last pass -- "OK", "FEW" (fewer rows used than ``exposure_min_used``), "FLAT" (the variance of the frame's
+    intensities over them is not above ``exposure_min_var``: a constant image says nothing about gain) or "RANGE" (the
+    solution lies outside ``exposure_gain`` / ``exposure_max_offset``).  A pass that is not OK leaves the pair as the
+    pass before left it (the identity, if it was the first) and ends the estimate: only an OK estimate is a correction
+    to apply.  used, seen: the rows of the last pass; rss: its residual sum of squares, in squared intensity;
+    history: per pass (status, used, seen, g, b, rss) with the float64 solution."""
+    gain: float
+    offset: float
+    status: str
+    used: int = 0
+    seen: int = 0
+    rss: float = 0.0
+    history: Optional[list] = None
+
+    @property
+    def ok(self) -> bool:
+        return self.status == "OK"
 
 
 def apply_twist(c2w, xi) -> Tensor:
@@ -765,10 +797,54 @@ class MapConfig:
     align_levels: int = 0
     align_level_steps: Optional[int] = None
     pyramid_rho: Optional[float] = None
+    # Localizer(mode="map"), with photo_scale: exposure compensation (csrc/map_exposure.hip).  The photometric term
+    # holds a row's colour against the frame's intensity as if every frame had the exposure of the first.  With the
+    # option a frame's gain and offset, gain * Y_frame + offset ~ Y_row, are estimated against the rows it sees
+    # (GaussianMap.estimate_exposure) at its start pose, its rgb is corrected (apply_exposure) and the intensity image,
+    # the pyramid and every alignment, pose information and loop constraint of the frame are made from the corrected
+    # image; before anything of the frame enters the map the raw image is corrected once more, with the estimate at the
+    # frame's final pose, for refine and insert_frame: the map stays in the exposure of its first frame.
+    # exposure_passes: 1 .. 4 least-squares passes; from the second on a row whose corrected intensity misses its
+    # colour by more than exposure_max_residual is left out.  exposure_rho: a row is seen when its depth is within this
+    # fraction of its pixel's (None: align_rho, or 0.05 when that is None).  exposure_saturation: intensities outside
+    # this range, of the frame or of the row, are clipped and follow no affine model.  Fewer than exposure_min_used rows,
+    # a variance of the frame's intensities not above exposure_min_var, or a solution outside exposure_gain /
+    # exposure_max_offset is no estimate: the frame stays as it is and says so.  False: every launch, buffer and number
+    # is what it is without the field
+    photo_exposure: bool = False
+    exposure_passes: int = 2
+    exposure_rho: Optional[float] = None
+    exposure_max_residual: float = 0.1
+    exposure_saturation: Tuple[float, float] = (0.02, 0.98)
+    exposure_min_used: int = 256
+    exposure_gain: Tuple[float, float] = (0.5, 2.0)
+    exposure_max_offset: float = 0.25
+    exposure_min_var: float = 1e-4
 
     def __post_init__(self):
         whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
         number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer))  # noqa: E731
+        if not isinstance(self.photo_exposure, bool):
+            raise ValueError(f"photo_exposure {self.photo_exposure!r}: True or False")
+        if self.photo_exposure and self.photo_scale is None:
+            raise ValueError("photo_exposure=True needs photo_scale: the exposure is compensated for the photometric term")
+        if not whole(self.exposure_passes) or not 1 <= self.exposure_passes <= EXPOSURE_MAX_PASSES:
+            raise ValueError(f"exposure_passes {self.exposure_passes!r}: a whole number of passes, 1 .. "
+                             f"{EXPOSURE_MAX_PASSES}")
+        if self.exposure_rho is not None and (not number(self.exposure_rho) or not 0.0 <= self.exposure_rho < 1.0):
+            raise ValueError(f"exposure_rho {self.exposure_rho!r}: a fraction of the observed depth, inside [0, 1) (or "
+                             "None: align_rho, or 0.05)")
+        if not number(self.exposure_max_residual) or not 0.0 <= self.exposure_max_residual <= 1.0:
+            raise ValueError(f"exposure_max_residual {self.exposure_max_residual!r}: an intensity difference, inside "
+                             "[0, 1]")
+        _exposure_pair(self.exposure_saturation, "exposure_saturation")
+        _exposure_pair(self.exposure_gain, "exposure_gain")
+        if not whole(self.exposure_min_used) or self.exposure_min_used < 1:
+            raise ValueError(f"exposure_min_used {self.exposure_min_used!r}: a whole number of rows, at least 1")
+        for name in ("exposure_max_offset", "exposure_min_var"):
+            v = getattr(self, name)
+            if not number(v) or not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"{name} {v!r}: finite and not negative")
         if not whole(self.align_levels) or not 0 <= self.align_levels <= PYRAMID_MAX_LEVELS:
             raise ValueError(f"align_levels {self.align_levels!r}: a whole number of pyramid levels, 0 .. "
                              f"{PYRAMID_MAX_LEVELS}")
@@ -956,6 +1032,21 @@ class MapConfig:
             raise ValueError(f"view_occlusion_window {self.view_occlusion_window!r}: a whole number of cells, 0 .. 3")
 
 
+def _exposure_pair(v, name: str) -> Tuple[float, float]:
+    """``exposure_saturation`` (0 <= lo < hi <= 1) or ``exposure_gain`` (0 < lo <= 1 <= hi < inf) as two floats, refused
+    otherwise."""
+    number = lambda a: not isinstance(a, bool) and isinstance(a, (int, float, np.floating, np.integer))  # noqa: E731
+    ok = isinstance(v, (tuple, list)) and len(v) == 2 and number(v[0]) and number(v[1])
+    if ok and name == "exposure_saturation":
+        ok = 0.0 <= v[0] < v[1] <= 1.0
+    elif ok:
+        ok = 0.0 < v[0] <= 1.0 <= v[1] < math.inf
+    if not ok:
+        what = "0 <= lo < hi <= 1, intensities" if name == "exposure_saturation" else "0 < lo <= 1 <= hi < inf, gains"
+        raise ValueError(f"{name} {v!r}: a pair (lo, hi), {what}")
+    return float(v[0]), float(v[1])
+
+
 def _intr_and_pose(K, c2w) -> Tuple[Tuple[float, float, float, float], Tensor]:
     """K [3,3] -> (fx, fy, cx, cy); c2w -> a tensor (dtype and device as given), refused unless it is [4,4]."""
     Kc = torch.as_tensor(K, dtype=torch.float32).cpu()
@@ -1052,6 +1143,8 @@ class GaussianMap:
         self._correct_counters = None
         # covisibility: its buffer and the pose on first use; the rows the last call found outside its table
         self._covis = None
+        # estimate_exposure / apply_exposure: one buffer of 8-byte words -- record, sums, params -- and the pose, on first use
+        self._exposure = None
         self.last_covis_outside = 0
 
     def _alloc_ws(self):
@@ -1716,6 +1809,130 @@ class GaussianMap:
                 images.append(image_out[at:at + w * h].view(h, w))
             at += w * h
         return FramePyramid(levels, depths, images, sizes, keep)
+
+    # ---- exposure compensation: an affine brightness model of a frame against the map (csrc/map_exposure.hip) ---------
+    def _exposure_buffers(self):
+        """words int64: record [4][6], sums [7], then params as four float32 in two words; the start pose."""
+        if self._exposure is None:
+            n = EXPOSURE_MAX_PASSES * EXPOSURE_RECORD_WORDS + EXPOSURE_VALUES + 2
+            self._exposure = dict(words=torch.zeros(n, dtype=torch.int64, device=self.device),
+                                  w2c=torch.empty(16, device=self.device))
+            self._exposure["params"] = self._exposure["words"][n - 2:].view(torch.float32)
+            self._exposure["params"].copy_(torch.tensor([1.0, 0.0, 0.0, 0.0]))
+        return self._exposure
+
+    def _exposure_params(self, rho, max_residual, saturation, passes, min_used, gain, max_offset, min_var):
+        """The keyword arguments of ``estimate_exposure`` with the configuration's values where None is given, checked, in
+        the units of the entry point: (keep, beyond, sat_lo, sat_hi, max_residual, passes, min_used, gain_min, gain_max,
+        offset_max, min_var)."""
+        cfg = self.cfg
+        if rho is None:
+            rho = cfg.exposure_rho
+        if rho is None:
+            rho = 0.05 if cfg.align_rho is None else cfg.align_rho
+        if not 0.0 <= rho < 1.0:
+            raise ValueError(f"rho {rho!r}: a fraction of the observed depth, inside [0, 1)")
+        rmax = float(cfg.exposure_max_residual if max_residual is None else max_residual)
+        if not 0.0 <= rmax <= 1.0:
+            raise ValueError(f"max_residual {rmax!r}: an intensity difference, inside [0, 1]")
+        lo, hi = _exposure_pair(cfg.exposure_saturation if saturation is None else tuple(saturation), "exposure_saturation")
+        g_lo, g_hi = _exposure_pair(cfg.exposure_gain if gain is None else tuple(gain), "exposure_gain")
+        passes = cfg.exposure_passes if passes is None else passes
+        if isinstance(passes, bool) or not isinstance(passes, (int, np.integer)) or not 1 <= passes <= EXPOSURE_MAX_PASSES:
+            raise ValueError(f"passes {passes!r}: a whole number of passes, 1 .. {EXPOSURE_MAX_PASSES}")
+        min_used = int(cfg.exposure_min_used if min_used is None else min_used)
+        if min_used < 1:
+            raise ValueError(f"min_used {min_used!r}: at least 1 row")
+        max_offset = float(cfg.exposure_max_offset if max_offset is None else max_offset)
+        min_var = float(cfg.exposure_min_var if min_var is None else min_var)
+        if not (math.isfinite(max_offset) and max_offset >= 0.0 and math.isfinite(min_var) and min_var >= 0.0):
+            raise ValueError(f"max_offset / min_var {max_offset!r} / {min_var!r}: finite and not negative")
+        keep, beyond = float(np.float32(1.0) - np.float32(rho)), float(np.float32(1.0) + np.float32(rho))
+        lo32, hi32 = float(np.float32(lo)), float(np.float32(hi))
+        if not 0.0 <= lo32 < hi32 <= 1.0:
+            raise ValueError(f"saturation {(lo, hi)!r}: not a range as float32")
+        return (keep, beyond, lo32, hi32, float(np.float32(rmax)), int(passes), min_used, g_lo, g_hi, max_offset, min_var)
+
+    def _exposure_launch(self, depth: Tensor, image: Tensor, intr: Tuple[float, float, float, float], w2c: Tensor,
+                         near: float, params) -> np.ndarray:
+        """w2c [4,4] float32 on the host.  Its copy to the device, the entry point and the read-back of the one buffer,
+        the call's one synchronisation: the int64 words (record, sums, params)."""
+        assert depth.is_cuda, "GaussianMap.estimate_exposure: the rows are summed and solved by HIP kernels, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        e = self._exposure_buffers()
+        keep, beyond, lo, hi, rmax, passes, min_used, g_lo, g_hi, max_offset, min_var = params
+        e["w2c"].copy_(w2c.reshape(16))
+        base, n_rec = e["words"].data_ptr(), EXPOSURE_MAX_PASSES * EXPOSURE_RECORD_WORDS
+        _lib.check(lib.gsl_map_exposure_estimate(ptr(self.means), ptr(self.colors), self.n_live, ptr(e["w2c"]), *intr,
+                                                 ptr(depth), ptr(image), self.W, self.H, keep, beyond, near, lo, hi, rmax,
+                                                 passes, min_used, g_lo, g_hi, max_offset, min_var, base + 8 * n_rec,
+                                                 base + 8 * (n_rec + EXPOSURE_VALUES), base, st),
+                   "gsl_map_exposure_estimate")
+        return e["words"].cpu().numpy()
+
+    @torch.no_grad()
+    def estimate_exposure(self, depth, K, c2w, near_plane: float, rgb=None, intensity=None, rho: Optional[float] = None,
+                          max_residual: Optional[float] = None, saturation=None, passes: Optional[int] = None,
+                          min_used: Optional[int] = None, gain=None, max_offset: Optional[float] = None,
+                          min_var: Optional[float] = None) -> Exposure:
+        """The exposure of a frame against the map: gain and offset with gain * Y_frame + offset ~ Y_row over the live
+        rows that the frame at c2w [4,4] sees -- a row projects beyond ``near_plane`` onto a pixel whose depth [H,W]
+        (metres) is within ``rho`` of its own -- whose colour's intensity and the frame's at that pixel both lie inside
+        ``saturation``, by ``passes`` least-squares passes, the later ones without the rows that miss by more than
+        ``max_residual`` (None: the ``exposure_*`` fields of the configuration; the rule: include/gsloc_hip.h).  The
+        frame is given as ``rgb`` [H,W,3] in 0 .. 255 (its intensity image is made here, one more kernel) or as
+        ``intensity`` [H,W] (``intensity(rgb)``), one of the two.  Changes nothing in the map.  One fixed sequence of
+        1 + 3 ``passes`` launches, one read-back; the pair stays on the device for ``apply_exposure(rgb)``.  An empty
+        map gives the identity with status FEW and no launch."""
+        if (rgb is None) == (intensity is None):
+            raise ValueError("estimate_exposure takes the frame as rgb or as intensity, one of the two")
+        params = self._exposure_params(rho, max_residual, saturation, passes, min_used, gain, max_offset, min_var)
+        depth = self._depth_image(depth)
+        if rgb is not None:
+            rgb = self._image(rgb, (self.H, self.W, 3), "rgb")
+        else:
+            intensity = self._image(intensity, (self.H, self.W), "intensity")
+        intr, c2w = _intr_and_pose(K, c2w)
+        if self.n_live == 0:
+            if self._exposure is not None:
+                self._exposure["params"].copy_(torch.tensor([1.0, 0.0, 0.0, 0.0]))
+            return Exposure(1.0, 0.0, "FEW", 0, 0, 0.0, [])
+        image = self._intensity_launch(rgb) if rgb is not None else intensity
+        host = self._exposure_launch(depth, image, intr, _world_to_camera(c2w).contiguous(), float(near_plane), params)
+        return self._exposure_of(host, params[5])
+
+    def _exposure_of(self, host: np.ndarray, passes: int) -> Exposure:
+        """The ``Exposure`` of what a launch read back."""
+        n_rec = EXPOSURE_MAX_PASSES * EXPOSURE_RECORD_WORDS
+        rec = host[:passes * EXPOSURE_RECORD_WORDS].reshape(passes, EXPOSURE_RECORD_WORDS)
+        sol = rec[:, 3:].copy().view(np.float64)
+        pair = host[n_rec + EXPOSURE_VALUES:].copy().view(np.float32)
+        history = [(EXPOSURE_STATUS[int(r[0])], int(r[1]), int(r[2]), float(x[0]), float(x[1]), float(x[2]))
+                   for r, x in zip(rec, sol)]
+        last = history[-1]
+        return Exposure(float(pair[0]), float(pair[1]), last[0], last[1], last[2], last[5], history)
+
+    @torch.no_grad()
+    def apply_exposure(self, rgb, exposure=None) -> Tensor:
+        """rgb [H,W,3] in 0 .. 255 corrected by an exposure: a new float32 [H,W,3] on the map's device, gain * rgb + 255 *
+        offset clipped to 0 .. 255 -- its intensity image is gain * Y + offset.  exposure: None, the pair the last
+        ``estimate_exposure`` left on the device (no read-back; the identity before the first); an ``Exposure`` or a
+        (gain, offset) pair, uploaded.  One kernel, no synchronisation."""
+        rgb = self._image(rgb, (self.H, self.W, 3), "rgb")
+        if exposure is not None:
+            pair = (exposure.gain, exposure.offset) if isinstance(exposure, Exposure) else tuple(exposure)
+            if len(pair) != 2 or not all(math.isfinite(float(a)) for a in pair):
+                raise ValueError(f"exposure {exposure!r}: an Exposure or a finite (gain, offset) pair")
+            b = np.float32(pair[1])
+            pair = torch.from_numpy(np.array([np.float32(pair[0]), b, b * np.float32(255.0), 0.0], np.float32))
+        assert rgb.is_cuda, "GaussianMap.apply_exposure: the image is corrected by a HIP kernel, no CPU path"
+        lib, st, ptr = _lib.load_library(), _lib.current_stream(), _lib.ptr
+        e = self._exposure_buffers()
+        params = e["params"] if exposure is None else pair.to(self.device)
+        out = torch.empty(self.H, self.W, 3, device=self.device)
+        _lib.check(lib.gsl_map_exposure_apply(ptr(rgb), self.W, self.H, ptr(params), ptr(out), st),
+                   "gsl_map_exposure_apply")
+        return out
 
     def _levels_params(self, levels, level_steps, steps: int):
         """The ``levels`` / ``level_steps`` arguments of ``align_pose`` / ``align_poses`` with their defaults filled in

@@ -541,6 +541,53 @@ int64_t gsl_map_pyramid_floats(int width, int height, int levels);
 int gsl_map_pyramid(const float* depth, const float* intensity, int width, int height, int levels, float keep,
                     float* depth_out, float* intensity_out, void* stream);
 
+/* ---- exposure compensation for the photometric term: an affine brightness model per frame (csrc/map_exposure.hip) ----
+ * gain and offset with gain * Y_frame + offset ~ Y_row over the rows of the map that the frame sees, estimated on the
+ * device by least squares, and applied to the frame's rgb: Y(gain * rgb + 255 * offset) = gain * Y(rgb) + offset.
+ * gsl_map_exposure_estimate: means[n_rows,3], colors[n_rows,3] (0 .. 1), w2c[16], fx .. cy, depth[height,width] and
+ *   intensity[height,width] (gsl_map_photo_intensity of the frame) as for gsl_map_pose_info_photo.  On the device, not
+ *   initialised, not overlapping: sums[GSL_MAP_EXPOSURE_VALUES] int64, params[4] float32 = (gain, offset, 255 * offset,
+ *   0) and record[passes][GSL_MAP_EXPOSURE_RECORD_WORDS] 8-byte words, per pass int64 (status, rows used, rows seen), then
+ *   float64 (g, b, rss).  One initialising launch, params = (1, 0, 0, 0); then per pass a zeroing launch, the sums and a
+ *   one-thread kernel.  Per row, float32, one rounding per operation in the order written, comparisons false for a NaN:
+ *     seen = z > near_plane and 0 <= uf <= width - 1 and 0 <= vf <= height - 1 and d0 = depth[vf, uf] > 0 and < inf and
+ *            d0 * keep <= z <= d0 * beyond (the nearest pixel only: border pixels count);
+ *     Yi = (0.299f c.r + 0.587f c.g) + 0.114f c.b;  Y0 = intensity[vf, uf];
+ *     used = seen and sat_lo <= Yi, Y0 <= sat_hi and |(params[0] * Y0 + params[1]) - Yi| <= gate, gate +inf in the first
+ *            pass and max_residual afterwards;
+ *     sums = sum fix(Y0, Y0), fix(Y0, 1), fix(Y0, Yi), fix(Yi, 1), fix(Yi, Yi), rows used, rows seen, fix as above.
+ *   The one-thread kernel, in float64 with one rounding per operation in the order csrc/map_exposure.hip writes down:
+ *     a pass before this one was not OK: its status is repeated, g, b = params, rss = 0;
+ *     used < min_used: FEW;  det = n Sxx - Sx Sx, not (det / (n n) > min_var): FLAT (both: g, b = params, rss = 0);
+ *     g = (n Sxy - Sx Sy) / det, b = (Sy - g Sx) / n, rss = (Syy - g Sxy) - b Sy;
+ *     not (gain_min <= g <= gain_max and |b| <= offset_max): RANGE;  otherwise OK and params = ((float)g, (float)b,
+ *     (float)b * 255.f, 0).  Every status but OK leaves params as they were; the later passes still run and change
+ *     nothing but their record.  The status of the call is that of the last record.
+ *   No allocation, no synchronisation, no read-back, no memset node, no float atomics.  Returns GSL_ERR_BAD_ARG before
+ *   any launch for a NULL pointer, n_rows <= 0 or >= 2^31, width or height <= 0 or width * height > 2^31 - 1, fx or fy
+ *   not non-zero, keep outside (0, 1], beyond not in [1, inf), not 0 <= sat_lo < sat_hi <= 1 (what keeps every term of a
+ *   sum at 2^20 or less, every sum below 2^51), max_residual not in [0, inf), passes outside 1 ..
+ *   GSL_MAP_EXPOSURE_MAX_PASSES, min_used < 1, not 0 < gain_min <= 1 <= gain_max < inf, offset_max or min_var not in
+ *   [0, inf).
+ * gsl_map_exposure_apply: rgb[height,width,3] and out (the same size, not overlapping it) float32 on the device, params
+ *   as above: t = (params[0] * c) + params[2];  out = 0 where t < 0, 255 where t > 255, t otherwise (a NaN stays one).
+ *   One kernel, one thread per value.  Returns GSL_ERR_BAD_ARG before the launch for a NULL pointer or such a size. */
+#define GSL_MAP_EXPOSURE_VALUES 7
+#define GSL_MAP_EXPOSURE_RECORD_WORDS 6
+#define GSL_MAP_EXPOSURE_MAX_PASSES 4
+#define GSL_MAP_EXPOSURE_OK 0
+#define GSL_MAP_EXPOSURE_FEW 1
+#define GSL_MAP_EXPOSURE_FLAT 2
+#define GSL_MAP_EXPOSURE_RANGE 3
+int gsl_map_exposure_values(void);
+int gsl_map_exposure_estimate(const float* means, const float* colors, int64_t n_rows, const float* w2c, float fx,
+                              float fy, float cx, float cy, const float* depth, const float* intensity, int width,
+                              int height, float keep, float beyond, float near_plane, float sat_lo, float sat_hi,
+                              float max_residual, int passes, int min_used, double gain_min, double gain_max,
+                              double offset_max, double min_var, int64_t* sums, float* params, void* record,
+                              void* stream);
+int gsl_map_exposure_apply(const float* rgb, int width, int height, const float* params, float* out, void* stream);
+
 /* ---- place recognition: a 16 x 12 descriptor of a depth frame, and its match against keyframes (csrc/map_place.hip) ----
  * gsl_map_place_describe: depth[height,width] float32 on the device, row-major, metres; desc[192] int32 on the device,
  * row-major over GSL_MAP_PLACE_GH lines of GSL_MAP_PLACE_GW cells (gsl_map_place_cells() = 192).  It need not be
